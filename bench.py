@@ -18,9 +18,20 @@ stream and output buffers (pixel-art-raytracer_amd/pipeline.py); one frame alone
 kernels that leaves most of the chip idle. `value` is therefore a RATE with 4 frames in flight; the latency of one
 frame on its own is reported beside it (`one_frame_at_a_time`).
 
-Timing: W untimed warm-up steps (after a time-based clock ramp), then BLOCKS (30) blocks of exactly K steps, each
-bracketed by a barrier + torch.cuda.synchronize() on both sides; `ms_per_step` is the MEDIAN block's time / K (the
-spread over the blocks is reported too), with N > 1 the maximum over ranks of each block first.
+Timing: W untimed warm-up steps (after a time-based clock ramp), then exactly K timed steps in one block, bracketed
+by a barrier + torch.cuda.synchronize() on both sides; `ms_per_step` is the block's time / K, with N > 1 the maximum
+over ranks.
+
+A plain run does only that and prints the headline. `--full` adds everything else, untimed by the headline: the
+frames in flight checked against one blocking whole-frame render, the spread of ms_per_step over `--blocks` (30)
+further blocks of K steps (fewer where they would take over SPREAD_BUDGET_S), kernel spans, the roofline of the
+dominant kernel, one frame at a time, the all-rays-traced rate, the dense and default-scene side workloads, the CPU
+baseline (checked against the GPU frame), and with N > 1 where a frame's time goes on each rank.
+
+`--dump-outputs DIR` writes the planes the timed path produced in its last step (RGBA8 frame `fb`, palette index
+`palidx`) as float32 DIR/<plane>.npy, one row per pixel: every pixel of a frame up to DUMP_SAMPLE pixels, else the
+same seeded sample of DUMP_SAMPLE pixel positions (ascending) every run; DIR/<plane>_row_sums.npy (float64) holds the
+per-row sums over every pixel. With N > 1 rank 0 writes its frame (only `fb` is assembled there).
 
 Mrays/s is nominal = 2 * W * H * frames / seconds (the reference casts exactly one primary and one shadow ray per
 pixel, background included: alt:277-279, 703, 738). The GPU path skips the shadow ray of background pixels, whose
@@ -49,6 +60,8 @@ N_PRIMS = 1024
 SEED = 12345
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 BLOCKS = 30
+SPREAD_BUDGET_S = 120.0  # --full: time the spread blocks may take in all (fewer than --blocks if K is long)
+DUMP_SAMPLE = 1 << 21  # pixels --dump-outputs keeps of a larger frame (40 MB of float32 for both planes)
 ORACLE_ROWS = (3 * 4096 // 8, 5 * 4096 // 8)  # the band of the frame the CPU baseline renders (and the GPU is checked on)
 
 
@@ -109,6 +122,20 @@ def time_blocks(run_block, steps, blocks, barrier, reduce_max):
         out.append(reduce_max(time.perf_counter() - t0) / steps * 1e3)
         first += steps
     return out
+
+
+def dump_outputs(path, planes, width):
+    """--dump-outputs: `planes` (name -> uint8 array, one row per pixel, `width` pixels a frame row) as float32
+    <name>.npy (every pixel, or the seeded sample of DUMP_SAMPLE pixels) and float64 <name>_row_sums.npy."""
+    os.makedirs(path, exist_ok=True)
+    n_pix = len(next(iter(planes.values())))
+    idx = None
+    if n_pix > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(SEED).choice(n_pix, DUMP_SAMPLE, replace=False))
+    for name, a in planes.items():
+        np.save(os.path.join(path, name + ".npy"), (a if idx is None else a[idx]).astype(np.float32))
+        sums = a.reshape(n_pix // width, width, -1).sum(axis=1, dtype=np.float64)
+        np.save(os.path.join(path, name + "_row_sums.npy"), sums if a.ndim > 1 else sums[:, 0])
 
 
 def side_scene(par, pipeline, T, name, params, aabbs, light, sprite, device, depth, steps, counters_key=None):
@@ -257,12 +284,17 @@ def main():
     global W, H, L, N_PRIMS
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=1000)
+    ap.add_argument("--steps", type=int, default=1000, help="timed steps (frames), timed as one block")
     ap.add_argument("--warmup", type=int, default=200)
-    ap.add_argument("--blocks", type=int, default=BLOCKS, help="timed blocks of --steps steps (median reported)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the planes of the timed path's last frame to DIR as .npy (float32)")
+    ap.add_argument("--blocks", type=int, default=BLOCKS,
+                    help="--full: further blocks of --steps steps for the spread of ms_per_step (at most)")
     ap.add_argument("--inflight", type=int, default=4, help="frames in flight (contexts/streams/buffers)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the dense / default-scene side measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the dense / default-scene side measurements")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for tests)")
     ap.add_argument("--share-gpu", action="store_true", help="tests: every rank uses GPU 0 (needs --backend gloo)")
     ap.add_argument("--assemble", choices=("tiles", "blocks", "none"), default="tiles",
@@ -392,18 +424,19 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    # correctness of what is about to be timed: the frames in flight against one blocking whole-frame render
-    run_block(0, depth)
+    # --full: correctness of what is about to be timed: the frames in flight against one blocking whole-frame render
     verified_gpu = None
     hit_pixels = 0
     full = None
-    if world > 1 and args.assemble == "none":
+    if args.full:
+        run_block(0, depth)
+    if args.full and world > 1 and args.assemble == "none":
         # the frame stays sharded: every rank holds its block against its own render of the whole frame
         mine = r.render(("fb",))["fb"].view(np.uint8)
         ok = all(bool(np.array_equal(fb[k].cpu().numpy()[:(r1 - r0) * W * 4], mine[r0 * W * 4:r1 * W * 4]))
                  for k in range(depth)) if has_rows else True
         verified_gpu = bool(reduce_max(0.0 if ok else 1.0) == 0.0)
-    if rank == 0:
+    if args.full and rank == 0:
         full = r.render(("fb", "palidx"))
         if world > 1 and tile_gathers:
             verified_gpu = all(bool(np.array_equal(tg.frame.cpu().numpy(), full["fb"].view(np.uint8)))
@@ -436,27 +469,28 @@ def main():
     # warm-up (untimed, counted)
     run_block(0, max(args.warmup, 1))
 
-    # timed region: BLOCKS blocks of exactly K steps
-    per_step = time_blocks(run_block, args.steps, max(1, args.blocks), barrier, reduce_max)
-    ms_per_step = statistics.median(per_step)
+    # timed region: exactly K steps in one block
+    ms_per_step = time_blocks(run_block, args.steps, 1, barrier, reduce_max)[0]
     # no kernel flagged a failure in any frame of the timed region (the flag is sticky; stats() raises PAR_ERR_DEVICE)
     for s_ in pipe.slots:
         s_.renderer.stats()
 
-    # the frame's kernels while the timed configuration runs: workgroup time stamps of `depth` frames in mid-flight
-    kernels_pipelined = None
-    if world == 1:
-        pipe.submit_many(0, 6 * depth)
-        pipe.submit_many(6 * depth, depth, 1 << 29)
-        pipe.submit_many(7 * depth, 6 * depth)
-        drain()
-        kernels_pipelined = pipe.kernel_spans_us()
+    # what the last timed step computed, before anything else renders into the slots
+    if args.dump_outputs and rank == 0:
+        k_last = (args.steps - 1) % depth
+        if world > 1 and tile_gathers:
+            planes = {"fb": tile_gathers[k_last].frame.cpu().numpy()}
+        elif world > 1 and gather is not None:
+            planes = {"fb": gather.frame.cpu().numpy()}
+        else:  # (N = 1, or the frame left sharded: rank 0's row block)
+            n_px = (r1 - r0) * W
+            planes = {"fb": fb[k_last].cpu().numpy()[:n_px * 4], "palidx": pal[k_last].cpu().numpy()[:n_px]}
+        dump_outputs(args.dump_outputs, {k: v.reshape(-1, 4) if k == "fb" else v for k, v in planes.items()}, W)
 
     out = None
     if rank == 0:
         rays_per_frame = 2.0 * W * H
         value = rays_per_frame / (ms_per_step * 1e-3) / 1e6
-        srt = sorted(per_step)
         out = {
             "metric": f"Mrays/sec at {W}x{H}, {N_PRIMS} prims", "value": round(value, 1), "unit": "Mrays/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 5),
@@ -471,17 +505,45 @@ def main():
                                      "blocks": ", one RCCL gather of the row blocks to rank 0",
                                      "none": ", the frame left sharded (no exchange)"}[args.assemble]),
                        "frames_in_flight": depth, "streams_overlap_pairwise": bool(pipe.streams_overlap),
-                       "note": "value is a rate with frames_in_flight frames in flight; one_frame_at_a_time is the "
-                               "latency of a frame on its own"},
-            "ms_per_step_spread": {"blocks": len(per_step), "min": round(srt[0], 5), "p10": round(srt[len(srt) // 10], 5),
-                                   "median": round(ms_per_step, 5), "p90": round(srt[(9 * len(srt)) // 10], 5),
-                                   "max": round(srt[-1], 5), "mean": round(statistics.fmean(per_step), 5)},
+                       "note": "value is a rate with frames_in_flight frames in flight; one_frame_at_a_time (--full) "
+                               "is the latency of a frame on its own"},
             "frames_per_s": round(1e3 / ms_per_step, 1),
             "mpix_per_s": round(W * H / ms_per_step / 1e3, 1),
-            "rays": {"nominal_per_frame": int(rays_per_frame), "traced_per_frame": int(W * H + hit_pixels),
-                     "note": "shadow rays of background pixels are output-neutral and skipped"},
-            "verified_vs_single_gpu_frame": verified_gpu,
+            "rays": {"nominal_per_frame": int(rays_per_frame)},
         }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        pipe.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full from here on: nothing below is part of the headline ------------------------------------------
+    # the spread of ms_per_step: further blocks of exactly K steps, each bracketed like the headline's (as many as fit
+    # in about SPREAD_BUDGET_S, so that a long K keeps the whole run bounded; ms_per_step is the same on every rank)
+    n_blocks = max(1, min(args.blocks, int(SPREAD_BUDGET_S * 1e3 / (args.steps * ms_per_step))))
+    per_step = time_blocks(run_block, args.steps, n_blocks, barrier, reduce_max)
+
+    # the frame's kernels while the timed configuration runs: workgroup time stamps of `depth` frames in mid-flight
+    kernels_pipelined = None
+    if world == 1:
+        pipe.submit_many(0, 6 * depth)
+        pipe.submit_many(6 * depth, depth, 1 << 29)
+        pipe.submit_many(7 * depth, 6 * depth)
+        drain()
+        kernels_pipelined = pipe.kernel_spans_us()
+
+    if rank == 0:
+        srt = sorted(per_step)
+        out["ms_per_step_spread"] = {"blocks": len(per_step), "min": round(srt[0], 5),
+                                     "p10": round(srt[len(srt) // 10], 5), "median": round(statistics.median(srt), 5),
+                                     "p90": round(srt[(9 * len(srt)) // 10], 5), "max": round(srt[-1], 5),
+                                     "mean": round(statistics.fmean(per_step), 5),
+                                     "note": "each block `steps` steps, timed after the headline's block"}
+        out["rays"].update({"traced_per_frame": int(W * H + hit_pixels),
+                            "note": "shadow rays of background pixels are output-neutral and skipped"})
+        out["verified_vs_single_gpu_frame"] = verified_gpu
         if kernels_pipelined:
             out["kernels_ms_pipelined"] = {k: round(v / 1e3, 5) for k, v in kernels_pipelined.items()}
             out["kernels_ms_pipelined"]["note"] = ("first workgroup start to last workgroup end of each launch of one "

@@ -14,7 +14,6 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
-    config.addinivalue_line("markers", "reference: needs oracle/_ref (the reference mounted; build container only)")
 
 
 @pytest.fixture(scope="session")
@@ -36,10 +35,10 @@ def oracle():
 
 @pytest.fixture(scope="session")
 def reference():
+    """The reference's own functions (oracle/_ref, built only where the reference is mounted), else None: the tests
+    then hold the oracle to the answers committed under tests/golden/ alone."""
     from oracle.oracle import Reference
-    if not Reference.available():
-        pytest.skip("oracle/_ref/libref_path.so not built (reference not mounted on this machine)")
-    return Reference()
+    return Reference() if Reference.available() else None
 
 
 @pytest.fixture(scope="session")

@@ -43,3 +43,44 @@ def apply_key(key, aabbs, light):
 
 def synthetic_scene(par, n, w, h, l, seed):
     return par.scene_synthetic(n, w, h, l, seed)
+
+
+def random_stage_scene(seed):
+    """The random scene and light of test_oracle_vs_reference.test_random_scenes_all_stages[seed] (480x320x320)."""
+    rng = np.random.default_rng(seed)
+    n = int(rng.integers(50, 1500))
+    aabbs = np.zeros(n, dtype=T.AABB)
+    aabbs["px"] = rng.integers(-30, 490, n)
+    aabbs["py"] = rng.integers(-30, 250, n)
+    aabbs["pz"] = rng.integers(-70, 380, n)
+    aabbs["ex"] = rng.integers(1, 21, n)
+    aabbs["ey"] = rng.integers(0, 21, n)
+    aabbs["ez"] = rng.integers(0, 21, n)
+    light = T.make_light(int(rng.integers(0, 480)), int(rng.integers(0, 160)), int(rng.integers(0, 160)))
+    return aabbs, light
+
+
+def shadow_walk_cases():
+    """The scene and the 3000 (start bin, end bin, start entity, ray) walks of test_shadow_walk_direct."""
+    rng = np.random.default_rng(11)
+    n = 700
+    aabbs = np.zeros(n, dtype=T.AABB)
+    aabbs["px"] = rng.integers(0, 460, n)
+    aabbs["py"] = rng.integers(0, 200, n)
+    aabbs["pz"] = rng.integers(0, 300, n)
+    aabbs["ex"] = aabbs["ey"] = aabbs["ez"] = 20
+    walks = []
+    for _ in range(3000):
+        s = (int(rng.integers(0, 12)), int(rng.integers(0, 8)), int(rng.integers(0, 8)))
+        e = (int(rng.integers(0, 12)), int(rng.integers(0, 8)), int(rng.integers(0, 8)))
+        ray = np.zeros(1, dtype=T.RAY)
+        with np.errstate(divide="ignore"):
+            d = rng.integers(-3, 4, 3).astype(np.float32) / np.float32(7)
+            ray["inv_x"], ray["inv_y"], ray["inv_z"] = np.float32(1) / d
+        ray["ox"], ray["oy"], ray["oz"] = rng.integers(0, 480), rng.integers(0, 200), rng.integers(0, 320)
+        ent = int(rng.integers(0, n))
+        walks.append((s, e, ent, ray))
+    return aabbs, walks
+
+
+DEBUG_LINE_MICE = [(0, 0), (240, 160), (479, 319)]

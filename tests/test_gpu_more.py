@@ -535,7 +535,7 @@ def test_bench_multi_rank_control_flow(world, assemble):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
            "--gpus", str(world), "--steps", "12", "--warmup", "3", "--blocks", "3", "--backend", "gloo", "--share-gpu",
-           "--size", "1000" if world == 3 else "1024", "--no-cpu-baseline", "--assemble", assemble]
+           "--size", "1000" if world == 3 else "1024", "--full", "--no-cpu-baseline", "--assemble", assemble]
     # PAR_BENCH_RAMP_SKEW: the ranks' clocks WANT different numbers of untimed ramp iterations (each holds
     # collectives); the job only ends if they agree on one number all the same
     p = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=300,

@@ -6,9 +6,9 @@ commit=${2:-unknown}
 out=gpurun_out/prof_$tag
 mkdir -p $out
 export TMPDIR=/tmp
-python3 bench.py --steps 200 --warmup 50 > $out/bench.json 2> $out/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench -o bench -- python3 bench.py --steps 200 --warmup 50 --no-cpu-baseline --no-extras > $out/bench_profiled.json 2> $out/rocprof_bench.err
-python3 tools/kernel_durations.py $out/bench "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 200 --warmup 50 --no-cpu-baseline --no-extras" > $out/bench_kernel_durations.txt
+python3 bench.py --full --steps 200 --warmup 50 > $out/bench.json 2> $out/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench -o bench -- python3 bench.py --full --steps 200 --warmup 50 --no-cpu-baseline --no-extras > $out/bench_profiled.json 2> $out/rocprof_bench.err
+python3 tools/kernel_durations.py $out/bench "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 200 --warmup 50 --no-cpu-baseline --no-extras" > $out/bench_kernel_durations.txt
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/one -o one -- python3 tools/frames.py synthetic 300 > $out/one.log 2> $out/rocprof_one.err
 python3 tools/kernel_durations.py $out/one "rocprofv3 --kernel-trace --stats -- python3 tools/frames.py synthetic 300 (one frame at a time)" > $out/one_kernel_durations.txt
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/floor -o floor -- python3 tools/frames.py floor 60 > $out/floor.log 2> $out/rocprof_floor.err
