@@ -55,10 +55,7 @@ enum {
     /* par_render_device_timed only: time the frame's launches AS A PRODUCTION FRAME MAKES THEM (the background fill
      * riding with the hash-build and column launches) into par_frame_stats.ms_launch, instead of the kernels apart. */
     PAR_RENDER_TIMED_AS_LAUNCHED = 1u << 3
-    /* Bit 22 (tests): no self-contained work items, every column is rendered from its record; same pixels.
-     * Bit 23 (tests): build the spatial hash with two launches even where one would do; same pixels.
-     * Bits 24-28 switch parts of the frame OFF for timing experiments (tools/ablate.py, tools/overlap.py): the output
-     * is then wrong by design. Never set them in a render whose pixels are used. Bit 29: debug time stamps. */
+    /* other bits are rejected; bit 29 is reserved for the library's profiling time stamps */
 };
 
 /* Output planes of one render, each nullable. Every pointer addresses the element of (row_begin, column 0);

@@ -123,6 +123,7 @@ def lib():
         L.par_tiles_assemble.argtypes = [vp, vp, vp, vp, vp, i32, i32]
         L.par_scene_tile_map.argtypes = [vp, vp, i32, vp, i32]
         L.par_debug_read_stamps.argtypes = [vp, vp, C.c_size_t]
+        L.par_debug_set_hooks.argtypes = [vp, C.c_uint, i32]
         L.par_debug_line.restype = None
         L.par_debug_line.argtypes = [vp, vp, i32, vp, vp]
         _lib = L
@@ -314,6 +315,18 @@ class Renderer:
         st = FrameStats()
         self._check(lib().par_get_stats(self._ctx, C.byref(st)))
         return st
+
+    def set_test_hooks(self, force_generic=False, two_launch_build=False, record_items=False, lose_build_wg=False,
+                       bad_alloc=False, col_roles=0):
+        """Tests only (par_debug_set_hooks, not part of the public header): switches read by the frames enqueued from
+        now on. force_generic: every column through the overflow kernel; two_launch_build: the hash build always takes
+        two launches; record_items: every column rendered from its record; lose_build_wg: a build workgroup never
+        arrives at the one-launch build's barrier (PAR_ERR_DEVICE); bad_alloc: the host-allocating entry points fail
+        with PAR_ERR_OOM; col_roles: 1, 2, 4 or 8 wavefronts per column (0: the library's choice). No arguments:
+        production behaviour."""
+        hooks = (int(force_generic) | int(two_launch_build) << 1 | int(record_items) << 2 | int(lose_build_wg) << 3 |
+                 int(bad_alloc) << 4)
+        self._check(lib().par_debug_set_hooks(self._ctx, hooks, col_roles))
 
     def read_grid(self):
         """(count, map, bins) of the last frame in the reference's layout (alt:503-509); parity tooling."""

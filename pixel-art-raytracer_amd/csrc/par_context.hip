@@ -105,6 +105,19 @@ struct par_context {
     par_frame_stats stats{};
     unsigned last_flags = 0;
     std::string err;
+    // test hooks (par_debug_set_hooks), read when a frame is enqueued; 0 and 0 in production
+    unsigned hooks = 0;
+    int col_roles = 0;  // wavefronts per column of the column launch, 0 = its own choice
+};
+
+// par_debug_set_hooks's bits
+enum : unsigned {
+    PAR_HOOK_FORCE_GENERIC = 1u << 0,  // every column through render_overflow_kernel (par_render_args::dense)
+    PAR_HOOK_TWO_LAUNCHES = 1u << 1,   // the hash build always takes two launches
+    PAR_HOOK_RECORD_ITEMS = 1u << 2,   // columns emit no self-contained work items (PAR_FLAG_RECORD_ITEMS)
+    PAR_HOOK_LOSE_BUILD_WG = 1u << 3,  // build workgroup 0 never arrives at the one-launch build's barrier
+    PAR_HOOK_BAD_ALLOC = 1u << 4,      // the guarded host-allocating bodies fail as an exhausted heap would
+    PAR_HOOKS_ALL = (1u << 5) - 1
 };
 
 namespace {
@@ -122,10 +135,9 @@ int fail(par_context* c, int status, const std::string& msg) {
 }
 
 // No exception crosses the C boundary (par_raytracer.h): every entry point that allocates on the host runs its
-// body through this. PAR_TEST_BAD_ALLOC=1 (tests) makes the guarded bodies fail as an exhausted heap would.
-void test_alloc_hook() {
-    const char* e = std::getenv("PAR_TEST_BAD_ALLOC");
-    if (e && e[0] == '1') throw std::bad_alloc();
+// body through this. PAR_HOOK_BAD_ALLOC (tests) makes the guarded bodies fail as an exhausted heap would.
+void test_alloc_hook(const par_context* c) {
+    if (c->hooks & PAR_HOOK_BAD_ALLOC) throw std::bad_alloc();
 }
 
 template <class F>
@@ -427,6 +439,11 @@ int check_rows(par_context* ctx, int row_begin, int row_end) {
     return PAR_OK;
 }
 
+int check_flags(par_context* ctx, unsigned flags) {
+    if (flags & ~PAR_ACCEPTED_FLAGS) return fail(ctx, PAR_ERR_INVALID_ARG, "undefined render flag bits");
+    return PAR_OK;
+}
+
 int check_ready(par_context* ctx) {
     if (ctx->n_sprites <= 0) return fail(ctx, PAR_ERR_NOT_READY, "par_set_sprites has not been called");
     if (!ctx->have_entities) return fail(ctx, PAR_ERR_NOT_READY, "par_set_entities has not been called");
@@ -446,30 +463,23 @@ par_render_args make_render_args(const par_context* c, int set, int row_begin, i
     a.set = set;
     // every ray traced (as the reference does), or the lit plane requested
     a.trace_bg = ((flags & PAR_RENDER_TRACE_BACKGROUND) || out.lit) ? 1 : 0;
-    // PAR_FORCE_GENERIC=1 (testing): every column goes through render_overflow_kernel
-    static const bool force_generic = [] { const char* e = std::getenv("PAR_FORCE_GENERIC"); return e && e[0] == '1'; }();
-    a.dense = force_generic ? 1 : 0;
+    a.dense = (c->hooks & PAR_HOOK_FORCE_GENERIC) ? 1 : 0;
     a.magic_b = (uint32_t)((1ull << 32) / (uint64_t)B + 1ull);
     a.ambient = c->params.ambient;
     a.background = c->params.background;
-    a.flags = flags;
+    a.flags = flags | ((c->hooks & PAR_HOOK_RECORD_ITEMS) ? PAR_FLAG_RECORD_ITEMS : 0u);
     // Columns are visited as whole tiles only in DENSE frames, which get a launch for the tile items: enough columns
     // (a 64th of the grid, at least 16) whose entities' rectangles add up to the tile (the column kernel's own
     // criterion, over the visible entries). A frame with fewer visits every column entry by entry (tile_k 0) and keeps
     // its three launches. A captured graph serves later frames too: it always has the launch. Then: how many chunks
     // per tile item -- a frame with many lets a wavefront read what a column's chunks share once for several of them,
-    // a frame with few needs every wavefront it can get. PAR_TUNE_TILE_K overrides (tools; 0 is "never").
-    static const int tuned_k = [] {
-        const char* e = std::getenv("PAR_TUNE_TILE_K");
-        const int v = e ? std::atoi(e) : -1;
-        return v > 64 ? 64 : v;
-    }();
+    // a frame with few needs every wavefront it can get.
     const int64_t grid_cols = (int64_t)c->gx * c->gy;
     const bool dense_frame = dyn_from_device || c->cols_tileable >= std::max<int64_t>(16, grid_cols / 64);
     // (what the entities' rectangles add up to, but no more than every column of the grid as a whole tile: the entities
     // of a crowded small view overlap many times over)
     const int64_t chunks = std::min(c->total_items, max_items(c));
-    a.tile_k = tuned_k >= 0 ? tuned_k : (!dense_frame ? 0 : (chunks >= 65536 ? 5 : (chunks >= 16384 ? 3 : (chunks >= 8192 ? 2 : 1))));
+    a.tile_k = !dense_frame ? 0 : (chunks >= 65536 ? 5 : (chunks >= 16384 ? 3 : (chunks >= 8192 ? 2 : 1)));
     a.tile_k_magic = a.tile_k > 0 ? (uint32_t)(65536 / a.tile_k + 1) : 65537u;
     a.dyn = make_dyn(c, c->light);
     a.dyn_ptr = dyn_from_device ? c->d_dyn : nullptr;
@@ -495,8 +505,7 @@ par_bin_args make_bin_args(const par_context* c, int set, int row_begin, int row
     b.aabbs = c->d_aabbs;
     b.magic_b = (uint32_t)((1ull << 32) / (uint64_t)c->params.bin_size + 1ull);
     // tests: a build workgroup that never arrives at the one-launch hash build's barrier (PAR_ERR_DEVICE)
-    static const bool lose = [] { const char* e = std::getenv("PAR_TEST_LOSE_BUILD_WG"); return e && e[0] == '1'; }();
-    b.test_lose_wg = lose ? 1 : 0;
+    b.test_lose_wg = (c->hooks & PAR_HOOK_LOSE_BUILD_WG) ? 1 : 0;
     return b;
 }
 
@@ -555,10 +564,9 @@ int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, 
     // it is the plain streaming one it rides along with the first three launches (timed runs keep all kernels apart
     // so that the event pairs bracket single ones).
     par_fill_plan plan;
-    const bool no_fill = (flags & (1u << 28)) != 0;  // ablation (timing experiments only): no background fill
     // (a timed frame keeps its kernels apart unless it is asked to time the launches as a production frame makes them)
     const bool apart = ev && !(flags & PAR_RENDER_TIMED_AS_LAUNCHED);
-    const bool ride = !apart && !no_fill && par_plan_fill(r, &plan);
+    const bool ride = !apart && par_plan_fill(r, &plan);
     par_render_args rf = r;  // what rides along: the frame and palette-index planes
     rf.out.lit = nullptr;
     // A captured graph must also hold for later frames, whose pair count is unknown at capture time: the bound is
@@ -566,10 +574,9 @@ int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, 
     const bool stale = ctx->exact_stale;  // (asynchronous updates since the last blocking call: extents-only bounds)
     const int64_t pair_bound = graph_mode ? ctx->graph_pair_bound : (stale ? ctx->bound_pairs : ctx->total_pairs);
     // small scenes build the hash in one launch, large ones in two (timed runs keep the kernels apart)
-    static const bool two_env = [] { const char* e = std::getenv("PAR_BUILD_TWO_LAUNCHES"); return e && e[0] == '1'; }();
-    const bool two_launches = two_env || (flags & (1u << 23));  // bit 23 (tests): insert and resolve as two launches
-    hipError_t be = (apart || two_launches) ? hipErrorNotSupported
-                                         : par_launch_build(ctx->grid, b, pair_bound, &rf, ride ? &plan : nullptr, stream);
+    const bool two_launches = apart || (ctx->hooks & PAR_HOOK_TWO_LAUNCHES);
+    hipError_t be = two_launches ? hipErrorNotSupported
+                                 : par_launch_build(ctx->grid, b, pair_bound, &rf, ride ? &plan : nullptr, stream);
     if (be == hipErrorNotSupported) {
         PAR_HIP(par_launch_bin_insert(ctx->grid, b, &rf, ride ? &plan : nullptr, stream));
         PAR_HIP(par_launch_bin_resolve(ctx->grid, b, pair_bound, &rf, ride ? &plan : nullptr, stream));
@@ -580,17 +587,16 @@ int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, 
     // occupied columns <= the columns the entities reach one by one (<= their (entity, bin) pairs)
     const int64_t col_bound = graph_mode ? pair_bound : (stale ? ctx->bound_cols : ctx->total_cols);
     if (ride) {
-        PAR_HIP(par_launch_columns_fill(ctx->grid, rf, col_bound, plan, stream));
+        PAR_HIP(par_launch_columns_fill(ctx->grid, rf, col_bound, plan, ctx->col_roles, stream));
     } else {
-        PAR_HIP(par_launch_columns(ctx->grid, r, col_bound, stream));
+        PAR_HIP(par_launch_columns(ctx->grid, r, col_bound, ctx->col_roles, stream));
     }
     if (ev) PAR_HIP(hipEventRecord(ev[1], stream));
     // Otherwise the fill follows on the same stream. (Forking it onto a second stream beside the build was measured
     // slower, alone and with several frames in flight: the cross-stream events cost more than the overlap gains.)
     // It follows the column kernels because, when background rays are traced, it copies their results into the lit
     // plane.
-    if (no_fill) {
-    } else if (!ride) {
+    if (!ride) {
         PAR_HIP(par_launch_fill(ctx->grid, r, stream));
     } else if (r.out.lit) {  // the lit plane of the background: after the background rays
         par_render_args rl = r;
@@ -632,7 +638,9 @@ int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, 
 
 int render_to_host(par_context* ctx, int row_begin, int row_end, const par_outputs* host_out, unsigned flags) {
     if (!ctx || !host_out) return fail(ctx, PAR_ERR_INVALID_ARG, "null argument");
-    int rc = check_rows(ctx, row_begin, row_end);
+    int rc = check_flags(ctx, flags);
+    if (rc != PAR_OK) return rc;
+    rc = check_rows(ctx, row_begin, row_end);
     if (rc != PAR_OK) return rc;
     rc = check_ready(ctx);
     if (rc != PAR_OK) return rc;
@@ -804,7 +812,7 @@ void par_destroy(par_context* ctx) {
 
 static int par_set_sprites_impl(par_context* ctx, const par_sprite* sprites, int n_sprites) {
     if (!ctx || !sprites || n_sprites <= 0) return fail(ctx, PAR_ERR_INVALID_ARG, "sprites");
-    test_alloc_hook();
+    test_alloc_hook(ctx);
     for (int s = 0; s < n_sprites; s++) {
         for (int t = 0; t < PAR_SPRITE_TEXELS; t++) {
             const int c = sprites[s].color[t];
@@ -841,7 +849,7 @@ static int par_set_sprites_impl(par_context* ctx, const par_sprite* sprites, int
 
 static int par_set_entities_impl(par_context* ctx, const par_aabb* aabbs, const int32_t* sprite_ids, int n) {
     if (!ctx || n < 0 || (n > 0 && !aabbs)) return fail(ctx, PAR_ERR_INVALID_ARG, "entities");
-    test_alloc_hook();
+    test_alloc_hook(ctx);
     int max_id = 0;
     for (int i = 0; i < n; i++) {
         if (!extent_ok(aabbs[i])) {
@@ -913,7 +921,7 @@ static int par_set_entities_ref_layout_impl(par_context* ctx, const par_aabb* aa
     if (!ctx || n < 0 || (n > 0 && (!aabbs || !sprite_per_entity))) return fail(ctx, PAR_ERR_INVALID_ARG, "entities");
     // The reference stores one 16 000-byte Sprite per entity (alt:95,107). Keep each distinct sprite once: a 64-bit
     // hash of the bytes finds the candidates, memcmp decides.
-    test_alloc_hook();
+    test_alloc_hook(ctx);
     std::unordered_map<uint64_t, std::vector<int32_t>> seen;
     std::vector<par_sprite> table;
     std::vector<int32_t> ids((size_t)n);
@@ -1045,7 +1053,9 @@ static int par_render_rows_impl(par_context* ctx, int row_begin, int row_end, co
 static int par_render_device_impl(par_context* ctx, void* stream, int row_begin, int row_end, const par_outputs* device_out,
                       unsigned flags) {
     if (!ctx || !device_out) return fail(ctx, PAR_ERR_INVALID_ARG, "null argument");
-    int rc = check_rows(ctx, row_begin, row_end);
+    int rc = check_flags(ctx, flags);
+    if (rc != PAR_OK) return rc;
+    rc = check_rows(ctx, row_begin, row_end);
     if (rc != PAR_OK) return rc;
     rc = check_ready(ctx);
     if (rc != PAR_OK) return rc;
@@ -1062,7 +1072,9 @@ static int par_render_device_impl(par_context* ctx, void* stream, int row_begin,
 static int par_render_device_timed_impl(par_context* ctx, void* stream, int row_begin, int row_end,
                             const par_outputs* device_out, unsigned flags, par_frame_stats* stats) {
     if (!ctx || !device_out) return fail(ctx, PAR_ERR_INVALID_ARG, "null argument");
-    int rc = check_rows(ctx, row_begin, row_end);
+    int rc = check_flags(ctx, flags);
+    if (rc != PAR_OK) return rc;
+    rc = check_rows(ctx, row_begin, row_end);
     if (rc != PAR_OK) return rc;
     rc = check_ready(ctx);
     if (rc != PAR_OK) return rc;
@@ -1097,7 +1109,9 @@ static int par_graph_capture_impl(par_context* ctx, void* stream_v, int row_begi
     if (!ctx || !device_out) return fail(ctx, PAR_ERR_INVALID_ARG, "null argument");
     hipStream_t stream = (hipStream_t)stream_v;
     if (!stream) return fail(ctx, PAR_ERR_INVALID_ARG, "graph capture needs a non-default stream");
-    int rc = check_rows(ctx, row_begin, row_end);
+    int rc = check_flags(ctx, flags);
+    if (rc != PAR_OK) return rc;
+    rc = check_rows(ctx, row_begin, row_end);
     if (rc != PAR_OK) return rc;
     rc = check_ready(ctx);
     if (rc != PAR_OK) return rc;
@@ -1260,6 +1274,19 @@ int par_debug_read_stamps(par_context* ctx, unsigned long long* out, size_t coun
     return PAR_OK;
 }
 
+// Internal test aid (not part of the public header either): the context's test hooks (PAR_HOOK_* bits) and a forced
+// number of wavefronts per column (1, 2, 4 or 8; 0 keeps the column launch's own choice). Read when a frame is
+// enqueued; 0 and 0 restore production behaviour.
+int par_debug_set_hooks(par_context* ctx, unsigned hooks, int col_roles) {
+    if (!ctx) return PAR_ERR_INVALID_ARG;
+    if ((hooks & ~PAR_HOOKS_ALL) || !(col_roles == 0 || col_roles == 1 || col_roles == 2 || col_roles == 4 || col_roles == 8)) {
+        return fail(ctx, PAR_ERR_INVALID_ARG, "test hooks");
+    }
+    ctx->hooks = hooks;
+    ctx->col_roles = col_roles;
+    return PAR_OK;
+}
+
 static int par_read_grid_impl(par_context* ctx, int32_t* count, int32_t* map, par_aabb* bins) {
     if (!ctx || !count || !map || !bins) return fail(ctx, PAR_ERR_INVALID_ARG, "grid buffers");
     PAR_HIP(hipSetDevice(ctx->device));
@@ -1319,6 +1346,7 @@ static int par_render_device_slots_impl(par_context* const* ctxs, void* const* s
                                         int n_slots, int row_begin, int row_end, int first_frame, int n_frames,
                                         unsigned flags) {
     if (!ctxs || !streams || !device_outs || n_slots < 1 || n_frames < 0 || first_frame < 0) return PAR_ERR_INVALID_ARG;
+    if (flags & ~PAR_ACCEPTED_FLAGS) return PAR_ERR_INVALID_ARG;
     if (n_slots > 1) flags |= PAR_RENDER_PIPELINED;  // several frames in flight: throughput before latency
     for (int f = first_frame; f < first_frame + n_frames; f++) {
         const int k = f % n_slots;

@@ -26,16 +26,9 @@ constexpr int PAR_MAX_GRID_DIM = 1024;  // per-axis bin count (bin coordinates a
 // Per-column record built once per frame by columns_kernel and consumed by every wavefront rendering the column.
 constexpr int PAR_COL_NB = 32;          // occupied bins of one column it can describe
 constexpr int PAR_COL_ENT = 64;         // slot records of one column (one per lane of the rendering wavefront)
-// (experiments, tools/debug/variants.sh: -DPAR_EXP_BIN_WALK=... -DPAR_EXP_COL_WALK=... ; larger records bought nothing
-// on the graybox world and cost the big views)
-#if !defined(PAR_EXP_BIN_WALK)
-#define PAR_EXP_BIN_WALK 64
-#endif
-#if !defined(PAR_EXP_COL_WALK)
-#define PAR_EXP_COL_WALK 160
-#endif
-constexpr int PAR_BIN_WALK = PAR_EXP_BIN_WALK;  // occluder records of one start bin's shadow walk
-constexpr int PAR_COL_WALK = PAR_EXP_COL_WALK;  // occluder records of all walks of one column
+// (larger walk records bought nothing on the graybox world and cost the big views)
+constexpr int PAR_BIN_WALK = 64;        // occluder records of one start bin's shadow walk
+constexpr int PAR_COL_WALK = 160;       // occluder records of all walks of one column
 constexpr int PAR_MIN_BIN = 8, PAR_MAX_BIN = 160;  // supported bin sizes
 constexpr int PAR_TILE_MASKS = 64;      // chunks of a tile visit whose candidate masks the column record carries (one
                                         // lane of the column's wavefront each: bins up to 64 pixels a side)
@@ -119,9 +112,14 @@ struct par_frame_dyn {
     int32_t lbx, lby, lbz;  // its bin (alt:729-732)
 };
 
-// Render flags that make the render launch use its instrumented variant (ray counting, the timing-experiment bits
-// 24-26 and the time stamps, bit 29); a production frame has none of them and runs kernels compiled without them.
-constexpr uint32_t PAR_DEBUG_FLAGS = PAR_RENDER_COUNT_RAYS | (7u << 24) | (1u << 29);
+// Render flags that make the render launch use its instrumented variant (ray counting and the time stamps, bit 29);
+// a production frame has neither and runs kernels compiled without them.
+constexpr uint32_t PAR_DEBUG_FLAGS = PAR_RENDER_COUNT_RAYS | (1u << 29);
+// Every flag a caller may pass: the public ones and the time stamps. Anything else is rejected (PAR_ERR_INVALID_ARG).
+constexpr uint32_t PAR_ACCEPTED_FLAGS = 0xFu | (1u << 29);
+// Set by the library alone, never by a caller (the record-items-only test hook, par_debug_set_hooks): columns emit
+// no self-contained (simple) work items, every column is rendered from its record.
+constexpr uint32_t PAR_FLAG_RECORD_ITEMS = 1u << 22;
 constexpr int PAR_WAVE_NW = 4;          // wavefronts per render workgroup
 // Render work items: columns_kernel lists every 64-pixel chunk of every column with a record as one item (par_item);
 // pass = the entry whose rectangle is visited, PAR_ITEM_TILE = the whole tile. An item of a SIMPLE column (all its
@@ -177,7 +175,7 @@ struct par_bin_args {
     int32_t set;             // which head/count/node/colflag set this frame uses
     int32_t by_lo, by_hi;    // bin rows [by_lo, by_hi] the render of this frame touches (column-list filter)
     uint32_t flags;          // render flags (bit 29: debug time stamps)
-    int32_t test_lose_wg;    // tests (PAR_TEST_LOSE_BUILD_WG=1): build workgroup 0 never arrives at the barrier
+    int32_t test_lose_wg;    // tests (par_debug_set_hooks): build workgroup 0 never arrives at the barrier
     uint32_t magic_b;        // floor(n / B) == __umulhi(n, magic_b) for n * B < 2^32 (as par_render_args::magic_b)
     const par_aabb* aabbs;
 };
@@ -188,7 +186,7 @@ struct par_render_args {
     int32_t by_lo, by_hi;          // bin rows touched
     int32_t set;                   // grid set of this frame
     int32_t trace_bg;              // 1: background shadow rays are traced too (flag, or lit plane requested)
-    int32_t dense;                 // 1 (PAR_FORCE_GENERIC=1, tests): every column is rendered as if it had no record
+    int32_t dense;                 // 1 (tests, par_debug_set_hooks): every column is rendered as if it had no record
     uint32_t magic_b;              // floor(n / B) == __umulhi(n, magic_b) for n * B < 2^32
     float ambient;
     uint32_t background;           // gray level (alt:281)
@@ -235,10 +233,12 @@ hipError_t par_launch_bin_resolve(const par_grid_dev& g, const par_bin_args& a, 
                                   const par_render_args* fa, const par_fill_plan* fill, hipStream_t stream);
 // Per occupied column: compact slot list + the shadow walks of its bins (+ the background walks when a.trace_bg);
 // then, when a.trace_bg, the background rays themselves (one per x).
-hipError_t par_launch_columns(const par_grid_dev& g, const par_render_args& a, int64_t column_bound, hipStream_t stream);
+// `col_roles`: wavefronts per column (1, 2, 4 or 8), 0 = the launch's own choice (column_roles).
+hipError_t par_launch_columns(const par_grid_dev& g, const par_render_args& a, int64_t column_bound, int col_roles,
+                              hipStream_t stream);
 // Column records + the last share of the fill in one launch.
 hipError_t par_launch_columns_fill(const par_grid_dev& g, const par_render_args& a, int64_t column_bound,
-                                   const par_fill_plan& fill, hipStream_t stream);
+                                   const par_fill_plan& fill, int col_roles, hipStream_t stream);
 // Background for every pixel of the row range; the render kernel then overwrites the pixels primitives cover.
 // Independent of the hash.
 hipError_t par_launch_fill(const par_grid_dev& g, const par_render_args& a, hipStream_t stream);

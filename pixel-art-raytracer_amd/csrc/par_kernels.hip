@@ -17,7 +17,7 @@
 //   render_tiles_kernel     the same for the whole-tile items (render_tile_item: scalar-loaded entries and walk
 //                           records, lane masks in scalar registers); launched for dense frames only
 //   render_overflow_kernel  the columns that overflow a record: straight from the hash, walks in-kernel; launched
-//                           only when the host cannot rule an overflow out (PAR_FORCE_GENERIC=1: every column)
+//                           only when the host cannot rule an overflow out (every column under a test hook)
 //   (render_both_kernel     the render kernels in one launch for small frames, which are bound by their launches and
 //                           by their slowest wavefront: a wavefront for every item the fullest shard can hold)
 // The background fill (alt:281 -> alt:735, pure streaming) has no launch of its own: the first two launches each
@@ -37,7 +37,6 @@
 
 #include <algorithm>
 #include <type_traits>
-#include <cstdlib>
 
 namespace {
 
@@ -752,7 +751,7 @@ __device__ __forceinline__ void columns_wave(const par_grid_dev& g, const par_re
     // walks differ in length: fixed shares would turn away walks that fit), a lone wavefront counts for itself.
     int n_walk = 0;
     bool walk_failed = false;
-    if (!overflow && !(a.flags & (1u << 27))) {  // bit 27: ablation (timing experiments only), no walks
+    if (!overflow) {
         const par_frame_dyn dyn = a.dyn_ptr ? *a.dyn_ptr : a.dyn;
         for (int i = role; i < n_nb; i += ROLES) {
             const int sz = sm.nb[i].bz;
@@ -815,8 +814,8 @@ __device__ __forceinline__ void columns_wave(const par_grid_dev& g, const par_re
         // no walk from them met anything. Its items carry all the render kernel needs.
         const int distinct = n_entries - __popcll(dup_mask);
         const int bz_first = sm.nb[0].bz, bz_last = sm.nb[max(n_nb, 1) - 1].bz;
-        const bool simple = !(a.flags & (1u << 22)) && distinct == 1 && walks_empty && !tile_mode && n_nb >= 1 &&
-                            bz_last - bz_first == n_nb - 1;  // bit 22 (tests): no simple items
+        const bool simple = !(a.flags & PAR_FLAG_RECORD_ITEMS) && distinct == 1 && walks_empty && !tile_mode &&
+                            n_nb >= 1 && bz_last - bz_first == n_nb - 1;
         par_item it;
         it.ci = usable ? (uint32_t)ci : PAR_ITEM_NONE;
         it.where = (uint32_t)bx | ((uint32_t)by << 10) | (simple ? PAR_ITEM_SIMPLE : 0u);
@@ -1360,11 +1359,10 @@ __device__ __forceinline__ void render_chunk(const par_grid_dev& g, const par_re
     int pal_index = PAR_PALIDX_BACKGROUND;
     float bright = ambient;
     bool lit = true;
-    const bool shade = hit && !(fl & (1u << 26));  // bit 26: ablation (timing experiments only), no shading
     bool need_walk = false;  // the shadow ray still has to be resolved
     float inv_x = 0.f, inv_y = 0.f, inv_z = 0.f, b_lit = 0.f;
     int sy = 0, sz = 0, ox = 0, oy = 0, oz = 0;
-    if (shade) {
+    if (hit) {
         // normal (alt:349-350) + resolved palette colour (alt:352-354)
         par_texel ti = pre_ti;
         pal_index = pre_pal;
@@ -1476,7 +1474,7 @@ __device__ __forceinline__ void render_chunk(const par_grid_dev& g, const par_re
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
     }
-    if (shade) bright = lit ? b_lit : ambient;
+    if (hit) bright = lit ? b_lit : ambient;
     const bool lit_px = lit;
     if (!GENERIC) stamp(g, fl, 3, 4);
     if ((fl & PAR_RENDER_COUNT_RAYS) && a.ray_counter) {
@@ -1485,26 +1483,10 @@ __device__ __forceinline__ void render_chunk(const par_grid_dev& g, const par_re
     }
 
     // ---- quantise + store, alt:735, 757-758 -------------------------------------------------------------------
-    if (fl & (1u << 25)) {  // bit 25: ablation (timing only), no stores; keep the values alive
-        asm volatile("" ::"v"(rgba), "v"(bright), "v"(pal_index));
-    } else if (valid && hit) {  // (uncovered pixels keep what the fill wrote)
+    if (valid && hit) {  // (uncovered pixels keep what the fill wrote)
         const size_t o = (size_t)(row - a.row_begin) * W + col;
-#if !defined(PAR_EXP_STORE)
         if (a.out.fb) __builtin_nontemporal_store(color_scale(rgba, bright), reinterpret_cast<uint32_t*>(a.out.fb) + o);
         if (a.out.palidx) __builtin_nontemporal_store((uint8_t)pal_index, a.out.palidx + o);
-#elif PAR_EXP_STORE == 1  // (experiments, tools/debug/variants.sh: plain stores)
-        if (a.out.fb) reinterpret_cast<uint32_t*>(a.out.fb)[o] = color_scale(rgba, bright);
-        if (a.out.palidx) a.out.palidx[o] = (uint8_t)pal_index;
-#elif PAR_EXP_STORE == 2  // (timing only: no palette-index store)
-        if (a.out.fb) __builtin_nontemporal_store(color_scale(rgba, bright), reinterpret_cast<uint32_t*>(a.out.fb) + o);
-        asm volatile("" ::"v"(pal_index));
-#elif PAR_EXP_STORE == 3  // (timing only: no frame store)
-        asm volatile("" ::"v"(rgba), "v"(bright));
-        if (a.out.palidx) __builtin_nontemporal_store((uint8_t)pal_index, a.out.palidx + o);
-#elif PAR_EXP_STORE == 4  // (plain frame store, streaming palette index)
-        if (a.out.fb) reinterpret_cast<uint32_t*>(a.out.fb)[o] = color_scale(rgba, bright);
-        if (a.out.palidx) __builtin_nontemporal_store((uint8_t)pal_index, a.out.palidx + o);
-#endif
         if (FULL && a.out.brightness) a.out.brightness[o] = bright;
         if (FULL && a.out.lit) a.out.lit[o] = lit_px ? 1 : 0;
         if (FULL && a.out.gbuf) {
@@ -1523,7 +1505,7 @@ __device__ __forceinline__ void render_chunk(const par_grid_dev& g, const par_re
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// render_column_generic: a column WITHOUT a usable record (it overflowed one, or PAR_FORCE_GENERIC=1): the whole
+// render_column_generic: a column WITHOUT a usable record (it overflowed one, or a test hook forces it): the whole
 // tile, 64 pixels per wavefront; chunk k belongs to wavefront k mod (max_parts * PAR_WAVE_NW) of the column's
 // workgroups. The primary pass reads the column's bins straight from the hash, as the reference does, and the shadow
 // walks are done in the kernel (render_chunk<true>). Only bx, by of the record are read.
@@ -1640,7 +1622,7 @@ __device__ __forceinline__ void render_item(const par_grid_dev& g, const par_ren
     }
     // ---- what the column's RECORD says (not needed for a simple column: its item says it all) ------------------
     ColumnRegs cr;
-    int n_entries_rec, n_nb;
+    int n_entries, n_nb;
     uint64_t dup;
     if (simple) {
         // one entry (every lane holds it; it is entry 0 of the list and the pass), the occupied bins bins.first ..
@@ -1649,7 +1631,7 @@ __device__ __forceinline__ void render_item(const par_grid_dev& g, const par_ren
         cr.ent = ib;
         cr.ebz = bz_first;
         cr.nb = make_uint2((uint32_t)(uint16_t)(bz_first + lane), 0u);  // lane n: bin first + n, walk [0, 0)
-        n_entries_rec = 1;
+        n_entries = 1;
         n_nb = bz_last - bz_first + 1;
         dup = 0;
     } else {
@@ -1660,7 +1642,7 @@ __device__ __forceinline__ void render_item(const par_grid_dev& g, const par_ren
         const uint4 h0 = ld_uniform(reinterpret_cast<const uint4*>(&rec_));
         const uint4 h1 = ld_uniform(reinterpret_cast<const uint4*>(&rec_) + 1);
         n_nb = (int)(int16_t)(h0.x & 0xFFFFu);
-        n_entries_rec = (int)(int16_t)(h0.x >> 16);
+        n_entries = (int)(int16_t)(h0.x >> 16);
         dup = ((uint64_t)h1.z << 32) | h1.y;
         if ((h0.y >> 16) != 0) return;  // overflow: render_overflow_kernel's
     }
@@ -1672,7 +1654,6 @@ __device__ __forceinline__ void render_item(const par_grid_dev& g, const par_ren
     if (!simple && lane < n_nb && (int)(int16_t)(cr.nb.y >> 16) > 0) {
         touched = *reinterpret_cast<const uint32_t*>(rec_.walk + (cr.nb.y & 0xFFFFu));
     }
-    const int n_entries = (fl & (1u << 24)) ? 0 : n_entries_rec;  // bit 24: ablation (timing only)
     const par_frame_dyn dyn = a.dyn_ptr ? ld_uniform(a.dyn_ptr) : a.dyn;  // (graph replay: uploaded before the frame)
     // (a simple column's only entry sits in every lane: it is read as entry 0 whatever its index in the record was)
     const int own = tile_mode ? -1 : (simple ? 0 : (int)pass);
@@ -1901,7 +1882,6 @@ __device__ __forceinline__ void render_tile_item(const par_grid_dev& g, const pa
             todo = __ballot(e_r0 <= box_r1) & __ballot(e_r1 > box_r0) & __ballot(e_q0 <= box_q1) &
                    __ballot(e_q1 > box_q0) & eligible;
         }
-        if (DBG && (fl & (1u << 24))) todo = 0;  // bit 24: ablation (timing only), no primary pass
         lanemask done = ~valid;                  // lanes that look at no further entry (alt:372-374, or no pixel)
         lanemask adj1 = 0;                       // adjacent == 1 (alt:282, 368)
         lanemask hit_bin = 0;                    // hit_in_bin (alt:303, 365)
@@ -2002,7 +1982,6 @@ __device__ __forceinline__ void render_tile_item(const par_grid_dev& g, const pa
         stamp(g, fl, 3, 2);  // (debug frames: the primary pass of this workgroup's first wavefront is done)
         // (a pixel was hit exactly when `closest` moved: the comparison alt:344 is strict)
         lanemask hit = __ballot(closest != INT_MIN) & valid;
-        if (DBG && (fl & (1u << 26))) hit = 0;  // bit 26: ablation (timing experiments only), no shading
         if (!hit) continue;
 
         // ---- shading, alt:704-758 ------------------------------------------------------------------------------
@@ -2093,9 +2072,7 @@ __device__ __forceinline__ void render_tile_item(const par_grid_dev& g, const pa
         }
         const bool lit_px = lane_of(lit);
         const float bright = lit_px ? b_lit : ambient;
-        if (DBG && (fl & (1u << 25))) {  // bit 25: ablation (timing only), no stores; keep the values alive
-            asm volatile("" ::"v"(ti.rgba), "v"(bright), "v"(pal_index));
-        } else if (is_hit) {  // (uncovered pixels keep what the fill wrote)
+        if (is_hit) {  // (uncovered pixels keep what the fill wrote)
             const uint32_t o = (uint32_t)(rowr * W + colr);  // (below 2^23: a tile has at most 160 rows)
             if (a.out.fb) __builtin_nontemporal_store(color_scale(ti.rgba, bright), reinterpret_cast<uint32_t*>(a.out.fb) + corner + o);
             if (a.out.palidx) __builtin_nontemporal_store((uint8_t)pal_index, a.out.palidx + corner + o);
@@ -2154,13 +2131,8 @@ __device__ __forceinline__ void render_items(const par_grid_dev& g, const par_re
     }
 }
 
-#if defined(PAR_RENDER_SGPRS)  // (experiments: cap the entry kernel's scalar registers, tools/debug/variants.sh)
-#define PAR_RENDER_ATTR __attribute__((amdgpu_num_sgpr(PAR_RENDER_SGPRS)))
-#else
-#define PAR_RENDER_ATTR
-#endif
 template <bool DBG, bool IDS, bool FULL>
-__global__ __launch_bounds__(PAR_WAVE_NW * 64) PAR_RENDER_ATTR void render_items_kernel(par_grid_dev g, par_render_args a) {
+__global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_items_kernel(par_grid_dev g, par_render_args a) {
     stamp(g, DBG ? a.flags : 0u, 3, 0);
     const unsigned long long core0 = DBG ? __builtin_amdgcn_s_memtime() : 0ull;
     __builtin_amdgcn_s_setprio(3);  // latency-bound wavefronts go before the streaming fill's when both want to issue
@@ -2201,7 +2173,7 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_tiles_kernel(par_grid
 }
 
 // The columns that overflowed their record (columns_kernel lists them), or every column when a.dense
-// (PAR_FORCE_GENERIC=1, tests): the primary pass reads the column's bins straight from the hash, as the reference
+// (a test hook): the primary pass reads the column's bins straight from the hash, as the reference
 // does, and the shadow walks are done here, once per wavefront and distinct start bin. A rare path: the launch is
 // small and its workgroups leave at once when the list is empty.
 __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_overflow_kernel(par_grid_dev g, par_render_args a) {
@@ -2322,13 +2294,8 @@ bool par_plan_fill(const par_render_args& a, par_fill_plan* plan) {
     plan->cut[0] = 0;
     // (Measured at 4096^2, three frames in flight: 0/0/100 % 36.5 us per frame, 10/10/80 35.7, 20/20/60 34.1,
     // 25/25/50 34.5, 33/33/33 34.0.)
-    // (PAR_TUNE_FILL_BUILD_PCT: the hash build's share in percent, tools/sweep.py; default 40, half of it per launch
-    // when the build takes two)
-    static const int build_pct = [] {
-        const char* e = std::getenv("PAR_TUNE_FILL_BUILD_PCT");
-        const int v = e ? std::atoi(e) : 40;
-        return v < 0 ? 0 : (v > 100 ? 100 : v);
-    }();
+    // The hash build's share in percent, half of it per launch when the build takes two.
+    constexpr int build_pct = 40;
     plan->cut[1] = (int)(chunks * build_pct / 200);
     plan->cut[2] = (int)(chunks * build_pct / 100);
     plan->cut[3] = (int)chunks;
@@ -2340,12 +2307,7 @@ bool par_plan_fill(const par_render_args& a, par_fill_plan* plan) {
 // kernels cannot use. Measured at 4096^2 (three frames in flight / one), workgroups in the insert and resolve
 // launches / in the column launch: 256 / 1024: 34.6 / 59.5 us, 128 / 512: 32.7 / 58.3, 64 / 256: 31.5 / 58.1,
 // 32 / 128: 33.1 / 66.8, 16 / 64: 40.7 / 94.7.
-// (PAR_TUNE_FILL_WGS overrides the 64, tools/sweep.py)
-static const int PAR_FILL_RIDE_WGS = [] {
-    const char* e = std::getenv("PAR_TUNE_FILL_WGS");
-    const int v = e ? std::atoi(e) : 64;
-    return v < 1 ? 1 : (v > 4096 ? 4096 : v);
-}();
+constexpr int PAR_FILL_RIDE_WGS = 64;
 static int64_t fill_blocks(const par_fill_plan& p, int i, int waves, int64_t cap) {
     const int64_t chunks = p.cut[i + 1] - p.cut[i];
     int64_t n = (chunks + waves - 1) / waves;
@@ -2434,23 +2396,17 @@ static int64_t column_blocks(const par_grid_dev& g, const par_render_args& a, in
 // full floor 330 against 346 us; the 480x320 graybox scene, 94 columns, 13.5 against 12.0 us: few columns need the
 // second wavefront for their walks even then.)
 static bool one_wave_per_column(const par_grid_dev& g, const par_render_args& a, int64_t column_bound) {
-    static const bool off = [] { const char* e = std::getenv("PAR_TUNE_NO_PIPELINED"); return e && e[0] == '1'; }();
     const int64_t cols_in_range = (int64_t)g.gx * (a.by_hi - a.by_lo + 1);
-    return !off && (a.flags & PAR_RENDER_PIPELINED) != 0 && std::min(column_bound, cols_in_range) >= 1024;
+    return (a.flags & PAR_RENDER_PIPELINED) != 0 && std::min(column_bound, cols_in_range) >= 1024;
 }
 
 // Wavefronts per column (columns_wave's ROLES): one for a frame among several in flight that fills the chip anyway;
 // otherwise the fewer columns a frame has, the more wavefronts share a column's walks -- a frame with a hundred columns
 // leaves the chip empty, and its columns' walks, one after the other in one or two wavefronts, are most of its
-// column launch (the 480x320 graybox world alone: 13.4 us with two wavefronts per column). PAR_TUNE_COL_ROLES
-// overrides (1, 2, 4 or 8; tools).
-static int column_roles(const par_grid_dev& g, const par_render_args& a, int64_t column_bound) {
-    static const int tuned = [] {
-        const char* e = std::getenv("PAR_TUNE_COL_ROLES");
-        const int v = e ? std::atoi(e) : 0;
-        return (v == 1 || v == 2 || v == 4 || v == 8) ? v : 0;
-    }();
-    if (tuned) return tuned;
+// column launch (the 480x320 graybox world alone: 13.4 us with two wavefronts per column). `forced` (1, 2, 4 or 8;
+// a test hook, par_debug_set_hooks) overrides; 0 keeps this choice.
+static int column_roles(const par_grid_dev& g, const par_render_args& a, int64_t column_bound, int forced) {
+    if (forced) return forced;
     if (one_wave_per_column(g, a, column_bound)) return 1;
     const int64_t cols_in_range = (int64_t)g.gx * (a.by_hi - a.by_lo + 1);
     const int64_t cols = std::min(column_bound, cols_in_range);
@@ -2483,9 +2439,9 @@ static hipError_t launch_columns_as(const par_grid_dev& g, const par_render_args
 }
 
 static hipError_t launch_columns(const par_grid_dev& g, const par_render_args& a, int64_t column_bound,
-                                 const par_fill_plan* fill, hipStream_t stream) {
+                                 const par_fill_plan* fill, int col_roles, hipStream_t stream) {
     hipError_t e;
-    switch (column_roles(g, a, column_bound)) {
+    switch (column_roles(g, a, column_bound, col_roles)) {
         case 1: e = launch_columns_as<1>(g, a, column_bound, fill, stream); break;
         case 4: e = launch_columns_as<4>(g, a, column_bound, fill, stream); break;
         case 8: e = launch_columns_as<8>(g, a, column_bound, fill, stream); break;
@@ -2496,15 +2452,15 @@ static hipError_t launch_columns(const par_grid_dev& g, const par_render_args& a
     return hipGetLastError();
 }
 
-hipError_t par_launch_columns(const par_grid_dev& g, const par_render_args& a, int64_t column_bound,
+hipError_t par_launch_columns(const par_grid_dev& g, const par_render_args& a, int64_t column_bound, int col_roles,
                               hipStream_t stream) {
-    return launch_columns(g, a, column_bound, nullptr, stream);
+    return launch_columns(g, a, column_bound, nullptr, col_roles, stream);
 }
 
 // Column records + the last share of the fill in one launch.
 hipError_t par_launch_columns_fill(const par_grid_dev& g, const par_render_args& a, int64_t column_bound,
-                                   const par_fill_plan& fill, hipStream_t stream) {
-    return launch_columns(g, a, column_bound, &fill, stream);
+                                   const par_fill_plan& fill, int col_roles, hipStream_t stream) {
+    return launch_columns(g, a, column_bound, &fill, col_roles, stream);
 }
 
 hipError_t par_launch_fill(const par_grid_dev& g, const par_render_args& a, hipStream_t stream) {
@@ -2548,25 +2504,11 @@ static int64_t item_workgroups(int64_t item_bound) {
     // Frames with very many items (dense scenes: 260 000 at 4096^2) are rendered by wavefronts that take several items
     // one after the other: launching a wavefront costs the chip more than its loop's extra iteration (full floor:
     // 382 us with one item per wavefront, 353 with 8, 347 with 16, 345 with 32), while a frame with few items needs
-    // every wavefront it can get (480x320 graybox, 2 400 items: 11.8 us with one, 16.7 with 4). PAR_TUNE_ITEMS_PER_WAVE
-    // overrides (tools).
-    static const int tuned = [] {
-        const char* e = std::getenv("PAR_TUNE_ITEMS_PER_WAVE");
-        const int v = e ? std::atoi(e) : 0;
-        return v < 0 ? 0 : (v > 64 ? 64 : v);
-    }();
-    int64_t per_wave = tuned > 0 ? tuned : item_bound / 16384;
+    // every wavefront it can get (480x320 graybox, 2 400 items: 11.8 us with one, 16.7 with 4).
+    int64_t per_wave = item_bound / 16384;
     if (per_wave < 1) per_wave = 1;
     if (per_wave > 16) per_wave = 16;
     item_bound = (item_bound + per_wave - 1) / per_wave;
-    // (PAR_TUNE_ITEM_WAVES_PCT, tools: more wavefronts than the bound asks for, in percent: a shard with more items than
-    // its share of the wavefronts makes some of them take two)
-    static const int pct = [] {
-        const char* e = std::getenv("PAR_TUNE_ITEM_WAVES_PCT");
-        const int v = e ? std::atoi(e) : 100;
-        return v < 50 ? 50 : (v > 400 ? 400 : v);
-    }();
-    item_bound = item_bound * pct / 100;
     int64_t waves = (item_bound + unit - 1) / unit * unit;
     if (waves < unit) waves = unit;
     if (waves > (int64_t)1 << 24) waves = (int64_t)1 << 24;  // (the wavefronts then loop over their shard)
@@ -2582,15 +2524,12 @@ hipError_t par_launch_render(const par_grid_dev& g, const par_render_args& a, in
     int64_t wgs = item_workgroups(item_bound);
     if (a.tile_k > 0 && wgs > 1024) wgs = 1024;
     const dim3 grid((unsigned)wgs), block(PAR_WAVE_NW * 64);
-    // (experiments: PAR_EXP_RENDER_LDS bytes of unused LDS per workgroup cap the workgroups per CU, i.e. the wavefront
-    // slots the entry kernel can hold: how much of the frame time is wavefront-slot time?)
-    static const unsigned lds = [] { const char* e = std::getenv("PAR_EXP_RENDER_LDS"); return e ? (unsigned)std::atoi(e) : 0u; }();
     if (a.flags & PAR_DEBUG_FLAGS) {
-        hipLaunchKernelGGL((render_items_kernel<true, true, true>), grid, block, lds, stream, g, a);
+        hipLaunchKernelGGL((render_items_kernel<true, true, true>), grid, block, 0, stream, g, a);
     } else if (a.sprite_ids || a.out.brightness || a.out.lit || a.out.gbuf) {
-        hipLaunchKernelGGL((render_items_kernel<false, true, true>), grid, block, lds, stream, g, a);
+        hipLaunchKernelGGL((render_items_kernel<false, true, true>), grid, block, 0, stream, g, a);
     } else {  // every entity uses sprite 0 (the reference's own scenes), RGBA + palette index only
-        hipLaunchKernelGGL((render_items_kernel<false, false, false>), grid, block, lds, stream, g, a);
+        hipLaunchKernelGGL((render_items_kernel<false, false, false>), grid, block, 0, stream, g, a);
     }
     return hipGetLastError();
 }
@@ -2776,8 +2715,8 @@ hipError_t par_launch_tiles_assemble(const int32_t* d_map, int gx, int W, int B,
     const int per_row = wide ? W / 4 : W;
     const unsigned bx = (unsigned)((per_row + 255) / 256);
     // each workgroup streams a few rows: about 2 048 workgroups write at the rate HBM takes
-    static const int target = [] { const char* e = std::getenv("PAR_TUNE_ASSEMBLE_WGS"); return e ? std::atoi(e) : 2048; }();
-    unsigned by = (unsigned)std::max(1, std::min(std::min(rows, 65535), (int)((unsigned)std::max(target, 1) / bx)));
+    constexpr unsigned target = 2048;
+    unsigned by = (unsigned)std::max(1, std::min(std::min(rows, 65535), (int)(target / bx)));
     if (wide) {
         hipLaunchKernelGGL(tiles_assemble_kernel<4>, dim3(bx, by), dim3(256), 0, stream, d_map, gx, W, B, row_begin, row_end,
                            static_cast<const uint32_t*>(packed), static_cast<uint32_t*>(frame), rgba, magic_b);

@@ -8,7 +8,7 @@
 //   par_pipeline [--size S] [--prims N] [--frames F] [--inflight K] [--threads T] [--moving] [--check] [--flags X]
 //                [--stamps F0] [--block K]
 //
-// --flags X: render flags for every frame (the timing-experiment bits of par_raytracer.h; the output is then wrong).
+// --flags X: render flags for every frame (par_raytracer.h; the library rejects undefined bits).
 // --stamps F0 (with PAR_DEBUG_STAMPS=1 in the environment): the K frames from F0 on note the GPU's 100 MHz clock at
 // every workgroup's start and end; afterwards the span of each of their kernels is printed (a timeline of the
 // frames in flight without a profiler in the way).

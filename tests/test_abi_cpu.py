@@ -20,6 +20,14 @@ def test_exports_every_declared_symbol(par):
         assert getattr(L, name) is not None
 
 
+def test_library_carries_no_tuning_or_test_switches(par):
+    """Launch shapes are constants of the library and test switches are per-context hooks (par_debug_set_hooks):
+    nothing in the shipped library reads an environment variable that changes how it renders."""
+    blob = open(par.LIB_PATH, "rb").read()
+    for name in (b"PAR_TUNE_", b"PAR_EXP_", b"PAR_TEST_", b"PAR_FORCE_GENERIC", b"PAR_BUILD_TWO_LAUNCHES"):
+        assert name not in blob, name
+
+
 def test_default_params_and_grid(par, T):
     p = T.Params()
     par.lib().par_default_params(ctypes.byref(p))

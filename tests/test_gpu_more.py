@@ -95,7 +95,7 @@ def test_overflowing_columns_take_the_overflow_kernel(par, oracle, sprite, T):
 def test_long_shadow_walks_overflow_the_stage(par, oracle, sprite, T):
     # a row of full bins between the primitives and the light: the walk from the far end collects more occluder
     # records (11 bins x 7) than a start bin's list (64) holds, so the pixels starting there trace their shadow
-    # rays with trace_hash_for_light as written, per lane (the column keeps its record); PAR_FORCE_GENERIC
+    # rays with trace_hash_for_light as written, per lane (the column keeps its record); the force-generic hook
     # (test_overflow_kernel_on_every_column) takes the same scene through the in-kernel stage, which overflows too
     w, h, l = 480, 320, 320
     params = T.default_params(w, h, l)
@@ -233,104 +233,74 @@ def test_host_demo_binary(par, oracle, T, tmp_path):
             np.array_equal(rgb[:, 2], fb["blue"]), f"frame {f}"
 
 
-def test_overflow_kernel_on_every_column(tmp_path):
-    """PAR_FORCE_GENERIC=1 sends every column through render_overflow_kernel (primary pass straight from the hash,
-    shadow walks in-kernel): the path overflowed columns take. Run in a fresh process (the switch is read once) and
-    compare with the oracle."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = r'''
-import importlib, sys
-sys.path.insert(0, %r)
-import numpy as np
-par = importlib.import_module("pixel-art-raytracer_amd"); T = par.types
-from oracle.oracle import Oracle
-o = Oracle(); sprite = par.tile_floor()
-ALL = ("fb", "gbuf", "palidx", "brightness", "lit")
-for (w, h, l, n, seed) in [(480, 320, 320, 300, 5), (512, 512, 512, 64, 12345), (500, 333, 290, 200, 1)]:
-    params = T.default_params(w, h, l)
-    aabbs, light = par.scene_synthetic(n, w, h, l, seed)
-    exp = o.render(params, aabbs, sprite, light)
+def test_overflow_kernel_on_every_column(par, oracle, sprite, T):
+    """The force-generic test hook sends every column through render_overflow_kernel (primary pass straight from the
+    hash, shadow walks in-kernel): the path overflowed columns take. Compared with the oracle."""
+    o = oracle
+    for (w, h, l, n, seed) in [(480, 320, 320, 300, 5), (512, 512, 512, 64, 12345), (500, 333, 290, 200, 1)]:
+        params = T.default_params(w, h, l)
+        aabbs, light = par.scene_synthetic(n, w, h, l, seed)
+        exp = o.render(params, aabbs, sprite, light)
+        with par.Renderer(params) as r:
+            r.set_test_hooks(force_generic=True)
+            r.set_scene(aabbs, sprite, light)
+            for planes in (ALL, ("fb", "palidx", "brightness", "gbuf")):
+                out = r.render(planes)
+                for k in planes:
+                    assert out[k].tobytes() == exp[k].tobytes(), (w, h, k)
+    rng = np.random.default_rng(7)
+    for case in range(24):
+        b = int(rng.choice([8, 16, 20, 32, 40, 40, 64]))
+        w, h, l = int(rng.integers(5, 80)) * 8, int(rng.integers(40, 400)), int(rng.integers(40, 400))
+        n = int(rng.integers(1, 300))
+        params = T.default_params(w, h, l, b)
+        aabbs, light = par.scene_synthetic(n, w, h, l, int(rng.integers(1, 1 << 30)))
+        if case % 3 == 1:
+            aabbs["px"] = (aabbs["px"] % max(2 * b, 40)).astype(aabbs["px"].dtype)
+            aabbs["pz"] = (aabbs["pz"] % max(3 * b, 60)).astype(aabbs["pz"].dtype)
+        if case % 4 == 2:
+            light = T.make_light(int(rng.integers(-100, w + 100)), int(rng.integers(-100, h + 100)), int(rng.integers(-100, l + 100)))
+        exp = o.render(params, aabbs, sprite, light)
+        with par.Renderer(params) as r:
+            r.set_test_hooks(force_generic=True)
+            r.set_scene(aabbs, sprite, light)
+            for planes in (("fb", "palidx"), ALL):
+                out = r.render(planes)
+                for k in planes:
+                    assert out[k].tobytes() == exp[k].tobytes(), (case, w, h, l, b, n, k)
+    aab = par.scene_graybox(); light = T.make_light(480, 160, 80); params = T.default_params()
+    exp = o.render(params, aab, sprite, light)
     with par.Renderer(params) as r:
-        r.set_scene(aabbs, sprite, light)
-        for planes in (ALL, ("fb", "palidx", "brightness", "gbuf")):
-            out = r.render(planes)
-            for k in planes:
-                assert out[k].tobytes() == exp[k].tobytes(), (w, h, k)
-rng = np.random.default_rng(7)
-for case in range(24):
-    b = int(rng.choice([8, 16, 20, 32, 40, 40, 64]))
-    w, h, l = int(rng.integers(5, 80)) * 8, int(rng.integers(40, 400)), int(rng.integers(40, 400))
-    n = int(rng.integers(1, 300))
-    params = T.default_params(w, h, l, b)
-    aabbs, light = par.scene_synthetic(n, w, h, l, int(rng.integers(1, 1 << 30)))
-    if case %% 3 == 1:
-        aabbs["px"] = (aabbs["px"] %% max(2 * b, 40)).astype(aabbs["px"].dtype)
-        aabbs["pz"] = (aabbs["pz"] %% max(3 * b, 60)).astype(aabbs["pz"].dtype)
-    if case %% 4 == 2:
-        light = T.make_light(int(rng.integers(-100, w + 100)), int(rng.integers(-100, h + 100)), int(rng.integers(-100, l + 100)))
-    exp = o.render(params, aabbs, sprite, light)
-    with par.Renderer(params) as r:
-        r.set_scene(aabbs, sprite, light)
-        for planes in (("fb", "palidx"), ALL):
-            out = r.render(planes)
-            for k in planes:
-                assert out[k].tobytes() == exp[k].tobytes(), (case, w, h, l, b, n, k)
-aab = par.scene_graybox(); light = T.make_light(480, 160, 80); params = T.default_params()
-exp = o.render(params, aab, sprite, light)
-with par.Renderer(params) as r:
-    r.set_scene(aab, sprite, light)
-    out = r.render(ALL)
-    for k in ALL:
-        assert out[k].tobytes() == exp[k].tobytes(), k
-print("generic ok")
-''' % root
-    env = dict(os.environ, PAR_FORCE_GENERIC="1")
-    p = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "generic ok" in p.stdout, p.stderr[-3000:]
+        r.set_test_hooks(force_generic=True)
+        r.set_scene(aab, sprite, light)
+        out = r.render(ALL)
+        for k in ALL:
+            assert out[k].tobytes() == exp[k].tobytes(), k
 
 
-def test_column_teams_of_every_size():
+def test_column_teams_of_every_size(par, oracle, sprite, T):
     """The column launch's workgroups are teams of 1, 2, 4 or 8 wavefronts per column, chosen by the frame's size and
-    by whether it is one of several in flight; PAR_TUNE_COL_ROLES forces one size (read once per process: a fresh
-    process per size). Every size on a crowded small view (the graybox world: walls of many occupied bins per column,
-    lists that wrap), a mid-size random view, long walks to a far light and columns at the edge of a record -- every
-    plane against the oracle."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = r'''
-import importlib, sys
-sys.path.insert(0, %r)
-import numpy as np
-par = importlib.import_module("pixel-art-raytracer_amd"); T = par.types
-from oracle.oracle import Oracle
-o = Oracle(); sprite = par.tile_floor()
-ALL = ("fb", "gbuf", "palidx", "brightness", "lit")
-scenes = [(T.default_params(), par.scene_graybox(), T.make_light(480, 160, 80))]
-for (w, h, l, n, seed, b) in [(640, 400, 400, 300, 3, 40), (1024, 768, 512, 400, 9, 40), (320, 200, 1600, 250, 4, 8)]:
-    a, li = par.scene_synthetic(n, w, h, l, seed)
-    scenes.append((T.default_params(w, h, l, b), a, li))
-# one screen column crowded with boxes along z (many occupied bins, many walks, lists near the record's limits)
-rows = [(200 + (i %% 2) * 10, 40, 10 + 36 * i, 20, 20, 20) for i in range(30)] + [(100, 100, 100, 20, 20, 20)]
-scenes.append((T.default_params(480, 320, 1200), T.make_aabbs(rows), T.make_light(470, 300, 1100)))
-for params, aabbs, light in scenes:
-    exp = o.render(params, aabbs, sprite, light, nthreads=8)
-    with par.Renderer(params) as r:
-        r.set_scene(aabbs, sprite, light)
-        for planes in (("fb", "palidx"), ALL):
-            out = r.render(planes)
-            for k in planes:
-                assert out[k].tobytes() == exp[k].tobytes(), (params.width, params.height, k)
-print("teams ok")
-''' % root
-    for roles in ("1", "2", "4", "8"):
-        env = dict(os.environ, PAR_TUNE_COL_ROLES=roles)
-        p = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
-        assert p.returncode == 0 and "teams ok" in p.stdout, (roles, p.stderr[-3000:])
+    by whether it is one of several in flight; the col_roles test hook forces one size. Every size on a crowded small
+    view (the graybox world: walls of many occupied bins per column, lists that wrap), a mid-size random view, long
+    walks to a far light and columns at the edge of a record -- every plane against the oracle."""
+    o = oracle
+    scenes = [(T.default_params(), par.scene_graybox(), T.make_light(480, 160, 80))]
+    for (w, h, l, n, seed, b) in [(640, 400, 400, 300, 3, 40), (1024, 768, 512, 400, 9, 40), (320, 200, 1600, 250, 4, 8)]:
+        a, li = par.scene_synthetic(n, w, h, l, seed)
+        scenes.append((T.default_params(w, h, l, b), a, li))
+    # one screen column crowded with boxes along z (many occupied bins, many walks, lists near the record's limits)
+    rows = [(200 + (i % 2) * 10, 40, 10 + 36 * i, 20, 20, 20) for i in range(30)] + [(100, 100, 100, 20, 20, 20)]
+    scenes.append((T.default_params(480, 320, 1200), T.make_aabbs(rows), T.make_light(470, 300, 1100)))
+    for roles in (1, 2, 4, 8):
+        for params, aabbs, light in scenes:
+            exp = o.render(params, aabbs, sprite, light, nthreads=8)
+            with par.Renderer(params) as r:
+                r.set_test_hooks(col_roles=roles)
+                r.set_scene(aabbs, sprite, light)
+                for planes in (("fb", "palidx"), ALL):
+                    out = r.render(planes)
+                    for k in planes:
+                        assert out[k].tobytes() == exp[k].tobytes(), (roles, params.width, params.height, k)
 
 
 def test_every_ray_traced_mode(par, oracle, sprite, T):
@@ -475,10 +445,10 @@ def test_config5_full_run_frames_in_flight(par, oracle, sprite, T):
         pipe.close()
 
 
-def test_graph_is_dropped_with_its_sprite_table_and_reports_allocation_failure(par, sprite, T, monkeypatch):
+def test_graph_is_dropped_with_its_sprite_table_and_bad_alloc_hook_gives_oom(par, sprite, T):
     """par_set_sprites frees the tables a captured graph's kernels point at: the graph must be gone afterwards
     (PAR_ERR_NOT_READY, not a read of freed memory). And a host allocation failure inside the library comes back as
-    PAR_ERR_OOM through the C ABI, never as an exception (PAR_TEST_BAD_ALLOC=1 makes the guarded bodies throw)."""
+    PAR_ERR_OOM through the C ABI, never as an exception (the bad-alloc test hook makes the guarded bodies throw)."""
     import torch
     params = T.default_params(256, 256, 256)
     aabbs, light = par.scene_synthetic(40, 256, 256, 256, 3)
@@ -493,14 +463,14 @@ def test_graph_is_dropped_with_its_sprite_table_and_reports_allocation_failure(p
         with pytest.raises(par.ParError) as e:
             r.graph_launch(stream.cuda_stream)
         assert e.value.status == 8  # PAR_ERR_NOT_READY
-        monkeypatch.setenv("PAR_TEST_BAD_ALLOC", "1")
+        r.set_test_hooks(bad_alloc=True)
         with pytest.raises(par.ParError) as e:
             r.set_entities(aabbs)
         assert e.value.status == 4  # PAR_ERR_OOM
         with pytest.raises(par.ParError) as e:
             r.set_sprites(sprite)
         assert e.value.status == 4
-        monkeypatch.delenv("PAR_TEST_BAD_ALLOC")
+        r.set_test_hooks()
         r.set_scene(aabbs, sprite, light)  # the context is still usable
         assert r.render(("fb",))["fb"].shape[0] == 256 * 256
 
@@ -925,12 +895,12 @@ def test_cpp_ranks_host_gathers_over_rccl(par, tmp_path, gather):
         assert 0 < line["tiles"] < 26 * 26
 
 
-def test_one_launch_hash_build_equals_two_launches(par, oracle, sprite, T):
+def test_one_launch_hash_build_equals_two_launch_and_record_item_hooks(par, oracle, sprite, T):
     """Small scenes build the spatial hash in ONE launch (insert, a barrier among the build workgroups, resolve)
     instead of two, and the work items of columns that hold one entity and cast no shadow on themselves carry all the
     render kernel needs (it never reads their record). A moving scene, 120 frames with the riding fill in the same
-    launches: every frame equals the same frame built with two launches (flag bit 23) and rendered through the
-    records only (flag bit 22), and every 20th the oracle's."""
+    launches: every frame equals the same frame built with two launches and rendered through the records only (test
+    hooks, switched between the frames of one context), and every 20th the oracle's."""
     import torch
     w, h, l = 1024, 768, 640
     params = T.default_params(w, h, l)
@@ -949,9 +919,12 @@ def test_one_launch_hash_build_equals_two_launches(par, oracle, sprite, T):
             aabbs["py"] += vel[:, 1]
             aabbs["pz"] += vel[:, 2]
             r.update_aabbs(aabbs, 0, stream=stream.cuda_stream)
-            r.render_device(ptrs[0], stream=stream.cuda_stream)                  # one launch
-            r.render_device(ptrs[1], stream=stream.cuda_stream, flags=1 << 23)   # two launches
-            r.render_device(ptrs[2], stream=stream.cuda_stream, flags=1 << 22)   # every work item through its record
+            r.render_device(ptrs[0], stream=stream.cuda_stream)  # one launch
+            r.set_test_hooks(two_launch_build=True)
+            r.render_device(ptrs[1], stream=stream.cuda_stream)  # two launches
+            r.set_test_hooks(record_items=True)
+            r.render_device(ptrs[2], stream=stream.cuda_stream)  # every work item through its record
+            r.set_test_hooks()
             stream.synchronize()
             for k in ("fb", "palidx"):
                 assert torch.equal(bufs[0][k], bufs[1][k]), f"frame {f} plane {k}: one-launch build differs"
@@ -962,46 +935,75 @@ def test_one_launch_hash_build_equals_two_launches(par, oracle, sprite, T):
                 assert np.array_equal(bufs[0]["palidx"].cpu().numpy(), exp["palidx"]), f"frame {f}"
 
 
-def test_device_failure_is_reported_through_the_abi():
+def test_lost_build_workgroup_hook_is_reported_through_the_abi(par, T):
     """A kernel-side failure surfaces as PAR_ERR_DEVICE, once, from the first call that waits for the device.
-    PAR_TEST_LOSE_BUILD_WG=1 (read once per process: fresh process) makes build workgroup 0 of the one-launch hash build
-    never arrive at its barrier; the others give up after their (shortened) bound, skip resolve and set the sticky
-    error word. The frame is then empty, and every entry point that synchronises says so."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = r'''
-import importlib, sys
-sys.path.insert(0, %r)
-import numpy as np, torch
-par = importlib.import_module("pixel-art-raytracer_amd"); T = par.types
-params = T.default_params(512, 512, 512)
-aabbs, light = par.scene_synthetic(64, 512, 512, 512, 12345)
-with par.Renderer(params) as r:
-    r.set_scene(aabbs, par.tile_floor(), light)
-    try:
-        r.render(("fb",))
-        raise SystemExit("par_render did not report the lost workgroup")
-    except par.ParError as e:
-        assert e.status == 9, e.status       # PAR_ERR_DEVICE
-    # the asynchronous entry point cannot see it; the next call that waits does, once
-    fb = torch.zeros(512 * 512 * 4, dtype=torch.uint8, device="cuda")
-    r.render_device({"fb": fb.data_ptr()}, stream=torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    try:
-        r.stats()
-        raise SystemExit("par_get_stats did not report the lost workgroup")
-    except par.ParError as e:
-        assert e.status == 9, e.status
-    st = r.stats()                            # reported once: the flag is clear again, no frame since
-    assert st.occupied_columns == 0           # (resolve was skipped: the failed frame is visibly empty)
-    assert not fb.cpu().numpy().reshape(-1, 4)[:, 3].any() and (fb.cpu().numpy().reshape(-1, 4)[:, 0] == 31).all()
-print("device error ok")
-''' % root
-    env = dict(os.environ, PAR_TEST_LOSE_BUILD_WG="1")
-    p = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "device error ok" in p.stdout, (p.stdout[-2000:], p.stderr[-3000:])
+    The lose-build-wg test hook (on a context of its own) makes build workgroup 0 of the one-launch hash build never
+    arrive at its barrier; the others give up after their (shortened) bound, skip resolve and set the sticky error
+    word. The frame is then empty, and every entry point that synchronises says so."""
+    import torch
+    params = T.default_params(512, 512, 512)
+    aabbs, light = par.scene_synthetic(64, 512, 512, 512, 12345)
+    with par.Renderer(params) as r:
+        r.set_test_hooks(lose_build_wg=True)
+        r.set_scene(aabbs, par.tile_floor(), light)
+        with pytest.raises(par.ParError) as e:
+            r.render(("fb",))
+        assert e.value.status == 9, e.value.status  # PAR_ERR_DEVICE
+        # the asynchronous entry point cannot see it; the next call that waits does, once
+        fb = torch.zeros(512 * 512 * 4, dtype=torch.uint8, device="cuda")
+        r.render_device({"fb": fb.data_ptr()}, stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        with pytest.raises(par.ParError) as e:
+            r.stats()
+        assert e.value.status == 9, e.value.status
+        st = r.stats()                            # reported once: the flag is clear again, no frame since
+        assert st.occupied_columns == 0           # (resolve was skipped: the failed frame is visibly empty)
+        assert not fb.cpu().numpy().reshape(-1, 4)[:, 3].any() and (fb.cpu().numpy().reshape(-1, 4)[:, 0] == 31).all()
+
+
+def test_undefined_render_flags_are_rejected(par, sprite, T):
+    """Every entry point that takes render flags refuses a bit outside the four public flags and the profiling time
+    stamps (bit 29) with PAR_ERR_INVALID_ARG, and accepts those."""
+    import ctypes as C
+    import torch
+    w = h = l = 256
+    params = T.default_params(w, h, l)
+    aabbs, light = par.scene_synthetic(40, w, h, l, 3)
+    dev = {"fb": torch.zeros(w * h * 4, dtype=torch.uint8, device="cuda"),
+           "lit": torch.zeros(w * h, dtype=torch.uint8, device="cuda")}
+    ptrs = {k: v.data_ptr() for k, v in dev.items()}
+    host = {"fb": np.zeros(w * h * 4, dtype=np.uint8), "lit": np.zeros(w * h, dtype=np.uint8)}
+    stream = torch.cuda.Stream()
+    s = stream.cuda_stream
+    L = par.lib()
+    with par.Renderer(params) as r:
+        r.set_scene(aabbs, sprite, light)
+        host_out = T.Outputs(host["fb"].ctypes.data, None, None, None, host["lit"].ctypes.data)
+        slot_args = ((C.c_void_p * 1)(r._ctx), (C.c_void_p * 1)(s), (T.Outputs * 1)(T.Outputs(ptrs["fb"], None, None, None, ptrs["lit"])))
+
+        def status(call):
+            try:
+                call()
+            except par.ParError as e:
+                return e.status
+            return 0
+
+        entry_points = {
+            "par_render": lambda f: L.par_render(r._ctx, C.byref(host_out), f),
+            "par_render_rows": lambda f: status(lambda: r.render(("fb", "lit"), rows=(8, 200), flags=f)),
+            "par_render_device": lambda f: status(lambda: r.render_device(ptrs, flags=f, stream=s)),
+            "par_render_device_timed": lambda f: status(lambda: r.render_device(ptrs, flags=f, stream=s, timed=True)),
+            "par_render_device_slots": lambda f: L.par_render_device_slots(*slot_args, 1, 0, h, 0, 2, f),
+            "par_graph_capture": lambda f: status(lambda: r.graph_capture(ptrs, flags=f, stream=s)),
+        }
+        for flags in (1 << 24, 1 << 22, 1 << 31):
+            for name, call in entry_points.items():
+                assert call(flags) == 1, (name, hex(flags))  # PAR_ERR_INVALID_ARG
+        for flags in (0xF, 1 << 29):
+            for name, call in entry_points.items():
+                assert call(flags) == 0, (name, hex(flags))
+        stream.synchronize()
+        r.stats()  # (no device error behind the accepted frames)
 
 
 @pytest.mark.parametrize("pairs", [30, 31, 32, 33, 34])

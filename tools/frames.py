@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Render N frames of one workload (for rocprofv3 --kernel-trace --stats / --pmc runs on the GPU box).
-usage: frames.py [synthetic|floor|graybox|small|trace_bg] [frames] [extra render flags, e.g. the ablation bits 24-28]"""
+usage: frames.py [synthetic|floor|graybox|small|trace_bg] [frames] [extra render flags, e.g. 2 = count rays]"""
 import importlib, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

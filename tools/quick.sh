@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: the C++ host loop on the three reference workloads, four frames in flight and one (us per frame).
-# usage: tools/quick.sh [tag]   (environment: PAR_TUNE_* as set by the caller)
+# usage: tools/quick.sh [tag]
 EXE=pixel-art-raytracer_amd/lib/par_pipeline
 tag=${1:-quick}
 for k in 4 1; do
