@@ -24,6 +24,9 @@ extern "C" {
 
 typedef struct par_context par_context;
 
+/* Most lights one frame can be rendered with (par_set_lights): the `lit` plane holds one bit per light. */
+#define PAR_MAX_LIGHTS 8
+
 typedef enum par_status {
     PAR_OK = 0,
     PAR_ERR_INVALID_ARG = 1, /* null pointer, negative size, rows out of range, ambient outside [0,1] ... */
@@ -65,7 +68,8 @@ typedef struct par_outputs {
     par_pixel* gbuf;   /* G-buffer, `p_pixel_buffer` alt:511,379 */
     uint8_t* palidx;   /* sprite palette index per pixel (alt:352-354), PAR_PALIDX_BACKGROUND where uncovered */
     float* brightness; /* pre-quantise brightness factor: ambient or min(1, diffuse + ambient), alt:735,757-758 */
-    uint8_t* lit;      /* 1 where trace_hash_for_light returned true (alt:738) */
+    uint8_t* lit;      /* bit l set where trace_hash_for_light returned true for light l (alt:738): 1 or 0 with one
+                        * light, a bitmask of the lights that reach the pixel with several (par_set_lights) */
 } par_outputs;
 
 typedef struct par_frame_stats {
@@ -125,8 +129,25 @@ int par_update_aabbs(par_context* ctx, const par_aabb* aabbs, int first, int n);
  * entities' extents allow wherever they stand, and always carry the launch for overflowed columns), until a blocking
  * call (par_update_aabbs, par_set_entities, the graph calls) brings the exact bookkeeping up to date. */
 int par_update_aabbs_async(par_context* ctx, const par_aabb* aabbs, int first, int n, void* stream);
-/* lights[0] (alt:712-714, 729-732: the only light the reference reads). */
+/* lights[0] (alt:712-714, 729-732: the only light the reference reads). The same as par_set_lights(ctx, light, 1): it
+ * also returns a context that had several lights to one. */
 int par_set_light(par_context* ctx, const par_light* light);
+/* All of the reference's `lights` (alt:619-626), 1 <= n <= PAR_MAX_LIGHTS; the array may be reused when the call
+ * returns. PAR_ERR_INVALID_ARG, before any device work, for a null context, a null `lights` with n > 0 or n outside
+ * [1, PAR_MAX_LIGHTS]. The primary pass and the G-buffer do not change. For each light l a covered pixel gets what the
+ * reference's shading loop (alt:703-742) gives it with lights[0] replaced by lights[l]: the L1-normalised direction
+ * t_l to the light (spr:28-35), lit_l = trace_hash_for_light from the pixel's bin towards light l's bin, and
+ * d_l = std::max(0.f, n . t_l) (the dot product summed left to right, no contraction, alt:745-747). Then
+ *     s = 0.f; for l = 0 .. n-1 (ascending): if lit_l, s = s + d_l      (fp32 additions, one after the other)
+ *     brightness = std::min(1.f, s + ambient);  fb = Color::operator*(color, brightness)  (spr:8-16, truncating)
+ *     lit plane: bit l set <=> lit_l
+ * With n = 1 this is the reference's formula exactly. A background pixel keeps its colour (its normal is zero); its lit
+ * bits are traced only when rays are asked for (PAR_RENDER_TRACE_BACKGROUND or a lit plane), each the reference's
+ * background ray towards light l. `radius` is not read. With PAR_RENDER_COUNT_RAYS, shadow_rays counts (pixel, light)
+ * rays. A frame with n >= 2 runs the hash build, the background fill and one render launch (the light kernel); a
+ * timed one reports the light kernel as ms_render and ms_launch[2] and 0 for the launches it does not have.
+ * par_graph_capture and par_graph_launch on a context with more than one light return PAR_ERR_UNSUPPORTED. */
+int par_set_lights(par_context* ctx, const par_light* lights, int n);
 
 /* --- render: replaces alt:690-760 ----------------------------------------------------------------------------- */
 
@@ -156,6 +177,7 @@ int par_render_device_timed(par_context* ctx, void* stream, int row_begin, int r
  * per frame. `par_graph_stage` writes the next frame's AABBs/light into the pinned staging area the graph copies
  * from; it fails with PAR_ERR_UNSUPPORTED when the staged scene needs larger launch grids than were captured (about
  * twice the bin insertions of the captured frame): capture again then. */
+/* A context with more than one light (par_set_lights) cannot be captured: PAR_ERR_UNSUPPORTED. */
 int par_graph_capture(par_context* ctx, void* stream, int row_begin, int row_end, const par_outputs* device_out,
                       unsigned flags);
 int par_graph_stage(par_context* ctx, const par_aabb* aabbs, int first, int n, const par_light* light);

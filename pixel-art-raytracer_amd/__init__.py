@@ -39,8 +39,9 @@ ABI_SYMBOLS = (
     "par_graph_capture", "par_graph_stage", "par_graph_launch", "par_pick", "par_get_stats", "par_read_grid",
     "par_sprite_tile_floor", "par_scene_graybox", "par_scene_synthetic", "par_debug_line", "par_debug_units",
     "par_render_device_slots", "par_row_block", "par_scene_tiles", "par_tiles_pack", "par_tiles_unpack",
-    "par_background_fill", "par_tiles_assemble", "par_scene_tile_map",
+    "par_background_fill", "par_tiles_assemble", "par_scene_tile_map", "par_set_lights",
 )
+MAX_LIGHTS = 8  # PAR_MAX_LIGHTS
 
 
 class ParError(RuntimeError):
@@ -98,6 +99,7 @@ def lib():
         L.par_update_aabbs.argtypes = [vp, vp, i32, i32]
         L.par_update_aabbs_async.argtypes = [vp, vp, i32, i32, vp]
         L.par_set_light.argtypes = [vp, vp]
+        L.par_set_lights.argtypes = [vp, vp, i32]
         L.par_render.argtypes = [vp, vp, C.c_uint]
         L.par_render_rows.argtypes = [vp, i32, i32, vp, C.c_uint]
         L.par_render_device.argtypes = [vp, vp, i32, i32, vp, C.c_uint]
@@ -258,6 +260,12 @@ class Renderer:
         light = np.ascontiguousarray(light, dtype=LIGHT)
         self._check(lib().par_set_light(self._ctx, ptr(light)))
 
+    def set_lights(self, lights):
+        """All lights of the scene (par_set_lights): a LIGHT array of 1 .. MAX_LIGHTS entries. Each covered pixel sums
+        the diffuse terms of the lights that reach it; bit l of the `lit` plane says whether light l does."""
+        lights = np.ascontiguousarray(lights, dtype=LIGHT)
+        self._check(lib().par_set_lights(self._ctx, ptr(lights), len(lights)))
+
     def set_scene(self, aabbs, sprites, light, sprite_ids=None):
         self.set_sprites(sprites)
         self.set_entities(aabbs, sprite_ids)
@@ -317,15 +325,15 @@ class Renderer:
         return st
 
     def set_test_hooks(self, force_generic=False, two_launch_build=False, record_items=False, lose_build_wg=False,
-                       bad_alloc=False, col_roles=0):
+                       bad_alloc=False, col_roles=0, lights_path=False):
         """Tests only (par_debug_set_hooks, not part of the public header): switches read by the frames enqueued from
         now on. force_generic: every column through the overflow kernel; two_launch_build: the hash build always takes
         two launches; record_items: every column rendered from its record; lose_build_wg: a build workgroup never
         arrives at the one-launch build's barrier (PAR_ERR_DEVICE); bad_alloc: the host-allocating entry points fail
-        with PAR_ERR_OOM; col_roles: 1, 2, 4 or 8 wavefronts per column (0: the library's choice). No arguments:
-        production behaviour."""
+        with PAR_ERR_OOM; col_roles: 1, 2, 4 or 8 wavefronts per column (0: the library's choice); lights_path: a
+        one-light frame takes the path of several lights (the light kernel). No arguments: production behaviour."""
         hooks = (int(force_generic) | int(two_launch_build) << 1 | int(record_items) << 2 | int(lose_build_wg) << 3 |
-                 int(bad_alloc) << 4)
+                 int(bad_alloc) << 4 | int(lights_path) << 5)
         self._check(lib().par_debug_set_hooks(self._ctx, hooks, col_roles))
 
     def read_grid(self):

@@ -58,7 +58,9 @@ struct par_context {
     int64_t cols_tileable = 0;
     int n_entities = 0, n_sprites = 0, max_sprite_id = 0;
     bool have_light = false, have_entities = false;
-    par_light light{};
+    par_light light{};                  // lights[0]: what the one-light kernels and the graph path read
+    par_light lights[PAR_MAX_LIGHTS]{};  // par_set_lights; n_lights >= 2 (or the test hook) takes the light kernel
+    int n_lights = 0;
     int set = 0;  // head/count/node set the NEXT frame uses
     hipStream_t last_stream = nullptr;  // stream of the most recent asynchronous render (scene updates wait for it)
     bool has_last_stream = false;
@@ -117,7 +119,8 @@ enum : unsigned {
     PAR_HOOK_RECORD_ITEMS = 1u << 2,   // columns emit no self-contained work items (PAR_FLAG_RECORD_ITEMS)
     PAR_HOOK_LOSE_BUILD_WG = 1u << 3,  // build workgroup 0 never arrives at the one-launch build's barrier
     PAR_HOOK_BAD_ALLOC = 1u << 4,      // the guarded host-allocating bodies fail as an exhausted heap would
-    PAR_HOOKS_ALL = (1u << 5) - 1
+    PAR_HOOK_LIGHTS_PATH = 1u << 5,    // a one-light frame takes the path of several lights (render_lights_kernel)
+    PAR_HOOKS_ALL = (1u << 6) - 1
 };
 
 namespace {
@@ -526,6 +529,51 @@ int check_device_error(par_context* ctx) {
     return fail(ctx, PAR_ERR_DEVICE, what + "a frame rendered since the last check is not valid");
 }
 
+// A frame takes the light kernel when it has several lights (or the test hook asks for it with one).
+bool lights_path(const par_context* c) { return c->n_lights > 1 || (c->hooks & PAR_HOOK_LIGHTS_PATH); }
+
+// A frame with several lights: the hash build, the background fill (after the background rays when they are wanted)
+// and one launch of the light kernel over the occupied columns. No column records, no work items, no overflow list.
+// Timed frames bracket the launches with the same events as enqueue_frame: the light kernel is ms_render and
+// ms_launch[2]; the other render launches it does not have are 0.
+int enqueue_lights_frame(par_context* ctx, hipStream_t stream, const par_bin_args& b, const par_render_args& r,
+                         unsigned flags, hipEvent_t* ev) {
+    par_lights_dyn lights{};
+    lights.n = ctx->n_lights;
+    for (int l = 0; l < ctx->n_lights; l++) lights.l[l] = make_dyn(ctx, ctx->lights[l]);
+    if (flags & PAR_RENDER_COUNT_RAYS) PAR_HIP(hipMemsetAsync(ctx->d_ray_counter, 0, sizeof(unsigned long long), stream));
+    const bool apart = ev && !(flags & PAR_RENDER_TIMED_AS_LAUNCHED);
+    const bool stale = ctx->exact_stale;
+    const int64_t pair_bound = stale ? ctx->bound_pairs : ctx->total_pairs;
+    if (ev) PAR_HIP(hipEventRecord(ev[0], stream));
+    const bool two_launches = apart || (ctx->hooks & PAR_HOOK_TWO_LAUNCHES);
+    const hipError_t be = two_launches ? hipErrorNotSupported : par_launch_build(ctx->grid, b, pair_bound, &r, nullptr, stream);
+    if (be == hipErrorNotSupported) {
+        PAR_HIP(par_launch_bin_insert(ctx->grid, b, &r, nullptr, stream));
+        PAR_HIP(par_launch_bin_resolve(ctx->grid, b, pair_bound, &r, nullptr, stream));
+    } else if (be != hipSuccess) {
+        return hip_fail(ctx, be, "par_launch_build");
+    }
+    if (ev) {
+        PAR_HIP(hipEventRecord(ev[5], stream));
+        PAR_HIP(hipEventRecord(ev[1], stream));
+    }
+    if (r.trace_bg) PAR_HIP(par_launch_bglights(ctx->grid, r, lights, stream));
+    PAR_HIP(par_launch_fill(ctx->grid, r, stream));
+    if (ev) PAR_HIP(hipEventRecord(ev[3], stream));
+    const int64_t col_bound = stale ? ctx->bound_cols : ctx->total_cols;
+    PAR_HIP(par_launch_render_lights(ctx->grid, r, lights, col_bound, stream));
+    if (ev) {
+        PAR_HIP(hipEventRecord(ev[6], stream));
+        PAR_HIP(hipEventRecord(ev[4], stream));
+        PAR_HIP(hipEventRecord(ev[2], stream));
+        ctx->timed_tiles = false;
+        ctx->timed_overflow = false;
+        ctx->timed_both = false;
+    }
+    return PAR_OK;
+}
+
 // Enqueue one frame (alt:690-760) on `stream` using grid set `set`.
 int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, int row_end, const par_outputs& out,
                   unsigned flags, bool graph_mode, hipEvent_t* ev) {
@@ -550,6 +598,7 @@ int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, 
     }
     const par_bin_args b = make_bin_args(ctx, set, row_begin, row_end, flags);
     par_render_args r = make_render_args(ctx, set, row_begin, row_end, outs, flags, graph_mode);
+    if (lights_path(ctx)) return enqueue_lights_frame(ctx, stream, b, r, flags, ev);
     // The overflow list is empty for sure while no column has more pairs than a record holds (a captured graph also
     // serves later frames, whose columns nobody knows yet): then the frame has no launch for it, and the column
     // kernel flags the frame should a column overflow all the same.
@@ -1034,11 +1083,20 @@ static int par_update_aabbs_async_impl(par_context* ctx, const par_aabb* aabbs, 
     return PAR_OK;
 }
 
-static int par_set_light_impl(par_context* ctx, const par_light* light) {
-    if (!ctx || !light) return fail(ctx, PAR_ERR_INVALID_ARG, "light");
-    ctx->light = *light;
+static int par_set_lights_impl(par_context* ctx, const par_light* lights, int n) {
+    if (!ctx) return PAR_ERR_INVALID_ARG;
+    if (n < 1 || n > PAR_MAX_LIGHTS) return fail(ctx, PAR_ERR_INVALID_ARG, "lights: n must lie in [1, PAR_MAX_LIGHTS]");
+    if (!lights) return fail(ctx, PAR_ERR_INVALID_ARG, "lights");
+    for (int l = 0; l < n; l++) ctx->lights[l] = lights[l];
+    ctx->n_lights = n;
+    ctx->light = lights[0];
     ctx->have_light = true;
     return PAR_OK;
+}
+
+static int par_set_light_impl(par_context* ctx, const par_light* light) {
+    if (!ctx || !light) return fail(ctx, PAR_ERR_INVALID_ARG, "light");
+    return par_set_lights_impl(ctx, light, 1);
 }
 
 static int par_render_impl(par_context* ctx, const par_outputs* host_out, unsigned flags) {
@@ -1115,6 +1173,7 @@ static int par_graph_capture_impl(par_context* ctx, void* stream_v, int row_begi
     if (rc != PAR_OK) return rc;
     rc = check_ready(ctx);
     if (rc != PAR_OK) return rc;
+    if (lights_path(ctx)) return fail(ctx, PAR_ERR_UNSUPPORTED, "a frame with several lights cannot be captured");
     PAR_HIP(hipSetDevice(ctx->device));
     PAR_HIP(hipDeviceSynchronize());
     drop_graphs(ctx);
@@ -1186,7 +1245,7 @@ static int par_graph_stage_impl(par_context* ctx, const par_aabb* aabbs, int fir
     }
     commit_update_totals(ctx, aabbs, first, n, plan);
     mark_staged(ctx, first, n);  // (the staging areas are brought up to date by par_graph_launch)
-    if (light) ctx->light = *light;
+    if (light) ctx->light = ctx->lights[0] = *light;
     return PAR_OK;
 }
 
@@ -1197,6 +1256,7 @@ static int par_graph_launch_impl(par_context* ctx, void* stream) {
     if (ctx->total_pairs > ctx->graph_pair_bound) {
         return fail(ctx, PAR_ERR_UNSUPPORTED, "the scene exceeds what the captured graph was sized for; capture again");
     }
+    if (ctx->n_lights > 1) return fail(ctx, PAR_ERR_UNSUPPORTED, "a frame with several lights has no graph");
     const int s = ctx->set;
     if (!ctx->graph_exec[s]) return fail(ctx, PAR_ERR_NOT_READY, "no captured graph for this grid set");
     PAR_HIP(hipSetDevice(ctx->device));
@@ -1443,6 +1503,9 @@ int par_create(const par_params* params, int device, par_context** out) {
 
 int par_set_light(par_context* ctx, const par_light* light) {
     return guarded(ctx, [&] { return par_set_light_impl(ctx, light); });
+}
+int par_set_lights(par_context* ctx, const par_light* lights, int n) {
+    return guarded(ctx, [&] { return par_set_lights_impl(ctx, lights, n); });
 }
 int par_render(par_context* ctx, const par_outputs* host_out, unsigned flags) {
     return guarded(ctx, [&] { return par_render_impl(ctx, host_out, flags); });

@@ -112,6 +112,13 @@ struct par_frame_dyn {
     int32_t lbx, lby, lbz;  // its bin (alt:729-732)
 };
 
+// The lights of a frame with several (par_set_lights): each light's position and bin, as par_frame_dyn holds them for
+// the one light of the other kernels. A kernel argument of the light kernels.
+struct par_lights_dyn {
+    int32_t n;  // 1 .. PAR_MAX_LIGHTS
+    par_frame_dyn l[PAR_MAX_LIGHTS];
+};
+
 // Render flags that make the render launch use its instrumented variant (ray counting and the time stamps, bit 29);
 // a production frame has neither and runs kernels compiled without them.
 constexpr uint32_t PAR_DEBUG_FLAGS = PAR_RENDER_COUNT_RAYS | (1u << 29);
@@ -254,6 +261,16 @@ hipError_t par_launch_render_both(const par_grid_dev& g, const par_render_args& 
 // The columns that overflowed their record (every column when a.dense).
 hipError_t par_launch_render_overflow(const par_grid_dev& g, const par_render_args& a, int64_t column_bound,
                                       hipStream_t stream);
+
+// A frame with several lights (or one, forced by a test hook): after the hash build, every occupied column of col_list
+// in one launch of render_lights_kernel (`column_bound` as for par_launch_columns). The column, item, tile and overflow
+// kernels do not run.
+hipError_t par_launch_render_lights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,
+                                    int64_t column_bound, hipStream_t stream);
+// The background rays of such a frame (one per x and light, bit l of g.bglit[x] for light l); par_launch_fill then
+// copies them into the lit plane.
+hipError_t par_launch_bglights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,
+                               hipStream_t stream);
 
 // Sharded frames: tiles between a frame block and packed slots, and the background colour for whole rows.
 hipError_t par_launch_tiles_copy(bool pack, const int32_t* d_tiles, int n, int W, int H, int B, int row_begin, int row_end,

@@ -2227,6 +2227,243 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_both_kernel(par_grid_
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// render_lights_kernel: a frame with several lights (par_set_lights; one, by a test hook). ONE workgroup per occupied
+// column of col_list, no column record, no work items:
+//   A. the column's occupied bins (a scan of `count` along z), and from each of them the walk towards EVERY light's
+//      bin (wave_walk), the (bin, light) pairs dealt to the workgroup's wavefronts; the occluder records go into the
+//      workgroup's walk area, handed out walk by walk (a walk that does not fit is "not recorded");
+//   B. the column's tile, 64 pixels per wavefront: the primary pass straight from the hash (as render_chunk<GENERIC>),
+//      then per light the slab tests of the recorded walk of the pixel's start bin, or lane_shadow_walk where there is
+//      none (the start bin holds no primitive, or its walk did not fit), and the shading of the contract in
+//      par_raytracer.h (par_set_lights). Each walk is done once per column and light.
+// ------------------------------------------------------------------------------------------------------------
+constexpr int PAR_LIGHT_NB = 64;      // occupied bins of a column whose walks are recorded (the others: lane walks)
+constexpr int PAR_LIGHT_WALK = 1024;  // occluder records of all walks of a column (16 KiB)
+struct LightCol {  // LDS of one workgroup of render_lights_kernel
+    int32_t n_nb;         // occupied bins of the column (all of them; the first PAR_LIGHT_NB found are recorded)
+    int32_t walk_used;    // records of the walk area handed out so far
+    int16_t nb_bz[PAR_LIGHT_NB];
+    int16_t zslot[PAR_MAX_GRID_DIM];  // bin z -> its index in nb_bz, -1: no recorded walks start there
+    int16_t woff[PAR_LIGHT_NB * PAR_MAX_LIGHTS];  // walk of (bin i, light l) at [i * n + l]: walk[woff, woff + wcnt)
+    int16_t wcnt[PAR_LIGHT_NB * PAR_MAX_LIGHTS];  // -1: not recorded
+    par_slot walk[PAR_LIGHT_WALK];
+    par_slot stage[PAR_WAVE_NW][PAR_BIN_WALK];    // each wavefront's walk being done
+};
+static_assert(PAR_LIGHT_WALK <= 32767 && PAR_MAX_LIGHTS <= 8, "int16 walk offsets, one lit bit per light");
+
+__global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_grid_dev g, par_render_args a,
+                                                                            par_lights_dyn lights) {
+    __shared__ LightCol sh;
+    const int lane = (int)threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int n_lights = lights.n;
+    const int n_cols = g.counters[PAR_CNT_COLS];
+    const int W = a.W, H = a.H, B = a.B;
+    const float ambient = a.ambient;
+    const int32_t* depth0 = a.sprites[0].depth;
+    const bool has_ids = a.sprite_ids != nullptr;
+    for (int ci = (int)blockIdx.x; ci < n_cols; ci += (int)gridDim.x) {
+        const int col = g.col_list[ci];
+        const int bx = col / g.gy, by = col - bx * g.gy;
+        const int col_base = flat_index(g.gy, g.gz, bx, by, 0);
+        // ---- A: occupied bins, then the walks ---------------------------------------------------------------
+        __syncthreads();  // (the previous column's pixels are done with the LDS)
+        if (threadIdx.x == 0) {
+            sh.n_nb = 0;
+            sh.walk_used = 0;
+        }
+        for (int z = (int)threadIdx.x; z < g.gz; z += (int)blockDim.x) sh.zslot[z] = -1;
+        __syncthreads();
+        for (int z = (int)threadIdx.x; z < g.gz; z += (int)blockDim.x) {
+            if (a.count[col_base + z] != 0) {
+                const int i = atomicAdd(&sh.n_nb, 1);
+                if (i < PAR_LIGHT_NB) {
+                    sh.nb_bz[i] = (int16_t)z;
+                    sh.zslot[z] = (int16_t)i;
+                }
+            }
+        }
+        __syncthreads();
+        const int n_rec_nb = min(sh.n_nb, PAR_LIGHT_NB);
+        for (int p = wave; p < n_rec_nb * n_lights; p += PAR_WAVE_NW) {
+            const int i = p / n_lights, l = p - i * n_lights;
+            par_slot* stage = sh.stage[wave];
+            const int n_rec = wave_walk(g, a.count, a.slots, lights.l[l], bx, by, sh.nb_bz[i], stage);
+            int at = -1;
+            if (n_rec >= 0) {
+                if (lane == 0) at = atomicAdd(&sh.walk_used, n_rec);
+                at = wave_bcast(at, 0);
+                if (at + n_rec > PAR_LIGHT_WALK) at = -1;
+            }
+            if (at >= 0) {
+                for (int r = lane; r < n_rec; r += 64) sh.walk[at + r] = stage[r];
+            }
+            if (lane == 0) {
+                sh.woff[p] = (int16_t)max(at, 0);
+                sh.wcnt[p] = (int16_t)(at >= 0 ? n_rec : -1);
+            }
+            wave_lds_fence();  // (every lane has read the stage before the next walk overwrites it)
+        }
+        __syncthreads();
+
+        // ---- B: the column's tile, 64 pixels per wavefront --------------------------------------------------
+        const int c0 = bx * B;
+        const int rw = min(B, W - c0);
+        const int ry0 = max(by * B, a.row_begin), rows_hi = min(min((by + 1) * B, H), a.row_end);
+        const int rh = rows_hi - ry0;
+        if (rw <= 0 || rh <= 0) continue;
+        const int area = rw * rh;
+        const int n_chunks = (area + 63) >> 6;
+        const uint32_t magic_w = (uint32_t)(0xFFFFFFFFu / (uint32_t)rw) + 1u;
+        for (int c = wave; c < n_chunks; c += PAR_WAVE_NW) {
+            const int pidx = c * 64 + lane;
+            const int pyy = (rw == 1) ? pidx : (int)__umulhi((uint32_t)pidx, magic_w);
+            const int px_col = c0 + (pidx - pyy * rw), row = ry0 + pyy;
+            const bool valid = pidx < area;
+            // primary ray, alt:271-397: the column's bins as they lie in the hash (render_chunk<GENERIC>)
+            bool hit = false;
+            int p_entity = 0, p_y = 0, p_z = 0, p_tex = 0;
+            {
+                const int world_j = (int)(int16_t)(H - row);  // alt:280
+                int adjacent = 0;                             // alt:282
+                int closest = INT_MIN;                        // alt:289
+                int cur_bz = -2;
+                bool hit_in_bin = false;
+                bool done = !valid;
+                int w_ybase = 0, w_pz = 0, w_d = 0;
+                for (int bz = 0; bz < g.gz; bz++) {
+                    const int cnt = a.count[col_base + bz];  // (wave-uniform)
+                    if (cnt == 0) continue;
+                    adjacent += hit_in_bin ? 1 : 0;      // alt:368
+                    if (adjacent >= 2) done = true;      // alt:372-374
+                    if (bz != cur_bz + 1) adjacent = 0;  // an empty bin lies in between (alt:298-300)
+                    cur_bz = bz;
+                    hit_in_bin = false;
+                    if (__all(done)) break;
+                    for (int k = 0; k < cnt; k++) {
+                        const par_slot rec = a.slots[(size_t)(col_base + bz) * PAR_SLOTS + k];
+                        const int top = rec.py + rec.ey + rec.pz + rec.ez;
+                        const bool inside = (!done) & (px_col >= rec.px) & (px_col < rec.px + rec.ex) &
+                                            (world_j > rec.py + rec.pz) & (world_j <= top);  // alt:310-317
+                        if (inside) {
+                            const int sprite_row = top - world_j;                       // alt:324-326
+                            const int t = sprite_row * PAR_SPRITE_W + (px_col - rec.px);  // alt:330-332
+                            const int sid = has_ids ? a.sprite_ids[rec.entity] : 0;     // alt:321-322
+                            const int d = (sid == 0) ? depth0[t] : a.sprites[sid].depth[t];
+                            const int depth = rec.py - rec.pz + min(0, rec.ey - sprite_row) - d;  // alt:336-341
+                            if (closest < depth) {                                      // alt:344-346
+                                closest = depth;
+                                w_ybase = rec.py + rec.ey + rec.ez - sprite_row;        // alt:356-359
+                                w_pz = rec.pz;                                          // alt:360-361
+                                w_d = d;
+                                p_entity = rec.entity;                                  // alt:363
+                                p_tex = sid * PAR_SPRITE_TEXELS + t;
+                                hit = true;
+                                hit_in_bin = true;                                      // alt:365
+                            }
+                        }
+                    }
+                }
+                if (hit) {
+                    p_y = w_ybase - w_d;
+                    p_z = w_pz + w_d;
+                }
+            }
+            // shading, alt:704-758, one shadow ray per light
+            float nx = 0.f, ny = 0.f, nz = 0.f, bright = ambient;
+            uint32_t rgba = 0, lit_mask = 0;
+            int pal_index = PAR_PALIDX_BACKGROUND;
+            if (hit) {
+                const par_texel ti = a.texinfo[p_tex];  // normal (alt:349-350) + palette colour (alt:352-354)
+                nx = ti.nx; ny = ti.ny; nz = ti.nz;
+                rgba = ti.rgba;
+                if (a.out.palidx) {
+                    const int sid = p_tex / PAR_SPRITE_TEXELS;
+                    pal_index = a.sprites[sid].color[p_tex - sid * PAR_SPRITE_TEXELS];
+                }
+                // the start bin (alt:724-727): its row is this column's (render_chunk), its depth bin(z)
+                const int sz = div_bin(p_z, a.magic_b);
+                const int ox = (int)(int16_t)px_col, oy = (int)(int16_t)p_y, oz = (int)(int16_t)p_z;  // alt:720-722
+                const int zs = (sz >= 0 && sz < g.gz) ? (int)sh.zslot[sz] : -1;
+                float s = 0.f;
+                for (int l = 0; l < n_lights; l++) {
+                    const par_frame_dyn& dyn = lights.l[l];
+                    // towards_light = normalize_L1(light - world), alt:711-715 + spr:28-35
+                    const float dx = (float)(dyn.lx - px_col), dy = (float)(dyn.ly - p_y), dz = (float)(dyn.lz - p_z);
+                    float tx, ty, tz, inv_x, inv_y, inv_z;
+                    normalize_l1_and_inverse(dx, dy, dz, tx, ty, tz, inv_x, inv_y, inv_z);  // alt:711-719
+                    const float dot = nx * tx + ny * ty + nz * tz;  // alt:746-747 (no contraction)
+                    const float diffuse = std_max(0.f, dot);        // alt:745
+                    bool lit = true;
+                    const int wc = zs >= 0 ? (int)sh.wcnt[zs * n_lights + l] : -1;
+                    if (wc >= 0) {
+                        const int wo = sh.woff[zs * n_lights + l];
+                        for (int r = 0; r < wc; r++) {
+                            const par_slot rec = sh.walk[wo + r];
+                            if (rec.entity != p_entity && slab_hit(rec, ox, oy, oz, inv_x, inv_y, inv_z)) {  // alt:484-491
+                                lit = false;
+                                break;
+                            }
+                        }
+                    } else {  // no recorded walk: trace_hash_for_light as written, per lane
+                        lit = lane_shadow_walk(g, a.count, a.slots, bx, by, sz, dyn, p_entity, ox, oy, oz, inv_x,
+                                               inv_y, inv_z);
+                    }
+                    if (lit) {
+                        s = s + diffuse;
+                        lit_mask |= 1u << l;
+                    }
+                }
+                bright = std_min(1.f, s + ambient);
+            }
+            if ((a.flags & PAR_RENDER_COUNT_RAYS) && a.ray_counter) {
+                const unsigned long long m = __ballot(valid && hit);
+                if (lane == 0 && m) atomicAdd(a.ray_counter, (unsigned long long)__popcll(m) * (unsigned)n_lights);
+            }
+            // quantise + store, alt:735, 757-758 (uncovered pixels keep what the fill wrote)
+            if (valid && hit) {
+                const size_t o = (size_t)(row - a.row_begin) * W + px_col;
+                if (a.out.fb) reinterpret_cast<uint32_t*>(a.out.fb)[o] = color_scale(rgba, bright);
+                if (a.out.palidx) a.out.palidx[o] = (uint8_t)pal_index;
+                if (a.out.brightness) a.out.brightness[o] = bright;
+                if (a.out.lit) a.out.lit[o] = (uint8_t)lit_mask;
+                if (a.out.gbuf) {
+                    par_pixel pxl;
+                    pxl.normal = par_vec3{nx, ny, nz};
+                    pxl.color.red = (uint8_t)(rgba & 0xFF);
+                    pxl.color.green = (uint8_t)((rgba >> 8) & 0xFF);
+                    pxl.color.blue = (uint8_t)((rgba >> 16) & 0xFF);
+                    pxl.color.alpha = (uint8_t)(rgba >> 24);
+                    pxl.y = p_y;
+                    pxl.z = p_z;
+                    pxl.entity_index = p_entity;
+                    a.out.gbuf[o] = pxl;
+                }
+            }
+        }
+    }
+}
+
+// The background rays of a frame with several lights (bgline_kernel's, once per light): bit l of bglit[x] is the
+// shadow ray of a background pixel of screen column x towards light l, traced per lane as the reference writes it.
+__global__ __launch_bounds__(256) void bglights_kernel(par_grid_dev g, par_render_args a, par_lights_dyn lights) {
+    const int x = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (x >= a.W) return;
+    const int ox = (int)(int16_t)x;                        // alt:720-722
+    const int bx = div_bin(x, a.magic_b), sy = a.H / a.B;  // alt:724-727
+    uint32_t mask = 0;
+    for (int l = 0; l < lights.n; l++) {
+        const par_frame_dyn& dyn = lights.l[l];
+        // towards_light = normalize_L1(light - (x, 0, 0)), alt:711-715 + spr:28-35
+        const float dx = (float)(dyn.lx - x), dy = (float)(dyn.ly - 0), dz = (float)(dyn.lz - 0);
+        float tx, ty, tz, inv_x, inv_y, inv_z;
+        normalize_l1_and_inverse(dx, dy, dz, tx, ty, tz, inv_x, inv_y, inv_z);  // alt:711-719
+        if (lane_shadow_walk(g, a.count, a.slots, bx, sy, 0, dyn, 0, ox, 0, 0, inv_x, inv_y, inv_z)) mask |= 1u << l;
+    }
+    g.bglit[x] = (uint8_t)mask;
+}
+
 // Test hook (par_debug_units): the device functions of the reference's three arithmetic units on caller-supplied
 // vectors, one element per thread. kind 0: AABB::intersect alt:40-83 (a: par_aabb, b: {float inv[3]; int16 origin[3]}
 // -> u8 hit; 3, 4: the same on a walk record, as the render kernel tests it); 1: Color::operator* spr:8-16 (a: float r, g, b, a, v -> u8[4]); 2: Vector::normalize spr:28-35
@@ -2604,6 +2841,22 @@ hipError_t par_launch_render_overflow(const par_grid_dev& g, const par_render_ar
     // overflowed columns are the exception: a small strided grid (up to 8 workgroups share a column)
     const int64_t oblocks = a.dense ? (bound < 1024 ? bound : 1024) : (bound < 32 ? bound : 32);
     hipLaunchKernelGGL(render_overflow_kernel, dim3((unsigned)oblocks, 8u), dim3(PAR_WAVE_NW * 64), 0, stream, g, a);
+    return hipGetLastError();
+}
+
+hipError_t par_launch_render_lights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,
+                                    int64_t column_bound, hipStream_t stream) {
+    const int64_t cols_in_range = (int64_t)g.gx * (a.by_hi - a.by_lo + 1);
+    int64_t n = column_bound < cols_in_range ? column_bound : cols_in_range;
+    if (n <= 0) return hipSuccess;
+    if (n > 65536) n = 65536;  // (the workgroups then stride over the column list)
+    hipLaunchKernelGGL(render_lights_kernel, dim3((unsigned)n), dim3(PAR_WAVE_NW * 64), 0, stream, g, a, lights);
+    return hipGetLastError();
+}
+
+hipError_t par_launch_bglights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,
+                               hipStream_t stream) {
+    hipLaunchKernelGGL(bglights_kernel, dim3((unsigned)((a.W + 255) / 256)), dim3(256), 0, stream, g, a, lights);
     return hipGetLastError();
 }
 

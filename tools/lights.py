@@ -1,0 +1,100 @@
+"""Microseconds per frame with N = 1, 2, 4, 8 lights (par_set_lights) on the graybox world at 480x320 and on the 4096^2
+view with 1024 primitives: one frame alone (par_render_device_timed, the span of its launches, median) and four frames
+in flight (par_render_device_slots, wall time per frame). Also N = 1 forced through the light kernel (test hook
+lights_path) and through the overflow kernel on every column (force_generic), the two paths whose walks it replaces.
+Prints one JSON line.   python tools/lights.py [frames]"""
+import importlib
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+par = importlib.import_module("pixel-art-raytracer_amd")
+T = importlib.import_module("pixel-art-raytracer_amd.types")
+pipeline = importlib.import_module("pixel-art-raytracer_amd.pipeline")
+
+FRACTIONS = [(5 / 8, 1 / 2, 1 / 4), (1 / 8, 3 / 4, 1 / 16), (15 / 16, 1 / 16, 7 / 8), (1 / 2, 3 / 8, 1 / 2),
+             (1 / 4, 1 / 4, 3 / 4), (3 / 4, 5 / 8, 1 / 8), (1 / 16, 1 / 8, 1 / 2), (7 / 8, 7 / 8, 15 / 16)]
+
+
+def lights_for(params, n):
+    a = np.zeros(n, dtype=T.LIGHT)
+    for i, (fx, fy, fz) in enumerate(FRACTIONS[:n]):
+        a[i]["x"], a[i]["y"], a[i]["z"] = int(params.width * fx), int(params.height * fy), int(params.length * fz)
+        a[i]["radius"] = 10
+    return a
+
+
+def configure(r, lights, mode):
+    r.set_lights(lights)
+    r.set_test_hooks(lights_path=(mode == "kernel"), force_generic=(mode == "generic"))
+
+
+def alone_us(params, aabbs, sprite, lights, mode, frames):
+    with par.Renderer(params, 0) as r:
+        r.set_scene(aabbs, sprite, lights[0:1])
+        configure(r, lights, mode)
+        fb = torch.zeros(params.width * params.height * 4, dtype=torch.uint8, device="cuda")
+        pal = torch.zeros(params.width * params.height, dtype=torch.uint8, device="cuda")
+        ptrs = {"fb": fb.data_ptr(), "palidx": pal.data_ptr()}
+        spans = []
+        for i in range(frames + 3):
+            st = r.render_device(ptrs, timed=True, flags=par.RENDER_TIMED_AS_LAUNCHED)
+            if i >= 3:
+                spans.append(1000.0 * sum(v for v in st.ms_launch if v > 0))
+        return round(statistics.median(spans), 1)
+
+
+def inflight_us(params, aabbs, sprite, lights, mode, frames):
+    pipe = pipeline.FramePipeline(params, aabbs, sprite, lights[0:1], depth=4)
+    try:
+        for s in pipe.slots:
+            configure(s.renderer, lights, mode)
+        pipe.submit_many(0, 8)
+        pipe.synchronize()
+        best = None
+        for _ in range(3):
+            t0 = time.perf_counter()
+            pipe.submit_many(0, frames)
+            pipe.synchronize()
+            us = (time.perf_counter() - t0) * 1e6 / frames
+            best = us if best is None else min(best, us)
+        for s in pipe.slots:
+            s.renderer.stats()  # PAR_ERR_DEVICE raises
+        return round(best, 1)
+    finally:
+        pipe.close()
+
+
+def main():
+    frames = int(sys.argv[1]) if len(sys.argv) > 1 else 40
+    sprite = par.tile_floor()
+    scenes = {}
+    p = T.default_params()
+    scenes["graybox_480x320"] = (p, par.scene_graybox(480, 320))
+    p = T.default_params(4096, 4096, 4096)
+    scenes["synthetic_4096_1024"] = (p, par.scene_synthetic(1024, 4096, 4096, 4096, 12345)[0])
+    out = {"tool": "lights", "frames": frames, "us_per_frame": {}}
+    for name, (params, aabbs) in scenes.items():
+        res = {}
+        for n in (1, 2, 4, 8):
+            lights = lights_for(params, n)
+            res[f"n{n}"] = {"alone": alone_us(params, aabbs, sprite, lights, "auto", frames),
+                            "inflight4": inflight_us(params, aabbs, sprite, lights, "auto", frames)}
+        lights = lights_for(params, 1)
+        for mode in ("kernel", "generic"):
+            res[f"n1_{mode}"] = {"alone": alone_us(params, aabbs, sprite, lights, mode, frames),
+                                 "inflight4": inflight_us(params, aabbs, sprite, lights, mode, frames)}
+        out["us_per_frame"][name] = res
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
