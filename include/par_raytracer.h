@@ -146,7 +146,8 @@ int par_set_light(par_context* ctx, const par_light* light);
  * background ray towards light l. `radius` is not read. With PAR_RENDER_COUNT_RAYS, shadow_rays counts (pixel, light)
  * rays. A frame with n >= 2 runs the hash build, the background fill and one render launch (the light kernel); a
  * timed one reports the light kernel as ms_render and ms_launch[2] and 0 for the launches it does not have.
- * par_graph_capture and par_graph_launch on a context with more than one light return PAR_ERR_UNSUPPORTED. */
+ * par_graph_capture and par_graph_launch (on a one-light graph) on a context with more than one light return
+ * PAR_ERR_UNSUPPORTED; par_graph_capture_lights captures the frame of several lights. */
 int par_set_lights(par_context* ctx, const par_light* lights, int n);
 
 /* --- render: replaces alt:690-760 ----------------------------------------------------------------------------- */
@@ -177,11 +178,35 @@ int par_render_device_timed(par_context* ctx, void* stream, int row_begin, int r
  * per frame. `par_graph_stage` writes the next frame's AABBs/light into the pinned staging area the graph copies
  * from; it fails with PAR_ERR_UNSUPPORTED when the staged scene needs larger launch grids than were captured (about
  * twice the bin insertions of the captured frame): capture again then. */
-/* A context with more than one light (par_set_lights) cannot be captured: PAR_ERR_UNSUPPORTED. */
+/* A context with more than one light (par_set_lights) cannot be captured: PAR_ERR_UNSUPPORTED. Two kinds of graph:
+ * par_graph_capture's (the one-light path: the kernels of par_render_device with one light) and
+ * par_graph_capture_lights's (the light path). Capturing either drops the graphs captured before; so does
+ * par_set_sprites, after which par_graph_stage* and par_graph_launch return PAR_ERR_NOT_READY. par_graph_stage
+ * replaces lights[0] (the count is kept) when `light` is not NULL. par_graph_launch renders the context's lights as
+ * they are at launch time (par_set_light, par_set_lights, par_graph_stage, par_graph_stage_lights): a one-light graph
+ * returns PAR_ERR_UNSUPPORTED when there are several; a light-path graph renders any count from 1 to PAR_MAX_LIGHTS. */
 int par_graph_capture(par_context* ctx, void* stream, int row_begin, int row_end, const par_outputs* device_out,
                       unsigned flags);
 int par_graph_stage(par_context* ctx, const par_aabb* aabbs, int first, int n, const par_light* light);
 int par_graph_launch(par_context* ctx, void* stream);
+/* Capture the path of several lights: {pinned AABB upload, pinned lights upload -> hash build -> [background rays]
+ * -> fill -> light kernel}, one graph per grid set, like par_graph_capture. Works for a context with 1..PAR_MAX_LIGHTS
+ * lights. Later launches render whatever lights the context holds at launch time, any count from 1 to PAR_MAX_LIGHTS.
+ * Its argument, flag, row and readiness checks, the non-default stream, the launch grids' head-room and the stripping
+ * of PAR_RENDER_COUNT_RAYS are those of par_graph_capture; a failed capture leaves no graph. A frame it replays equals,
+ * bit for bit on every requested plane, what par_render_device gives for the same scene, lights, rows and flags. Each
+ * launch writes the lights into the staging block of its grid set once that set's previous launch has run, so frames
+ * can be staged and launched back to back without a host wait. */
+int par_graph_capture_lights(par_context* ctx, void* stream, int row_begin, int row_end,
+                             const par_outputs* device_out, unsigned flags);
+/* par_graph_stage, plus the whole light set: lights != NULL with 1 <= n_lights <= PAR_MAX_LIGHTS replaces it (as
+ * par_set_lights would); lights == NULL with n_lights == 0 keeps it. Everything is checked before anything changes: a
+ * rejected call leaves the AABBs, the lights and the staging areas as they were. PAR_ERR_NOT_READY: no context or no
+ * captured graph; PAR_ERR_INVALID_ARG: n_lights outside [0, PAR_MAX_LIGHTS], or `lights` and `n_lights` disagree about
+ * being empty; PAR_ERR_UNSUPPORTED: n_lights >= 2 on a one-light graph (par_graph_capture); the AABB range, extent and
+ * bound errors exactly as par_graph_stage. */
+int par_graph_stage_lights(par_context* ctx, const par_aabb* aabbs, int first, int n,
+                           const par_light* lights, int n_lights);
 
 /* Mouse pick (alt:380-382, 698-700): the G-buffer texel under (x, y) of the last frame rendered with a gbuf
  * plane is the caller's to read; this helper renders just that pixel's row. */

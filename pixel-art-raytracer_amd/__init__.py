@@ -39,7 +39,8 @@ ABI_SYMBOLS = (
     "par_graph_capture", "par_graph_stage", "par_graph_launch", "par_pick", "par_get_stats", "par_read_grid",
     "par_sprite_tile_floor", "par_scene_graybox", "par_scene_synthetic", "par_debug_line", "par_debug_units",
     "par_render_device_slots", "par_row_block", "par_scene_tiles", "par_tiles_pack", "par_tiles_unpack",
-    "par_background_fill", "par_tiles_assemble", "par_scene_tile_map", "par_set_lights",
+    "par_background_fill", "par_tiles_assemble", "par_scene_tile_map", "par_set_lights", "par_graph_capture_lights",
+    "par_graph_stage_lights",
 )
 MAX_LIGHTS = 8  # PAR_MAX_LIGHTS
 
@@ -107,6 +108,8 @@ def lib():
         L.par_graph_capture.argtypes = [vp, vp, i32, i32, vp, C.c_uint]
         L.par_graph_stage.argtypes = [vp, vp, i32, i32, vp]
         L.par_graph_launch.argtypes = [vp, vp]
+        L.par_graph_capture_lights.argtypes = [vp, vp, i32, i32, vp, C.c_uint]
+        L.par_graph_stage_lights.argtypes = [vp, vp, i32, i32, vp, i32]
         L.par_pick.argtypes = [vp, i32, i32, vp]
         L.par_get_stats.argtypes = [vp, vp]
         L.par_read_grid.argtypes = [vp, vp, vp, vp]
@@ -306,10 +309,26 @@ class Renderer:
         o = Outputs(*[device_ptrs.get(k) for k in _PLANES])
         self._check(lib().par_graph_capture(self._ctx, C.c_void_p(stream), r0, r1, C.byref(o), flags))
 
-    def graph_stage(self, aabbs=None, first=0, light=None):
+    def graph_capture_lights(self, device_ptrs, rows=None, flags=0, stream=0):
+        """A graph of the light path (par_graph_capture_lights): its launches render whatever lights the context holds
+        then, 1 .. MAX_LIGHTS of them."""
+        r0, r1 = rows or (0, self.height)
+        o = Outputs(*[device_ptrs.get(k) for k in _PLANES])
+        self._check(lib().par_graph_capture_lights(self._ctx, C.c_void_p(stream), r0, r1, C.byref(o), flags))
+
+    def graph_stage(self, aabbs=None, first=0, light=None, lights=None):
+        """The next graph frame's AABBs [first, first + len(aabbs)), and either lights[0] (`light`, par_graph_stage) or
+        the whole light set (`lights`, a LIGHT array: par_graph_stage_lights)."""
         a = None if aabbs is None else np.ascontiguousarray(aabbs, dtype=AABB)
+        n = 0 if a is None else len(a)
+        if lights is not None:
+            if light is not None:
+                raise ValueError("graph_stage: pass light or lights, not both")
+            ls = np.ascontiguousarray(lights, dtype=LIGHT).reshape(-1)
+            self._check(lib().par_graph_stage_lights(self._ctx, ptr(a), first, n, ptr(ls), len(ls)))
+            return
         l = None if light is None else np.ascontiguousarray(light, dtype=LIGHT)
-        self._check(lib().par_graph_stage(self._ctx, ptr(a), first, 0 if a is None else len(a), ptr(l)))
+        self._check(lib().par_graph_stage(self._ctx, ptr(a), first, n, ptr(l)))
 
     def graph_launch(self, stream=0):
         self._check(lib().par_graph_launch(self._ctx, C.c_void_p(stream)))

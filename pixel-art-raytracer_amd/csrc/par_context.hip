@@ -27,6 +27,13 @@ struct par_footprint {
     int64_t pairs() const { return (int64_t)cols() * nz; }  // (entity, bin) insertions, alt:243-267
 };
 
+// The staged lights of a light-path graph: par_lights_dyn padded to a whole number of 64-byte lines.
+struct par_lights_block {
+    par_lights_dyn lights;
+    int32_t pad_[(256 - sizeof(par_lights_dyn)) / sizeof(int32_t)];
+};
+static_assert(sizeof(par_lights_block) == 256, "lights staging block");
+
 struct par_context {
     par_params params{};
     int device = 0;
@@ -98,6 +105,11 @@ struct par_context {
     bool ev_update_pending = false;
     hipStream_t update_stream = nullptr;
     par_frame_dyn* d_dyn = nullptr;
+    // The light path's graphs (par_graph_capture_lights) read the frame's lights from d_lights, which each graph's
+    // copy node fills from the staging block of its set, pin_lights[s] (same event discipline as pin_dyn).
+    bool graph_lights = false;  // the kind of the captured graphs: false one-light (par_graph_capture), true light path
+    par_lights_block* d_lights = nullptr;
+    par_lights_block* pin_lights[2] = {nullptr, nullptr};
     int graph_set = 0;
     int64_t graph_pair_bound = 0;  // (entity, bin) pairs a captured graph's launch grids can take
     int64_t graph_item_bound = 0;  // ... and render work items
@@ -532,19 +544,28 @@ int check_device_error(par_context* ctx) {
 // A frame takes the light kernel when it has several lights (or the test hook asks for it with one).
 bool lights_path(const par_context* c) { return c->n_lights > 1 || (c->hooks & PAR_HOOK_LIGHTS_PATH); }
 
+par_lights_dyn make_lights_dyn(const par_context* c) {
+    par_lights_dyn lights{};
+    lights.n = c->n_lights;
+    for (int l = 0; l < c->n_lights; l++) lights.l[l] = make_dyn(c, c->lights[l]);
+    return lights;
+}
+
 // A frame with several lights: the hash build, the background fill (after the background rays when they are wanted)
 // and one launch of the light kernel over the occupied columns. No column records, no work items, no overflow list.
 // Timed frames bracket the launches with the same events as enqueue_frame: the light kernel is ms_render and
-// ms_launch[2]; the other render launches it does not have are 0.
+// ms_launch[2]; the other render launches it does not have are 0. In graph mode (par_graph_capture_lights) the
+// launches are sized by what the graph accepts (graph_pair_bound) and the kernels read the lights from d_lights, which
+// the graph's copy node fills before them: one graph serves any count of lights.
 int enqueue_lights_frame(par_context* ctx, hipStream_t stream, const par_bin_args& b, const par_render_args& r,
-                         unsigned flags, hipEvent_t* ev) {
-    par_lights_dyn lights{};
-    lights.n = ctx->n_lights;
-    for (int l = 0; l < ctx->n_lights; l++) lights.l[l] = make_dyn(ctx, ctx->lights[l]);
-    if (flags & PAR_RENDER_COUNT_RAYS) PAR_HIP(hipMemsetAsync(ctx->d_ray_counter, 0, sizeof(unsigned long long), stream));
+                         unsigned flags, bool graph_mode, hipEvent_t* ev) {
+    const par_lights_dyn lights = make_lights_dyn(ctx);
+    if ((flags & PAR_RENDER_COUNT_RAYS) && !graph_mode) {
+        PAR_HIP(hipMemsetAsync(ctx->d_ray_counter, 0, sizeof(unsigned long long), stream));
+    }
     const bool apart = ev && !(flags & PAR_RENDER_TIMED_AS_LAUNCHED);
     const bool stale = ctx->exact_stale;
-    const int64_t pair_bound = stale ? ctx->bound_pairs : ctx->total_pairs;
+    const int64_t pair_bound = graph_mode ? ctx->graph_pair_bound : (stale ? ctx->bound_pairs : ctx->total_pairs);
     if (ev) PAR_HIP(hipEventRecord(ev[0], stream));
     const bool two_launches = apart || (ctx->hooks & PAR_HOOK_TWO_LAUNCHES);
     const hipError_t be = two_launches ? hipErrorNotSupported : par_launch_build(ctx->grid, b, pair_bound, &r, nullptr, stream);
@@ -558,11 +579,16 @@ int enqueue_lights_frame(par_context* ctx, hipStream_t stream, const par_bin_arg
         PAR_HIP(hipEventRecord(ev[5], stream));
         PAR_HIP(hipEventRecord(ev[1], stream));
     }
-    if (r.trace_bg) PAR_HIP(par_launch_bglights(ctx->grid, r, lights, stream));
+    if (r.trace_bg) {
+        PAR_HIP(graph_mode ? par_launch_bglights(ctx->grid, r, &ctx->d_lights->lights, stream)
+                           : par_launch_bglights(ctx->grid, r, lights, stream));
+    }
     PAR_HIP(par_launch_fill(ctx->grid, r, stream));
     if (ev) PAR_HIP(hipEventRecord(ev[3], stream));
-    const int64_t col_bound = stale ? ctx->bound_cols : ctx->total_cols;
-    PAR_HIP(par_launch_render_lights(ctx->grid, r, lights, col_bound, stream));
+    // (occupied columns <= (entity, bin) pairs, as in enqueue_frame)
+    const int64_t col_bound = graph_mode ? pair_bound : (stale ? ctx->bound_cols : ctx->total_cols);
+    PAR_HIP(graph_mode ? par_launch_render_lights(ctx->grid, r, &ctx->d_lights->lights, col_bound, stream)
+                       : par_launch_render_lights(ctx->grid, r, lights, col_bound, stream));
     if (ev) {
         PAR_HIP(hipEventRecord(ev[6], stream));
         PAR_HIP(hipEventRecord(ev[4], stream));
@@ -598,7 +624,8 @@ int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, 
     }
     const par_bin_args b = make_bin_args(ctx, set, row_begin, row_end, flags);
     par_render_args r = make_render_args(ctx, set, row_begin, row_end, outs, flags, graph_mode);
-    if (lights_path(ctx)) return enqueue_lights_frame(ctx, stream, b, r, flags, ev);
+    // (a captured graph takes the path of its kind, chosen when it is captured)
+    if (graph_mode ? ctx->graph_lights : lights_path(ctx)) return enqueue_lights_frame(ctx, stream, b, r, flags, graph_mode, ev);
     // The overflow list is empty for sure while no column has more pairs than a record holds (a captured graph also
     // serves later frames, whose columns nobody knows yet): then the frame has no launch for it, and the column
     // kernel flags the frame should a column overflow all the same.
@@ -804,6 +831,7 @@ static int par_create_impl(const par_params* params, int device, par_context** o
     if ((e = hipMalloc(&ctx->d_palette, PAR_MAX_PALETTE * sizeof(par_color))) != hipSuccess) return bail(e);
     if ((e = hipMalloc(&ctx->d_ray_counter, sizeof(unsigned long long))) != hipSuccess) return bail(e);
     if ((e = hipMalloc(&ctx->d_dyn, sizeof(par_frame_dyn))) != hipSuccess) return bail(e);
+    if ((e = hipMalloc(&ctx->d_lights, sizeof(par_lights_block))) != hipSuccess) return bail(e);
     if ((e = hipMemcpy(ctx->d_palette, p.palette, PAR_MAX_PALETTE * sizeof(par_color), hipMemcpyHostToDevice)) != hipSuccess) return bail(e);
     if ((e = hipMemset(ctx->grid.slots, 0, (size_t)ctx->volume * PAR_SLOTS * sizeof(par_slot))) != hipSuccess) return bail(e);
     for (int i = 0; i < 7; i++) {
@@ -838,7 +866,7 @@ void par_destroy(par_context* ctx) {
         if (p) (void)hipFree(p);
     }
     void* ptrs[] = {ctx->grid.slots, ctx->grid.node_counter, ctx->d_palette, ctx->d_ray_counter, ctx->d_dyn,
-                    ctx->d_aabbs, ctx->d_sprite_ids, ctx->d_sprites, ctx->d_texinfo};
+                    ctx->d_lights, ctx->d_aabbs, ctx->d_sprite_ids, ctx->d_sprites, ctx->d_texinfo};
     for (void* p : ptrs) {
         if (p) (void)hipFree(p);
     }
@@ -850,6 +878,7 @@ void par_destroy(par_context* ctx) {
     for (int s = 0; s < 2; s++) {
         if (ctx->pin_aabbs[s]) (void)hipHostFree(ctx->pin_aabbs[s]);
         if (ctx->pin_dyn[s]) (void)hipHostFree(ctx->pin_dyn[s]);
+        if (ctx->pin_lights[s]) (void)hipHostFree(ctx->pin_lights[s]);
         if (ctx->ev_graph[s]) (void)hipEventDestroy(ctx->ev_graph[s]);
     }
     for (int i = 0; i < 7; i++) {
@@ -1162,8 +1191,9 @@ static int par_render_device_timed_impl(par_context* ctx, void* stream, int row_
     return check_device_error(ctx);
 }
 
-static int par_graph_capture_impl(par_context* ctx, void* stream_v, int row_begin, int row_end, const par_outputs* device_out,
-                      unsigned flags) {
+// par_graph_capture (lights_kind false: the one-light path) and par_graph_capture_lights (true: the light path).
+static int graph_capture(par_context* ctx, void* stream_v, int row_begin, int row_end, const par_outputs* device_out,
+                         unsigned flags, bool lights_kind) {
     if (!ctx || !device_out) return fail(ctx, PAR_ERR_INVALID_ARG, "null argument");
     hipStream_t stream = (hipStream_t)stream_v;
     if (!stream) return fail(ctx, PAR_ERR_INVALID_ARG, "graph capture needs a non-default stream");
@@ -1173,7 +1203,9 @@ static int par_graph_capture_impl(par_context* ctx, void* stream_v, int row_begi
     if (rc != PAR_OK) return rc;
     rc = check_ready(ctx);
     if (rc != PAR_OK) return rc;
-    if (lights_path(ctx)) return fail(ctx, PAR_ERR_UNSUPPORTED, "a frame with several lights cannot be captured");
+    if (!lights_kind && lights_path(ctx)) {
+        return fail(ctx, PAR_ERR_UNSUPPORTED, "a frame with several lights cannot be captured (par_graph_capture_lights)");
+    }
     PAR_HIP(hipSetDevice(ctx->device));
     PAR_HIP(hipDeviceSynchronize());
     drop_graphs(ctx);
@@ -1195,19 +1227,30 @@ static int par_graph_capture_impl(par_context* ctx, void* stream_v, int row_begi
             PAR_HIP(hipHostMalloc(&ctx->pin_aabbs[s], (size_t)std::max(ctx->aabb_capacity, 1) * sizeof(par_aabb), hipHostMallocDefault));
         }
         if (!ctx->pin_dyn[s]) PAR_HIP(hipHostMalloc(&ctx->pin_dyn[s], sizeof(par_frame_dyn), hipHostMallocDefault));
+        if (lights_kind && !ctx->pin_lights[s]) {
+            PAR_HIP(hipHostMalloc(&ctx->pin_lights[s], sizeof(par_lights_block), hipHostMallocDefault));
+        }
         if (!ctx->ev_graph[s]) PAR_HIP(hipEventCreateWithFlags(&ctx->ev_graph[s], hipEventDisableTiming));
         ctx->ev_graph_pending[s] = false;
         std::memcpy(ctx->pin_aabbs[s], ctx->h_aabbs.data(), (size_t)ctx->n_entities * sizeof(par_aabb));
         *ctx->pin_dyn[s] = make_dyn(ctx, ctx->light);
+        if (lights_kind) ctx->pin_lights[s]->lights = make_lights_dyn(ctx);
         ctx->stage_lo[s] = ctx->stage_hi[s] = 0;
     }
+    ctx->graph_lights = lights_kind;  // (what enqueue_frame captures; no graph is left behind should the capture fail)
     // The frame alternates between the two grid sets, and a captured kernel node bakes its pointers: one graph
-    // per set, launched alternately; each uploads the scene from its own staging area.
+    // per set, launched alternately; each uploads the scene from its own staging area (the light path: the AABBs and
+    // the lights, ahead of every kernel of the frame).
     for (int s = 0; s < 2; s++) {
         PAR_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
         hipError_t e = hipMemcpyAsync(ctx->d_aabbs, ctx->pin_aabbs[s], (size_t)ctx->n_entities * sizeof(par_aabb),
                                       hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(ctx->d_dyn, ctx->pin_dyn[s], sizeof(par_frame_dyn), hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess && !lights_kind) {
+            e = hipMemcpyAsync(ctx->d_dyn, ctx->pin_dyn[s], sizeof(par_frame_dyn), hipMemcpyHostToDevice, stream);
+        }
+        if (e == hipSuccess && lights_kind) {
+            e = hipMemcpyAsync(ctx->d_lights, ctx->pin_lights[s], sizeof(par_lights_block), hipMemcpyHostToDevice, stream);
+        }
         int erc = PAR_OK;
         if (e == hipSuccess) erc = enqueue_frame(ctx, stream, s, row_begin, row_end, *device_out, flags & ~PAR_RENDER_COUNT_RAYS, true, nullptr);
         hipGraph_t g = nullptr;
@@ -1230,22 +1273,62 @@ static int par_graph_capture_impl(par_context* ctx, void* stream_v, int row_begi
     return PAR_OK;
 }
 
-static int par_graph_stage_impl(par_context* ctx, const par_aabb* aabbs, int first, int n, const par_light* light) {
-    if (!ctx || !ctx->graph_exec[0]) return fail(ctx, PAR_ERR_NOT_READY, "no captured graph");
+static int par_graph_capture_impl(par_context* ctx, void* stream_v, int row_begin, int row_end, const par_outputs* device_out,
+                      unsigned flags) {
+    return graph_capture(ctx, stream_v, row_begin, row_end, device_out, flags, false);
+}
+
+static int par_graph_capture_lights_impl(par_context* ctx, void* stream_v, int row_begin, int row_end,
+                                         const par_outputs* device_out, unsigned flags) {
+    return graph_capture(ctx, stream_v, row_begin, row_end, device_out, flags, true);
+}
+
+// The checks of par_graph_stage for AABBs [first, first + n), with the plan of the update when they pass. They change
+// nothing but the freshness of the exact bookkeeping.
+static int graph_stage_check(par_context* ctx, const par_aabb* aabbs, int first, int n, par_update_plan* plan) {
     if (n < 0 || first < 0 || first + n > ctx->n_entities || (n > 0 && !aabbs)) return fail(ctx, PAR_ERR_INVALID_ARG, "stage range");
     for (int i = 0; i < n; i++) {
         if (!extent_ok(aabbs[i])) return fail(ctx, PAR_ERR_EXTENT, "extent needs 0<=ex<=20, ey,ez>=0, ey+ez<=40");
     }
     if (ctx->exact_stale) refresh_exact(ctx);  // (the footprints and totals; the histograms may stay behind)
-    par_update_plan plan;
-    plan_update(ctx, aabbs, first, n, &plan);
+    plan_update(ctx, aabbs, first, n, plan);
 
-    if (plan.pairs > ctx->graph_pair_bound || plan.pairs > ctx->grid.capacity) {
+    if (plan->pairs > ctx->graph_pair_bound || plan->pairs > ctx->grid.capacity) {
         return fail(ctx, PAR_ERR_UNSUPPORTED, "staged frame exceeds what the captured graph was sized for; capture again");
     }
+    return PAR_OK;
+}
+
+static int par_graph_stage_impl(par_context* ctx, const par_aabb* aabbs, int first, int n, const par_light* light) {
+    if (!ctx || !ctx->graph_exec[0]) return fail(ctx, PAR_ERR_NOT_READY, "no captured graph");
+    par_update_plan plan;
+    const int rc = graph_stage_check(ctx, aabbs, first, n, &plan);
+    if (rc != PAR_OK) return rc;
     commit_update_totals(ctx, aabbs, first, n, plan);
     mark_staged(ctx, first, n);  // (the staging areas are brought up to date by par_graph_launch)
     if (light) ctx->light = ctx->lights[0] = *light;
+    return PAR_OK;
+}
+
+static int par_graph_stage_lights_impl(par_context* ctx, const par_aabb* aabbs, int first, int n,
+                                       const par_light* lights, int n_lights) {
+    if (!ctx || !ctx->graph_exec[0]) return fail(ctx, PAR_ERR_NOT_READY, "no captured graph");
+    if (n_lights < 0 || n_lights > PAR_MAX_LIGHTS || (lights == nullptr) != (n_lights == 0)) {
+        return fail(ctx, PAR_ERR_INVALID_ARG, "lights: NULL with 0, or 1 <= n_lights <= PAR_MAX_LIGHTS");
+    }
+    if (n_lights > 1 && !ctx->graph_lights) {
+        return fail(ctx, PAR_ERR_UNSUPPORTED, "a one-light graph cannot render several lights (par_graph_capture_lights)");
+    }
+    par_update_plan plan;
+    const int rc = graph_stage_check(ctx, aabbs, first, n, &plan);
+    if (rc != PAR_OK) return rc;
+    commit_update_totals(ctx, aabbs, first, n, plan);
+    mark_staged(ctx, first, n);  // (the staging areas are brought up to date by par_graph_launch)
+    if (n_lights > 0) {  // (as par_set_lights)
+        for (int l = 0; l < n_lights; l++) ctx->lights[l] = lights[l];
+        ctx->n_lights = n_lights;
+        ctx->light = lights[0];
+    }
     return PAR_OK;
 }
 
@@ -1256,12 +1339,14 @@ static int par_graph_launch_impl(par_context* ctx, void* stream) {
     if (ctx->total_pairs > ctx->graph_pair_bound) {
         return fail(ctx, PAR_ERR_UNSUPPORTED, "the scene exceeds what the captured graph was sized for; capture again");
     }
-    if (ctx->n_lights > 1) return fail(ctx, PAR_ERR_UNSUPPORTED, "a frame with several lights has no graph");
+    if (ctx->n_lights > 1 && !ctx->graph_lights) {
+        return fail(ctx, PAR_ERR_UNSUPPORTED, "a frame with several lights has no one-light graph (par_graph_capture_lights)");
+    }
     const int s = ctx->set;
     if (!ctx->graph_exec[s]) return fail(ctx, PAR_ERR_NOT_READY, "no captured graph for this grid set");
     PAR_HIP(hipSetDevice(ctx->device));
     // This graph's staging area: free once its previous launch has run (its copy nodes read the area when they
-    // execute, not when the graph is launched), then brought up to date with the host mirror and the light.
+    // execute, not when the graph is launched), then brought up to date with the host mirror and the light(s).
     if (ctx->ev_graph_pending[s]) {
         if (hipEventQuery(ctx->ev_graph[s]) != hipSuccess) PAR_HIP(hipEventSynchronize(ctx->ev_graph[s]));
         ctx->ev_graph_pending[s] = false;
@@ -1271,7 +1356,11 @@ static int par_graph_launch_impl(par_context* ctx, void* stream) {
                     (size_t)(ctx->stage_hi[s] - ctx->stage_lo[s]) * sizeof(par_aabb));
         ctx->stage_lo[s] = ctx->stage_hi[s] = 0;
     }
-    *ctx->pin_dyn[s] = make_dyn(ctx, ctx->light);
+    if (ctx->graph_lights) {
+        ctx->pin_lights[s]->lights = make_lights_dyn(ctx);
+    } else {
+        *ctx->pin_dyn[s] = make_dyn(ctx, ctx->light);
+    }
     // an asynchronous scene update on another stream: this frame comes after it
     if (ctx->ev_update_pending && ctx->update_stream != (hipStream_t)stream) {
         PAR_HIP(hipStreamWaitEvent((hipStream_t)stream, ctx->ev_update, 0));
@@ -1493,6 +1582,14 @@ int par_graph_capture(par_context* ctx, void* stream_v, int row_begin, int row_e
 }
 int par_graph_stage(par_context* ctx, const par_aabb* aabbs, int first, int n, const par_light* light) {
     return guarded(ctx, [&] { return par_graph_stage_impl(ctx, aabbs, first, n, light); });
+}
+int par_graph_capture_lights(par_context* ctx, void* stream, int row_begin, int row_end, const par_outputs* device_out,
+                             unsigned flags) {
+    return guarded(ctx, [&] { return par_graph_capture_lights_impl(ctx, stream, row_begin, row_end, device_out, flags); });
+}
+int par_graph_stage_lights(par_context* ctx, const par_aabb* aabbs, int first, int n, const par_light* lights,
+                           int n_lights) {
+    return guarded(ctx, [&] { return par_graph_stage_lights_impl(ctx, aabbs, first, n, lights, n_lights); });
 }
 int par_get_stats(par_context* ctx, par_frame_stats* stats) {
     return guarded(ctx, [&] { return par_get_stats_impl(ctx, stats); });

@@ -113,7 +113,8 @@ struct par_frame_dyn {
 };
 
 // The lights of a frame with several (par_set_lights): each light's position and bin, as par_frame_dyn holds them for
-// the one light of the other kernels. A kernel argument of the light kernels.
+// the one light of the other kernels. A kernel argument of the light kernels; in graph mode it lives in device memory
+// (par_launch_render_lights / par_launch_bglights with a pointer).
 struct par_lights_dyn {
     int32_t n;  // 1 .. PAR_MAX_LIGHTS
     par_frame_dyn l[PAR_MAX_LIGHTS];
@@ -270,6 +271,12 @@ hipError_t par_launch_render_lights(const par_grid_dev& g, const par_render_args
 // The background rays of such a frame (one per x and light, bit l of g.bglit[x] for light l); par_launch_fill then
 // copies them into the lit plane.
 hipError_t par_launch_bglights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,
+                               hipStream_t stream);
+// The same two launches for a captured graph: the kernels read the frame's lights from `d_lights` (device memory a
+// copy node of the graph fills before them), once per workgroup, so one graph serves any count of lights.
+hipError_t par_launch_render_lights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn* d_lights,
+                                    int64_t column_bound, hipStream_t stream);
+hipError_t par_launch_bglights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn* d_lights,
                                hipStream_t stream);
 
 // Sharded frames: tiles between a frame block and packed slots, and the background colour for whole rows.

@@ -2237,6 +2237,8 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_both_kernel(par_grid_
 //      then per light the slab tests of the recorded walk of the pixel's start bin, or lane_shadow_walk where there is
 //      none (the start bin holds no primitive, or its walk did not fit), and the shading of the contract in
 //      par_raytracer.h (par_set_lights). Each walk is done once per column and light.
+// Two instantiations: the lights as a kernel argument (direct frames), or read from device memory once per workgroup
+// into LDS (a captured graph, whose copy node uploads them before the frame): frame_lights.
 // ------------------------------------------------------------------------------------------------------------
 constexpr int PAR_LIGHT_NB = 64;      // occupied bins of a column whose walks are recorded (the others: lane walks)
 constexpr int PAR_LIGHT_WALK = 1024;  // occluder records of all walks of a column (16 KiB)
@@ -2252,9 +2254,30 @@ struct LightCol {  // LDS of one workgroup of render_lights_kernel
 };
 static_assert(PAR_LIGHT_WALK <= 32767 && PAR_MAX_LIGHTS <= 8, "int16 walk offsets, one lit bit per light");
 
+// The lights a light kernel reads: its kernel argument (direct frames), or the frame's lights in device memory, where
+// the copy node of a captured graph leaves them, read once per workgroup into LDS (one dword per thread, then one
+// barrier). There n is clamped to [1, PAR_MAX_LIGHTS]: the kernel's LDS arrays are sized by it.
+__device__ __forceinline__ const par_lights_dyn& frame_lights(const par_lights_dyn& lights) { return lights; }
+__device__ __forceinline__ const par_lights_dyn& frame_lights(const par_lights_dyn* src) {
+    __shared__ par_lights_dyn sl;
+    constexpr int N = (int)(sizeof(par_lights_dyn) / sizeof(int32_t));
+    static_assert(sizeof(par_lights_dyn) % sizeof(int32_t) == 0 && N <= 256, "one dword per thread of a workgroup");
+    const int t = (int)threadIdx.x;
+    if (t == 0) {
+        sl.n = min(max(src->n, 1), PAR_MAX_LIGHTS);
+    } else if (t < N) {
+        reinterpret_cast<int32_t*>(&sl)[t] = reinterpret_cast<const int32_t*>(src)[t];
+    }
+    __syncthreads();
+    return sl;
+}
+
+// LightsArg: par_lights_dyn (direct frames) or const par_lights_dyn* (graph replay), see frame_lights.
+template <class LightsArg>
 __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_grid_dev g, par_render_args a,
-                                                                            par_lights_dyn lights) {
+                                                                            LightsArg lights_arg) {
     __shared__ LightCol sh;
+    const par_lights_dyn& lights = frame_lights(lights_arg);
     const int lane = (int)threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int n_lights = lights.n;
@@ -2447,7 +2470,9 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
 
 // The background rays of a frame with several lights (bgline_kernel's, once per light): bit l of bglit[x] is the
 // shadow ray of a background pixel of screen column x towards light l, traced per lane as the reference writes it.
-__global__ __launch_bounds__(256) void bglights_kernel(par_grid_dev g, par_render_args a, par_lights_dyn lights) {
+template <class LightsArg>
+__global__ __launch_bounds__(256) void bglights_kernel(par_grid_dev g, par_render_args a, LightsArg lights_arg) {
+    const par_lights_dyn& lights = frame_lights(lights_arg);  // (every thread meets its barrier before any returns)
     const int x = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (x >= a.W) return;
     const int ox = (int)(int16_t)x;                        // alt:720-722
@@ -2844,19 +2869,43 @@ hipError_t par_launch_render_overflow(const par_grid_dev& g, const par_render_ar
     return hipGetLastError();
 }
 
+// Workgroups of a light-kernel launch: one per column the bound allows in the rendered rows, at most 65536 (the
+// workgroups then stride over the column list).
+static int64_t render_lights_grid(const par_grid_dev& g, const par_render_args& a, int64_t column_bound) {
+    const int64_t cols_in_range = (int64_t)g.gx * (a.by_hi - a.by_lo + 1);
+    const int64_t n = column_bound < cols_in_range ? column_bound : cols_in_range;
+    return n > 65536 ? 65536 : n;
+}
+
 hipError_t par_launch_render_lights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,
                                     int64_t column_bound, hipStream_t stream) {
-    const int64_t cols_in_range = (int64_t)g.gx * (a.by_hi - a.by_lo + 1);
-    int64_t n = column_bound < cols_in_range ? column_bound : cols_in_range;
+    const int64_t n = render_lights_grid(g, a, column_bound);
     if (n <= 0) return hipSuccess;
-    if (n > 65536) n = 65536;  // (the workgroups then stride over the column list)
-    hipLaunchKernelGGL(render_lights_kernel, dim3((unsigned)n), dim3(PAR_WAVE_NW * 64), 0, stream, g, a, lights);
+    hipLaunchKernelGGL(render_lights_kernel<par_lights_dyn>, dim3((unsigned)n), dim3(PAR_WAVE_NW * 64), 0, stream, g, a,
+                       lights);
+    return hipGetLastError();
+}
+
+hipError_t par_launch_render_lights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn* d_lights,
+                                    int64_t column_bound, hipStream_t stream) {
+    const int64_t n = render_lights_grid(g, a, column_bound);
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(render_lights_kernel<const par_lights_dyn*>, dim3((unsigned)n), dim3(PAR_WAVE_NW * 64), 0, stream,
+                       g, a, d_lights);
     return hipGetLastError();
 }
 
 hipError_t par_launch_bglights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,
                                hipStream_t stream) {
-    hipLaunchKernelGGL(bglights_kernel, dim3((unsigned)((a.W + 255) / 256)), dim3(256), 0, stream, g, a, lights);
+    hipLaunchKernelGGL(bglights_kernel<par_lights_dyn>, dim3((unsigned)((a.W + 255) / 256)), dim3(256), 0, stream, g, a,
+                       lights);
+    return hipGetLastError();
+}
+
+hipError_t par_launch_bglights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn* d_lights,
+                               hipStream_t stream) {
+    hipLaunchKernelGGL(bglights_kernel<const par_lights_dyn*>, dim3((unsigned)((a.W + 255) / 256)), dim3(256), 0, stream,
+                       g, a, d_lights);
     return hipGetLastError();
 }
 
