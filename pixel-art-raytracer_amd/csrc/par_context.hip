@@ -4,6 +4,7 @@
 // it owns the work arrays (alt:503-517), takes the scene the caller built (alt:517-599, 619-626), and runs one
 // frame = bin + trace + shade (alt:690-760) per render call. There is no CPU rendering path in this library.
 #include <algorithm>
+#include <array>
 #include <new>
 #include <cstdio>
 #include <cstdlib>
@@ -27,7 +28,8 @@ struct par_footprint {
     int64_t pairs() const { return (int64_t)cols() * nz; }  // (entity, bin) insertions, alt:243-267
 };
 
-// The staged lights of a light-path graph: par_lights_dyn padded to a whole number of 64-byte lines.
+// The staged lights of a captured graph: par_lights_dyn padded to a whole number of 64-byte lines. A one-light graph's
+// kernels read their par_frame_dyn from lights.l[0].
 struct par_lights_block {
     par_lights_dyn lights;
     int32_t pad_[(256 - sizeof(par_lights_dyn)) / sizeof(int32_t)];
@@ -64,10 +66,9 @@ struct par_context {
     std::vector<int32_t> h_colchunks;
     int64_t cols_tileable = 0;
     int n_entities = 0, n_sprites = 0, max_sprite_id = 0;
-    bool have_light = false, have_entities = false;
-    par_light light{};                  // lights[0]: what the one-light kernels and the graph path read
-    par_light lights[PAR_MAX_LIGHTS]{};  // par_set_lights; n_lights >= 2 (or the test hook) takes the light kernel
-    int n_lights = 0;
+    bool have_entities = false;
+    par_light lights[PAR_MAX_LIGHTS]{};  // set_lights; n_lights >= 2 (or the test hook) takes the light kernel
+    int n_lights = 0;                    // 0 until a light is set
     int set = 0;  // head/count/node set the NEXT frame uses
     hipStream_t last_stream = nullptr;  // stream of the most recent asynchronous render (scene updates wait for it)
     bool has_last_stream = false;
@@ -85,17 +86,18 @@ struct par_context {
     int aabb_capacity = 0;
 
     // device output planes for the host-buffer entry points
-    void* d_out[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    uint8_t* d_out[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     size_t d_out_bytes[5] = {0, 0, 0, 0, 0};
 
     // hipGraph path: one executable graph per grid set, a pinned staging area they copy from
     hipGraphExec_t graph_exec[2] = {nullptr, nullptr};
     hipGraph_t graph[2] = {nullptr, nullptr};
-    // Each graph copies the scene from a pinned staging area of its own (the copy node reads it when the graph RUNS,
-    // which may be long after it was launched): the area of set s is rewritten only after the event recorded behind
-    // set s's last launch. `stage_lo/hi`: entities changed since the area last matched the host mirror.
+    // Each graph copies the scene (AABBs into d_aabbs, the lights into d_lights) from a pinned staging area of its own
+    // (the copy nodes read it when the graph RUNS, which may be long after it was launched): the area of set s is
+    // rewritten only after the event recorded behind set s's last launch. `stage_lo/hi`: entities changed since the
+    // area last matched the host mirror.
     par_aabb* pin_aabbs[2] = {nullptr, nullptr};
-    par_frame_dyn* pin_dyn[2] = {nullptr, nullptr};
+    par_lights_block* pin_lights[2] = {nullptr, nullptr};
     hipEvent_t ev_graph[2] = {nullptr, nullptr};
     bool ev_graph_pending[2] = {false, false};
     int stage_lo[2] = {0, 0}, stage_hi[2] = {0, 0};
@@ -104,18 +106,15 @@ struct par_context {
     hipEvent_t ev_update = nullptr;   // its last copy
     bool ev_update_pending = false;
     hipStream_t update_stream = nullptr;
-    par_frame_dyn* d_dyn = nullptr;
-    // The light path's graphs (par_graph_capture_lights) read the frame's lights from d_lights, which each graph's
-    // copy node fills from the staging block of its set, pin_lights[s] (same event discipline as pin_dyn).
-    bool graph_lights = false;  // the kind of the captured graphs: false one-light (par_graph_capture), true light path
+    // The captured kernels read the frame's lights from d_lights (a one-light graph's from the first light alone).
+    bool graph_lights = false;  // which kernels were captured: false one-light (par_graph_capture), true light path
     par_lights_block* d_lights = nullptr;
-    par_lights_block* pin_lights[2] = {nullptr, nullptr};
     int graph_set = 0;
     int64_t graph_pair_bound = 0;  // (entity, bin) pairs a captured graph's launch grids can take
     int64_t graph_item_bound = 0;  // ... and render work items
 
     bool timed_tiles = false, timed_overflow = false, timed_both = false;  // the last timed frame launched these kernels
-    hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // EV_START .. EV_END
     par_frame_stats stats{};
     unsigned last_flags = 0;
     std::string err;
@@ -133,6 +132,17 @@ enum : unsigned {
     PAR_HOOK_BAD_ALLOC = 1u << 4,      // the guarded host-allocating bodies fail as an exhausted heap would
     PAR_HOOK_LIGHTS_PATH = 1u << 5,    // a one-light frame takes the path of several lights (render_lights_kernel)
     PAR_HOOKS_ALL = (1u << 6) - 1
+};
+
+// The events of a timed frame (par_context::ev), in the order a frame records them.
+enum : int {
+    EV_START,
+    EV_BUILT,     // after the hash build
+    EV_COLUMNS,   // after the column launch (a frame with several lights has none: with EV_BUILT)
+    EV_FILLED,    // after the background fill
+    EV_ITEMS,     // after the render launch of the work items (or of all render kernels, or the light kernel)
+    EV_RENDERED,  // after the render launches
+    EV_END        // after the launch for the overflow list
 };
 
 namespace {
@@ -278,61 +288,74 @@ void bounds_after(const par_context* c, const par_aabb* aabbs, int first, int n,
     }
 }
 
-void commit_update(par_context* c, const par_aabb* aabbs, int first, int n, const par_update_plan& plan) {
+// `commit`: the per-column histograms follow when `hist`; par_graph_stage leaves them behind (hist_stale).
+void commit_update(par_context* c, const par_aabb* aabbs, int first, int n, const par_update_plan& plan, bool hist) {
     par_bound bt;
     bounds_after(c, aabbs, first, n, &bt);
     c->bound_pairs = bt.pairs; c->bound_cols = bt.cols; c->bound_items = bt.items;
     for (int i = 0; i < n; i++) {
         par_footprint& slot = c->h_fp[(size_t)(first + i)];
-        col_hist(c, slot, -1);
-        col_hist(c, plan.fp[(size_t)i], +1);
+        if (hist) {
+            col_hist(c, slot, -1);
+            col_hist(c, plan.fp[(size_t)i], +1);
+        }
         slot = plan.fp[(size_t)i];
         c->h_aabbs[(size_t)(first + i)] = aabbs[i];
     }
     c->total_pairs = plan.pairs;
     c->total_cols = plan.cols;
     c->total_items = plan.items;
+    if (!hist) c->hist_stale = true;
 }
 
-// The exact bookkeeping (footprints, totals, per-column histograms) from the host's copy of the AABBs, after
-// asynchronous updates left it stale.
-void refresh_exact(par_context* c) {
-    if (!c->exact_stale && !c->hist_stale) return;
+// The footprints of aabbs[0, n) into fp, and their totals.
+par_bound footprints(const par_context* c, const par_aabb* aabbs, int n, par_footprint* fp) {
+    par_bound t{0, 0, 0};
+    for (int i = 0; i < n; i++) {
+        fp[i] = footprint_of(c, aabbs[i]);
+        t.pairs += fp[i].pairs();
+        t.cols += fp[i].cols();
+        t.items += fp[i].items;
+    }
+    return t;
+}
+
+// Both per-column histograms from the footprints (h_fp): then they are current.
+void rebuild_hist(par_context* c) {
     c->h_colpairs.assign((size_t)c->gx * c->gy, 0);
     c->h_colchunks.assign((size_t)c->gx * c->gy, 0);
     c->cols_over = 0;
     c->cols_tileable = 0;
-    c->total_pairs = c->total_cols = c->total_items = 0;
-    for (int i = 0; i < c->n_entities; i++) {
-        const par_footprint f = footprint_of(c, c->h_aabbs[(size_t)i]);
-        c->h_fp[(size_t)i] = f;
-        col_hist(c, f, +1);
-        c->total_pairs += f.pairs();
-        c->total_cols += f.cols();
-        c->total_items += f.items;
-    }
-    c->exact_stale = false;
+    for (const par_footprint& f : c->h_fp) col_hist(c, f, +1);
     c->hist_stale = false;
 }
 
-// commit_update without the per-column histograms (they go stale: hist_stale).
-void commit_update_totals(par_context* c, const par_aabb* aabbs, int first, int n, const par_update_plan& plan) {
-    par_bound bt;
-    bounds_after(c, aabbs, first, n, &bt);
-    c->bound_pairs = bt.pairs; c->bound_cols = bt.cols; c->bound_items = bt.items;
-    for (int i = 0; i < n; i++) {
-        c->h_fp[(size_t)(first + i)] = plan.fp[(size_t)i];
-        c->h_aabbs[(size_t)(first + i)] = aabbs[i];
-    }
-    c->total_pairs = plan.pairs;
-    c->total_cols = plan.cols;
-    c->total_items = plan.items;
-    c->hist_stale = true;
+// The exact bookkeeping (footprints, totals, per-column histograms) from the host's copy of the AABBs, after
+// asynchronous updates or graph staging left it stale.
+void refresh_exact(par_context* c) {
+    if (!c->exact_stale && !c->hist_stale) return;
+    const par_bound t = footprints(c, c->h_aabbs.data(), c->n_entities, c->h_fp.data());
+    c->total_pairs = t.pairs; c->total_cols = t.cols; c->total_items = t.items;
+    rebuild_hist(c);
+    c->exact_stale = false;
 }
 
 bool extent_ok(const par_aabb& a) {
     // The sprite is 20 wide and 40 tall (alt:330, spr:67-71): texel row = (ey + ez) - 1 at most, column < ex.
     return a.ex >= 0 && a.ey >= 0 && a.ez >= 0 && a.ex <= PAR_SPRITE_W && (int)a.ey + (int)a.ez <= PAR_SPRITE_H;
+}
+
+// The checks of an update of entities [first, first + n) (par_update_aabbs[_async], par_graph_stage): a range outside
+// the uploaded entities or no AABBs is PAR_ERR_INVALID_ARG (the stage takes NULL with n == 0: `null_ok`), then an
+// extent the sprite cannot take PAR_ERR_EXTENT.
+int check_update(par_context* ctx, const par_aabb* aabbs, int first, int n, bool null_ok) {
+    if (first < 0 || n < 0 || !ctx->have_entities || first + n > ctx->n_entities || (!aabbs && !(null_ok && n == 0))) {
+        return fail(ctx, PAR_ERR_INVALID_ARG, null_ok ? "stage range" : "update range outside the uploaded entities");
+    }
+    for (int i = 0; i < n; i++) {
+        if (!extent_ok(aabbs[i])) return fail(ctx, PAR_ERR_EXTENT, "extent needs 0<=ex<=20, ey,ez>=0, ey+ez<=40");
+    }
+    return PAR_OK;
 }
 
 // What a frame can hold at most of render work items: every column visited as a whole tile.
@@ -341,10 +364,35 @@ int64_t max_items(const par_context* c) {
     return (int64_t)c->gx * c->gy * ((B * B + 63) / 64);
 }
 
-bool items_fit(const par_context* c, int64_t items, int64_t cols) {
+// One shard of the render work-item list holds the items of the columns whose index is congruent to it: at most
+// every item of the frame, and at most its share of the occupied columns (<= `cols`), each visited as a whole tile.
+int64_t items_per_shard(const par_context* c, int64_t items, int64_t cols) {
     const int64_t B = c->params.bin_size;
     cols = std::min<int64_t>(cols, (int64_t)c->gx * c->gy);
-    return std::min(items, (cols / PAR_ITEM_SHARDS + 1) * ((B * B + 63) / 64)) <= c->grid.item_capacity;
+    return std::min(items, (cols / PAR_ITEM_SHARDS + 1) * ((B * B + 63) / 64));
+}
+
+// *p replaced by a fresh buffer of n elements, in device memory or (`pinned`) pinned host memory; the old contents
+// are not kept. *p is null until the new buffer is there.
+template <class T>
+hipError_t reallocate(T** p, size_t n, bool pinned = false) {
+    if (*p) {
+        const hipError_t e = pinned ? hipHostFree(*p) : hipFree(*p);
+        if (e != hipSuccess) return e;
+    }
+    *p = nullptr;
+    const size_t bytes = n * sizeof(T);
+    return pinned ? hipHostMalloc((void**)p, bytes, hipHostMallocDefault) : hipMalloc((void**)p, bytes);
+}
+
+// Grow-on-demand memory: reallocate, with the capacity the caller keeps for the buffer (*cap) 0 until the new one of
+// n elements is there.
+template <class T, class N>
+hipError_t grow(T** p, N* cap, N n, bool pinned = false) {
+    *cap = 0;
+    const hipError_t e = reallocate(p, (size_t)n, pinned);
+    if (e == hipSuccess) *cap = n;
+    return e;
 }
 
 void free_pool(par_context* c) {
@@ -360,12 +408,9 @@ void free_pool(par_context* c) {
     c->grid.capacity = 0;
 }
 
-// One shard of the render work-item list holds the items of the columns whose index is congruent to it: at most
-// every item of the frame, and at most its share of the occupied columns (<= `cols`), each visited as a whole tile.
+// The render work-item list sized for a frame of `items` items over `cols` occupied columns (items_per_shard).
 int ensure_items(par_context* ctx, int64_t items, int64_t cols) {
-    const int64_t B = ctx->params.bin_size;
-    cols = std::min<int64_t>(cols, (int64_t)ctx->gx * ctx->gy);
-    const int64_t need = std::min(items, (cols / PAR_ITEM_SHARDS + 1) * ((B * B + 63) / 64));
+    const int64_t need = items_per_shard(ctx, items, cols);
     if (need <= ctx->grid.item_capacity) return PAR_OK;
     if (ctx->graph_exec[0]) return fail(ctx, PAR_ERR_UNSUPPORTED, "work-item list would grow under a captured graph; capture again");
     const int64_t cap = std::max<int64_t>(need + need / 2, 1 << 10);
@@ -447,23 +492,25 @@ par_frame_dyn make_dyn(const par_context* c, const par_light& l) {
     return d;
 }
 
-int check_rows(par_context* ctx, int row_begin, int row_end) {
+// The context's light set: lights[0, n) replaced, `count` lights in all (par_graph_stage replaces the first alone and
+// keeps the count).
+void set_lights(par_context* c, const par_light* lights, int n, int count) {
+    for (int l = 0; l < n; l++) c->lights[l] = lights[l];
+    c->n_lights = count;
+}
+
+// What every entry point that renders or captures a frame checks first, in this order, then the context's device.
+int frame_prologue(par_context* ctx, const par_outputs* out, int row_begin, int row_end, unsigned flags) {
+    if (!ctx || !out) return fail(ctx, PAR_ERR_INVALID_ARG, "null argument");
+    if (flags & ~PAR_ACCEPTED_FLAGS) return fail(ctx, PAR_ERR_INVALID_ARG, "undefined render flag bits");
     if (row_begin < 0 || row_end > ctx->params.height || row_begin >= row_end) {
         return fail(ctx, PAR_ERR_INVALID_ARG, "rows must satisfy 0 <= row_begin < row_end <= height");
     }
-    return PAR_OK;
-}
-
-int check_flags(par_context* ctx, unsigned flags) {
-    if (flags & ~PAR_ACCEPTED_FLAGS) return fail(ctx, PAR_ERR_INVALID_ARG, "undefined render flag bits");
-    return PAR_OK;
-}
-
-int check_ready(par_context* ctx) {
     if (ctx->n_sprites <= 0) return fail(ctx, PAR_ERR_NOT_READY, "par_set_sprites has not been called");
     if (!ctx->have_entities) return fail(ctx, PAR_ERR_NOT_READY, "par_set_entities has not been called");
-    if (!ctx->have_light) return fail(ctx, PAR_ERR_NOT_READY, "par_set_light has not been called");
+    if (ctx->n_lights <= 0) return fail(ctx, PAR_ERR_NOT_READY, "par_set_light has not been called");
     if (ctx->max_sprite_id >= ctx->n_sprites) return fail(ctx, PAR_ERR_SPRITE_ID, "an entity names a sprite that was not uploaded");
+    PAR_HIP(hipSetDevice(ctx->device));
     return PAR_OK;
 }
 
@@ -496,8 +543,8 @@ par_render_args make_render_args(const par_context* c, int set, int row_begin, i
     const int64_t chunks = std::min(c->total_items, max_items(c));
     a.tile_k = !dense_frame ? 0 : (chunks >= 65536 ? 5 : (chunks >= 16384 ? 3 : (chunks >= 8192 ? 2 : 1)));
     a.tile_k_magic = a.tile_k > 0 ? (uint32_t)(65536 / a.tile_k + 1) : 65537u;
-    a.dyn = make_dyn(c, c->light);
-    a.dyn_ptr = dyn_from_device ? c->d_dyn : nullptr;
+    a.dyn = make_dyn(c, c->lights[0]);
+    a.dyn_ptr = dyn_from_device ? &c->d_lights->lights.l[0] : nullptr;
     a.count = c->grid.count[set];
     a.slots = c->grid.slots;
     a.sprites = c->d_sprites;
@@ -551,6 +598,31 @@ par_lights_dyn make_lights_dyn(const par_context* c) {
     return lights;
 }
 
+// What a frame's launches are sized by: (entity, bin) pairs, occupied columns (<= the columns the entities reach one by
+// one, <= their pairs) and render work items. A captured graph must also hold for later frames, whose counts are
+// unknown at capture time: what par_graph_stage accepts (graph_pair_bound; beyond it the caller captures again). After
+// asynchronous updates since the last blocking call: what the extents allow.
+par_bound frame_bounds(const par_context* c, bool graph_mode) {
+    if (graph_mode) return par_bound{c->graph_pair_bound, c->graph_pair_bound, c->graph_item_bound};
+    if (c->exact_stale) return par_bound{c->bound_pairs, c->bound_cols, c->bound_items};
+    return par_bound{c->total_pairs, c->total_cols, c->total_items};
+}
+
+// The hash build: small scenes in one launch, large ones in two (and frames that keep their kernels `apart`, and the
+// test hook). `fa`, `fill`: the share of the background fill that rides along, if any.
+int enqueue_build(par_context* ctx, hipStream_t stream, const par_bin_args& b, int64_t pair_bound,
+                  const par_render_args* fa, const par_fill_plan* fill, bool apart) {
+    const bool two_launches = apart || (ctx->hooks & PAR_HOOK_TWO_LAUNCHES);
+    const hipError_t be = two_launches ? hipErrorNotSupported : par_launch_build(ctx->grid, b, pair_bound, fa, fill, stream);
+    if (be == hipErrorNotSupported) {
+        PAR_HIP(par_launch_bin_insert(ctx->grid, b, fa, fill, stream));
+        PAR_HIP(par_launch_bin_resolve(ctx->grid, b, pair_bound, fa, fill, stream));
+    } else if (be != hipSuccess) {
+        return hip_fail(ctx, be, "par_launch_build");
+    }
+    return PAR_OK;
+}
+
 // A frame with several lights: the hash build, the background fill (after the background rays when they are wanted)
 // and one launch of the light kernel over the occupied columns. No column records, no work items, no overflow list.
 // Timed frames bracket the launches with the same events as enqueue_frame: the light kernel is ms_render and
@@ -558,41 +630,26 @@ par_lights_dyn make_lights_dyn(const par_context* c) {
 // launches are sized by what the graph accepts (graph_pair_bound) and the kernels read the lights from d_lights, which
 // the graph's copy node fills before them: one graph serves any count of lights.
 int enqueue_lights_frame(par_context* ctx, hipStream_t stream, const par_bin_args& b, const par_render_args& r,
-                         unsigned flags, bool graph_mode, hipEvent_t* ev) {
+                         const par_bound& bound, bool graph_mode, bool apart, hipEvent_t* ev) {
     const par_lights_dyn lights = make_lights_dyn(ctx);
-    if ((flags & PAR_RENDER_COUNT_RAYS) && !graph_mode) {
-        PAR_HIP(hipMemsetAsync(ctx->d_ray_counter, 0, sizeof(unsigned long long), stream));
-    }
-    const bool apart = ev && !(flags & PAR_RENDER_TIMED_AS_LAUNCHED);
-    const bool stale = ctx->exact_stale;
-    const int64_t pair_bound = graph_mode ? ctx->graph_pair_bound : (stale ? ctx->bound_pairs : ctx->total_pairs);
-    if (ev) PAR_HIP(hipEventRecord(ev[0], stream));
-    const bool two_launches = apart || (ctx->hooks & PAR_HOOK_TWO_LAUNCHES);
-    const hipError_t be = two_launches ? hipErrorNotSupported : par_launch_build(ctx->grid, b, pair_bound, &r, nullptr, stream);
-    if (be == hipErrorNotSupported) {
-        PAR_HIP(par_launch_bin_insert(ctx->grid, b, &r, nullptr, stream));
-        PAR_HIP(par_launch_bin_resolve(ctx->grid, b, pair_bound, &r, nullptr, stream));
-    } else if (be != hipSuccess) {
-        return hip_fail(ctx, be, "par_launch_build");
-    }
+    const int rc = enqueue_build(ctx, stream, b, bound.pairs, &r, nullptr, apart);
+    if (rc != PAR_OK) return rc;
     if (ev) {
-        PAR_HIP(hipEventRecord(ev[5], stream));
-        PAR_HIP(hipEventRecord(ev[1], stream));
+        PAR_HIP(hipEventRecord(ev[EV_BUILT], stream));
+        PAR_HIP(hipEventRecord(ev[EV_COLUMNS], stream));
     }
     if (r.trace_bg) {
         PAR_HIP(graph_mode ? par_launch_bglights(ctx->grid, r, &ctx->d_lights->lights, stream)
                            : par_launch_bglights(ctx->grid, r, lights, stream));
     }
     PAR_HIP(par_launch_fill(ctx->grid, r, stream));
-    if (ev) PAR_HIP(hipEventRecord(ev[3], stream));
-    // (occupied columns <= (entity, bin) pairs, as in enqueue_frame)
-    const int64_t col_bound = graph_mode ? pair_bound : (stale ? ctx->bound_cols : ctx->total_cols);
-    PAR_HIP(graph_mode ? par_launch_render_lights(ctx->grid, r, &ctx->d_lights->lights, col_bound, stream)
-                       : par_launch_render_lights(ctx->grid, r, lights, col_bound, stream));
+    if (ev) PAR_HIP(hipEventRecord(ev[EV_FILLED], stream));
+    PAR_HIP(graph_mode ? par_launch_render_lights(ctx->grid, r, &ctx->d_lights->lights, bound.cols, stream)
+                       : par_launch_render_lights(ctx->grid, r, lights, bound.cols, stream));
     if (ev) {
-        PAR_HIP(hipEventRecord(ev[6], stream));
-        PAR_HIP(hipEventRecord(ev[4], stream));
-        PAR_HIP(hipEventRecord(ev[2], stream));
+        PAR_HIP(hipEventRecord(ev[EV_ITEMS], stream));
+        PAR_HIP(hipEventRecord(ev[EV_RENDERED], stream));
+        PAR_HIP(hipEventRecord(ev[EV_END], stream));
         ctx->timed_tiles = false;
         ctx->timed_overflow = false;
         ctx->timed_both = false;
@@ -610,11 +667,7 @@ int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, 
         const size_t need = (size_t)(row_end - row_begin) * ctx->params.width;
         if (ctx->scratch_lit_bytes < need) {
             if (graph_mode) return fail(ctx, PAR_ERR_NOT_READY, "render once with PAR_RENDER_TRACE_BACKGROUND before capturing it");
-            if (ctx->d_scratch_lit) PAR_HIP(hipFree(ctx->d_scratch_lit));
-            ctx->d_scratch_lit = nullptr;
-            ctx->scratch_lit_bytes = 0;
-            PAR_HIP(hipMalloc(&ctx->d_scratch_lit, need));
-            ctx->scratch_lit_bytes = need;
+            PAR_HIP(grow(&ctx->d_scratch_lit, &ctx->scratch_lit_bytes, need));
         }
         outs.lit = ctx->d_scratch_lit;
     }
@@ -624,50 +677,38 @@ int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, 
     }
     const par_bin_args b = make_bin_args(ctx, set, row_begin, row_end, flags);
     par_render_args r = make_render_args(ctx, set, row_begin, row_end, outs, flags, graph_mode);
-    // (a captured graph takes the path of its kind, chosen when it is captured)
-    if (graph_mode ? ctx->graph_lights : lights_path(ctx)) return enqueue_lights_frame(ctx, stream, b, r, flags, graph_mode, ev);
-    // The overflow list is empty for sure while no column has more pairs than a record holds (a captured graph also
-    // serves later frames, whose columns nobody knows yet): then the frame has no launch for it, and the column
-    // kernel flags the frame should a column overflow all the same.
-    const bool may_overflow = graph_mode || ctx->cols_over > 0 || ctx->exact_stale || ctx->hist_stale || r.dense ||
-                              (ev && !(flags & PAR_RENDER_TIMED_AS_LAUNCHED));
-    r.overflow_launched = may_overflow ? 1 : 0;
+    // (a timed frame keeps its kernels apart unless it is asked to time the launches as a production frame makes them)
+    const bool apart = ev && !(flags & PAR_RENDER_TIMED_AS_LAUNCHED);
+    const par_bound bound = frame_bounds(ctx, graph_mode);
     if ((flags & PAR_RENDER_COUNT_RAYS) && !graph_mode) {
         PAR_HIP(hipMemsetAsync(ctx->d_ray_counter, 0, sizeof(unsigned long long), stream));
     }
-    if (ev) PAR_HIP(hipEventRecord(ev[0], stream));
+    if (ev) PAR_HIP(hipEventRecord(ev[EV_START], stream));
+    // (a captured graph takes the path of its kind, chosen when it is captured)
+    if (graph_mode ? ctx->graph_lights : lights_path(ctx)) {
+        return enqueue_lights_frame(ctx, stream, b, r, bound, graph_mode, apart, ev);
+    }
+    // The overflow list is empty for sure while no column has more pairs than a record holds (a captured graph also
+    // serves later frames, whose columns nobody knows yet): then the frame has no launch for it, and the column
+    // kernel flags the frame should a column overflow all the same.
+    const bool may_overflow = graph_mode || ctx->cols_over > 0 || ctx->exact_stale || ctx->hist_stale || r.dense || apart;
+    r.overflow_launched = may_overflow ? 1 : 0;
     // The background fill depends on nothing earlier in the frame and the render kernels come after all of it: when
     // it is the plain streaming one it rides along with the first three launches (timed runs keep all kernels apart
     // so that the event pairs bracket single ones).
     par_fill_plan plan;
-    // (a timed frame keeps its kernels apart unless it is asked to time the launches as a production frame makes them)
-    const bool apart = ev && !(flags & PAR_RENDER_TIMED_AS_LAUNCHED);
     const bool ride = !apart && par_plan_fill(r, &plan);
     par_render_args rf = r;  // what rides along: the frame and palette-index planes
     rf.out.lit = nullptr;
-    // A captured graph must also hold for later frames, whose pair count is unknown at capture time: the bound is
-    // what par_graph_stage accepts (graph_pair_bound); beyond it the caller captures again.
-    const bool stale = ctx->exact_stale;  // (asynchronous updates since the last blocking call: extents-only bounds)
-    const int64_t pair_bound = graph_mode ? ctx->graph_pair_bound : (stale ? ctx->bound_pairs : ctx->total_pairs);
-    // small scenes build the hash in one launch, large ones in two (timed runs keep the kernels apart)
-    const bool two_launches = apart || (ctx->hooks & PAR_HOOK_TWO_LAUNCHES);
-    hipError_t be = two_launches ? hipErrorNotSupported
-                                 : par_launch_build(ctx->grid, b, pair_bound, &rf, ride ? &plan : nullptr, stream);
-    if (be == hipErrorNotSupported) {
-        PAR_HIP(par_launch_bin_insert(ctx->grid, b, &rf, ride ? &plan : nullptr, stream));
-        PAR_HIP(par_launch_bin_resolve(ctx->grid, b, pair_bound, &rf, ride ? &plan : nullptr, stream));
-    } else if (be != hipSuccess) {
-        return hip_fail(ctx, be, "par_launch_build");
-    }
-    if (ev) PAR_HIP(hipEventRecord(ev[5], stream));  // (behind the hash build)
-    // occupied columns <= the columns the entities reach one by one (<= their (entity, bin) pairs)
-    const int64_t col_bound = graph_mode ? pair_bound : (stale ? ctx->bound_cols : ctx->total_cols);
+    const int rc = enqueue_build(ctx, stream, b, bound.pairs, &rf, ride ? &plan : nullptr, apart);
+    if (rc != PAR_OK) return rc;
+    if (ev) PAR_HIP(hipEventRecord(ev[EV_BUILT], stream));
     if (ride) {
-        PAR_HIP(par_launch_columns_fill(ctx->grid, rf, col_bound, plan, ctx->col_roles, stream));
+        PAR_HIP(par_launch_columns_fill(ctx->grid, rf, bound.cols, plan, ctx->col_roles, stream));
     } else {
-        PAR_HIP(par_launch_columns(ctx->grid, r, col_bound, ctx->col_roles, stream));
+        PAR_HIP(par_launch_columns(ctx->grid, r, bound.cols, ctx->col_roles, stream));
     }
-    if (ev) PAR_HIP(hipEventRecord(ev[1], stream));
+    if (ev) PAR_HIP(hipEventRecord(ev[EV_COLUMNS], stream));
     // Otherwise the fill follows on the same stream. (Forking it onto a second stream beside the build was measured
     // slower, alone and with several frames in flight: the cross-stream events cost more than the overlap gains.)
     // It follows the column kernels because, when background rays are traced, it copies their results into the lit
@@ -680,14 +721,13 @@ int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, 
         rl.out.palidx = nullptr;
         PAR_HIP(par_launch_fill(ctx->grid, rl, stream));
     }
-    if (ev) PAR_HIP(hipEventRecord(ev[3], stream));
+    if (ev) PAR_HIP(hipEventRecord(ev[EV_FILLED], stream));
     // work items <= what the entities can cause one by one, and <= every column of the rendered rows as a whole tile
     const int64_t item_cap_rows = max_items(ctx) / ctx->gy * (r.by_hi - r.by_lo + 1);
-    const int64_t item_bound = std::min(graph_mode ? ctx->graph_item_bound : (stale ? ctx->bound_items : ctx->total_items),
-                                        item_cap_rows);
+    const int64_t item_bound = std::min(bound.items, item_cap_rows);
     bool both = false;
     if (!apart) {  // small frames: one launch for both render kernels
-        const hipError_t e = par_launch_render_both(ctx->grid, r, col_bound, item_bound, may_overflow, stream);
+        const hipError_t e = par_launch_render_both(ctx->grid, r, bound.cols, item_bound, may_overflow, stream);
         if (e == hipSuccess) {
             both = true;
         } else if (e != hipErrorNotSupported) {
@@ -696,14 +736,14 @@ int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, 
     }
     if (!both) {
         PAR_HIP(par_launch_render(ctx->grid, r, item_bound, stream));
-        if (ev) PAR_HIP(hipEventRecord(ev[6], stream));
+        if (ev) PAR_HIP(hipEventRecord(ev[EV_ITEMS], stream));
         PAR_HIP(par_launch_render_tiles(ctx->grid, r, item_bound, stream));  // (dense frames only: r.tile_k > 0)
     } else if (ev) {
-        PAR_HIP(hipEventRecord(ev[6], stream));
+        PAR_HIP(hipEventRecord(ev[EV_ITEMS], stream));
     }
-    if (ev) PAR_HIP(hipEventRecord(ev[4], stream));
-    if (!both && may_overflow) PAR_HIP(par_launch_render_overflow(ctx->grid, r, col_bound, stream));
-    if (ev) PAR_HIP(hipEventRecord(ev[2], stream));
+    if (ev) PAR_HIP(hipEventRecord(ev[EV_RENDERED], stream));
+    if (!both && may_overflow) PAR_HIP(par_launch_render_overflow(ctx->grid, r, bound.cols, stream));
+    if (ev) PAR_HIP(hipEventRecord(ev[EV_END], stream));
     if (ev) {  // which of the optional launches this frame had (par_frame_stats::ms_launch)
         ctx->timed_tiles = !both && r.tile_k > 0;
         ctx->timed_overflow = !both && may_overflow;
@@ -713,14 +753,8 @@ int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, 
 }
 
 int render_to_host(par_context* ctx, int row_begin, int row_end, const par_outputs* host_out, unsigned flags) {
-    if (!ctx || !host_out) return fail(ctx, PAR_ERR_INVALID_ARG, "null argument");
-    int rc = check_flags(ctx, flags);
+    int rc = frame_prologue(ctx, host_out, row_begin, row_end, flags);
     if (rc != PAR_OK) return rc;
-    rc = check_rows(ctx, row_begin, row_end);
-    if (rc != PAR_OK) return rc;
-    rc = check_ready(ctx);
-    if (rc != PAR_OK) return rc;
-    PAR_HIP(hipSetDevice(ctx->device));
     void* host[5] = {host_out->fb, host_out->gbuf, host_out->palidx, host_out->brightness, host_out->lit};
     const size_t n = (size_t)(row_end - row_begin) * ctx->params.width;
     void* dev[5];
@@ -728,13 +762,7 @@ int render_to_host(par_context* ctx, int row_begin, int row_end, const par_outpu
         dev[i] = nullptr;
         if (!host[i]) continue;
         const size_t bytes = n * kPlaneElem[i];
-        if (ctx->d_out_bytes[i] < bytes) {
-            if (ctx->d_out[i]) PAR_HIP(hipFree(ctx->d_out[i]));
-            ctx->d_out[i] = nullptr;
-            ctx->d_out_bytes[i] = 0;
-            PAR_HIP(hipMalloc(&ctx->d_out[i], bytes));
-            ctx->d_out_bytes[i] = bytes;
-        }
+        if (ctx->d_out_bytes[i] < bytes) PAR_HIP(grow(&ctx->d_out[i], &ctx->d_out_bytes[i], bytes));
         dev[i] = ctx->d_out[i];
     }
     par_outputs d{(par_color*)dev[0], (par_pixel*)dev[1], (uint8_t*)dev[2], (float*)dev[3], (uint8_t*)dev[4]};
@@ -747,6 +775,40 @@ int render_to_host(par_context* ctx, int row_begin, int row_end, const par_outpu
     }
     PAR_HIP(hipStreamSynchronize(ctx->stream));
     return check_device_error(ctx);
+}
+
+// The context's fixed device buffers: par_create allocates those of more than 0 bytes and sets every byte of those
+// with a fill, par_destroy frees them all. (What grows on demand is freed beside them.)
+struct par_dev_buffer {
+    void** ptr;
+    size_t bytes;
+    int fill;  // the byte the buffer starts with, or -1
+};
+
+std::array<par_dev_buffer, 19> dev_buffers(par_context* c, bool stamps) {
+    par_grid_dev& g = c->grid;
+    const size_t vol = (size_t)c->volume, cols = (size_t)c->gx * c->gy, i32 = sizeof(int32_t);
+    return {{
+        {(void**)&g.head[0], vol * i32, -1},
+        {(void**)&g.head[1], vol * i32, -1},
+        {(void**)&g.count[0], vol, -1},
+        {(void**)&g.count[1], vol, -1},
+        {(void**)&g.colflag[0], cols * i32, -1},
+        {(void**)&g.colflag[1], cols * i32, -1},
+        {(void**)&g.col_list, cols * i32, -1},
+        {(void**)&g.slow_list, cols * i32, -1},
+        {(void**)&g.counters, PAR_CNT_TOTAL * i32, -1},
+        {(void**)&g.node_counter, 2 * i32, -1},
+        {(void**)&g.build_sync, 64 * i32, 0},
+        {(void**)&g.item_counters, (size_t)PAR_ITEM_LISTS * PAR_ITEM_SHARDS * PAR_ITEM_COUNTER_STRIDE * i32, 0},
+        {(void**)&g.stamps, stamps ? (size_t)PAR_STAMP_ROWS * PAR_STAMP_WGS * PAR_STAMP_SLOTS * sizeof(unsigned long long) : 0, 0},
+        {(void**)&g.bgwalk, (size_t)c->gx * sizeof(par_bgwalk), -1},
+        {(void**)&g.bglit, (size_t)c->params.width + 64, 1},
+        {(void**)&g.slots, vol * PAR_SLOTS * sizeof(par_slot), 0},
+        {(void**)&c->d_palette, PAR_MAX_PALETTE * sizeof(par_color), -1},  // (par_create copies the palette in)
+        {(void**)&c->d_ray_counter, sizeof(unsigned long long), -1},
+        {(void**)&c->d_lights, sizeof(par_lights_block), -1},
+    }};
 }
 
 }  // namespace
@@ -803,39 +865,15 @@ static int par_create_impl(const par_params* params, int device, par_context** o
     hipError_t e;
     if ((e = hipSetDevice(device)) != hipSuccess) return bail(e);
     if ((e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) != hipSuccess) return bail(e);
-    for (int s = 0; s < 2; s++) {
-        if ((e = hipMalloc(&ctx->grid.head[s], (size_t)ctx->volume * sizeof(int32_t))) != hipSuccess) return bail(e);
-        if ((e = hipMalloc(&ctx->grid.count[s], (size_t)ctx->volume)) != hipSuccess) return bail(e);
-        if ((e = hipMalloc(&ctx->grid.colflag[s], (size_t)gx * gy * sizeof(int32_t))) != hipSuccess) return bail(e);
+    const char* dbg = std::getenv("PAR_DEBUG_STAMPS");
+    for (const par_dev_buffer& b : dev_buffers(ctx, dbg && dbg[0] == '1')) {
+        if (b.bytes == 0) continue;
+        if ((e = hipMalloc(b.ptr, b.bytes)) != hipSuccess) return bail(e);
+        if (b.fill >= 0 && (e = hipMemset(*b.ptr, b.fill, b.bytes)) != hipSuccess) return bail(e);
     }
-    if ((e = hipMalloc(&ctx->grid.col_list, (size_t)gx * gy * sizeof(int32_t))) != hipSuccess) return bail(e);
-    if ((e = hipMalloc(&ctx->grid.counters, PAR_CNT_TOTAL * sizeof(int32_t))) != hipSuccess) return bail(e);
-    if ((e = hipMalloc(&ctx->grid.build_sync, 64 * sizeof(int32_t))) != hipSuccess) return bail(e);
-    if ((e = hipMemset(ctx->grid.build_sync, 0, 64 * sizeof(int32_t))) != hipSuccess) return bail(e);
-    {
-        const size_t bytes = (size_t)PAR_ITEM_LISTS * PAR_ITEM_SHARDS * PAR_ITEM_COUNTER_STRIDE * sizeof(int32_t);
-        if ((e = hipMalloc(&ctx->grid.item_counters, bytes)) != hipSuccess) return bail(e);
-        if ((e = hipMemset(ctx->grid.item_counters, 0, bytes)) != hipSuccess) return bail(e);
-    }
-    if (const char* dbg = std::getenv("PAR_DEBUG_STAMPS"); dbg && dbg[0] == '1') {
-        const size_t bytes = (size_t)PAR_STAMP_ROWS * PAR_STAMP_WGS * PAR_STAMP_SLOTS * sizeof(unsigned long long);
-        if ((e = hipMalloc(&ctx->grid.stamps, bytes)) != hipSuccess) return bail(e);
-        if ((e = hipMemset(ctx->grid.stamps, 0, bytes)) != hipSuccess) return bail(e);
-    }
-    if ((e = hipMalloc(&ctx->grid.slow_list, (size_t)gx * gy * sizeof(int32_t))) != hipSuccess) return bail(e);
-    if ((e = hipMalloc(&ctx->grid.bgwalk, (size_t)gx * sizeof(par_bgwalk))) != hipSuccess) return bail(e);
-    if ((e = hipMalloc(&ctx->grid.bglit, (size_t)p.width + 64)) != hipSuccess) return bail(e);
-    if ((e = hipMemset(ctx->grid.bglit, 1, (size_t)p.width + 64)) != hipSuccess) return bail(e);
-    if ((e = hipMalloc(&ctx->grid.slots, (size_t)ctx->volume * PAR_SLOTS * sizeof(par_slot))) != hipSuccess) return bail(e);
-    if ((e = hipMalloc(&ctx->grid.node_counter, 2 * sizeof(int32_t))) != hipSuccess) return bail(e);
-    if ((e = hipMalloc(&ctx->d_palette, PAR_MAX_PALETTE * sizeof(par_color))) != hipSuccess) return bail(e);
-    if ((e = hipMalloc(&ctx->d_ray_counter, sizeof(unsigned long long))) != hipSuccess) return bail(e);
-    if ((e = hipMalloc(&ctx->d_dyn, sizeof(par_frame_dyn))) != hipSuccess) return bail(e);
-    if ((e = hipMalloc(&ctx->d_lights, sizeof(par_lights_block))) != hipSuccess) return bail(e);
     if ((e = hipMemcpy(ctx->d_palette, p.palette, PAR_MAX_PALETTE * sizeof(par_color), hipMemcpyHostToDevice)) != hipSuccess) return bail(e);
-    if ((e = hipMemset(ctx->grid.slots, 0, (size_t)ctx->volume * PAR_SLOTS * sizeof(par_slot))) != hipSuccess) return bail(e);
-    for (int i = 0; i < 7; i++) {
-        if ((e = hipEventCreate(&ctx->ev[i])) != hipSuccess) return bail(e);
+    for (hipEvent_t& ev : ctx->ev) {
+        if ((e = hipEventCreate(&ev)) != hipSuccess) return bail(e);
     }
     if (reset_grid(ctx) != PAR_OK) {
         par_destroy(ctx);
@@ -855,34 +893,23 @@ void par_destroy(par_context* ctx) {
     (void)hipDeviceSynchronize();
     drop_graphs(ctx);
     free_pool(ctx);
-    for (int s = 0; s < 2; s++) {
-        if (ctx->grid.head[s]) (void)hipFree(ctx->grid.head[s]);
-        if (ctx->grid.count[s]) (void)hipFree(ctx->grid.count[s]);
-        if (ctx->grid.colflag[s]) (void)hipFree(ctx->grid.colflag[s]);
+    for (const par_dev_buffer& b : dev_buffers(ctx, false)) {
+        if (*b.ptr) (void)hipFree(*b.ptr);
     }
-    void* lists[] = {ctx->grid.col_list, ctx->grid.counters, ctx->grid.slow_list, ctx->grid.stamps, ctx->grid.bgwalk,
-                     ctx->grid.bglit, ctx->d_scratch_lit, ctx->grid.items, ctx->grid.item_counters, ctx->grid.build_sync};
-    for (void* p : lists) {
+    void* grown[] = {ctx->d_scratch_lit, ctx->grid.items, ctx->d_aabbs, ctx->d_sprite_ids, ctx->d_sprites, ctx->d_texinfo,
+                     ctx->d_out[0], ctx->d_out[1], ctx->d_out[2], ctx->d_out[3], ctx->d_out[4]};
+    for (void* p : grown) {
         if (p) (void)hipFree(p);
-    }
-    void* ptrs[] = {ctx->grid.slots, ctx->grid.node_counter, ctx->d_palette, ctx->d_ray_counter, ctx->d_dyn,
-                    ctx->d_lights, ctx->d_aabbs, ctx->d_sprite_ids, ctx->d_sprites, ctx->d_texinfo};
-    for (void* p : ptrs) {
-        if (p) (void)hipFree(p);
-    }
-    for (int i = 0; i < 5; i++) {
-        if (ctx->d_out[i]) (void)hipFree(ctx->d_out[i]);
     }
     if (ctx->pin_update) (void)hipHostFree(ctx->pin_update);
     if (ctx->ev_update) (void)hipEventDestroy(ctx->ev_update);
     for (int s = 0; s < 2; s++) {
         if (ctx->pin_aabbs[s]) (void)hipHostFree(ctx->pin_aabbs[s]);
-        if (ctx->pin_dyn[s]) (void)hipHostFree(ctx->pin_dyn[s]);
         if (ctx->pin_lights[s]) (void)hipHostFree(ctx->pin_lights[s]);
         if (ctx->ev_graph[s]) (void)hipEventDestroy(ctx->ev_graph[s]);
     }
-    for (int i = 0; i < 7; i++) {
-        if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
+    for (hipEvent_t ev : ctx->ev) {
+        if (ev) (void)hipEventDestroy(ev);
     }
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -902,10 +929,8 @@ static int par_set_sprites_impl(par_context* ctx, const par_sprite* sprites, int
     PAR_HIP(hipSetDevice(ctx->device));
     PAR_HIP(hipDeviceSynchronize());
     drop_graphs(ctx);  // (a captured graph bakes the table's pointers)
-    if (ctx->d_sprites) PAR_HIP(hipFree(ctx->d_sprites));
-    ctx->d_sprites = nullptr;
     ctx->n_sprites = 0;
-    PAR_HIP(hipMalloc(&ctx->d_sprites, (size_t)n_sprites * sizeof(par_sprite)));
+    PAR_HIP(reallocate(&ctx->d_sprites, (size_t)n_sprites));
     PAR_HIP(hipMemcpy(ctx->d_sprites, sprites, (size_t)n_sprites * sizeof(par_sprite), hipMemcpyHostToDevice));
     // per-texel shading record: normal + the palette colour its index resolves to (alt:349-354)
     std::vector<par_texel> tex((size_t)n_sprites * PAR_SPRITE_TEXELS);
@@ -917,9 +942,7 @@ static int par_set_sprites_impl(par_context* ctx, const par_sprite* sprites, int
             x.rgba = (uint32_t)pc.red | ((uint32_t)pc.green << 8) | ((uint32_t)pc.blue << 16) | ((uint32_t)pc.alpha << 24);
         }
     }
-    if (ctx->d_texinfo) PAR_HIP(hipFree(ctx->d_texinfo));
-    ctx->d_texinfo = nullptr;
-    PAR_HIP(hipMalloc(&ctx->d_texinfo, tex.size() * sizeof(par_texel)));
+    PAR_HIP(reallocate(&ctx->d_texinfo, tex.size()));
     PAR_HIP(hipMemcpy(ctx->d_texinfo, tex.data(), tex.size() * sizeof(par_texel), hipMemcpyHostToDevice));
     ctx->n_sprites = n_sprites;
     return PAR_OK;
@@ -941,16 +964,9 @@ static int par_set_entities_impl(par_context* ctx, const par_aabb* aabbs, const 
     PAR_HIP(hipSetDevice(ctx->device));
     PAR_HIP(hipDeviceSynchronize());
     drop_graphs(ctx);
+    // (an entity's pairs are at most the grid's volume, which par_create holds below 2^30)
     std::vector<par_footprint> fps((size_t)n);
-    int64_t total = 0, total_cols = 0, total_items = 0;
-    for (int i = 0; i < n; i++) {
-        const par_footprint f = footprint_of(ctx, aabbs[i]);
-        if (f.pairs() > 0x7FFFFFFF) return fail(ctx, PAR_ERR_UNSUPPORTED, "entity spans too many bins");
-        fps[(size_t)i] = f;
-        total += f.pairs();
-        total_cols += f.cols();
-        total_items += f.items;
-    }
+    const par_bound total = footprints(ctx, aabbs, n, fps.data());
     // (pools and lists by what the extents allow: they then hold wherever the entities move)
     par_bound bt{0, 0, 0};
     for (int i = 0; i < n; i++) {
@@ -958,17 +974,11 @@ static int par_set_entities_impl(par_context* ctx, const par_aabb* aabbs, const 
         bt.pairs += b.pairs; bt.cols += b.cols; bt.items += b.items;
     }
     if (bt.pairs > 0x3FFFFFFF) return fail(ctx, PAR_ERR_UNSUPPORTED, "too many (entity, bin) pairs");
-    int rc = ensure_pool(ctx, std::max(total, bt.pairs));
+    int rc = ensure_pool(ctx, std::max(total.pairs, bt.pairs));
     if (rc != PAR_OK) return rc;
-    rc = ensure_items(ctx, std::max(total_items, bt.items), std::max(total_cols, bt.cols));
+    rc = ensure_items(ctx, std::max(total.items, bt.items), std::max(total.cols, bt.cols));
     if (rc != PAR_OK) return rc;
-    if (n > ctx->aabb_capacity) {
-        if (ctx->d_aabbs) PAR_HIP(hipFree(ctx->d_aabbs));
-        ctx->d_aabbs = nullptr;
-        ctx->aabb_capacity = 0;
-        PAR_HIP(hipMalloc(&ctx->d_aabbs, (size_t)std::max(n, 1) * sizeof(par_aabb)));
-        ctx->aabb_capacity = std::max(n, 1);
-    }
+    if (n > ctx->aabb_capacity) PAR_HIP(grow(&ctx->d_aabbs, &ctx->aabb_capacity, std::max(n, 1)));
     if (ctx->d_sprite_ids) PAR_HIP(hipFree(ctx->d_sprite_ids));
     ctx->d_sprite_ids = nullptr;
     if (n > 0) PAR_HIP(hipMemcpy(ctx->d_aabbs, aabbs, (size_t)n * sizeof(par_aabb), hipMemcpyHostToDevice));
@@ -977,16 +987,10 @@ static int par_set_entities_impl(par_context* ctx, const par_aabb* aabbs, const 
         PAR_HIP(hipMemcpy(ctx->d_sprite_ids, sprite_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     ctx->h_aabbs.assign(aabbs, aabbs + n);
-    ctx->h_colpairs.assign((size_t)ctx->gx * ctx->gy, 0);
-    ctx->cols_over = 0;
-    ctx->h_colchunks.assign((size_t)ctx->gx * ctx->gy, 0);
-    ctx->cols_tileable = 0;
-    for (int i = 0; i < n; i++) col_hist(ctx, fps[(size_t)i], +1);
     ctx->h_fp.swap(fps);
-    ctx->total_pairs = total;
-    ctx->total_cols = total_cols;
-    ctx->total_items = total_items;
+    ctx->total_pairs = total.pairs; ctx->total_cols = total.cols; ctx->total_items = total.items;
     ctx->bound_pairs = bt.pairs; ctx->bound_cols = bt.cols; ctx->bound_items = bt.items;
+    rebuild_hist(ctx);  // (current again, whatever par_graph_stage left behind)
     ctx->exact_stale = false;
     ctx->n_entities = n;
     ctx->max_sprite_id = max_id;
@@ -1037,19 +1041,16 @@ static int par_set_entities_ref_layout_impl(par_context* ctx, const par_aabb* aa
 }
 
 static int par_update_aabbs_impl(par_context* ctx, const par_aabb* aabbs, int first, int n) {
-    if (!ctx || !aabbs || first < 0 || n < 0 || !ctx->have_entities || first + n > ctx->n_entities) {
-        return fail(ctx, PAR_ERR_INVALID_ARG, "update range outside the uploaded entities");
-    }
-    for (int i = 0; i < n; i++) {
-        if (!extent_ok(aabbs[i])) return fail(ctx, PAR_ERR_EXTENT, "extent needs 0<=ex<=20, ey,ez>=0, ey+ez<=40");
-    }
+    if (!ctx) return PAR_ERR_INVALID_ARG;
+    int rc = check_update(ctx, aabbs, first, n, false);
+    if (rc != PAR_OK) return rc;
     refresh_exact(ctx);  // (asynchronous updates may have left the exact bookkeeping behind)
     par_update_plan plan;
     plan_update(ctx, aabbs, first, n, &plan);
     par_bound bt;
     bounds_after(ctx, aabbs, first, n, &bt);
     PAR_HIP(hipSetDevice(ctx->device));
-    int rc = ensure_pool(ctx, std::max(plan.pairs, bt.pairs));
+    rc = ensure_pool(ctx, std::max(plan.pairs, bt.pairs));
     if (rc != PAR_OK) return rc;
     rc = ensure_items(ctx, std::max(plan.items, bt.items), std::max(plan.cols, bt.cols));
     if (rc != PAR_OK) return rc;
@@ -1061,19 +1062,16 @@ static int par_update_aabbs_impl(par_context* ctx, const par_aabb* aabbs, int fi
     }
     PAR_HIP(hipMemcpyAsync(ctx->d_aabbs + first, aabbs, (size_t)n * sizeof(par_aabb), hipMemcpyHostToDevice, ctx->stream));
     PAR_HIP(hipStreamSynchronize(ctx->stream));
-    commit_update(ctx, aabbs, first, n, plan);
+    commit_update(ctx, aabbs, first, n, plan, true);
     mark_staged(ctx, first, n);  // (a captured graph uploads the scene from its staging area)
     return PAR_OK;
 }
 
 static int par_update_aabbs_async_impl(par_context* ctx, const par_aabb* aabbs, int first, int n, void* stream_v) {
-    if (!ctx || !aabbs || first < 0 || n < 0 || !ctx->have_entities || first + n > ctx->n_entities) {
-        return fail(ctx, PAR_ERR_INVALID_ARG, "update range outside the uploaded entities");
-    }
+    if (!ctx) return PAR_ERR_INVALID_ARG;
+    const int rc = check_update(ctx, aabbs, first, n, false);
+    if (rc != PAR_OK) return rc;
     hipStream_t stream = (hipStream_t)stream_v;
-    for (int i = 0; i < n; i++) {
-        if (!extent_ok(aabbs[i])) return fail(ctx, PAR_ERR_EXTENT, "extent needs 0<=ex<=20, ey,ez>=0, ey+ez<=40");
-    }
     // No cull and range arithmetic here (it cost a moving scene more host time per frame than its launches): the
     // frame's launches are sized by what the EXTENTS allow (bound_of) until a blocking call refreshes the exact
     // bookkeeping, and the frame gets its launch for the overflow list whatever the columns hold.
@@ -1082,7 +1080,7 @@ static int par_update_aabbs_async_impl(par_context* ctx, const par_aabb* aabbs, 
     PAR_HIP(hipSetDevice(ctx->device));
     // the node pool and the item list grow rarely (only when extents grow); that path frees device memory and has to
     // wait for everything in flight
-    if (bt.pairs > ctx->grid.capacity || !items_fit(ctx, bt.items, bt.cols)) {
+    if (bt.pairs > ctx->grid.capacity || items_per_shard(ctx, bt.items, bt.cols) > ctx->grid.item_capacity) {
         return par_update_aabbs(ctx, aabbs, first, n);
     }
     // frames enqueued on another stream are not ordered with this copy: wait for them
@@ -1090,11 +1088,7 @@ static int par_update_aabbs_async_impl(par_context* ctx, const par_aabb* aabbs, 
     if (ctx->pin_update_capacity < ctx->aabb_capacity) {
         if (ctx->ev_update_pending) PAR_HIP(hipEventSynchronize(ctx->ev_update));
         ctx->ev_update_pending = false;
-        if (ctx->pin_update) PAR_HIP(hipHostFree(ctx->pin_update));
-        ctx->pin_update = nullptr;
-        ctx->pin_update_capacity = 0;
-        PAR_HIP(hipHostMalloc(&ctx->pin_update, (size_t)ctx->aabb_capacity * sizeof(par_aabb), hipHostMallocDefault));
-        ctx->pin_update_capacity = ctx->aabb_capacity;
+        PAR_HIP(grow(&ctx->pin_update, &ctx->pin_update_capacity, ctx->aabb_capacity, true));
     }
     if (!ctx->ev_update) PAR_HIP(hipEventCreateWithFlags(&ctx->ev_update, hipEventDisableTiming));
     // the staging area is free again once the previous update's copy has run (normally long ago)
@@ -1116,10 +1110,7 @@ static int par_set_lights_impl(par_context* ctx, const par_light* lights, int n)
     if (!ctx) return PAR_ERR_INVALID_ARG;
     if (n < 1 || n > PAR_MAX_LIGHTS) return fail(ctx, PAR_ERR_INVALID_ARG, "lights: n must lie in [1, PAR_MAX_LIGHTS]");
     if (!lights) return fail(ctx, PAR_ERR_INVALID_ARG, "lights");
-    for (int l = 0; l < n; l++) ctx->lights[l] = lights[l];
-    ctx->n_lights = n;
-    ctx->light = lights[0];
-    ctx->have_light = true;
+    set_lights(ctx, lights, n, n);
     return PAR_OK;
 }
 
@@ -1139,14 +1130,8 @@ static int par_render_rows_impl(par_context* ctx, int row_begin, int row_end, co
 
 static int par_render_device_impl(par_context* ctx, void* stream, int row_begin, int row_end, const par_outputs* device_out,
                       unsigned flags) {
-    if (!ctx || !device_out) return fail(ctx, PAR_ERR_INVALID_ARG, "null argument");
-    int rc = check_flags(ctx, flags);
+    int rc = frame_prologue(ctx, device_out, row_begin, row_end, flags);
     if (rc != PAR_OK) return rc;
-    rc = check_rows(ctx, row_begin, row_end);
-    if (rc != PAR_OK) return rc;
-    rc = check_ready(ctx);
-    if (rc != PAR_OK) return rc;
-    PAR_HIP(hipSetDevice(ctx->device));
     rc = enqueue_frame(ctx, (hipStream_t)stream, ctx->set, row_begin, row_end, *device_out, flags, false, nullptr);
     if (rc != PAR_OK) return rc;
     ctx->set ^= 1;
@@ -1158,32 +1143,27 @@ static int par_render_device_impl(par_context* ctx, void* stream, int row_begin,
 
 static int par_render_device_timed_impl(par_context* ctx, void* stream, int row_begin, int row_end,
                             const par_outputs* device_out, unsigned flags, par_frame_stats* stats) {
-    if (!ctx || !device_out) return fail(ctx, PAR_ERR_INVALID_ARG, "null argument");
-    int rc = check_flags(ctx, flags);
+    int rc = frame_prologue(ctx, device_out, row_begin, row_end, flags);
     if (rc != PAR_OK) return rc;
-    rc = check_rows(ctx, row_begin, row_end);
-    if (rc != PAR_OK) return rc;
-    rc = check_ready(ctx);
-    if (rc != PAR_OK) return rc;
-    PAR_HIP(hipSetDevice(ctx->device));
     rc = enqueue_frame(ctx, (hipStream_t)stream, ctx->set, row_begin, row_end, *device_out, flags, false, ctx->ev);
     if (rc != PAR_OK) return rc;
     ctx->set ^= 1;
     ctx->last_flags = flags;
-    PAR_HIP(hipEventSynchronize(ctx->ev[2]));
-    PAR_HIP(hipEventElapsedTime(&ctx->stats.ms_bin, ctx->ev[0], ctx->ev[1]));
-    PAR_HIP(hipEventElapsedTime(&ctx->stats.ms_fill, ctx->ev[1], ctx->ev[3]));
-    PAR_HIP(hipEventElapsedTime(&ctx->stats.ms_render, ctx->ev[3], ctx->ev[4]));
-    PAR_HIP(hipEventElapsedTime(&ctx->stats.ms_overflow, ctx->ev[4], ctx->ev[2]));
+    const hipEvent_t* ev = ctx->ev;
+    PAR_HIP(hipEventSynchronize(ev[EV_END]));
+    PAR_HIP(hipEventElapsedTime(&ctx->stats.ms_bin, ev[EV_START], ev[EV_COLUMNS]));
+    PAR_HIP(hipEventElapsedTime(&ctx->stats.ms_fill, ev[EV_COLUMNS], ev[EV_FILLED]));
+    PAR_HIP(hipEventElapsedTime(&ctx->stats.ms_render, ev[EV_FILLED], ev[EV_RENDERED]));
+    PAR_HIP(hipEventElapsedTime(&ctx->stats.ms_overflow, ev[EV_RENDERED], ev[EV_END]));
     for (float& v : ctx->stats.ms_launch) v = -1.f;
     ctx->stats.render_merged = 0;
     if (flags & PAR_RENDER_TIMED_AS_LAUNCHED) {
         ctx->stats.render_merged = ctx->timed_both ? 1 : 0;
-        PAR_HIP(hipEventElapsedTime(&ctx->stats.ms_launch[0], ctx->ev[0], ctx->ev[5]));
-        PAR_HIP(hipEventElapsedTime(&ctx->stats.ms_launch[1], ctx->ev[5], ctx->ev[3]));
-        PAR_HIP(hipEventElapsedTime(&ctx->stats.ms_launch[2], ctx->ev[3], ctx->ev[6]));
-        PAR_HIP(hipEventElapsedTime(&ctx->stats.ms_launch[3], ctx->ev[6], ctx->ev[4]));
-        PAR_HIP(hipEventElapsedTime(&ctx->stats.ms_launch[4], ctx->ev[4], ctx->ev[2]));
+        PAR_HIP(hipEventElapsedTime(&ctx->stats.ms_launch[0], ev[EV_START], ev[EV_BUILT]));
+        PAR_HIP(hipEventElapsedTime(&ctx->stats.ms_launch[1], ev[EV_BUILT], ev[EV_FILLED]));
+        PAR_HIP(hipEventElapsedTime(&ctx->stats.ms_launch[2], ev[EV_FILLED], ev[EV_ITEMS]));
+        PAR_HIP(hipEventElapsedTime(&ctx->stats.ms_launch[3], ev[EV_ITEMS], ev[EV_RENDERED]));
+        PAR_HIP(hipEventElapsedTime(&ctx->stats.ms_launch[4], ev[EV_RENDERED], ev[EV_END]));
         if (!ctx->timed_tiles) ctx->stats.ms_launch[3] = 0.f;  // (an empty bracket still measures the events themselves)
         if (!ctx->timed_overflow) ctx->stats.ms_launch[4] = 0.f;
     }
@@ -1194,19 +1174,14 @@ static int par_render_device_timed_impl(par_context* ctx, void* stream, int row_
 // par_graph_capture (lights_kind false: the one-light path) and par_graph_capture_lights (true: the light path).
 static int graph_capture(par_context* ctx, void* stream_v, int row_begin, int row_end, const par_outputs* device_out,
                          unsigned flags, bool lights_kind) {
-    if (!ctx || !device_out) return fail(ctx, PAR_ERR_INVALID_ARG, "null argument");
     hipStream_t stream = (hipStream_t)stream_v;
-    if (!stream) return fail(ctx, PAR_ERR_INVALID_ARG, "graph capture needs a non-default stream");
-    int rc = check_flags(ctx, flags);
-    if (rc != PAR_OK) return rc;
-    rc = check_rows(ctx, row_begin, row_end);
-    if (rc != PAR_OK) return rc;
-    rc = check_ready(ctx);
+    // (after the prologue's refusal of null arguments, before its other checks)
+    if (ctx && device_out && !stream) return fail(ctx, PAR_ERR_INVALID_ARG, "graph capture needs a non-default stream");
+    int rc = frame_prologue(ctx, device_out, row_begin, row_end, flags);
     if (rc != PAR_OK) return rc;
     if (!lights_kind && lights_path(ctx)) {
         return fail(ctx, PAR_ERR_UNSUPPORTED, "a frame with several lights cannot be captured (par_graph_capture_lights)");
     }
-    PAR_HIP(hipSetDevice(ctx->device));
     PAR_HIP(hipDeviceSynchronize());
     drop_graphs(ctx);
     refresh_exact(ctx);
@@ -1226,29 +1201,22 @@ static int graph_capture(par_context* ctx, void* stream_v, int row_begin, int ro
         if (!ctx->pin_aabbs[s]) {
             PAR_HIP(hipHostMalloc(&ctx->pin_aabbs[s], (size_t)std::max(ctx->aabb_capacity, 1) * sizeof(par_aabb), hipHostMallocDefault));
         }
-        if (!ctx->pin_dyn[s]) PAR_HIP(hipHostMalloc(&ctx->pin_dyn[s], sizeof(par_frame_dyn), hipHostMallocDefault));
-        if (lights_kind && !ctx->pin_lights[s]) {
-            PAR_HIP(hipHostMalloc(&ctx->pin_lights[s], sizeof(par_lights_block), hipHostMallocDefault));
-        }
+        if (!ctx->pin_lights[s]) PAR_HIP(hipHostMalloc(&ctx->pin_lights[s], sizeof(par_lights_block), hipHostMallocDefault));
         if (!ctx->ev_graph[s]) PAR_HIP(hipEventCreateWithFlags(&ctx->ev_graph[s], hipEventDisableTiming));
         ctx->ev_graph_pending[s] = false;
         std::memcpy(ctx->pin_aabbs[s], ctx->h_aabbs.data(), (size_t)ctx->n_entities * sizeof(par_aabb));
-        *ctx->pin_dyn[s] = make_dyn(ctx, ctx->light);
-        if (lights_kind) ctx->pin_lights[s]->lights = make_lights_dyn(ctx);
+        ctx->pin_lights[s]->lights = make_lights_dyn(ctx);
         ctx->stage_lo[s] = ctx->stage_hi[s] = 0;
     }
     ctx->graph_lights = lights_kind;  // (what enqueue_frame captures; no graph is left behind should the capture fail)
     // The frame alternates between the two grid sets, and a captured kernel node bakes its pointers: one graph
-    // per set, launched alternately; each uploads the scene from its own staging area (the light path: the AABBs and
-    // the lights, ahead of every kernel of the frame).
+    // per set, launched alternately; each uploads the scene from its own staging area (the AABBs and the lights,
+    // ahead of every kernel of the frame).
     for (int s = 0; s < 2; s++) {
         PAR_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
         hipError_t e = hipMemcpyAsync(ctx->d_aabbs, ctx->pin_aabbs[s], (size_t)ctx->n_entities * sizeof(par_aabb),
                                       hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess && !lights_kind) {
-            e = hipMemcpyAsync(ctx->d_dyn, ctx->pin_dyn[s], sizeof(par_frame_dyn), hipMemcpyHostToDevice, stream);
-        }
-        if (e == hipSuccess && lights_kind) {
+        if (e == hipSuccess) {
             e = hipMemcpyAsync(ctx->d_lights, ctx->pin_lights[s], sizeof(par_lights_block), hipMemcpyHostToDevice, stream);
         }
         int erc = PAR_OK;
@@ -1273,45 +1241,10 @@ static int graph_capture(par_context* ctx, void* stream_v, int row_begin, int ro
     return PAR_OK;
 }
 
-static int par_graph_capture_impl(par_context* ctx, void* stream_v, int row_begin, int row_end, const par_outputs* device_out,
-                      unsigned flags) {
-    return graph_capture(ctx, stream_v, row_begin, row_end, device_out, flags, false);
-}
-
-static int par_graph_capture_lights_impl(par_context* ctx, void* stream_v, int row_begin, int row_end,
-                                         const par_outputs* device_out, unsigned flags) {
-    return graph_capture(ctx, stream_v, row_begin, row_end, device_out, flags, true);
-}
-
-// The checks of par_graph_stage for AABBs [first, first + n), with the plan of the update when they pass. They change
-// nothing but the freshness of the exact bookkeeping.
-static int graph_stage_check(par_context* ctx, const par_aabb* aabbs, int first, int n, par_update_plan* plan) {
-    if (n < 0 || first < 0 || first + n > ctx->n_entities || (n > 0 && !aabbs)) return fail(ctx, PAR_ERR_INVALID_ARG, "stage range");
-    for (int i = 0; i < n; i++) {
-        if (!extent_ok(aabbs[i])) return fail(ctx, PAR_ERR_EXTENT, "extent needs 0<=ex<=20, ey,ez>=0, ey+ez<=40");
-    }
-    if (ctx->exact_stale) refresh_exact(ctx);  // (the footprints and totals; the histograms may stay behind)
-    plan_update(ctx, aabbs, first, n, plan);
-
-    if (plan->pairs > ctx->graph_pair_bound || plan->pairs > ctx->grid.capacity) {
-        return fail(ctx, PAR_ERR_UNSUPPORTED, "staged frame exceeds what the captured graph was sized for; capture again");
-    }
-    return PAR_OK;
-}
-
-static int par_graph_stage_impl(par_context* ctx, const par_aabb* aabbs, int first, int n, const par_light* light) {
-    if (!ctx || !ctx->graph_exec[0]) return fail(ctx, PAR_ERR_NOT_READY, "no captured graph");
-    par_update_plan plan;
-    const int rc = graph_stage_check(ctx, aabbs, first, n, &plan);
-    if (rc != PAR_OK) return rc;
-    commit_update_totals(ctx, aabbs, first, n, plan);
-    mark_staged(ctx, first, n);  // (the staging areas are brought up to date by par_graph_launch)
-    if (light) ctx->light = ctx->lights[0] = *light;
-    return PAR_OK;
-}
-
-static int par_graph_stage_lights_impl(par_context* ctx, const par_aabb* aabbs, int first, int n,
-                                       const par_light* lights, int n_lights) {
+// par_graph_stage (keep_count: `lights` replaces lights[0] and the count stays) and par_graph_stage_lights (the whole
+// light set) for AABBs [first, first + n). A refused call changes nothing but the freshness of the exact bookkeeping.
+static int graph_stage(par_context* ctx, const par_aabb* aabbs, int first, int n, const par_light* lights, int n_lights,
+                       bool keep_count) {
     if (!ctx || !ctx->graph_exec[0]) return fail(ctx, PAR_ERR_NOT_READY, "no captured graph");
     if (n_lights < 0 || n_lights > PAR_MAX_LIGHTS || (lights == nullptr) != (n_lights == 0)) {
         return fail(ctx, PAR_ERR_INVALID_ARG, "lights: NULL with 0, or 1 <= n_lights <= PAR_MAX_LIGHTS");
@@ -1319,16 +1252,17 @@ static int par_graph_stage_lights_impl(par_context* ctx, const par_aabb* aabbs, 
     if (n_lights > 1 && !ctx->graph_lights) {
         return fail(ctx, PAR_ERR_UNSUPPORTED, "a one-light graph cannot render several lights (par_graph_capture_lights)");
     }
-    par_update_plan plan;
-    const int rc = graph_stage_check(ctx, aabbs, first, n, &plan);
+    const int rc = check_update(ctx, aabbs, first, n, true);
     if (rc != PAR_OK) return rc;
-    commit_update_totals(ctx, aabbs, first, n, plan);
-    mark_staged(ctx, first, n);  // (the staging areas are brought up to date by par_graph_launch)
-    if (n_lights > 0) {  // (as par_set_lights)
-        for (int l = 0; l < n_lights; l++) ctx->lights[l] = lights[l];
-        ctx->n_lights = n_lights;
-        ctx->light = lights[0];
+    if (ctx->exact_stale) refresh_exact(ctx);  // (the footprints and totals; the histograms may stay behind)
+    par_update_plan plan;
+    plan_update(ctx, aabbs, first, n, &plan);
+    if (plan.pairs > ctx->graph_pair_bound || plan.pairs > ctx->grid.capacity) {
+        return fail(ctx, PAR_ERR_UNSUPPORTED, "staged frame exceeds what the captured graph was sized for; capture again");
     }
+    commit_update(ctx, aabbs, first, n, plan, false);
+    mark_staged(ctx, first, n);  // (the staging areas are brought up to date by par_graph_launch)
+    if (n_lights > 0) set_lights(ctx, lights, n_lights, keep_count ? ctx->n_lights : n_lights);
     return PAR_OK;
 }
 
@@ -1356,11 +1290,7 @@ static int par_graph_launch_impl(par_context* ctx, void* stream) {
                     (size_t)(ctx->stage_hi[s] - ctx->stage_lo[s]) * sizeof(par_aabb));
         ctx->stage_lo[s] = ctx->stage_hi[s] = 0;
     }
-    if (ctx->graph_lights) {
-        ctx->pin_lights[s]->lights = make_lights_dyn(ctx);
-    } else {
-        *ctx->pin_dyn[s] = make_dyn(ctx, ctx->light);
-    }
+    ctx->pin_lights[s]->lights = make_lights_dyn(ctx);
     // an asynchronous scene update on another stream: this frame comes after it
     if (ctx->ev_update_pending && ctx->update_stream != (hipStream_t)stream) {
         PAR_HIP(hipStreamWaitEvent((hipStream_t)stream, ctx->ev_update, 0));
@@ -1578,18 +1508,18 @@ int par_read_grid(par_context* ctx, int32_t* count, int32_t* map, par_aabb* bins
     return guarded(ctx, [&] { return par_read_grid_impl(ctx, count, map, bins); });
 }
 int par_graph_capture(par_context* ctx, void* stream_v, int row_begin, int row_end, const par_outputs* device_out, unsigned flags) {
-    return guarded(ctx, [&] { return par_graph_capture_impl(ctx, stream_v, row_begin, row_end, device_out, flags); });
+    return guarded(ctx, [&] { return graph_capture(ctx, stream_v, row_begin, row_end, device_out, flags, false); });
 }
 int par_graph_stage(par_context* ctx, const par_aabb* aabbs, int first, int n, const par_light* light) {
-    return guarded(ctx, [&] { return par_graph_stage_impl(ctx, aabbs, first, n, light); });
+    return guarded(ctx, [&] { return graph_stage(ctx, aabbs, first, n, light, light ? 1 : 0, true); });
 }
 int par_graph_capture_lights(par_context* ctx, void* stream, int row_begin, int row_end, const par_outputs* device_out,
                              unsigned flags) {
-    return guarded(ctx, [&] { return par_graph_capture_lights_impl(ctx, stream, row_begin, row_end, device_out, flags); });
+    return guarded(ctx, [&] { return graph_capture(ctx, stream, row_begin, row_end, device_out, flags, true); });
 }
 int par_graph_stage_lights(par_context* ctx, const par_aabb* aabbs, int first, int n, const par_light* lights,
                            int n_lights) {
-    return guarded(ctx, [&] { return par_graph_stage_lights_impl(ctx, aabbs, first, n, lights, n_lights); });
+    return guarded(ctx, [&] { return graph_stage(ctx, aabbs, first, n, lights, n_lights, false); });
 }
 int par_get_stats(par_context* ctx, par_frame_stats* stats) {
     return guarded(ctx, [&] { return par_get_stats_impl(ctx, stats); });

@@ -105,8 +105,9 @@ struct par_bgwalk {
     par_slot rec[PAR_BIN_WALK];
 };
 
-// Per-frame values that change without the scene being re-uploaded. In the hipGraph path they live in device memory
-// (updated by a memcpy node); otherwise they travel as kernel arguments.
+// Per-frame values that change without the scene being re-uploaded. In the hipGraph path the kernels read them from
+// the first light of the graph's device copy of the lights (par_lights_dyn::l[0], updated by a memcpy node);
+// otherwise they travel as kernel arguments.
 struct par_frame_dyn {
     int32_t lx, ly, lz;     // lights[0] position (alt:712-714)
     int32_t lbx, lby, lbz;  // its bin (alt:729-732)

@@ -475,6 +475,31 @@ def test_graph_is_dropped_with_its_sprite_table_and_bad_alloc_hook_gives_oom(par
         assert r.render(("fb",))["fb"].shape[0] == 256 * 256
 
 
+def test_set_entities_after_graph_staging_needs_no_overflow_launch(par, sprite, T):
+    """par_graph_stage lets the per-column histograms lag; par_set_entities rebuilds them, so the frames after it are
+    enqueued without a launch for the overflow list again when no column needs one. The headline scene needs none
+    (a timed frame, timed as launched, shows no overflow launch); after a capture, a stage and par_set_entities of the
+    same scene, the same timed frame has none either, and the same picture."""
+    import torch
+    w = h = l = 4096
+    params = T.default_params(w, h, l)
+    aabbs, light = par.scene_synthetic(1024, w, h, l, 12345)
+    fb = [torch.zeros(w * h * 4, dtype=torch.uint8, device="cuda") for _ in range(2)]
+    stream = torch.cuda.Stream()
+    s = stream.cuda_stream
+    with par.Renderer(params) as r:
+        r.set_scene(aabbs, sprite, light)
+        st = r.render_device({"fb": fb[0].data_ptr()}, stream=s, timed=True, flags=par.RENDER_TIMED_AS_LAUNCHED)
+        assert st.ms_launch[4] == 0 and st.render_merged == 0, (list(st.ms_launch), st.render_merged)
+        r.graph_capture({"fb": fb[1].data_ptr()}, stream=s)
+        r.graph_stage(aabbs, 0)
+        r.set_entities(aabbs)
+        st = r.render_device({"fb": fb[1].data_ptr()}, stream=s, timed=True, flags=par.RENDER_TIMED_AS_LAUNCHED)
+        assert st.ms_launch[4] == 0, "par_set_entities left the per-column histograms marked stale"
+        stream.synchronize()
+        assert torch.equal(fb[0], fb[1])
+
+
 def test_config1_default_scene_128(par, oracle, sprite, T):
     """BASELINE config 1: 128x128 view of the reference's default graybox world (alt:517-599 parameterised on the
     view), light at (W, H/2, L/4) as alt:625-626 (its bin-x equals the grid width: the out-of-range case)."""
