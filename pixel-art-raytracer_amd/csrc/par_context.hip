@@ -632,6 +632,7 @@ int enqueue_build(par_context* ctx, hipStream_t stream, const par_bin_args& b, i
 int enqueue_lights_frame(par_context* ctx, hipStream_t stream, const par_bin_args& b, const par_render_args& r,
                          const par_bound& bound, bool graph_mode, bool apart, hipEvent_t* ev) {
     const par_lights_dyn lights = make_lights_dyn(ctx);
+    const par_lights_dyn* d_lights = graph_mode ? &ctx->d_lights->lights : nullptr;
     const int rc = enqueue_build(ctx, stream, b, bound.pairs, &r, nullptr, apart);
     if (rc != PAR_OK) return rc;
     if (ev) {
@@ -639,13 +640,11 @@ int enqueue_lights_frame(par_context* ctx, hipStream_t stream, const par_bin_arg
         PAR_HIP(hipEventRecord(ev[EV_COLUMNS], stream));
     }
     if (r.trace_bg) {
-        PAR_HIP(graph_mode ? par_launch_bglights(ctx->grid, r, &ctx->d_lights->lights, stream)
-                           : par_launch_bglights(ctx->grid, r, lights, stream));
+        PAR_HIP(par_launch_bglights(ctx->grid, r, lights, d_lights, stream));
     }
     PAR_HIP(par_launch_fill(ctx->grid, r, stream));
     if (ev) PAR_HIP(hipEventRecord(ev[EV_FILLED], stream));
-    PAR_HIP(graph_mode ? par_launch_render_lights(ctx->grid, r, &ctx->d_lights->lights, bound.cols, stream)
-                       : par_launch_render_lights(ctx->grid, r, lights, bound.cols, stream));
+    PAR_HIP(par_launch_render_lights(ctx->grid, r, lights, d_lights, bound.cols, stream));
     if (ev) {
         PAR_HIP(hipEventRecord(ev[EV_ITEMS], stream));
         PAR_HIP(hipEventRecord(ev[EV_RENDERED], stream));

@@ -267,18 +267,15 @@ hipError_t par_launch_render_overflow(const par_grid_dev& g, const par_render_ar
 // A frame with several lights (or one, forced by a test hook): after the hash build, every occupied column of col_list
 // in one launch of render_lights_kernel (`column_bound` as for par_launch_columns). The column, item, tile and overflow
 // kernels do not run.
+// The kernels take `lights` as a kernel argument, or, when `d_lights` is not null (a captured graph), read the frame's
+// lights from that device memory (a copy node of the graph fills it before them), once per workgroup, so one graph
+// serves any count of lights.
 hipError_t par_launch_render_lights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,
-                                    int64_t column_bound, hipStream_t stream);
+                                    const par_lights_dyn* d_lights, int64_t column_bound, hipStream_t stream);
 // The background rays of such a frame (one per x and light, bit l of g.bglit[x] for light l); par_launch_fill then
-// copies them into the lit plane.
+// copies them into the lit plane. `lights`, `d_lights` as above.
 hipError_t par_launch_bglights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,
-                               hipStream_t stream);
-// The same two launches for a captured graph: the kernels read the frame's lights from `d_lights` (device memory a
-// copy node of the graph fills before them), once per workgroup, so one graph serves any count of lights.
-hipError_t par_launch_render_lights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn* d_lights,
-                                    int64_t column_bound, hipStream_t stream);
-hipError_t par_launch_bglights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn* d_lights,
-                               hipStream_t stream);
+                               const par_lights_dyn* d_lights, hipStream_t stream);
 
 // Sharded frames: tiles between a frame block and packed slots, and the background colour for whole rows.
 hipError_t par_launch_tiles_copy(bool pack, const int32_t* d_tiles, int n, int W, int H, int B, int row_begin, int row_end,

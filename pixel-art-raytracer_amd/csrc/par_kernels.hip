@@ -243,20 +243,16 @@ __global__ __launch_bounds__(256) void bin_insert_kernel(par_grid_dev g, par_bin
     stamp(g, a.flags, 0, 7);
 }
 
-// `tid` of `n_threads` (one thread per node, or a grid-stride loop over the nodes when the launch is smaller).
-template <bool COH>
-__device__ __forceinline__ void bin_resolve_node(const par_grid_dev& g, const par_bin_args& a, int tid);
-
-template <bool COH = false>
-__device__ __forceinline__ void bin_resolve_body(const par_grid_dev& g, const par_bin_args& a, int block, int n_blocks) {
-    const int tid0 = block * blockDim.x + threadIdx.x;
-    const int s = a.set;
-    // insert has consumed the other set's counter: free it for the next frame's inserts
-    if (tid0 == 0) g.node_counter[s ^ 1] = 0;
-    const int n_nodes = min(ld_shared<COH>(&g.node_counter[s]), g.capacity);
-    for (int tid = tid0; tid < n_nodes; tid += n_blocks * blockDim.x) bin_resolve_node<COH>(g, a, tid);
+// The slot record of entity `entity`, whose AABB is `box`.
+__device__ __forceinline__ par_slot slot_of(const par_aabb& box, int entity) {
+    par_slot rec;
+    rec.px = box.px; rec.py = box.py; rec.pz = box.pz;
+    rec.ex = box.ex; rec.ey = box.ey; rec.ez = box.ez;
+    rec.entity = entity;
+    return rec;
 }
 
+// Node `tid`: the thread of a bin's most recent insertion resolves the bin.
 template <bool COH>
 __device__ __forceinline__ void bin_resolve_node(const par_grid_dev& g, const par_bin_args& a, int tid) {
     const int s = a.set;
@@ -284,12 +280,7 @@ __device__ __forceinline__ void bin_resolve_node(const par_grid_dev& g, const pa
     for (int i = 0; i < 7; i++) {
         if (i < c) {  // slot c-1-i holds the (i+1)-th largest index: slots ascend in insertion order
             const int e = top[i];
-            const par_aabb box = a.aabbs[e];
-            par_slot rec;
-            rec.px = box.px; rec.py = box.py; rec.pz = box.pz;
-            rec.ex = box.ex; rec.ey = box.ey; rec.ez = box.ez;
-            rec.entity = e;
-            g.slots[(size_t)b * PAR_SLOTS + (c - 1 - i)] = rec;
+            g.slots[(size_t)b * PAR_SLOTS + (c - 1 - i)] = slot_of(a.aabbs[e], e);
         }
     }
     g.count[s][b] = (uint8_t)c;
@@ -309,6 +300,17 @@ __device__ __forceinline__ void bin_resolve_node(const par_grid_dev& g, const pa
             g.col_list[base + __popcll(m & ((1ull << lane) - 1ull))] = col;
         }
     }
+}
+
+// One thread per node, or a grid-stride loop over the nodes when the launch is smaller.
+template <bool COH = false>
+__device__ __forceinline__ void bin_resolve_body(const par_grid_dev& g, const par_bin_args& a, int block, int n_blocks) {
+    const int tid0 = block * blockDim.x + threadIdx.x;
+    const int s = a.set;
+    // insert has consumed the other set's counter: free it for the next frame's inserts
+    if (tid0 == 0) g.node_counter[s ^ 1] = 0;
+    const int n_nodes = min(ld_shared<COH>(&g.node_counter[s]), g.capacity);
+    for (int tid = tid0; tid < n_nodes; tid += n_blocks * blockDim.x) bin_resolve_node<COH>(g, a, tid);
 }
 
 __global__ __launch_bounds__(256) void bin_resolve_kernel(par_grid_dev g, par_bin_args a) {
@@ -424,6 +426,58 @@ __device__ __forceinline__ void normalize_l1_and_inverse(float x, float y, float
     }
 }
 
+// The direction towards light `l` from world point (x, y, z): towards_light = normalize_L1(light - world), alt:711-715
+// + spr:28-35, and its inverse, alt:717-719.
+struct LightDir {
+    float tx, ty, tz, ix, iy, iz;
+};
+__device__ __forceinline__ LightDir light_dir(const par_frame_dyn& l, int x, int y, int z) {
+    const float dx = (float)(l.lx - x), dy = (float)(l.ly - y), dz = (float)(l.lz - z);
+    LightDir d;
+    normalize_l1_and_inverse(dx, dy, dz, d.tx, d.ty, d.tz, d.ix, d.iy, d.iz);
+    return d;
+}
+// The diffuse term of a texel with normal n towards that light, alt:745-747 (no contraction).
+__device__ __forceinline__ float diffuse(const LightDir& d, float nx, float ny, float nz) {
+    const float dot = nx * d.tx + ny * d.ty + nz * d.tz;
+    return std_max(0.f, dot);
+}
+
+// The light of a one-light frame: the kernel argument, or where a captured graph's copy node leaves it (graph replay).
+__device__ __forceinline__ par_frame_dyn frame_dyn(const par_render_args& a) { return a.dyn_ptr ? *a.dyn_ptr : a.dyn; }
+
+// The G-buffer record of a pixel (par_pixel): normal, colour (RGBA little-endian), world y, z and entity.
+__device__ __forceinline__ par_pixel gbuf_pixel(float nx, float ny, float nz, uint32_t rgba, int y, int z, int entity) {
+    par_pixel p;
+    p.normal = par_vec3{nx, ny, nz};
+    p.color.red = (uint8_t)(rgba & 0xFF);
+    p.color.green = (uint8_t)((rgba >> 8) & 0xFF);
+    p.color.blue = (uint8_t)((rgba >> 16) & 0xFF);
+    p.color.alpha = (uint8_t)(rgba >> 24);
+    p.y = y;
+    p.z = z;
+    p.entity_index = entity;
+    return p;
+}
+// The pixels of screen column (bx, by) that a launch renders: columns [c0, c0 + tw) of the tile, rows
+// [rows_lo, rows_hi) (the tile's rows within the launch's row range). Nothing when tw or rows_hi - rows_lo is <= 0.
+struct TileRect {
+    int c0, tw, rows_lo, rows_hi;
+};
+__device__ __forceinline__ TileRect tile_rect(const par_render_args& a, int bx, int by) {
+    const int c0 = bx * a.B;
+    return TileRect{c0, min(a.B, a.W - c0), max(by * a.B, a.row_begin), min(min((by + 1) * a.B, a.H), a.row_end)};
+}
+
+// Row-major order over a rectangle `w` pixels wide: the row of pixel p is floor(p / w) == __umulhi(p, magic) for
+// p * w < 2^32; a 1-pixel-wide rectangle has no such multiplier.
+struct RowMajor {
+    int w;
+    uint32_t magic;
+    __device__ __forceinline__ int row(int p) const { return (w == 1) ? p : (int)__umulhi((uint32_t)p, magic); }
+};
+__device__ __forceinline__ RowMajor row_major(int w) { return RowMajor{w, (uint32_t)(0xFFFFFFFFu / (uint32_t)w) + 1u}; }
+
 // ------------------------------------------------------------------------------------------------------------
 // wave_walk: ONE wavefront walks from bin (sx, sy, sz) to the light's bin as trace_hash_for_light does
 // (alt:399-500) and stages the slot records of every occupied bin on the way (start bin excluded, alt:471-473) in
@@ -470,6 +524,14 @@ __device__ __forceinline__ void walk_chain_block(float& vx, float& vy, float& vz
 #else
     (void)vx; (void)vy; (void)vz; (void)sx; (void)sy; (void)sz; (void)lanes;
 #endif
+}
+
+// LDS written and read by the same wavefront: its LDS operations complete in order; keep the compiler from moving
+// reads above writes.
+__device__ __forceinline__ void wave_lds_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 __device__ int wave_walk(const par_grid_dev& g, const uint8_t* count, const par_slot* slots, const par_frame_dyn& dyn,
@@ -538,18 +600,8 @@ __device__ int wave_walk(const par_grid_dev& g, const uint8_t* count, const par_
         }
         n_rec += wave_total;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_fence();
     return n_rec;
-}
-
-// LDS written and read by the same wavefront: its LDS operations complete in order; keep the compiler from moving
-// reads above writes.
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -599,15 +651,14 @@ __device__ __forceinline__ void tile_chunk_box(const par_strips& st, int tw, int
 // against that box (one ballot per chunk). The render kernel reads a chunk's mask with one scalar load.
 __device__ __forceinline__ void tile_candidate_masks(const par_render_args& a, const ColWave& sm, par_colrec* rec,
                                                      int n_entries, uint64_t dup_mask, int bx, int by, int lane) {
-    const int c0 = bx * a.B, ty = by * a.B;
-    const int tw = min(a.B, a.W - c0);
-    const int rows_lo = max(ty, a.row_begin), rows_hi = min(min(ty + a.B, a.H), a.row_end);
-    const int rh = rows_hi - rows_lo;
+    const TileRect t = tile_rect(a, bx, by);
+    const int c0 = t.c0, tw = t.tw, ty = by * a.B;
+    const int rh = t.rows_hi - t.rows_lo;
     if (tw <= 0 || rh <= 0) return;
     const int tile_chunks = (tw * rh + 63) >> 6;
     const par_strips st = par_strips_of(tw);
     int b_r0, b_r1, b_q0, b_q1;
-    tile_chunk_box(st, tw, rh, rows_lo - ty, min(lane, tile_chunks - 1), b_r0, b_r1, b_q0, b_q1);
+    tile_chunk_box(st, tw, rh, t.rows_lo - ty, min(lane, tile_chunks - 1), b_r0, b_r1, b_q0, b_q1);
     int e_r0 = 0, e_r1 = 0, e_q0 = 0, e_q1 = 0;
     if (lane < n_entries && !((dup_mask >> lane) & 1)) {
         const par_slot r = sm.entries[lane];
@@ -646,9 +697,8 @@ __device__ __forceinline__ void columns_wave(const par_grid_dev& g, const par_re
     if (ci >= n_cols_bound) {
         const int bx = ci - n_cols_bound;
         if (!a.trace_bg || bx >= g.gx || role != 0) return;
-        const par_frame_dyn dyn = a.dyn_ptr ? *a.dyn_ptr : a.dyn;
         // world (x, 0, 0): ray_bin = (x / B, (H - 0 - 0) / B, 0), alt:724-727
-        const int n_rec = wave_walk(g, a.count, a.slots, dyn, bx, a.H / a.B, 0, sm.stage);
+        const int n_rec = wave_walk(g, a.count, a.slots, frame_dyn(a), bx, a.H / a.B, 0, sm.stage);
         par_bgwalk* out = g.bgwalk + bx;
         for (int r = lane; r < n_rec; r += 64) out->rec[r] = sm.stage[r];
         if (lane == 0) out->cnt = n_rec;
@@ -712,8 +762,8 @@ __device__ __forceinline__ void columns_wave(const par_grid_dev& g, const par_re
     // The column's share of its shard of the item list is reserved here, BEFORE the walks, with one atomic on one of
     // PAR_ITEM_SHARDS words that lie a cache line apart: its result is needed only after the walks, which hide its
     // latency.
-    const int c0 = bx * a.B, tw = min(a.B, a.W - c0);
-    const int rows_lo = max(by * a.B, a.row_begin), rows_hi = min(min((by + 1) * a.B, a.H), a.row_end);
+    const TileRect t = tile_rect(a, bx, by);
+    const int c0 = t.c0, tw = t.tw, rows_lo = t.rows_lo, rows_hi = t.rows_hi;
     const int tile_chunks = (tw * max(rows_hi - rows_lo, 0) + 63) >> 6;
     const int shard = ci & (PAR_ITEM_SHARDS - 1);
     int my_chunks = 0;
@@ -752,7 +802,7 @@ __device__ __forceinline__ void columns_wave(const par_grid_dev& g, const par_re
     int n_walk = 0;
     bool walk_failed = false;
     if (!overflow) {
-        const par_frame_dyn dyn = a.dyn_ptr ? *a.dyn_ptr : a.dyn;
+        const par_frame_dyn dyn = frame_dyn(a);
         for (int i = role; i < n_nb; i += ROLES) {
             const int sz = sm.nb[i].bz;
             const int n_rec = wave_walk(g, a.count, a.slots, dyn, bx, by, sz, sm.stage, i == 0 ? a.flags : 0u);
@@ -927,9 +977,58 @@ __global__ __launch_bounds__(col_waves<ROLES>() * 64) void columns_kernel(par_gr
     stamp(g, a.flags, 2, 7);
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// Per-lane shadow walk: trace_hash_for_light (alt:399-500) exactly as written, for the rare pixel whose shadow ray
+// starts in a bin that holds no primitive (negative world z, sprite depths outside the box) or whose walk was too
+// long to record, in the render kernels.
+// ------------------------------------------------------------------------------------------------------------
 __device__ bool lane_shadow_walk(const par_grid_dev& g, const uint8_t* count, const par_slot* slots, int sx, int sy,
                                  int sz, const par_frame_dyn& dyn, int self, int ox, int oy, int oz, float ix,
-                                 float iy, float iz);
+                                 float iy, float iz) {
+    const float bsx = (float)sx, bsy = (float)sy, bsz = (float)sz;             // alt:406-408
+    const float dx = (float)dyn.lbx - bsx, dy = (float)dyn.lby - bsy, dz = (float)dyn.lbz - bsz;  // alt:410-416
+    float largest = __builtin_fabsf(dx);                                          // alt:419-421
+    if (largest < __builtin_fabsf(dy)) largest = __builtin_fabsf(dy);
+    if (largest < __builtin_fabsf(dz)) largest = __builtin_fabsf(dz);
+    const float stx = dx / largest, sty = dy / largest, stz = dz / largest;       // alt:423-425
+    float cx = bsx, cy = bsy, cz = bsz, tx = bsx, ty = bsy, tz = bsz;             // alt:427-428
+    int counter = 0;                                                              // alt:429
+    const int start = flat_index(g.gy, g.gz, sx, sy, sz);                         // alt:430
+    for (int i = 0; i < (int)largest;) {                                          // alt:432
+        cx = tx; cy = ty; cz = tz;                                                // alt:436
+        if (counter == 0) { cx = tx + stx; counter++; }                           // alt:438-440
+        else if (counter == 1) { cy = ty + sty; counter++; }                      // alt:441-443
+        else if (counter == 2) { cz = tz + stz; counter++; }                      // alt:444-446
+        else if (counter == 3) { cx = tx + stx; cy = ty + sty; counter++; }       // alt:447-450
+        else if (counter == 4) { cx = tx + stx; cz = tz + stz; counter++; }       // alt:451-454
+        else if (counter == 5) { cy = ty + sty; cz = tz + stz; counter++; }       // alt:455-458
+        else {                                                                    // alt:459-466
+            cx = cx + stx; cy = cy + sty; cz = cz + stz;
+            tx = cx; ty = cy; tz = cz;
+            counter = 0;
+            i++;
+        }
+        const int b = flat_index(g.gy, g.gz, (int)cx, (int)cy, (int)cz);          // alt:468-470
+        if (b == start) continue;                                                 // alt:471-473
+        if (b < 0 || b >= g.volume) continue;  // out-of-range flat index reads as an empty bin (alt:476)
+        const int cnt = count[b];
+        for (int j = 0; j < cnt; j++) {                                           // alt:480
+            const par_slot rec = slots[(size_t)b * PAR_SLOTS + j];
+            if (rec.entity == self) continue;                                     // alt:484-487
+            if (slab_hit(rec, ox, oy, oz, ix, iy, iz)) return false;              // alt:489-491
+        }
+    }
+    return true;
+}
+
+// The background pixels of screen column x: world (x, 0, 0), normal 0, entity 0 (alt:281, 707-709). Their shadow rays
+// start in bin (x / B, H / B, 0) (alt:720-727); lane_shadow_walk traces one as the reference writes it (self = 0).
+struct BgRay {
+    int ox, bx, sy;
+};
+__device__ __forceinline__ BgRay bg_ray(const par_render_args& a, int x) {
+    return BgRay{(int)(int16_t)x, div_bin(x, a.magic_b), a.H / a.B};
+}
 
 // ------------------------------------------------------------------------------------------------------------
 // bgline_kernel: the shadow ray of the background pixels of screen column x (alt:704-742 for a texel with normal 0,
@@ -939,26 +1038,22 @@ __device__ bool lane_shadow_walk(const par_grid_dev& g, const uint8_t* count, co
 __global__ __launch_bounds__(256) void bgline_kernel(par_grid_dev g, par_render_args a) {
     const int x = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (x >= a.W) return;
-    const par_frame_dyn dyn = a.dyn_ptr ? *a.dyn_ptr : a.dyn;
-    // towards_light = normalize_L1(light - (x, 0, 0)), alt:711-715 + spr:28-35
-    const float dx = (float)(dyn.lx - x), dy = (float)(dyn.ly - 0), dz = (float)(dyn.lz - 0);
-    float tx, ty, tz, inv_x, inv_y, inv_z;
-    normalize_l1_and_inverse(dx, dy, dz, tx, ty, tz, inv_x, inv_y, inv_z);  // alt:711-719
-    const int ox = (int)(int16_t)x;                                    // alt:720-722
-    const int bx = div_bin(x, a.magic_b), sy = a.H / a.B;              // alt:724-727
+    const par_frame_dyn dyn = frame_dyn(a);
+    const LightDir d = light_dir(dyn, x, 0, 0);
+    const BgRay ray = bg_ray(a, x);
     bool lit = true;
-    const par_bgwalk* w = g.bgwalk + bx;
+    const par_bgwalk* w = g.bgwalk + ray.bx;
     const int n = w->cnt;
     if (n >= 0) {
         for (int r = 0; r < n; r++) {
             const par_slot rec = w->rec[r];
-            if (rec.entity != 0 && slab_hit(rec, ox, 0, 0, inv_x, inv_y, inv_z)) {  // self = entity 0, alt:484-491
+            if (rec.entity != 0 && slab_hit(rec, ray.ox, 0, 0, d.ix, d.iy, d.iz)) {  // self = entity 0, alt:484-491
                 lit = false;
                 break;
             }
         }
     } else {
-        lit = lane_shadow_walk(g, a.count, a.slots, bx, sy, 0, dyn, 0, ox, 0, 0, inv_x, inv_y, inv_z);
+        lit = lane_shadow_walk(g, a.count, a.slots, ray.bx, ray.sy, 0, dyn, 0, ray.ox, 0, 0, d.ix, d.iy, d.iz);
     }
     g.bglit[x] = lit ? 1 : 0;
 }
@@ -1132,11 +1227,8 @@ __global__ __launch_bounds__(256) void build_fill_kernel(par_grid_dev g, par_bin
 __global__ __launch_bounds__(256) void fill_generic_kernel(par_render_args a, uint32_t out_rgba, int do_fb,
                                                             int do_pal, int do_lit, const uint8_t* bglit) {
     const long long npix = (long long)(a.row_end - a.row_begin) * a.W;
-    par_pixel px;
-    px.normal = par_vec3{0.f, 0.f, 0.f};
-    px.color.red = px.color.green = px.color.blue = (uint8_t)a.background;
-    px.color.alpha = 0;
-    px.y = 0; px.z = 0; px.entity_index = 0;
+    const uint32_t gray = (uint8_t)a.background;
+    const par_pixel px = gbuf_pixel(0.f, 0.f, 0.f, gray | (gray << 8) | (gray << 16), 0, 0, 0);
     for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix;
          p += (long long)gridDim.x * blockDim.x) {
         if (do_fb && a.out.fb) reinterpret_cast<uint32_t*>(a.out.fb)[p] = out_rgba;
@@ -1145,50 +1237,6 @@ __global__ __launch_bounds__(256) void fill_generic_kernel(par_render_args a, ui
         if (a.out.gbuf) a.out.gbuf[p] = px;
         if (do_lit && a.out.lit) a.out.lit[p] = bglit[p % a.W];
     }
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// Per-lane shadow walk: trace_hash_for_light (alt:399-500) exactly as written, for the rare pixel whose shadow ray
-// starts in a bin that holds no primitive (negative world z, sprite depths outside the box) or whose walk was too
-// long to record, in the render kernels.
-// ------------------------------------------------------------------------------------------------------------
-__device__ bool lane_shadow_walk(const par_grid_dev& g, const uint8_t* count, const par_slot* slots, int sx, int sy,
-                                 int sz, const par_frame_dyn& dyn, int self, int ox, int oy, int oz, float ix,
-                                 float iy, float iz) {
-    const float bsx = (float)sx, bsy = (float)sy, bsz = (float)sz;             // alt:406-408
-    const float dx = (float)dyn.lbx - bsx, dy = (float)dyn.lby - bsy, dz = (float)dyn.lbz - bsz;  // alt:410-416
-    float largest = __builtin_fabsf(dx);                                          // alt:419-421
-    if (largest < __builtin_fabsf(dy)) largest = __builtin_fabsf(dy);
-    if (largest < __builtin_fabsf(dz)) largest = __builtin_fabsf(dz);
-    const float stx = dx / largest, sty = dy / largest, stz = dz / largest;       // alt:423-425
-    float cx = bsx, cy = bsy, cz = bsz, tx = bsx, ty = bsy, tz = bsz;             // alt:427-428
-    int counter = 0;                                                              // alt:429
-    const int start = flat_index(g.gy, g.gz, sx, sy, sz);                         // alt:430
-    for (int i = 0; i < (int)largest;) {                                          // alt:432
-        cx = tx; cy = ty; cz = tz;                                                // alt:436
-        if (counter == 0) { cx = tx + stx; counter++; }                           // alt:438-440
-        else if (counter == 1) { cy = ty + sty; counter++; }                      // alt:441-443
-        else if (counter == 2) { cz = tz + stz; counter++; }                      // alt:444-446
-        else if (counter == 3) { cx = tx + stx; cy = ty + sty; counter++; }       // alt:447-450
-        else if (counter == 4) { cx = tx + stx; cz = tz + stz; counter++; }       // alt:451-454
-        else if (counter == 5) { cy = ty + sty; cz = tz + stz; counter++; }       // alt:455-458
-        else {                                                                    // alt:459-466
-            cx = cx + stx; cy = cy + sty; cz = cz + stz;
-            tx = cx; ty = cy; tz = cz;
-            counter = 0;
-            i++;
-        }
-        const int b = flat_index(g.gy, g.gz, (int)cx, (int)cy, (int)cz);          // alt:468-470
-        if (b == start) continue;                                                 // alt:471-473
-        if (b < 0 || b >= g.volume) continue;  // out-of-range flat index reads as an empty bin (alt:476)
-        const int cnt = count[b];
-        for (int j = 0; j < cnt; j++) {                                           // alt:480
-            const par_slot rec = slots[(size_t)b * PAR_SLOTS + j];
-            if (rec.entity == self) continue;                                     // alt:484-487
-            if (slab_hit(rec, ox, oy, oz, ix, iy, iz)) return false;              // alt:489-491
-        }
-    }
-    return true;
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1227,8 +1275,8 @@ struct OwnTexel {
     par_texel ti;
 };
 
-// DBG: the debug / instrumentation flags of the frame are looked at (ablation bits 24-26, time stamps bit 29, ray
-// counting); the production kernels are compiled without them.
+// DBG: the debug / instrumentation flags of the frame are looked at (time stamps bit 29, ray counting); the production
+// kernels are compiled without them.
 // IDS: the scene may have a sprite-id table (looked at at run time); without one (the render launch knows) every
 // entity uses sprite 0 and the table arithmetic (two 32-bit multiplies per candidate entry) is compiled out.
 // FULL: the parity planes (brightness, lit, G-buffer) may be asked for; a production frame (RGBA + palette index)
@@ -1376,13 +1424,9 @@ __device__ __forceinline__ void render_chunk(const par_grid_dev& g, const par_re
         nx = ti.nx; ny = ti.ny; nz = ti.nz;
         rgba = ti.rgba;
         const int wx = col, wy = p_y, wz = p_z;  // alt:707-709
-        // towards_light = normalize_L1(light - world), alt:711-715 + spr:28-35
-        const float dx = (float)(dyn.lx - wx), dy = (float)(dyn.ly - wy), dz = (float)(dyn.lz - wz);
-        float tx, ty, tz;
-        normalize_l1_and_inverse(dx, dy, dz, tx, ty, tz, inv_x, inv_y, inv_z);  // alt:711-719
-        const float dot = nx * tx + ny * ty + nz * tz;                     // alt:746-747 (no contraction)
-        const float diffuse = std_max(0.f, dot);                           // alt:745
-        b_lit = std_min(1.f, diffuse + ambient);                           // alt:758
+        const LightDir ld = light_dir(dyn, wx, wy, wz);
+        inv_x = ld.ix; inv_y = ld.iy; inv_z = ld.iz;
+        b_lit = std_min(1.f, diffuse(ld, nx, ny, nz) + ambient);          // alt:758
         // alt:725-726: the start bin's row is bin(H - wy - wz). wy + wz is world_j whatever the texel's depth (it is
         // subtracted from y and added to z, alt:356-361), and H - world_j is the pixel's screen row (alt:280; no
         // view is taller than a `short` holds, par_create): a row of this column's tile, whose bin row is `by`. The
@@ -1467,11 +1511,7 @@ __device__ __forceinline__ void render_chunk(const par_grid_dev& g, const par_re
                 }
                 need_walk = false;
             }
-            // the next walk overwrites the stage: every lane has read it (LDS operations of one wavefront complete
-            // in order; keep the compiler from moving them)
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_fence();  // (every lane has read the stage before the next walk overwrites it)
         }
     }
     if (hit) bright = lit ? b_lit : ambient;
@@ -1489,18 +1529,7 @@ __device__ __forceinline__ void render_chunk(const par_grid_dev& g, const par_re
         if (a.out.palidx) __builtin_nontemporal_store((uint8_t)pal_index, a.out.palidx + o);
         if (FULL && a.out.brightness) a.out.brightness[o] = bright;
         if (FULL && a.out.lit) a.out.lit[o] = lit_px ? 1 : 0;
-        if (FULL && a.out.gbuf) {
-            par_pixel pxl;
-            pxl.normal = par_vec3{nx, ny, nz};
-            pxl.color.red = (uint8_t)(rgba & 0xFF);
-            pxl.color.green = (uint8_t)((rgba >> 8) & 0xFF);
-            pxl.color.blue = (uint8_t)((rgba >> 16) & 0xFF);
-            pxl.color.alpha = (uint8_t)(rgba >> 24);
-            pxl.y = p_y;
-            pxl.z = p_z;
-            pxl.entity_index = p_entity;
-            a.out.gbuf[o] = pxl;
-        }
+        if (FULL && a.out.gbuf) a.out.gbuf[o] = gbuf_pixel(nx, ny, nz, rgba, p_y, p_z, p_entity);
     }
 }
 
@@ -1521,25 +1550,21 @@ __device__ __forceinline__ void render_column_generic(const par_grid_dev& g, con
     cr.ebz = 0;
     cr.nb = make_uint2(0, 0);
     const int n_workers = max_parts * PAR_WAVE_NW, worker = part * PAR_WAVE_NW + wave;
-    const int W = a.W, H = a.H, B = a.B;
-    const par_frame_dyn dyn = a.dyn_ptr ? *a.dyn_ptr : a.dyn;
-    const int c0 = bx * B;
-    const int rw = min(B, W - c0);
-    const int ry0 = max(by * B, a.row_begin), rows_hi = min(min((by + 1) * B, H), a.row_end);
-    const int rh = rows_hi - ry0;
+    const par_frame_dyn dyn = frame_dyn(a);
+    const TileRect t = tile_rect(a, bx, by);
+    const int c0 = t.c0, rw = t.tw, ry0 = t.rows_lo;
+    const int rh = t.rows_hi - ry0;
     if (rw <= 0 || rh <= 0) return;
     const int area = rw * rh;
     const int n_chunks = (area + 63) >> 6;
-    // floor(p / rw) == __umulhi(p, magic_w) for p * rw < 2^32; a 1-pixel-wide rectangle has no such multiplier
-    const uint32_t magic_w = (uint32_t)(0xFFFFFFFFu / (uint32_t)rw) + 1u;
+    const RowMajor rm = row_major(rw);
     for (int c = worker; c < n_chunks; c += n_workers) {
         const int pidx = c * 64 + lane;
-        const int pyy = (rw == 1) ? pidx : (int)__umulhi((uint32_t)pidx, magic_w);
+        const int pyy = rm.row(pidx);
         const int col = c0 + (pidx - pyy * rw), row = ry0 + pyy;
         // the chunk's first and last row (wave-uniform)
         const int p_first = c * 64, p_last = min(p_first + 63, area - 1);
-        const int row_lo = ry0 + ((rw == 1) ? p_first : (int)__umulhi((uint32_t)p_first, magic_w));
-        const int row_hi = ry0 + ((rw == 1) ? p_last : (int)__umulhi((uint32_t)p_last, magic_w));
+        const int row_lo = ry0 + rm.row(p_first), row_hi = ry0 + rm.row(p_last);
         render_chunk<true, true>(g, a, rec_, cr, 0, dyn, 0, 0, bx, by, -1, col, row, row_lo, row_hi, c0, c0 + rw - 1, pidx < area, lane,
                            ws + wave);
     }
@@ -1565,11 +1590,10 @@ __device__ __forceinline__ void render_item(const par_grid_dev& g, const par_ren
     // ---- everything the ITEM says: the column, the rectangle visited, this lane's pixel, and (entry passes) the
     // texel of the pass's own entry, the likeliest winner of the pixel. Its depth, normal, colour and palette index
     // are fetched right away, beside the column's record, instead of one and two round trips after it.
-    const int W = a.W, H = a.H, B = a.B;
+    const int H = a.H;
     const int bx = (int)(ia.z & 0x3FFu), by = (int)((ia.z >> 10) & 0x3FFu);
-    const int c0 = bx * B;
-    const int tw = min(B, W - c0);
-    const int rows_lo = max(by * B, a.row_begin), rows_hi = min(min((by + 1) * B, H), a.row_end);
+    const TileRect tr = tile_rect(a, bx, by);
+    const int c0 = tr.c0, tw = tr.tw, rows_lo = tr.rows_lo, rows_hi = tr.rows_hi;
     par_slot own_rec;  // the pass's entry as the item carries it (par_slot as it lies in memory)
     own_rec.px = (int16_t)(ib.x & 0xFFFFu); own_rec.py = (int16_t)(ib.x >> 16);
     own_rec.pz = (int16_t)(ib.y & 0xFFFFu); own_rec.ex = (int16_t)(ib.y >> 16);
@@ -2078,18 +2102,7 @@ __device__ __forceinline__ void render_tile_item(const par_grid_dev& g, const pa
             if (a.out.palidx) __builtin_nontemporal_store((uint8_t)pal_index, a.out.palidx + corner + o);
             if (FULL && a.out.brightness) a.out.brightness[corner + o] = bright;
             if (FULL && a.out.lit) a.out.lit[corner + o] = lit_px ? 1 : 0;
-            if (FULL && a.out.gbuf) {
-                par_pixel pxl;
-                pxl.normal = par_vec3{ti.nx, ti.ny, ti.nz};
-                pxl.color.red = (uint8_t)(ti.rgba & 0xFF);
-                pxl.color.green = (uint8_t)((ti.rgba >> 8) & 0xFF);
-                pxl.color.blue = (uint8_t)((ti.rgba >> 16) & 0xFF);
-                pxl.color.alpha = (uint8_t)(ti.rgba >> 24);
-                pxl.y = p_y;
-                pxl.z = p_z;
-                pxl.entity_index = w_ent;
-                a.out.gbuf[corner + o] = pxl;
-            }
+            if (FULL && a.out.gbuf) a.out.gbuf[corner + o] = gbuf_pixel(ti.nx, ti.ny, ti.nz, ti.rgba, p_y, p_z, w_ent);
         }
     }
 }
@@ -2282,7 +2295,7 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int n_lights = lights.n;
     const int n_cols = g.counters[PAR_CNT_COLS];
-    const int W = a.W, H = a.H, B = a.B;
+    const int W = a.W, H = a.H;
     const float ambient = a.ambient;
     const int32_t* depth0 = a.sprites[0].depth;
     const bool has_ids = a.sprite_ids != nullptr;
@@ -2331,17 +2344,16 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
         __syncthreads();
 
         // ---- B: the column's tile, 64 pixels per wavefront --------------------------------------------------
-        const int c0 = bx * B;
-        const int rw = min(B, W - c0);
-        const int ry0 = max(by * B, a.row_begin), rows_hi = min(min((by + 1) * B, H), a.row_end);
-        const int rh = rows_hi - ry0;
+        const TileRect t = tile_rect(a, bx, by);
+        const int c0 = t.c0, rw = t.tw, ry0 = t.rows_lo;
+        const int rh = t.rows_hi - ry0;
         if (rw <= 0 || rh <= 0) continue;
         const int area = rw * rh;
         const int n_chunks = (area + 63) >> 6;
-        const uint32_t magic_w = (uint32_t)(0xFFFFFFFFu / (uint32_t)rw) + 1u;
+        const RowMajor rm = row_major(rw);
         for (int c = wave; c < n_chunks; c += PAR_WAVE_NW) {
             const int pidx = c * 64 + lane;
-            const int pyy = (rw == 1) ? pidx : (int)__umulhi((uint32_t)pidx, magic_w);
+            const int pyy = rm.row(pidx);
             const int px_col = c0 + (pidx - pyy * rw), row = ry0 + pyy;
             const bool valid = pidx < area;
             // primary ray, alt:271-397: the column's bins as they lie in the hash (render_chunk<GENERIC>)
@@ -2412,12 +2424,9 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
                 float s = 0.f;
                 for (int l = 0; l < n_lights; l++) {
                     const par_frame_dyn& dyn = lights.l[l];
-                    // towards_light = normalize_L1(light - world), alt:711-715 + spr:28-35
-                    const float dx = (float)(dyn.lx - px_col), dy = (float)(dyn.ly - p_y), dz = (float)(dyn.lz - p_z);
-                    float tx, ty, tz, inv_x, inv_y, inv_z;
-                    normalize_l1_and_inverse(dx, dy, dz, tx, ty, tz, inv_x, inv_y, inv_z);  // alt:711-719
-                    const float dot = nx * tx + ny * ty + nz * tz;  // alt:746-747 (no contraction)
-                    const float diffuse = std_max(0.f, dot);        // alt:745
+                    const LightDir d = light_dir(dyn, px_col, p_y, p_z);
+                    const float inv_x = d.ix, inv_y = d.iy, inv_z = d.iz;
+                    const float dif = diffuse(d, nx, ny, nz);
                     bool lit = true;
                     const int wc = zs >= 0 ? (int)sh.wcnt[zs * n_lights + l] : -1;
                     if (wc >= 0) {
@@ -2434,7 +2443,7 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
                                                inv_y, inv_z);
                     }
                     if (lit) {
-                        s = s + diffuse;
+                        s = s + dif;
                         lit_mask |= 1u << l;
                     }
                 }
@@ -2451,18 +2460,7 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
                 if (a.out.palidx) a.out.palidx[o] = (uint8_t)pal_index;
                 if (a.out.brightness) a.out.brightness[o] = bright;
                 if (a.out.lit) a.out.lit[o] = (uint8_t)lit_mask;
-                if (a.out.gbuf) {
-                    par_pixel pxl;
-                    pxl.normal = par_vec3{nx, ny, nz};
-                    pxl.color.red = (uint8_t)(rgba & 0xFF);
-                    pxl.color.green = (uint8_t)((rgba >> 8) & 0xFF);
-                    pxl.color.blue = (uint8_t)((rgba >> 16) & 0xFF);
-                    pxl.color.alpha = (uint8_t)(rgba >> 24);
-                    pxl.y = p_y;
-                    pxl.z = p_z;
-                    pxl.entity_index = p_entity;
-                    a.out.gbuf[o] = pxl;
-                }
+                if (a.out.gbuf) a.out.gbuf[o] = gbuf_pixel(nx, ny, nz, rgba, p_y, p_z, p_entity);
             }
         }
     }
@@ -2475,16 +2473,14 @@ __global__ __launch_bounds__(256) void bglights_kernel(par_grid_dev g, par_rende
     const par_lights_dyn& lights = frame_lights(lights_arg);  // (every thread meets its barrier before any returns)
     const int x = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (x >= a.W) return;
-    const int ox = (int)(int16_t)x;                        // alt:720-722
-    const int bx = div_bin(x, a.magic_b), sy = a.H / a.B;  // alt:724-727
+    const BgRay ray = bg_ray(a, x);
     uint32_t mask = 0;
     for (int l = 0; l < lights.n; l++) {
         const par_frame_dyn& dyn = lights.l[l];
-        // towards_light = normalize_L1(light - (x, 0, 0)), alt:711-715 + spr:28-35
-        const float dx = (float)(dyn.lx - x), dy = (float)(dyn.ly - 0), dz = (float)(dyn.lz - 0);
-        float tx, ty, tz, inv_x, inv_y, inv_z;
-        normalize_l1_and_inverse(dx, dy, dz, tx, ty, tz, inv_x, inv_y, inv_z);  // alt:711-719
-        if (lane_shadow_walk(g, a.count, a.slots, bx, sy, 0, dyn, 0, ox, 0, 0, inv_x, inv_y, inv_z)) mask |= 1u << l;
+        const LightDir d = light_dir(dyn, x, 0, 0);
+        if (lane_shadow_walk(g, a.count, a.slots, ray.bx, ray.sy, 0, dyn, 0, ray.ox, 0, 0, d.ix, d.iy, d.iz)) {
+            mask |= 1u << l;
+        }
     }
     g.bglit[x] = (uint8_t)mask;
 }
@@ -2501,23 +2497,14 @@ __global__ __launch_bounds__(256) void units_kernel(int kind, const void* in_a, 
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (i >= n) return;
     if (kind == 0) {
-        const par_aabb box = static_cast<const par_aabb*>(in_a)[i];
+        const par_slot rec = slot_of(static_cast<const par_aabb*>(in_a)[i], 0);
         const unit_ray ray = static_cast<const unit_ray*>(in_b)[i];
-        par_slot rec;
-        rec.px = box.px; rec.py = box.py; rec.pz = box.pz;
-        rec.ex = box.ex; rec.ey = box.ey; rec.ez = box.ez;
-        rec.entity = 0;
         static_cast<uint8_t*>(out)[i] = slab_hit(rec, ray.ox, ray.oy, ray.oz, ray.inv_x, ray.inv_y, ray.inv_z) ? 1 : 0;
     } else if (kind == 3 || kind == 4) {
         // the same test as the render kernel runs it: on a walk record, through the hardware min / max when the
         // inverse direction is finite (kind 3; the kernel's choice, made per element here) or never (kind 4)
-        const par_aabb box = static_cast<const par_aabb*>(in_a)[i];
         const unit_ray ray = static_cast<const unit_ray*>(in_b)[i];
-        par_slot rec;
-        rec.px = box.px; rec.py = box.py; rec.pz = box.pz;
-        rec.ex = box.ex; rec.ey = box.ey; rec.ez = box.ez;
-        rec.entity = 0;
-        const par_walkrec w = walkrec_of(rec);
+        const par_walkrec w = walkrec_of(slot_of(static_cast<const par_aabb*>(in_a)[i], 0));
         const v2f rx = {w.x_lo, w.x_hi}, ry = {w.y_lo, w.y_hi}, rz = {w.z_lo, w.z_hi};
         const float fox = (float)ray.ox, foy = (float)ray.oy, foz = (float)ray.oz;
         const bool finite = kind == 3 && __builtin_isfinite(ray.inv_x) && __builtin_isfinite(ray.inv_y) &&
@@ -2545,12 +2532,21 @@ __global__ __launch_bounds__(256) void units_kernel(int kind, const void* in_a, 
 // (insert 5.6 us, resolve 5.6 us, column records 17.6 us at 4096^2 / 1024 primitives; the fill writes about 5 MB per
 // microsecond). A lit plane is filled afterwards (it needs the background rays, bgline_kernel). Returns false when
 // the whole fill has to be launched on its own (par_launch_fill).
+// Color{127,127,127,0} * ambient, spr:8-16 (the same truncation on the host): a background pixel.
+static uint32_t background_rgba(const par_render_args& a) {
+    const uint32_t ch = (uint32_t)(uint8_t)((float)a.background * a.ambient);
+    return ch | (ch << 8) | (ch << 16);
+}
+// A plane fill_kernel can write: given, whole 8-pixel runs per row, `align`-byte aligned.
+static bool fill_fast(const void* plane, const par_render_args& a, uintptr_t align) {
+    return plane && (a.W % 8 == 0) && ((uintptr_t)plane % align == 0);
+}
+
 bool par_plan_fill(const par_render_args& a, par_fill_plan* plan) {
-    const bool fb_fast = a.out.fb && (a.W % 8 == 0) && ((uintptr_t)a.out.fb % 16 == 0);
-    const bool pal_fast = !a.out.palidx || ((a.W % 8 == 0) && ((uintptr_t)a.out.palidx % 8 == 0));
+    const bool fb_fast = fill_fast(a.out.fb, a, 16);
+    const bool pal_fast = !a.out.palidx || fill_fast(a.out.palidx, a, 8);
     if (!fb_fast || !pal_fast || a.out.brightness || a.out.gbuf) return false;
-    const uint32_t ch = (uint32_t)(uint8_t)((float)a.background * a.ambient);  // Color{127,127,127,0} * ambient
-    plan->out_rgba = ch | (ch << 8) | (ch << 16);
+    plan->out_rgba = background_rgba(a);
     const int64_t chunks = (int64_t)(a.row_end - a.row_begin) * ((a.W + 511) / 512);
     if (chunks > 0x7FFFFFFF) return false;
     plan->cut[0] = 0;
@@ -2641,13 +2637,16 @@ hipError_t par_launch_bin_resolve(const par_grid_dev& g, const par_bin_args& a, 
     return hipGetLastError();
 }
 
-// Columns of the launch: the occupied columns (at most `column_bound`, at most those of the rendered rows) and, when
-// background rays are traced, one background walk per bin column; `per_block` of them per workgroup.
+// The occupied columns a launch is sized for: at most `column_bound`, at most every column of the rendered rows.
+static int64_t columns_in_rows(const par_grid_dev& g, const par_render_args& a, int64_t column_bound) {
+    return std::min(column_bound, (int64_t)g.gx * (a.by_hi - a.by_lo + 1));
+}
+
+// Columns of the launch: the occupied columns (columns_in_rows) and, when background rays are traced, one background
+// walk per bin column; `per_block` of them per workgroup.
 static int64_t column_blocks(const par_grid_dev& g, const par_render_args& a, int64_t column_bound, int per_block,
                              int64_t* n_cols) {
-    const int64_t cols_in_range = (int64_t)g.gx * (a.by_hi - a.by_lo + 1);
-    int64_t n = column_bound < cols_in_range ? column_bound : cols_in_range;
-    if (n < 0) n = 0;
+    int64_t n = std::max(columns_in_rows(g, a, column_bound), (int64_t)0);
     *n_cols = n;
     if (a.trace_bg) n += g.gx;  // the background walks
     return (n + per_block - 1) / per_block;
@@ -2658,8 +2657,7 @@ static int64_t column_blocks(const par_grid_dev& g, const par_render_args& a, in
 // full floor 330 against 346 us; the 480x320 graybox scene, 94 columns, 13.5 against 12.0 us: few columns need the
 // second wavefront for their walks even then.)
 static bool one_wave_per_column(const par_grid_dev& g, const par_render_args& a, int64_t column_bound) {
-    const int64_t cols_in_range = (int64_t)g.gx * (a.by_hi - a.by_lo + 1);
-    return (a.flags & PAR_RENDER_PIPELINED) != 0 && std::min(column_bound, cols_in_range) >= 1024;
+    return (a.flags & PAR_RENDER_PIPELINED) != 0 && columns_in_rows(g, a, column_bound) >= 1024;
 }
 
 // Wavefronts per column (columns_wave's ROLES): one for a frame among several in flight that fills the chip anyway;
@@ -2670,8 +2668,7 @@ static bool one_wave_per_column(const par_grid_dev& g, const par_render_args& a,
 static int column_roles(const par_grid_dev& g, const par_render_args& a, int64_t column_bound, int forced) {
     if (forced) return forced;
     if (one_wave_per_column(g, a, column_bound)) return 1;
-    const int64_t cols_in_range = (int64_t)g.gx * (a.by_hi - a.by_lo + 1);
-    const int64_t cols = std::min(column_bound, cols_in_range);
+    const int64_t cols = columns_in_rows(g, a, column_bound);
     // (measured alone / four in flight, us per frame, 2 -> 4 -> 8 wavefronts per column: graybox 43.4 / 12.3 -> 40.4 /
     // 11.5 -> 40.2 / 11.5; 512^2 with 64 primitives 26.3 / 7.0 -> 23.8 / 6.9 -> 23.7 / 6.9; 1024^2 with 512: 40.8 /
     // 14.5 -> 39.2 / 14.6 -> 36.7 / 16.1; 4096^2 with 1 024: 42.5 / 23.5 -> 47.1 / 26.5 -> 59.1 / 36.5)
@@ -2726,13 +2723,11 @@ hipError_t par_launch_columns_fill(const par_grid_dev& g, const par_render_args&
 }
 
 hipError_t par_launch_fill(const par_grid_dev& g, const par_render_args& a, hipStream_t stream) {
-    // Color{127,127,127,0} * ambient, spr:8-16 (same truncation on the host)
-    const uint32_t ch = (uint32_t)(uint8_t)((float)a.background * a.ambient);
-    const uint32_t out_rgba = ch | (ch << 8) | (ch << 16);
+    const uint32_t out_rgba = background_rgba(a);
     const int64_t npix = (int64_t)(a.row_end - a.row_begin) * a.W;
-    const bool fb_fast = a.out.fb && (a.W % 8 == 0) && ((uintptr_t)a.out.fb % 16 == 0);
-    const bool pal_fast = a.out.palidx && (a.W % 8 == 0) && ((uintptr_t)a.out.palidx % 8 == 0);
-    const bool lit_fast = a.out.lit && (a.W % 8 == 0) && ((uintptr_t)a.out.lit % 8 == 0);
+    const bool fb_fast = fill_fast(a.out.fb, a, 16);
+    const bool pal_fast = fill_fast(a.out.palidx, a, 8);
+    const bool lit_fast = fill_fast(a.out.lit, a, 8);
     if (fb_fast || pal_fast || lit_fast) {
         par_render_args f = a;
         if (!fb_fast) f.out.fb = nullptr;
@@ -2777,6 +2772,22 @@ static int64_t item_workgroups(int64_t item_bound) {
     return waves / PAR_WAVE_NW;
 }
 
+// Which instantiation <DBG, IDS, FULL> of an item kernel a frame runs: the instrumented one for the debug flags; the
+// one with the sprite-id table and the parity planes when any of them is asked for; else the production one (every
+// entity uses sprite 0, as in the reference's own scenes; RGBA + palette index only). `launch(dbg, full)` gets them
+// as std::bool_constant; IDS = FULL.
+template <class Launch>
+static hipError_t launch_render_variant(const par_render_args& a, Launch launch) {
+    if (a.flags & PAR_DEBUG_FLAGS) {
+        launch(std::true_type{}, std::true_type{});
+    } else if (a.sprite_ids || a.out.brightness || a.out.lit || a.out.gbuf) {
+        launch(std::false_type{}, std::true_type{});
+    } else {
+        launch(std::false_type{}, std::false_type{});
+    }
+    return hipGetLastError();
+}
+
 hipError_t par_launch_render(const par_grid_dev& g, const par_render_args& a, int64_t item_bound,
                              hipStream_t stream) {
     if (item_bound <= 0 || a.dense) return hipSuccess;
@@ -2786,14 +2797,9 @@ hipError_t par_launch_render(const par_grid_dev& g, const par_render_args& a, in
     int64_t wgs = item_workgroups(item_bound);
     if (a.tile_k > 0 && wgs > 1024) wgs = 1024;
     const dim3 grid((unsigned)wgs), block(PAR_WAVE_NW * 64);
-    if (a.flags & PAR_DEBUG_FLAGS) {
-        hipLaunchKernelGGL((render_items_kernel<true, true, true>), grid, block, 0, stream, g, a);
-    } else if (a.sprite_ids || a.out.brightness || a.out.lit || a.out.gbuf) {
-        hipLaunchKernelGGL((render_items_kernel<false, true, true>), grid, block, 0, stream, g, a);
-    } else {  // every entity uses sprite 0 (the reference's own scenes), RGBA + palette index only
-        hipLaunchKernelGGL((render_items_kernel<false, false, false>), grid, block, 0, stream, g, a);
-    }
-    return hipGetLastError();
+    return launch_render_variant(a, [&](auto dbg, auto full) {
+        hipLaunchKernelGGL((render_items_kernel<dbg(), full(), full()>), grid, block, 0, stream, g, a);
+    });
 }
 
 // Tile items cover a.tile_k chunks each: `item_bound` chunks are at most that many fewer items (rounded up per column,
@@ -2809,22 +2815,16 @@ hipError_t par_launch_render_tiles(const par_grid_dev& g, const par_render_args&
     // (several items per wavefront in big frames, item_workgroups: full floor at 4096^2, tile_k 5: 220 us with one
     // item per wavefront, 197 with three)
     const dim3 grid((unsigned)item_workgroups(tile_item_bound(a, item_bound))), block(PAR_WAVE_NW * 64);
-    if (a.flags & PAR_DEBUG_FLAGS) {
-        hipLaunchKernelGGL((render_tiles_kernel<true, true, true>), grid, block, 0, stream, g, a);
-    } else if (a.sprite_ids || a.out.brightness || a.out.lit || a.out.gbuf) {
-        hipLaunchKernelGGL((render_tiles_kernel<false, true, true>), grid, block, 0, stream, g, a);
-    } else {
-        hipLaunchKernelGGL((render_tiles_kernel<false, false, false>), grid, block, 0, stream, g, a);
-    }
-    return hipGetLastError();
+    return launch_render_variant(a, [&](auto dbg, auto full) {
+        hipLaunchKernelGGL((render_tiles_kernel<dbg(), full(), full()>), grid, block, 0, stream, g, a);
+    });
 }
 
 // Small frames: work items, tile items and overflowed columns in one launch. hipErrorNotSupported (nothing launched)
 // for large frames, where the kernels' different register needs matter.
 hipError_t par_launch_render_both(const par_grid_dev& g, const par_render_args& a, int64_t column_bound,
                                   int64_t item_bound, bool may_overflow, hipStream_t stream) {
-    const int64_t cols_in_range = (int64_t)g.gx * (a.by_hi - a.by_lo + 1);
-    const int64_t bound = column_bound < cols_in_range ? column_bound : cols_in_range;
+    const int64_t bound = columns_in_rows(g, a, column_bound);
     if (bound >= 2048 || a.dense) return hipErrorNotSupported;
     if (bound <= 0) return hipSuccess;
     const int over_parts = 8;
@@ -2860,8 +2860,7 @@ hipError_t par_launch_render_both(const par_grid_dev& g, const par_render_args& 
 
 hipError_t par_launch_render_overflow(const par_grid_dev& g, const par_render_args& a, int64_t column_bound,
                                       hipStream_t stream) {
-    const int64_t cols_in_range = (int64_t)g.gx * (a.by_hi - a.by_lo + 1);
-    const int64_t bound = column_bound < cols_in_range ? column_bound : cols_in_range;
+    const int64_t bound = columns_in_rows(g, a, column_bound);
     if (bound <= 0) return hipSuccess;
     // overflowed columns are the exception: a small strided grid (up to 8 workgroups share a column)
     const int64_t oblocks = a.dense ? (bound < 1024 ? bound : 1024) : (bound < 32 ? bound : 32);
@@ -2869,43 +2868,29 @@ hipError_t par_launch_render_overflow(const par_grid_dev& g, const par_render_ar
     return hipGetLastError();
 }
 
-// Workgroups of a light-kernel launch: one per column the bound allows in the rendered rows, at most 65536 (the
-// workgroups then stride over the column list).
-static int64_t render_lights_grid(const par_grid_dev& g, const par_render_args& a, int64_t column_bound) {
-    const int64_t cols_in_range = (int64_t)g.gx * (a.by_hi - a.by_lo + 1);
-    const int64_t n = column_bound < cols_in_range ? column_bound : cols_in_range;
-    return n > 65536 ? 65536 : n;
-}
-
+// One workgroup per column the bound allows in the rendered rows, at most 65536 (the workgroups then stride over the
+// column list). `d_lights` non-null: a captured graph's kernels read the lights from there, else `lights`.
 hipError_t par_launch_render_lights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,
-                                    int64_t column_bound, hipStream_t stream) {
-    const int64_t n = render_lights_grid(g, a, column_bound);
+                                    const par_lights_dyn* d_lights, int64_t column_bound, hipStream_t stream) {
+    const int64_t n = std::min(columns_in_rows(g, a, column_bound), (int64_t)65536);
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(render_lights_kernel<par_lights_dyn>, dim3((unsigned)n), dim3(PAR_WAVE_NW * 64), 0, stream, g, a,
-                       lights);
-    return hipGetLastError();
-}
-
-hipError_t par_launch_render_lights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn* d_lights,
-                                    int64_t column_bound, hipStream_t stream) {
-    const int64_t n = render_lights_grid(g, a, column_bound);
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(render_lights_kernel<const par_lights_dyn*>, dim3((unsigned)n), dim3(PAR_WAVE_NW * 64), 0, stream,
-                       g, a, d_lights);
+    const dim3 grid((unsigned)n), block(PAR_WAVE_NW * 64);
+    if (d_lights) {
+        hipLaunchKernelGGL(render_lights_kernel<const par_lights_dyn*>, grid, block, 0, stream, g, a, d_lights);
+    } else {
+        hipLaunchKernelGGL(render_lights_kernel<par_lights_dyn>, grid, block, 0, stream, g, a, lights);
+    }
     return hipGetLastError();
 }
 
 hipError_t par_launch_bglights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,
-                               hipStream_t stream) {
-    hipLaunchKernelGGL(bglights_kernel<par_lights_dyn>, dim3((unsigned)((a.W + 255) / 256)), dim3(256), 0, stream, g, a,
-                       lights);
-    return hipGetLastError();
-}
-
-hipError_t par_launch_bglights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn* d_lights,
-                               hipStream_t stream) {
-    hipLaunchKernelGGL(bglights_kernel<const par_lights_dyn*>, dim3((unsigned)((a.W + 255) / 256)), dim3(256), 0, stream,
-                       g, a, d_lights);
+                               const par_lights_dyn* d_lights, hipStream_t stream) {
+    const dim3 grid((unsigned)((a.W + 255) / 256)), block(256);
+    if (d_lights) {
+        hipLaunchKernelGGL(bglights_kernel<const par_lights_dyn*>, grid, block, 0, stream, g, a, d_lights);
+    } else {
+        hipLaunchKernelGGL(bglights_kernel<par_lights_dyn>, grid, block, 0, stream, g, a, lights);
+    }
     return hipGetLastError();
 }
 
