@@ -13,20 +13,8 @@
 #include <unordered_map>
 #include <vector>
 
+#include "par_book.h"
 #include "par_internal.h"
-
-// The bins one entity is inserted into (cull and ranges of alt:202-240, computed once per AABB the host is given):
-// bin columns [x0, x1) x [y0, y1), nz bins deep; empty when x1 <= x0. Everything the host sizes launches and lists
-// with follows from it.
-struct par_footprint {
-    int16_t x0 = 0, x1 = 0, y0 = 0, y1 = 0;
-    int32_t nz = 0;
-    int32_t items = 0;  // render work items (64-pixel chunks) the entity can cause, see footprint_of
-    int16_t px = 0, ex = 0;     // its sprite rectangle on screen (alt:310-317): columns [px, px + ex),
-    int32_t row0 = 0, rh = 0;   // rows [row0, row0 + rh) = H - (py + ey + pz + ez) .. H - (py + pz)
-    int32_t cols() const { return (x1 - x0) * (y1 - y0); }
-    int64_t pairs() const { return (int64_t)cols() * nz; }  // (entity, bin) insertions, alt:243-267
-};
 
 // The staged lights of a captured graph: par_lights_dyn padded to a whole number of 64-byte lines. A one-light graph's
 // kernels read their par_frame_dyn from lights.l[0].
@@ -42,29 +30,7 @@ struct par_context {
     int gx = 0, gy = 0, gz = 0, volume = 0;
     hipStream_t stream = nullptr;   // used by the synchronous host-buffer entry points
 
-    // host mirrors
-    std::vector<par_aabb> h_aabbs;
-    std::vector<par_footprint> h_fp;  // per entity: the bins it is inserted into (alt:202-240) and what follows from them
-    int64_t total_pairs = 0;
-    int64_t total_cols = 0;        // >= the occupied columns of the frame
-    int64_t total_items = 0;       // >= the render work items (64-pixel chunks) of the frame, see footprint_of
-    // The same three from the entities' EXTENTS alone (bound_of: wherever an entity stands it reaches no more): what
-    // pools and lists are sized by, and what a frame's launches are sized by while the exact bookkeeping above is
-    // stale -- par_update_aabbs_async does not keep it (a moving scene would pay the cull and range arithmetic of
-    // every moved entity on the host, every frame); the next blocking call brings it up to date (refresh_exact).
-    int64_t bound_pairs = 0, bound_cols = 0, bound_items = 0;
-    bool exact_stale = false;
-    // The per-column histograms alone lag behind the footprints (par_graph_stage keeps footprints and totals exact --
-    // it has to refuse a frame the captured launches cannot hold -- but not the histograms, which cost a moving scene
-    // more host time per frame than everything else the stage does; a captured graph does not read them).
-    bool hist_stale = false;
-    std::vector<int32_t> h_colpairs;  // (entity, bin) pairs per screen column (>= its occupied bins, >= its entries)
-    int64_t cols_over = 0;            // columns with more pairs than a column record is sure to hold
-    // 64-pixel chunks of the entities' sprite rectangles per screen column (what the column kernel adds up, over the
-    // visible entries only, to choose between visiting a column entry by entry and as a whole tile), and the columns
-    // where that reaches the tile's own chunks: only those can be visited as tiles
-    std::vector<int32_t> h_colchunks;
-    int64_t cols_tileable = 0;
+    par_book book;  // the host's copy of the scene and what frames are sized by (par_book.h)
     int n_entities = 0, n_sprites = 0, max_sprite_id = 0;
     bool have_entities = false;
     par_light lights[PAR_MAX_LIGHTS]{};  // set_lights; n_lights >= 2 (or the test hook) takes the light kernel
@@ -109,9 +75,6 @@ struct par_context {
     // The captured kernels read the frame's lights from d_lights (a one-light graph's from the first light alone).
     bool graph_lights = false;  // which kernels were captured: false one-light (par_graph_capture), true light path
     par_lights_block* d_lights = nullptr;
-    int graph_set = 0;
-    int64_t graph_pair_bound = 0;  // (entity, bin) pairs a captured graph's launch grids can take
-    int64_t graph_item_bound = 0;  // ... and render work items
 
     bool timed_tiles = false, timed_overflow = false, timed_both = false;  // the last timed frame launched these kernels
     hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // EV_START .. EV_END
@@ -187,159 +150,6 @@ int hip_fail(par_context* c, hipError_t e, const char* what) {
         if (e_ != hipSuccess) return hip_fail(ctx, e_, #call); \
     } while (0)
 
-// The cull and range math of alt:202-240 for one AABB. `items`: the render work items it can cause: its sprite
-// rectangle (ex wide, ey + ez tall, alt:310-317) is cut by the screen columns it reaches into that many pieces, each
-// visited in whole 64-pixel chunks: sum of ceil(area_i / 64) <= floor(area / 64) + pieces. (A column switches to
-// visiting its whole tile only when that takes fewer chunks.)
-par_footprint footprint_of(const par_context* c, const par_aabb& a) {
-    par_footprint f;
-    const int W = c->params.width, H = c->params.height, L = c->params.length, B = c->params.bin_size;
-    const int minx = a.px, miny = a.py, minz = a.pz;
-    const int maxx = minx + a.ex, maxy = miny + a.ey, maxz = minz + a.ez;
-    if ((maxx < 0) || (minx >= W) || (maxy < 0 - maxz) || (miny >= H - minz + B) || (maxz < -a.ez - B) ||
-        (minz > L + B)) {
-        return f;
-    }
-    const int x0 = std::max(0, minx / B), y0 = std::max(0, (H - maxy - maxz) / B), z0 = std::max(0, minz / B);
-    const int x1 = std::min(c->gx, (maxx + B - 1) / B), y1 = std::min(c->gy, (H - miny - minz + B - 1) / B);
-    const int z1 = std::min(c->gz, (maxz + B - 1) / B);
-    if (x1 <= x0 || y1 <= y0 || z1 <= z0) return f;
-    f.x0 = (int16_t)x0; f.x1 = (int16_t)x1; f.y0 = (int16_t)y0; f.y1 = (int16_t)y1;
-    f.nz = z1 - z0;
-    f.items = (int32_t)((int)a.ex * ((int)a.ey + (int)a.ez) / 64 + f.cols());
-    f.px = a.px; f.ex = a.ex;
-    f.row0 = H - ((int)a.py + a.ey + a.pz + a.ez);
-    f.rh = (int)a.ey + (int)a.ez;
-    return f;
-}
-
-// What an entity of these extents can cause at most, wherever it stands: an interval of length d meets at most
-// ceil(d / B) + 1 bins of width B (alt:222-240), its sprite rectangle is ex x (ey + ez) pixels (alt:310-317).
-struct par_bound {
-    int64_t pairs, cols, items;
-};
-par_bound bound_of(const par_context* c, const par_aabb& a) {
-    const int B = c->params.bin_size;
-    const int64_t nx = std::min<int64_t>(c->gx, ((int)a.ex + B - 1) / B + 1);
-    const int64_t ny = std::min<int64_t>(c->gy, ((int)a.ey + (int)a.ez + B - 1) / B + 1);
-    const int64_t nz = std::min<int64_t>(c->gz, ((int)a.ez + B - 1) / B + 1);
-    return par_bound{nx * ny * nz, nx * ny, (int64_t)a.ex * ((int)a.ey + (int)a.ez) / 64 + nx * ny};
-}
-
-// Adds (sign = +1) or removes (-1) a footprint's pairs in the per-column histogram. A column whose pairs exceed
-// PAR_COL_NB (<= PAR_COL_ENT) may overflow its record; while there is none, no column can, and the frame needs no
-// launch for the overflow list.
-void col_hist(par_context* c, const par_footprint& f, int sign) {
-    constexpr int kSure = PAR_COL_NB < PAR_COL_ENT ? PAR_COL_NB : PAR_COL_ENT;
-    const int W = c->params.width, H = c->params.height, B = c->params.bin_size;
-    for (int x = f.x0; x < f.x1; x++) {
-        const int cx0 = x * B, tw = std::min(B, W - cx0);
-        const int w = std::min(f.px + f.ex, cx0 + tw) - std::max((int)f.px, cx0);
-        for (int y = f.y0; y < f.y1; y++) {
-            int32_t& n = c->h_colpairs[(size_t)x * c->gy + y];
-            const bool was = n > kSure;
-            n += sign * f.nz;
-            c->cols_over += (int)(n > kSure) - (int)was;
-            const int ry0 = y * B, th = std::min(B, H - ry0);
-            const int h = std::min(f.row0 + f.rh, ry0 + th) - std::max(f.row0, ry0);
-            if (w > 0 && h > 0) {
-                const int tile_chunks = (tw * th + 63) / 64;
-                int32_t& k = c->h_colchunks[(size_t)x * c->gy + y];
-                const bool could = k >= tile_chunks;
-                k += sign * ((w * h + 63) / 64);
-                c->cols_tileable += (int)(k >= tile_chunks) - (int)could;
-            }
-        }
-    }
-}
-
-// What an update of aabbs[first, first + n) does to the host's bookkeeping, in two steps: `plan` computes the new
-// footprints and totals (so that the caller can grow pools or refuse before anything changes), `commit` applies them.
-struct par_update_plan {
-    std::vector<par_footprint> fp;
-    int64_t pairs = 0, cols = 0, items = 0;  // the new totals
-};
-
-void plan_update(const par_context* c, const par_aabb* aabbs, int first, int n, par_update_plan* plan) {
-    plan->fp.resize((size_t)n);
-    plan->pairs = c->total_pairs;
-    plan->cols = c->total_cols;
-    plan->items = c->total_items;
-    for (int i = 0; i < n; i++) {
-        const par_footprint f = footprint_of(c, aabbs[i]);
-        const par_footprint& old = c->h_fp[(size_t)(first + i)];
-        plan->fp[(size_t)i] = f;
-        plan->pairs += f.pairs() - old.pairs();
-        plan->cols += f.cols() - old.cols();
-        plan->items += f.items - old.items;
-    }
-}
-
-// The bound totals after aabbs[first, first + n) replace the entities there (extents rarely change: then nothing does).
-void bounds_after(const par_context* c, const par_aabb* aabbs, int first, int n, par_bound* total) {
-    *total = par_bound{c->bound_pairs, c->bound_cols, c->bound_items};
-    for (int i = 0; i < n; i++) {
-        const par_aabb& old = c->h_aabbs[(size_t)(first + i)];
-        if (old.ex == aabbs[i].ex && old.ey == aabbs[i].ey && old.ez == aabbs[i].ez) continue;
-        const par_bound o = bound_of(c, old), b = bound_of(c, aabbs[i]);
-        total->pairs += b.pairs - o.pairs;
-        total->cols += b.cols - o.cols;
-        total->items += b.items - o.items;
-    }
-}
-
-// `commit`: the per-column histograms follow when `hist`; par_graph_stage leaves them behind (hist_stale).
-void commit_update(par_context* c, const par_aabb* aabbs, int first, int n, const par_update_plan& plan, bool hist) {
-    par_bound bt;
-    bounds_after(c, aabbs, first, n, &bt);
-    c->bound_pairs = bt.pairs; c->bound_cols = bt.cols; c->bound_items = bt.items;
-    for (int i = 0; i < n; i++) {
-        par_footprint& slot = c->h_fp[(size_t)(first + i)];
-        if (hist) {
-            col_hist(c, slot, -1);
-            col_hist(c, plan.fp[(size_t)i], +1);
-        }
-        slot = plan.fp[(size_t)i];
-        c->h_aabbs[(size_t)(first + i)] = aabbs[i];
-    }
-    c->total_pairs = plan.pairs;
-    c->total_cols = plan.cols;
-    c->total_items = plan.items;
-    if (!hist) c->hist_stale = true;
-}
-
-// The footprints of aabbs[0, n) into fp, and their totals.
-par_bound footprints(const par_context* c, const par_aabb* aabbs, int n, par_footprint* fp) {
-    par_bound t{0, 0, 0};
-    for (int i = 0; i < n; i++) {
-        fp[i] = footprint_of(c, aabbs[i]);
-        t.pairs += fp[i].pairs();
-        t.cols += fp[i].cols();
-        t.items += fp[i].items;
-    }
-    return t;
-}
-
-// Both per-column histograms from the footprints (h_fp): then they are current.
-void rebuild_hist(par_context* c) {
-    c->h_colpairs.assign((size_t)c->gx * c->gy, 0);
-    c->h_colchunks.assign((size_t)c->gx * c->gy, 0);
-    c->cols_over = 0;
-    c->cols_tileable = 0;
-    for (const par_footprint& f : c->h_fp) col_hist(c, f, +1);
-    c->hist_stale = false;
-}
-
-// The exact bookkeeping (footprints, totals, per-column histograms) from the host's copy of the AABBs, after
-// asynchronous updates or graph staging left it stale.
-void refresh_exact(par_context* c) {
-    if (!c->exact_stale && !c->hist_stale) return;
-    const par_bound t = footprints(c, c->h_aabbs.data(), c->n_entities, c->h_fp.data());
-    c->total_pairs = t.pairs; c->total_cols = t.cols; c->total_items = t.items;
-    rebuild_hist(c);
-    c->exact_stale = false;
-}
-
 bool extent_ok(const par_aabb& a) {
     // The sprite is 20 wide and 40 tall (alt:330, spr:67-71): texel row = (ey + ez) - 1 at most, column < ex.
     return a.ex >= 0 && a.ey >= 0 && a.ez >= 0 && a.ex <= PAR_SPRITE_W && (int)a.ey + (int)a.ez <= PAR_SPRITE_H;
@@ -356,20 +166,6 @@ int check_update(par_context* ctx, const par_aabb* aabbs, int first, int n, bool
         if (!extent_ok(aabbs[i])) return fail(ctx, PAR_ERR_EXTENT, "extent needs 0<=ex<=20, ey,ez>=0, ey+ez<=40");
     }
     return PAR_OK;
-}
-
-// What a frame can hold at most of render work items: every column visited as a whole tile.
-int64_t max_items(const par_context* c) {
-    const int64_t B = c->params.bin_size;
-    return (int64_t)c->gx * c->gy * ((B * B + 63) / 64);
-}
-
-// One shard of the render work-item list holds the items of the columns whose index is congruent to it: at most
-// every item of the frame, and at most its share of the occupied columns (<= `cols`), each visited as a whole tile.
-int64_t items_per_shard(const par_context* c, int64_t items, int64_t cols) {
-    const int64_t B = c->params.bin_size;
-    cols = std::min<int64_t>(cols, (int64_t)c->gx * c->gy);
-    return std::min(items, (cols / PAR_ITEM_SHARDS + 1) * ((B * B + 63) / 64));
 }
 
 // *p replaced by a fresh buffer of n elements, in device memory or (`pinned`) pinned host memory; the old contents
@@ -408,22 +204,6 @@ void free_pool(par_context* c) {
     c->grid.capacity = 0;
 }
 
-// The render work-item list sized for a frame of `items` items over `cols` occupied columns (items_per_shard).
-int ensure_items(par_context* ctx, int64_t items, int64_t cols) {
-    const int64_t need = items_per_shard(ctx, items, cols);
-    if (need <= ctx->grid.item_capacity) return PAR_OK;
-    if (ctx->graph_exec[0]) return fail(ctx, PAR_ERR_UNSUPPORTED, "work-item list would grow under a captured graph; capture again");
-    const int64_t cap = std::max<int64_t>(need + need / 2, 1 << 10);
-    if (cap > 0x3FFFFFFF / (PAR_ITEM_LISTS * PAR_ITEM_SHARDS)) return fail(ctx, PAR_ERR_UNSUPPORTED, "too many render work items");
-    PAR_HIP(hipDeviceSynchronize());
-    if (ctx->grid.items) PAR_HIP(hipFree(ctx->grid.items));
-    ctx->grid.items = nullptr;
-    ctx->grid.item_capacity = 0;
-    PAR_HIP(hipMalloc(&ctx->grid.items, (size_t)cap * PAR_ITEM_LISTS * PAR_ITEM_SHARDS * sizeof(par_item)));
-    ctx->grid.item_capacity = (int32_t)cap;
-    return PAR_OK;
-}
-
 // Wipe both head/count sets and the node counters (context creation, and whenever the node pool is replaced and
 // the record of which bins the previous frame touched is lost with it).
 int reset_grid(par_context* ctx) {
@@ -457,6 +237,24 @@ int ensure_pool(par_context* ctx, int64_t pairs) {
     ctx->grid.col_capacity = (int32_t)col_cap;
     ctx->grid.capacity = (int32_t)cap;
     return reset_grid(ctx);
+}
+
+// Device memory for a frame of `b`: the node pool, then the render work-item list (par_book::items_per_shard).
+int ensure_room(par_context* ctx, const par_bound& b) {
+    const int rc = ensure_pool(ctx, b.pairs);
+    if (rc != PAR_OK) return rc;
+    const int64_t need = ctx->book.items_per_shard(b.items, b.cols);
+    if (need <= ctx->grid.item_capacity) return PAR_OK;
+    if (ctx->graph_exec[0]) return fail(ctx, PAR_ERR_UNSUPPORTED, "work-item list would grow under a captured graph; capture again");
+    const int64_t cap = std::max<int64_t>(need + need / 2, 1 << 10);
+    if (cap > 0x3FFFFFFF / (PAR_ITEM_LISTS * PAR_ITEM_SHARDS)) return fail(ctx, PAR_ERR_UNSUPPORTED, "too many render work items");
+    PAR_HIP(hipDeviceSynchronize());
+    if (ctx->grid.items) PAR_HIP(hipFree(ctx->grid.items));
+    ctx->grid.items = nullptr;
+    ctx->grid.item_capacity = 0;
+    PAR_HIP(hipMalloc(&ctx->grid.items, (size_t)cap * PAR_ITEM_LISTS * PAR_ITEM_SHARDS * sizeof(par_item)));
+    ctx->grid.item_capacity = (int32_t)cap;
+    return PAR_OK;
 }
 
 void drop_graphs(par_context* c) {
@@ -535,12 +333,9 @@ par_render_args make_render_args(const par_context* c, int set, int row_begin, i
     // criterion, over the visible entries). A frame with fewer visits every column entry by entry (tile_k 0) and keeps
     // its three launches. A captured graph serves later frames too: it always has the launch. Then: how many chunks
     // per tile item -- a frame with many lets a wavefront read what a column's chunks share once for several of them,
-    // a frame with few needs every wavefront it can get.
-    const int64_t grid_cols = (int64_t)c->gx * c->gy;
-    const bool dense_frame = dyn_from_device || c->cols_tileable >= std::max<int64_t>(16, grid_cols / 64);
-    // (what the entities' rectangles add up to, but no more than every column of the grid as a whole tile: the entities
-    // of a crowded small view overlap many times over)
-    const int64_t chunks = std::min(c->total_items, max_items(c));
+    // a frame with few needs every wavefront it can get. (Both can lag behind the scene, see par_book::dense.)
+    const bool dense_frame = dyn_from_device || c->book.dense();
+    const int64_t chunks = c->book.chunks();
     a.tile_k = !dense_frame ? 0 : (chunks >= 65536 ? 5 : (chunks >= 16384 ? 3 : (chunks >= 8192 ? 2 : 1)));
     a.tile_k_magic = a.tile_k > 0 ? (uint32_t)(65536 / a.tile_k + 1) : 65537u;
     a.dyn = make_dyn(c, c->lights[0]);
@@ -598,16 +393,6 @@ par_lights_dyn make_lights_dyn(const par_context* c) {
     return lights;
 }
 
-// What a frame's launches are sized by: (entity, bin) pairs, occupied columns (<= the columns the entities reach one by
-// one, <= their pairs) and render work items. A captured graph must also hold for later frames, whose counts are
-// unknown at capture time: what par_graph_stage accepts (graph_pair_bound; beyond it the caller captures again). After
-// asynchronous updates since the last blocking call: what the extents allow.
-par_bound frame_bounds(const par_context* c, bool graph_mode) {
-    if (graph_mode) return par_bound{c->graph_pair_bound, c->graph_pair_bound, c->graph_item_bound};
-    if (c->exact_stale) return par_bound{c->bound_pairs, c->bound_cols, c->bound_items};
-    return par_bound{c->total_pairs, c->total_cols, c->total_items};
-}
-
 // The hash build: small scenes in one launch, large ones in two (and frames that keep their kernels `apart`, and the
 // test hook). `fa`, `fill`: the share of the background fill that rides along, if any.
 int enqueue_build(par_context* ctx, hipStream_t stream, const par_bin_args& b, int64_t pair_bound,
@@ -627,7 +412,7 @@ int enqueue_build(par_context* ctx, hipStream_t stream, const par_bin_args& b, i
 // and one launch of the light kernel over the occupied columns. No column records, no work items, no overflow list.
 // Timed frames bracket the launches with the same events as enqueue_frame: the light kernel is ms_render and
 // ms_launch[2]; the other render launches it does not have are 0. In graph mode (par_graph_capture_lights) the
-// launches are sized by what the graph accepts (graph_pair_bound) and the kernels read the lights from d_lights, which
+// launches are sized by what the graph accepts (par_book::graph) and the kernels read the lights from d_lights, which
 // the graph's copy node fills before them: one graph serves any count of lights.
 int enqueue_lights_frame(par_context* ctx, hipStream_t stream, const par_bin_args& b, const par_render_args& r,
                          const par_bound& bound, bool graph_mode, bool apart, hipEvent_t* ev) {
@@ -678,7 +463,7 @@ int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, 
     par_render_args r = make_render_args(ctx, set, row_begin, row_end, outs, flags, graph_mode);
     // (a timed frame keeps its kernels apart unless it is asked to time the launches as a production frame makes them)
     const bool apart = ev && !(flags & PAR_RENDER_TIMED_AS_LAUNCHED);
-    const par_bound bound = frame_bounds(ctx, graph_mode);
+    const par_bound bound = ctx->book.frame_bounds(graph_mode);
     if ((flags & PAR_RENDER_COUNT_RAYS) && !graph_mode) {
         PAR_HIP(hipMemsetAsync(ctx->d_ray_counter, 0, sizeof(unsigned long long), stream));
     }
@@ -690,7 +475,7 @@ int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, 
     // The overflow list is empty for sure while no column has more pairs than a record holds (a captured graph also
     // serves later frames, whose columns nobody knows yet): then the frame has no launch for it, and the column
     // kernel flags the frame should a column overflow all the same.
-    const bool may_overflow = graph_mode || ctx->cols_over > 0 || ctx->exact_stale || ctx->hist_stale || r.dense || apart;
+    const bool may_overflow = graph_mode || ctx->book.may_overflow() || r.dense || apart;
     r.overflow_launched = may_overflow ? 1 : 0;
     // The background fill depends on nothing earlier in the frame and the render kernels come after all of it: when
     // it is the plain streaming one it rides along with the first three launches (timed runs keep all kernels apart
@@ -722,7 +507,7 @@ int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, 
     }
     if (ev) PAR_HIP(hipEventRecord(ev[EV_FILLED], stream));
     // work items <= what the entities can cause one by one, and <= every column of the rendered rows as a whole tile
-    const int64_t item_cap_rows = max_items(ctx) / ctx->gy * (r.by_hi - r.by_lo + 1);
+    const int64_t item_cap_rows = ctx->book.max_items() / ctx->gy * (r.by_hi - r.by_lo + 1);
     const int64_t item_bound = std::min(bound.items, item_cap_rows);
     bool both = false;
     if (!apart) {  // small frames: one launch for both render kernels
@@ -852,6 +637,7 @@ static int par_create_impl(const par_params* params, int device, par_context** o
     ctx->params = p;
     ctx->device = device;
     ctx->gx = gx; ctx->gy = gy; ctx->gz = gz; ctx->volume = gx * gy * gz;
+    ctx->book.init(p, gx, gy, gz);
     ctx->grid.gx = gx; ctx->grid.gy = gy; ctx->grid.gz = gz; ctx->grid.volume = ctx->volume;
     ctx->stats.shadow_rays = -1; ctx->stats.ms_bin = -1.f; ctx->stats.ms_fill = -1.f; ctx->stats.ms_render = -1.f;
     ctx->stats.ms_overflow = -1.f;
@@ -878,7 +664,7 @@ static int par_create_impl(const par_params* params, int device, par_context** o
         par_destroy(ctx);
         return PAR_ERR_HIP;
     }
-    if (ensure_pool(ctx, 1) != PAR_OK || ensure_items(ctx, 1, 1) != PAR_OK) {
+    if (ensure_room(ctx, par_bound{1, 1, 1}) != PAR_OK) {
         par_destroy(ctx);
         return PAR_ERR_OOM;
     }
@@ -963,19 +749,8 @@ static int par_set_entities_impl(par_context* ctx, const par_aabb* aabbs, const 
     PAR_HIP(hipSetDevice(ctx->device));
     PAR_HIP(hipDeviceSynchronize());
     drop_graphs(ctx);
-    // (an entity's pairs are at most the grid's volume, which par_create holds below 2^30)
-    std::vector<par_footprint> fps((size_t)n);
-    const par_bound total = footprints(ctx, aabbs, n, fps.data());
-    // (pools and lists by what the extents allow: they then hold wherever the entities move)
-    par_bound bt{0, 0, 0};
-    for (int i = 0; i < n; i++) {
-        const par_bound b = bound_of(ctx, aabbs[i]);
-        bt.pairs += b.pairs; bt.cols += b.cols; bt.items += b.items;
-    }
-    if (bt.pairs > 0x3FFFFFFF) return fail(ctx, PAR_ERR_UNSUPPORTED, "too many (entity, bin) pairs");
-    int rc = ensure_pool(ctx, std::max(total.pairs, bt.pairs));
-    if (rc != PAR_OK) return rc;
-    rc = ensure_items(ctx, std::max(total.items, bt.items), std::max(total.cols, bt.cols));
+    // (pools and lists by what the extents allow too: they then hold wherever the entities move)
+    const int rc = ensure_room(ctx, ctx->book.plan(par_change::SET, aabbs, 0, n).need);
     if (rc != PAR_OK) return rc;
     if (n > ctx->aabb_capacity) PAR_HIP(grow(&ctx->d_aabbs, &ctx->aabb_capacity, std::max(n, 1)));
     if (ctx->d_sprite_ids) PAR_HIP(hipFree(ctx->d_sprite_ids));
@@ -985,12 +760,7 @@ static int par_set_entities_impl(par_context* ctx, const par_aabb* aabbs, const 
         PAR_HIP(hipMalloc(&ctx->d_sprite_ids, (size_t)n * sizeof(int32_t)));
         PAR_HIP(hipMemcpy(ctx->d_sprite_ids, sprite_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
     }
-    ctx->h_aabbs.assign(aabbs, aabbs + n);
-    ctx->h_fp.swap(fps);
-    ctx->total_pairs = total.pairs; ctx->total_cols = total.cols; ctx->total_items = total.items;
-    ctx->bound_pairs = bt.pairs; ctx->bound_cols = bt.cols; ctx->bound_items = bt.items;
-    rebuild_hist(ctx);  // (current again, whatever par_graph_stage left behind)
-    ctx->exact_stale = false;
+    ctx->book.commit();
     ctx->n_entities = n;
     ctx->max_sprite_id = max_id;
     ctx->have_entities = true;
@@ -1043,15 +813,9 @@ static int par_update_aabbs_impl(par_context* ctx, const par_aabb* aabbs, int fi
     if (!ctx) return PAR_ERR_INVALID_ARG;
     int rc = check_update(ctx, aabbs, first, n, false);
     if (rc != PAR_OK) return rc;
-    refresh_exact(ctx);  // (asynchronous updates may have left the exact bookkeeping behind)
-    par_update_plan plan;
-    plan_update(ctx, aabbs, first, n, &plan);
-    par_bound bt;
-    bounds_after(ctx, aabbs, first, n, &bt);
+    const par_bound need = ctx->book.plan(par_change::UPDATE, aabbs, first, n).need;
     PAR_HIP(hipSetDevice(ctx->device));
-    rc = ensure_pool(ctx, std::max(plan.pairs, bt.pairs));
-    if (rc != PAR_OK) return rc;
-    rc = ensure_items(ctx, std::max(plan.items, bt.items), std::max(plan.cols, bt.cols));
+    rc = ensure_room(ctx, need);
     if (rc != PAR_OK) return rc;
     // a frame enqueued asynchronously by par_render_device may still be reading the AABBs: wait for it
     if (ctx->has_last_stream) PAR_HIP(hipStreamSynchronize(ctx->last_stream));
@@ -1061,7 +825,7 @@ static int par_update_aabbs_impl(par_context* ctx, const par_aabb* aabbs, int fi
     }
     PAR_HIP(hipMemcpyAsync(ctx->d_aabbs + first, aabbs, (size_t)n * sizeof(par_aabb), hipMemcpyHostToDevice, ctx->stream));
     PAR_HIP(hipStreamSynchronize(ctx->stream));
-    commit_update(ctx, aabbs, first, n, plan, true);
+    ctx->book.commit();
     mark_staged(ctx, first, n);  // (a captured graph uploads the scene from its staging area)
     return PAR_OK;
 }
@@ -1072,14 +836,13 @@ static int par_update_aabbs_async_impl(par_context* ctx, const par_aabb* aabbs, 
     if (rc != PAR_OK) return rc;
     hipStream_t stream = (hipStream_t)stream_v;
     // No cull and range arithmetic here (it cost a moving scene more host time per frame than its launches): the
-    // frame's launches are sized by what the EXTENTS allow (bound_of) until a blocking call refreshes the exact
-    // bookkeeping, and the frame gets its launch for the overflow list whatever the columns hold.
-    par_bound bt;
-    bounds_after(ctx, aabbs, first, n, &bt);
+    // book keeps the extents alone (EXTENTS_ONLY) until a blocking call refreshes it, and the frame's launches are
+    // sized by them and include the one for the overflow list whatever the columns hold.
+    const par_bound need = ctx->book.plan(par_change::ASYNC, aabbs, first, n).need;
     PAR_HIP(hipSetDevice(ctx->device));
     // the node pool and the item list grow rarely (only when extents grow); that path frees device memory and has to
     // wait for everything in flight
-    if (bt.pairs > ctx->grid.capacity || items_per_shard(ctx, bt.items, bt.cols) > ctx->grid.item_capacity) {
+    if (need.pairs > ctx->grid.capacity || ctx->book.items_per_shard(need.items, need.cols) > ctx->grid.item_capacity) {
         return par_update_aabbs(ctx, aabbs, first, n);
     }
     // frames enqueued on another stream are not ordered with this copy: wait for them
@@ -1098,9 +861,7 @@ static int par_update_aabbs_async_impl(par_context* ctx, const par_aabb* aabbs, 
     PAR_HIP(hipEventRecord(ctx->ev_update, stream));
     ctx->ev_update_pending = true;
     ctx->update_stream = stream;
-    ctx->bound_pairs = bt.pairs; ctx->bound_cols = bt.cols; ctx->bound_items = bt.items;
-    std::memcpy(ctx->h_aabbs.data() + first, aabbs, (size_t)n * sizeof(par_aabb));
-    ctx->exact_stale = true;
+    ctx->book.commit();
     mark_staged(ctx, first, n);  // (a captured graph uploads the scene from its staging area)
     return PAR_OK;
 }
@@ -1183,18 +944,7 @@ static int graph_capture(par_context* ctx, void* stream_v, int row_begin, int ro
     }
     PAR_HIP(hipDeviceSynchronize());
     drop_graphs(ctx);
-    refresh_exact(ctx);
-    // Head-room for moving primitives: pair counts of later frames are only bounded by the pool.
-    ctx->graph_pair_bound = ctx->total_pairs * 2 + 4096;
-    rc = ensure_pool(ctx, ctx->graph_pair_bound);
-    if (rc != PAR_OK) return rc;
-    {   // wherever the entities move: each reaches at most this many screen columns (cull and ranges of alt:212-240)
-        const int B = ctx->params.bin_size;
-        const int64_t cols_max = (int64_t)((PAR_SPRITE_W + B - 1) / B + 1) * ((PAR_SPRITE_H + B - 1) / B + 1);
-        ctx->graph_item_bound = std::min<int64_t>(
-            (int64_t)ctx->n_entities * ((int64_t)PAR_SPRITE_W * PAR_SPRITE_H / 64 + cols_max), max_items(ctx));
-    }
-    rc = ensure_items(ctx, ctx->graph_item_bound, ctx->graph_pair_bound);
+    rc = ensure_room(ctx, ctx->book.capture());
     if (rc != PAR_OK) return rc;
     for (int s = 0; s < 2; s++) {
         if (!ctx->pin_aabbs[s]) {
@@ -1203,7 +953,7 @@ static int graph_capture(par_context* ctx, void* stream_v, int row_begin, int ro
         if (!ctx->pin_lights[s]) PAR_HIP(hipHostMalloc(&ctx->pin_lights[s], sizeof(par_lights_block), hipHostMallocDefault));
         if (!ctx->ev_graph[s]) PAR_HIP(hipEventCreateWithFlags(&ctx->ev_graph[s], hipEventDisableTiming));
         ctx->ev_graph_pending[s] = false;
-        std::memcpy(ctx->pin_aabbs[s], ctx->h_aabbs.data(), (size_t)ctx->n_entities * sizeof(par_aabb));
+        std::memcpy(ctx->pin_aabbs[s], ctx->book.aabbs.data(), (size_t)ctx->n_entities * sizeof(par_aabb));
         ctx->pin_lights[s]->lights = make_lights_dyn(ctx);
         ctx->stage_lo[s] = ctx->stage_hi[s] = 0;
     }
@@ -1236,12 +986,11 @@ static int graph_capture(par_context* ctx, void* stream_v, int row_begin, int ro
         if (e2 != hipSuccess) return hip_fail(ctx, e2, "hipStreamEndCapture");
         return hip_fail(ctx, e3, "hipGraphInstantiate");
     }
-    ctx->graph_set = ctx->set;
     return PAR_OK;
 }
 
 // par_graph_stage (keep_count: `lights` replaces lights[0] and the count stays) and par_graph_stage_lights (the whole
-// light set) for AABBs [first, first + n). A refused call changes nothing but the freshness of the exact bookkeeping.
+// light set) for AABBs [first, first + n). A refused call changes nothing but the freshness of the book.
 static int graph_stage(par_context* ctx, const par_aabb* aabbs, int first, int n, const par_light* lights, int n_lights,
                        bool keep_count) {
     if (!ctx || !ctx->graph_exec[0]) return fail(ctx, PAR_ERR_NOT_READY, "no captured graph");
@@ -1253,13 +1002,11 @@ static int graph_stage(par_context* ctx, const par_aabb* aabbs, int first, int n
     }
     const int rc = check_update(ctx, aabbs, first, n, true);
     if (rc != PAR_OK) return rc;
-    if (ctx->exact_stale) refresh_exact(ctx);  // (the footprints and totals; the histograms may stay behind)
-    par_update_plan plan;
-    plan_update(ctx, aabbs, first, n, &plan);
-    if (plan.pairs > ctx->graph_pair_bound || plan.pairs > ctx->grid.capacity) {
+    const int64_t pairs = ctx->book.plan(par_change::STAGE, aabbs, first, n).exact.pairs;
+    if (pairs > ctx->book.graph.pairs || pairs > ctx->grid.capacity) {
         return fail(ctx, PAR_ERR_UNSUPPORTED, "staged frame exceeds what the captured graph was sized for; capture again");
     }
-    commit_update(ctx, aabbs, first, n, plan, false);
+    ctx->book.commit();
     mark_staged(ctx, first, n);  // (the staging areas are brought up to date by par_graph_launch)
     if (n_lights > 0) set_lights(ctx, lights, n_lights, keep_count ? ctx->n_lights : n_lights);
     return PAR_OK;
@@ -1268,8 +1015,8 @@ static int graph_stage(par_context* ctx, const par_aabb* aabbs, int first, int n
 static int par_graph_launch_impl(par_context* ctx, void* stream) {
     if (!ctx || !ctx->graph_exec[0]) return fail(ctx, PAR_ERR_NOT_READY, "no captured graph");
     // (the scene may also have been changed by par_update_aabbs[_async]: same limit as par_graph_stage)
-    if (ctx->exact_stale) refresh_exact(ctx);
-    if (ctx->total_pairs > ctx->graph_pair_bound) {
+    ctx->book.refresh(par_book_state::HIST_BEHIND);
+    if (ctx->book.exact.pairs > ctx->book.graph.pairs) {
         return fail(ctx, PAR_ERR_UNSUPPORTED, "the scene exceeds what the captured graph was sized for; capture again");
     }
     if (ctx->n_lights > 1 && !ctx->graph_lights) {
@@ -1285,7 +1032,7 @@ static int par_graph_launch_impl(par_context* ctx, void* stream) {
         ctx->ev_graph_pending[s] = false;
     }
     if (ctx->stage_hi[s] > ctx->stage_lo[s]) {
-        std::memcpy(ctx->pin_aabbs[s] + ctx->stage_lo[s], ctx->h_aabbs.data() + ctx->stage_lo[s],
+        std::memcpy(ctx->pin_aabbs[s] + ctx->stage_lo[s], ctx->book.aabbs.data() + ctx->stage_lo[s],
                     (size_t)(ctx->stage_hi[s] - ctx->stage_lo[s]) * sizeof(par_aabb));
         ctx->stage_lo[s] = ctx->stage_hi[s] = 0;
     }

@@ -476,28 +476,60 @@ def test_graph_is_dropped_with_its_sprite_table_and_bad_alloc_hook_gives_oom(par
 
 
 def test_set_entities_after_graph_staging_needs_no_overflow_launch(par, sprite, T):
-    """par_graph_stage lets the per-column histograms lag; par_set_entities rebuilds them, so the frames after it are
-    enqueued without a launch for the overflow list again when no column needs one. The headline scene needs none
-    (a timed frame, timed as launched, shows no overflow launch); after a capture, a stage and par_set_entities of the
-    same scene, the same timed frame has none either, and the same picture."""
+    """The host's scene bookkeeping is CURRENT, HIST_BEHIND (par_graph_stage lets the per-column histograms lag) or
+    EXTENTS_ONLY (par_update_aabbs_async keeps the extents' totals alone). A frame gets its launch for the overflow
+    list exactly when the bookkeeping is not CURRENT, as none of these scenes has a column that needs one; the state
+    decides nothing else about the frame's launches here. A timed frame, timed as launched, after each call that
+    moves the bookkeeping between states (the scene itself stays the same), shows which launches it had, and the
+    same picture. par_set_entities after a stage makes it CURRENT again.
+    The headline scene (1024 primitives in 4096^2) is sparse: no launch for the tile items. A 2048^2 floor is dense:
+    it has that launch. Neither frame is small enough for the one merged render launch, in any state (the occupied
+    columns of the exact bookkeeping and of the extents are both >= 2048)."""
     import torch
-    w = h = l = 4096
-    params = T.default_params(w, h, l)
-    aabbs, light = par.scene_synthetic(1024, w, h, l, 12345)
-    fb = [torch.zeros(w * h * 4, dtype=torch.uint8, device="cuda") for _ in range(2)]
+    fw = 2048
+    floor = T.make_aabbs([(i * 20, 0, j * 20, 20, 20, 20) for i in range(fw // 20) for j in range(fw // 20)])
+    scenes = [(4096, *par.scene_synthetic(1024, 4096, 4096, 4096, 12345), False),
+              (fw, floor, T.make_light(1280, 1024, 512), True)]
     stream = torch.cuda.Stream()
     s = stream.cuda_stream
-    with par.Renderer(params) as r:
-        r.set_scene(aabbs, sprite, light)
-        st = r.render_device({"fb": fb[0].data_ptr()}, stream=s, timed=True, flags=par.RENDER_TIMED_AS_LAUNCHED)
-        assert st.ms_launch[4] == 0 and st.render_merged == 0, (list(st.ms_launch), st.render_merged)
-        r.graph_capture({"fb": fb[1].data_ptr()}, stream=s)
-        r.graph_stage(aabbs, 0)
-        r.set_entities(aabbs)
-        st = r.render_device({"fb": fb[1].data_ptr()}, stream=s, timed=True, flags=par.RENDER_TIMED_AS_LAUNCHED)
-        assert st.ms_launch[4] == 0, "par_set_entities left the per-column histograms marked stale"
-        stream.synchronize()
-        assert torch.equal(fb[0], fb[1])
+    for w, aabbs, light, tiles in scenes:
+        params = T.default_params(w, w, w)
+        fb = [torch.zeros(w * w * 4, dtype=torch.uint8, device="cuda") for _ in range(3)]  # first, later, graph
+        with par.Renderer(params) as r:
+            def capture_stage():
+                r.graph_capture({"fb": fb[2].data_ptr()}, stream=s)
+                r.graph_stage(aabbs, 0)
+
+            def stage_launch():
+                r.graph_stage(aabbs, 0)
+                r.graph_launch(s)
+
+            def async_launch():
+                r.update_aabbs(aabbs, 0, stream=s)
+                r.graph_launch(s)
+
+            def stage_set_entities():
+                r.graph_stage(aabbs, 0)
+                r.set_entities(aabbs)
+
+            steps = [("set_scene", lambda: r.set_scene(aabbs, sprite, light), "CURRENT"),
+                     ("async update", lambda: r.update_aabbs(aabbs, 0, stream=s), "EXTENTS_ONLY"),
+                     ("blocking update", lambda: r.update_aabbs(aabbs, 0), "CURRENT"),
+                     ("capture + stage", capture_stage, "HIST_BEHIND"),
+                     ("stage + launch", stage_launch, "HIST_BEHIND"),
+                     ("async + launch", async_launch, "CURRENT"),
+                     ("stage + set_entities", stage_set_entities, "CURRENT")]
+            for k, (what, step, state) in enumerate(steps):
+                step()
+                out = fb[0 if k == 0 else 1]
+                st = r.render_device({"fb": out.data_ptr()}, stream=s, timed=True, flags=par.RENDER_TIMED_AS_LAUNCHED)
+                tag = (w, what, state, list(st.ms_launch), st.render_merged)
+                assert (st.ms_launch[4] == 0) == (state == "CURRENT"), tag
+                assert (st.ms_launch[3] > 0) == tiles and st.render_merged == 0, tag
+                stream.synchronize()
+                assert torch.equal(out, fb[0]), tag
+                if "launch" in what:
+                    assert torch.equal(fb[2], fb[0]), tag
 
 
 def test_config1_default_scene_128(par, oracle, sprite, T):
