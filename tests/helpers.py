@@ -83,4 +83,53 @@ def shadow_walk_cases():
     return aabbs, walks
 
 
+# ---- the shadow walk's bin sequence, restated on the host -------------------------------------------------------
+
+WALK_MASKS = [(1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1)]
+
+
+def _trunc_div(a, b):
+    """C's integer division: truncation towards zero (Python's // floors)."""
+    q = abs(a) // abs(b)
+    return q if (a < 0) == (b < 0) else -q
+
+
+def light_bin(params, light_pos):
+    """The bin a light lies in, as the shading loop computes it (alt:729-732): C division, no clamping."""
+    x, y, z = (int(v) for v in light_pos)
+    B = params.bin_size
+    return (_trunc_div(x, B), _trunc_div(params.height - y - z, B), _trunc_div(z, B))
+
+
+def walk_probes(start, end, gy, gz):
+    """Flat bin indices probed by the shadow walk from bin `start` to bin `end` (alt:399-500, par_oracle_shadow), in
+    order, the start bin and out-of-range indices included: the step is accumulated in float32, every iteration
+    probes the seven neighbours of its position, and the seventh probe advances the walk."""
+    f32 = np.float32
+    s = [f32(v) for v in start]
+    d = [f32(e) - a for e, a in zip(end, s)]
+    largest = max(abs(d[0]), abs(d[1]), abs(d[2]))
+    if int(largest) == 0:
+        return []
+    st = [v / largest for v in d]  # float32 / float32
+    t, out = list(s), []
+    for _ in range(int(largest)):
+        for k, mk in enumerate(WALK_MASKS):
+            c = [t[a] + st[a] if mk[a] else t[a] for a in range(3)]
+            if k == 6:
+                t = c
+            x, y, z = (int(v) for v in c)  # truncation, as the (int) casts of alt:468
+            out.append((x * gy + y) * gz + z)
+    return out
+
+
+def walk_record_bounds(count, start, end, gy, gz):
+    """(lower, upper) bounds of the occluder records a wavefront stages for the walk from bin `start` to bin `end`:
+    every distinct probe of an iteration is staged once, so the records number at least the sum of `count` over the
+    distinct probed bins and at most the sum over all probes (start bin and out-of-range indices left out)."""
+    b0 = (start[0] * gy + start[1]) * gz + start[2]
+    live = [b for b in walk_probes(start, end, gy, gz) if b != b0 and 0 <= b < len(count)]
+    return int(sum(int(count[b]) for b in set(live))), int(sum(int(count[b]) for b in live))
+
+
 DEBUG_LINE_MICE = [(0, 0), (240, 160), (479, 319)]
