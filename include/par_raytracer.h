@@ -143,12 +143,38 @@ int par_set_light(par_context* ctx, const par_light* light);
  *     lit plane: bit l set <=> lit_l
  * With n = 1 this is the reference's formula exactly. A background pixel keeps its colour (its normal is zero); its lit
  * bits are traced only when rays are asked for (PAR_RENDER_TRACE_BACKGROUND or a lit plane), each the reference's
- * background ray towards light l. `radius` is not read. With PAR_RENDER_COUNT_RAYS, shadow_rays counts (pixel, light)
+ * background ray towards light l. `radius` is not read (but see par_set_light_model). With PAR_RENDER_COUNT_RAYS, shadow_rays counts (pixel, light)
  * rays. A frame with n >= 2 runs the hash build, the background fill and one render launch (the light kernel); a
  * timed one reports the light kernel as ms_render and ms_launch[2] and 0 for the launches it does not have.
  * par_graph_capture and par_graph_launch (on a one-light graph) on a context with more than one light return
  * PAR_ERR_UNSUPPORTED; par_graph_capture_lights captures the frame of several lights. */
 int par_set_lights(par_context* ctx, const par_light* lights, int n);
+
+/* The light model of a context. A new context is PAR_LIGHTS_UNBOUNDED: everything above, `radius` not read. */
+enum { PAR_LIGHTS_UNBOUNDED = 0, PAR_LIGHTS_RANGED = 1 };
+/* PAR_ERR_INVALID_ARG, before any device work, for a null context or a model that is neither of the two. Under
+ * PAR_LIGHTS_RANGED everything par_set_lights says holds, with these changes for light l at (lx, ly, lz) with radius
+ * r_l and a covered pixel at P = (x, gbuf.y, gbuf.z):
+ *   r_l <= 0: the light is unbounded, treated exactly as under PAR_LIGHTS_UNBOUNDED (a sun beside torches).
+ *   r_l > 0:  with dx, dy, dz the fp32 differences the shading loop forms (alt:712-714) and
+ *             len = (|dx| + |dy|) + |dz|, the L1 length Vector::normalize divides by (spr:28-35; the distance of the
+ *             reference's own commented-out attenuation, alt:748-755), the pixel is IN RANGE iff len < (float)r_l.
+ *       out of range: the light contributes nothing, bit l of `lit` is 0 and no shadow ray is traced towards it;
+ *       in range:     lit_l as before, w_l = 1.f - len / (float)r_l (one IEEE division, one subtraction, no
+ *                     contraction), and the sum becomes: if lit_l, s = s + d_l * w_l (the product rounded, then the
+ *                     addition, no fma). An unbounded light keeps s = s + d_l.
+ *   brightness, fb, the order of the sum, the G-buffer and the palette index are unchanged.
+ *   A background pixel's position is (x, 0, 0) as in the reference (alt:707-709 on a zeroed Pixel): its bit l, traced
+ *   only when rays are asked for, is (in range && the background ray towards light l), by the same len.
+ *   With PAR_RENDER_COUNT_RAYS, shadow_rays counts the (covered pixel, light) pairs that are in range or unbounded.
+ *   A frame takes the light kernel whatever the light count (one light too). par_graph_capture on a ranged context,
+ *   and par_graph_launch of a one-light graph on one, return PAR_ERR_UNSUPPORTED. par_graph_capture_lights captures the
+ *   model the context has; par_set_light_model with a DIFFERENT model drops the captured graphs as par_set_sprites
+ *   does (PAR_ERR_NOT_READY from the stage and launch calls afterwards); the same model again does nothing. Radii
+ *   staged with par_graph_stage_lights, par_graph_stage or set with par_set_light[s] reach the next launch as the
+ *   positions do.
+ *   With every r_l <= 0 a ranged frame equals the unbounded frame, byte for byte on every plane. */
+int par_set_light_model(par_context* ctx, int model);
 
 /* --- render: replaces alt:690-760 ----------------------------------------------------------------------------- */
 

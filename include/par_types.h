@@ -57,7 +57,9 @@ typedef struct par_aabb {
     int16_t pad_[2];
 } par_aabb;
 
-/* `Light`, alt:619-622. `radius` is carried but, as in the reference, never read. */
+/* `Light`, alt:619-622. `radius` is not read, as in the reference, unless the context's light model is
+ * PAR_LIGHTS_RANGED (par_set_light_model, par_raytracer.h): then a radius > 0 bounds and attenuates the light by the L1
+ * distance, and a radius <= 0 leaves it unbounded. */
 typedef struct par_light {
     int16_t x, y, z;
     int16_t radius;

@@ -40,9 +40,10 @@ ABI_SYMBOLS = (
     "par_sprite_tile_floor", "par_scene_graybox", "par_scene_synthetic", "par_debug_line", "par_debug_units",
     "par_render_device_slots", "par_row_block", "par_scene_tiles", "par_tiles_pack", "par_tiles_unpack",
     "par_background_fill", "par_tiles_assemble", "par_scene_tile_map", "par_set_lights", "par_graph_capture_lights",
-    "par_graph_stage_lights",
+    "par_graph_stage_lights", "par_set_light_model",
 )
 MAX_LIGHTS = 8  # PAR_MAX_LIGHTS
+LIGHTS_UNBOUNDED, LIGHTS_RANGED = 0, 1  # par_set_light_model
 
 
 class ParError(RuntimeError):
@@ -101,6 +102,7 @@ def lib():
         L.par_update_aabbs_async.argtypes = [vp, vp, i32, i32, vp]
         L.par_set_light.argtypes = [vp, vp]
         L.par_set_lights.argtypes = [vp, vp, i32]
+        L.par_set_light_model.argtypes = [vp, i32]
         L.par_render.argtypes = [vp, vp, C.c_uint]
         L.par_render_rows.argtypes = [vp, i32, i32, vp, C.c_uint]
         L.par_render_device.argtypes = [vp, vp, i32, i32, vp, C.c_uint]
@@ -129,6 +131,7 @@ def lib():
         L.par_scene_tile_map.argtypes = [vp, vp, i32, vp, i32]
         L.par_debug_read_stamps.argtypes = [vp, vp, C.c_size_t]
         L.par_debug_set_hooks.argtypes = [vp, C.c_uint, i32]
+        L.par_debug_read_light_walks.argtypes = [vp, vp]
         L.par_debug_line.restype = None
         L.par_debug_line.argtypes = [vp, vp, i32, vp, vp]
         _lib = L
@@ -269,6 +272,12 @@ class Renderer:
         lights = np.ascontiguousarray(lights, dtype=LIGHT)
         self._check(lib().par_set_lights(self._ctx, ptr(lights), len(lights)))
 
+    def set_light_model(self, model):
+        """LIGHTS_UNBOUNDED (a new renderer: `radius` is not read) or LIGHTS_RANGED (par_set_light_model): a light with
+        radius > 0 reaches the pixels whose L1 distance to it is below the radius and fades out towards it; a radius
+        <= 0 leaves a light unbounded. A different model drops captured graphs."""
+        self._check(lib().par_set_light_model(self._ctx, int(model)))
+
     def set_scene(self, aabbs, sprites, light, sprite_ids=None):
         self.set_sprites(sprites)
         self.set_entities(aabbs, sprite_ids)
@@ -354,6 +363,14 @@ class Renderer:
         hooks = (int(force_generic) | int(two_launch_build) << 1 | int(record_items) << 2 | int(lose_build_wg) << 3 |
                  int(bad_alloc) << 4 | int(lights_path) << 5)
         self._check(lib().par_debug_set_hooks(self._ctx, hooks, col_roles))
+
+    def light_walks(self):
+        """Tests only (par_debug_read_light_walks, not part of the public header): the (start bin, light) pairs the
+        ranged light kernel (walked, culled) in the last frame, which must have been rendered with RENDER_COUNT_RAYS
+        (else (-1, -1))."""
+        out = np.zeros(2, dtype=np.int64)
+        self._check(lib().par_debug_read_light_walks(self._ctx, ptr(out)))
+        return int(out[0]), int(out[1])
 
     def read_grid(self):
         """(count, map, bins) of the last frame in the reference's layout (alt:503-509); parity tooling."""

@@ -16,11 +16,13 @@
 #include "par_book.h"
 #include "par_internal.h"
 
-// The staged lights of a captured graph: par_lights_dyn padded to a whole number of 64-byte lines. A one-light graph's
+// The staged lights of a captured graph: par_lights_dyn, then the lights' radii (read by the ranged light kernels
+// alone), padded to a whole number of 64-byte lines; the graph's copy node copies the whole block. A one-light graph's
 // kernels read their par_frame_dyn from lights.l[0].
 struct par_lights_block {
     par_lights_dyn lights;
-    int32_t pad_[(256 - sizeof(par_lights_dyn)) / sizeof(int32_t)];
+    par_light_radii radii;
+    int32_t pad_[(256 - sizeof(par_lights_dyn) - sizeof(par_light_radii)) / sizeof(int32_t)];
 };
 static_assert(sizeof(par_lights_block) == 256, "lights staging block");
 
@@ -35,6 +37,8 @@ struct par_context {
     bool have_entities = false;
     par_light lights[PAR_MAX_LIGHTS]{};  // set_lights; n_lights >= 2 (or the test hook) takes the light kernel
     int n_lights = 0;                    // 0 until a light is set
+    int depth_min = 0, depth_max = 0;    // least and largest texel depth of the sprite table (par_set_sprites)
+    int light_model = PAR_LIGHTS_UNBOUNDED;  // par_set_light_model; PAR_LIGHTS_RANGED always takes the light kernel
     int set = 0;  // head/count/node set the NEXT frame uses
     hipStream_t last_stream = nullptr;  // stream of the most recent asynchronous render (scene updates wait for it)
     bool has_last_stream = false;
@@ -74,6 +78,7 @@ struct par_context {
     hipStream_t update_stream = nullptr;
     // The captured kernels read the frame's lights from d_lights (a one-light graph's from the first light alone).
     bool graph_lights = false;  // which kernels were captured: false one-light (par_graph_capture), true light path
+                                // (then of the light model the context had, which only changes with the graphs dropped)
     par_lights_block* d_lights = nullptr;
 
     bool timed_tiles = false, timed_overflow = false, timed_both = false;  // the last timed frame launched these kernels
@@ -383,14 +388,30 @@ int check_device_error(par_context* ctx) {
     return fail(ctx, PAR_ERR_DEVICE, what + "a frame rendered since the last check is not valid");
 }
 
-// A frame takes the light kernel when it has several lights (or the test hook asks for it with one).
-bool lights_path(const par_context* c) { return c->n_lights > 1 || (c->hooks & PAR_HOOK_LIGHTS_PATH); }
+// A frame takes the light kernel when it has several lights, or ranged ones (or the test hook asks for it with one).
+bool ranged(const par_context* c) { return c->light_model == PAR_LIGHTS_RANGED; }
+bool lights_path(const par_context* c) { return c->n_lights > 1 || ranged(c) || (c->hooks & PAR_HOOK_LIGHTS_PATH); }
 
 par_lights_dyn make_lights_dyn(const par_context* c) {
     par_lights_dyn lights{};
     lights.n = c->n_lights;
     for (int l = 0; l < c->n_lights; l++) lights.l[l] = make_dyn(c, c->lights[l]);
     return lights;
+}
+
+// Their radii for the ranged light kernels (<= 0: unbounded; the lights the context does not have read as that).
+par_light_radii make_light_radii(const par_context* c) {
+    par_light_radii radii{};
+    for (int l = 0; l < c->n_lights; l++) radii.r[l] = c->lights[l].radius;
+    radii.depth_min = c->depth_min;
+    radii.depth_max = c->depth_max;
+    return radii;
+}
+
+// Staging area `s` of the captured graphs: the context's lights as they are now.
+void stage_lights(par_context* c, int s) {
+    c->pin_lights[s]->lights = make_lights_dyn(c);
+    c->pin_lights[s]->radii = make_light_radii(c);
 }
 
 // The hash build: small scenes in one launch, large ones in two (and frames that keep their kernels `apart`, and the
@@ -413,11 +434,15 @@ int enqueue_build(par_context* ctx, hipStream_t stream, const par_bin_args& b, i
 // Timed frames bracket the launches with the same events as enqueue_frame: the light kernel is ms_render and
 // ms_launch[2]; the other render launches it does not have are 0. In graph mode (par_graph_capture_lights) the
 // launches are sized by what the graph accepts (par_book::graph) and the kernels read the lights from d_lights, which
-// the graph's copy node fills before them: one graph serves any count of lights.
+// the graph's copy node fills before them: one graph serves any count of lights. A ranged context (PAR_LIGHTS_RANGED)
+// launches the ranged kernels, with the radii beside the lights.
 int enqueue_lights_frame(par_context* ctx, hipStream_t stream, const par_bin_args& b, const par_render_args& r,
                          const par_bound& bound, bool graph_mode, bool apart, hipEvent_t* ev) {
     const par_lights_dyn lights = make_lights_dyn(ctx);
     const par_lights_dyn* d_lights = graph_mode ? &ctx->d_lights->lights : nullptr;
+    const par_light_radii radii_v = make_light_radii(ctx);
+    const par_light_radii* radii = ranged(ctx) ? &radii_v : nullptr;
+    const par_light_radii* d_radii = graph_mode ? &ctx->d_lights->radii : nullptr;
     const int rc = enqueue_build(ctx, stream, b, bound.pairs, &r, nullptr, apart);
     if (rc != PAR_OK) return rc;
     if (ev) {
@@ -425,11 +450,11 @@ int enqueue_lights_frame(par_context* ctx, hipStream_t stream, const par_bin_arg
         PAR_HIP(hipEventRecord(ev[EV_COLUMNS], stream));
     }
     if (r.trace_bg) {
-        PAR_HIP(par_launch_bglights(ctx->grid, r, lights, d_lights, stream));
+        PAR_HIP(par_launch_bglights(ctx->grid, r, lights, d_lights, radii, d_radii, stream));
     }
     PAR_HIP(par_launch_fill(ctx->grid, r, stream));
     if (ev) PAR_HIP(hipEventRecord(ev[EV_FILLED], stream));
-    PAR_HIP(par_launch_render_lights(ctx->grid, r, lights, d_lights, bound.cols, stream));
+    PAR_HIP(par_launch_render_lights(ctx->grid, r, lights, d_lights, radii, d_radii, bound.cols, stream));
     if (ev) {
         PAR_HIP(hipEventRecord(ev[EV_ITEMS], stream));
         PAR_HIP(hipEventRecord(ev[EV_RENDERED], stream));
@@ -465,7 +490,7 @@ int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, 
     const bool apart = ev && !(flags & PAR_RENDER_TIMED_AS_LAUNCHED);
     const par_bound bound = ctx->book.frame_bounds(graph_mode);
     if ((flags & PAR_RENDER_COUNT_RAYS) && !graph_mode) {
-        PAR_HIP(hipMemsetAsync(ctx->d_ray_counter, 0, sizeof(unsigned long long), stream));
+        PAR_HIP(hipMemsetAsync(ctx->d_ray_counter, 0, 3 * sizeof(unsigned long long), stream));
     }
     if (ev) PAR_HIP(hipEventRecord(ev[EV_START], stream));
     // (a captured graph takes the path of its kind, chosen when it is captured)
@@ -590,7 +615,7 @@ std::array<par_dev_buffer, 19> dev_buffers(par_context* c, bool stamps) {
         {(void**)&g.bglit, (size_t)c->params.width + 64, 1},
         {(void**)&g.slots, vol * PAR_SLOTS * sizeof(par_slot), 0},
         {(void**)&c->d_palette, PAR_MAX_PALETTE * sizeof(par_color), -1},  // (par_create copies the palette in)
-        {(void**)&c->d_ray_counter, sizeof(unsigned long long), -1},
+        {(void**)&c->d_ray_counter, 3 * sizeof(unsigned long long), -1},  // (par_render_args::ray_counter)
         {(void**)&c->d_lights, sizeof(par_lights_block), -1},
     }};
 }
@@ -729,6 +754,16 @@ static int par_set_sprites_impl(par_context* ctx, const par_sprite* sprites, int
     }
     PAR_HIP(reallocate(&ctx->d_texinfo, tex.size()));
     PAR_HIP(hipMemcpy(ctx->d_texinfo, tex.data(), tex.size() * sizeof(par_texel), hipMemcpyHostToDevice));
+    // the depths' range, for the range cull of ranged lights (clamped far outside any bin: the arithmetic stays in int)
+    int dmin = INT32_MAX, dmax = INT32_MIN;
+    for (int s = 0; s < n_sprites; s++) {
+        for (int t = 0; t < PAR_SPRITE_TEXELS; t++) {
+            dmin = std::min(dmin, (int)sprites[s].depth[t]);
+            dmax = std::max(dmax, (int)sprites[s].depth[t]);
+        }
+    }
+    ctx->depth_min = std::max(dmin, -(1 << 24));
+    ctx->depth_max = std::min(dmax, 1 << 24);
     ctx->n_sprites = n_sprites;
     return PAR_OK;
 }
@@ -874,6 +909,19 @@ static int par_set_lights_impl(par_context* ctx, const par_light* lights, int n)
     return PAR_OK;
 }
 
+static int par_set_light_model_impl(par_context* ctx, int model) {
+    if (!ctx) return PAR_ERR_INVALID_ARG;
+    if (model != PAR_LIGHTS_UNBOUNDED && model != PAR_LIGHTS_RANGED) {
+        return fail(ctx, PAR_ERR_INVALID_ARG, "light model: PAR_LIGHTS_UNBOUNDED or PAR_LIGHTS_RANGED");
+    }
+    if (model == ctx->light_model) return PAR_OK;
+    PAR_HIP(hipSetDevice(ctx->device));
+    PAR_HIP(hipDeviceSynchronize());
+    drop_graphs(ctx);  // (a captured graph bakes the kernels of the model it was captured with)
+    ctx->light_model = model;
+    return PAR_OK;
+}
+
 static int par_set_light_impl(par_context* ctx, const par_light* light) {
     if (!ctx || !light) return fail(ctx, PAR_ERR_INVALID_ARG, "light");
     return par_set_lights_impl(ctx, light, 1);
@@ -939,6 +987,9 @@ static int graph_capture(par_context* ctx, void* stream_v, int row_begin, int ro
     if (ctx && device_out && !stream) return fail(ctx, PAR_ERR_INVALID_ARG, "graph capture needs a non-default stream");
     int rc = frame_prologue(ctx, device_out, row_begin, row_end, flags);
     if (rc != PAR_OK) return rc;
+    if (!lights_kind && ranged(ctx)) {
+        return fail(ctx, PAR_ERR_UNSUPPORTED, "a frame with ranged lights cannot be captured (par_graph_capture_lights)");
+    }
     if (!lights_kind && lights_path(ctx)) {
         return fail(ctx, PAR_ERR_UNSUPPORTED, "a frame with several lights cannot be captured (par_graph_capture_lights)");
     }
@@ -954,7 +1005,7 @@ static int graph_capture(par_context* ctx, void* stream_v, int row_begin, int ro
         if (!ctx->ev_graph[s]) PAR_HIP(hipEventCreateWithFlags(&ctx->ev_graph[s], hipEventDisableTiming));
         ctx->ev_graph_pending[s] = false;
         std::memcpy(ctx->pin_aabbs[s], ctx->book.aabbs.data(), (size_t)ctx->n_entities * sizeof(par_aabb));
-        ctx->pin_lights[s]->lights = make_lights_dyn(ctx);
+        stage_lights(ctx, s);
         ctx->stage_lo[s] = ctx->stage_hi[s] = 0;
     }
     ctx->graph_lights = lights_kind;  // (what enqueue_frame captures; no graph is left behind should the capture fail)
@@ -1022,6 +1073,9 @@ static int par_graph_launch_impl(par_context* ctx, void* stream) {
     if (ctx->n_lights > 1 && !ctx->graph_lights) {
         return fail(ctx, PAR_ERR_UNSUPPORTED, "a frame with several lights has no one-light graph (par_graph_capture_lights)");
     }
+    if (ranged(ctx) && !ctx->graph_lights) {
+        return fail(ctx, PAR_ERR_UNSUPPORTED, "a frame with ranged lights has no one-light graph (par_graph_capture_lights)");
+    }
     const int s = ctx->set;
     if (!ctx->graph_exec[s]) return fail(ctx, PAR_ERR_NOT_READY, "no captured graph for this grid set");
     PAR_HIP(hipSetDevice(ctx->device));
@@ -1036,7 +1090,7 @@ static int par_graph_launch_impl(par_context* ctx, void* stream) {
                     (size_t)(ctx->stage_hi[s] - ctx->stage_lo[s]) * sizeof(par_aabb));
         ctx->stage_lo[s] = ctx->stage_hi[s] = 0;
     }
-    ctx->pin_lights[s]->lights = make_lights_dyn(ctx);
+    stage_lights(ctx, s);
     // an asynchronous scene update on another stream: this frame comes after it
     if (ctx->ev_update_pending && ctx->update_stream != (hipStream_t)stream) {
         PAR_HIP(hipStreamWaitEvent((hipStream_t)stream, ctx->ev_update, 0));
@@ -1096,6 +1150,21 @@ int par_debug_read_stamps(par_context* ctx, unsigned long long* out, size_t coun
     const size_t n = (size_t)PAR_STAMP_ROWS * PAR_STAMP_WGS * PAR_STAMP_SLOTS;
     if (hipDeviceSynchronize() != hipSuccess) return PAR_ERR_HIP;
     if (hipMemcpy(out, ctx->grid.stamps, (count < n ? count : n) * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return PAR_ERR_HIP;
+    return PAR_OK;
+}
+
+// Internal test aid (not part of the public header either): the (start bin, light) pairs the ranged light kernel walked
+// (out[0]) and culled (out[1]) in the last frame rendered with PAR_RENDER_COUNT_RAYS; -1 and -1 when the last frame
+// was not. Pairs of the bins whose walks the kernel records (the first 64 occupied bins of a column).
+int par_debug_read_light_walks(par_context* ctx, int64_t* out) {
+    if (!ctx || !out) return PAR_ERR_INVALID_ARG;
+    out[0] = out[1] = -1;
+    if (!(ctx->last_flags & PAR_RENDER_COUNT_RAYS)) return PAR_OK;
+    unsigned long long v[2] = {0, 0};
+    if (hipSetDevice(ctx->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return PAR_ERR_HIP;
+    if (hipMemcpy(v, ctx->d_ray_counter + 1, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return PAR_ERR_HIP;
+    out[0] = (int64_t)v[0];
+    out[1] = (int64_t)v[1];
     return PAR_OK;
 }
 
@@ -1279,6 +1348,9 @@ int par_set_light(par_context* ctx, const par_light* light) {
 }
 int par_set_lights(par_context* ctx, const par_light* lights, int n) {
     return guarded(ctx, [&] { return par_set_lights_impl(ctx, lights, n); });
+}
+int par_set_light_model(par_context* ctx, int model) {
+    return guarded(ctx, [&] { return par_set_light_model_impl(ctx, model); });
 }
 int par_render(par_context* ctx, const par_outputs* host_out, unsigned flags) {
     return guarded(ctx, [&] { return par_render_impl(ctx, host_out, flags); });

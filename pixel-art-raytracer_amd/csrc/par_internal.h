@@ -121,6 +121,14 @@ struct par_lights_dyn {
     par_frame_dyn l[PAR_MAX_LIGHTS];
 };
 
+// The radii of those lights under PAR_LIGHTS_RANGED (par_light.radius; <= 0: the light is unbounded), which only the
+// ranged instantiations of the light kernels take: a second kernel argument, or, in graph mode, device memory right
+// behind the graph's par_lights_dyn (the same copy node uploads both).
+struct par_light_radii {
+    int32_t r[PAR_MAX_LIGHTS];
+    int32_t depth_min, depth_max;  // least and largest texel depth of the sprite table (the range cull, par_lightbox.h)
+};
+
 // Render flags that make the render launch use its instrumented variant (ray counting and the time stamps, bit 29);
 // a production frame has neither and runs kernels compiled without them.
 constexpr uint32_t PAR_DEBUG_FLAGS = PAR_RENDER_COUNT_RAYS | (1u << 29);
@@ -213,7 +221,7 @@ struct par_render_args {
     const int32_t* sprite_ids;     // nullable
     const par_color* palette;
     par_outputs out;               // device pointers, addressing (row_begin, 0)
-    unsigned long long* ray_counter;
+    unsigned long long* ray_counter;  // [3]: shadow rays; (start bin, light) pairs the ranged light kernel walked, culled
 };
 
 // PAR_CNT_ERROR is STICKY: kernels only ever set bits in it (a frame's insert resets the other counters, not this
@@ -269,13 +277,17 @@ hipError_t par_launch_render_overflow(const par_grid_dev& g, const par_render_ar
 // kernels do not run.
 // The kernels take `lights` as a kernel argument, or, when `d_lights` is not null (a captured graph), read the frame's
 // lights from that device memory (a copy node of the graph fills it before them), once per workgroup, so one graph
-// serves any count of lights.
+// serves any count of lights. `radii` null: the unbounded kernels; else the ranged ones (PAR_LIGHTS_RANGED), which take
+// the radii as an argument too or, with `d_lights`, read them from `d_radii`. Under PAR_RENDER_COUNT_RAYS the ranged
+// light kernel also adds the (start bin, light) pairs it walked and culled to a.ray_counter[1] and [2].
 hipError_t par_launch_render_lights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,
-                                    const par_lights_dyn* d_lights, int64_t column_bound, hipStream_t stream);
+                                    const par_lights_dyn* d_lights, const par_light_radii* radii,
+                                    const par_light_radii* d_radii, int64_t column_bound, hipStream_t stream);
 // The background rays of such a frame (one per x and light, bit l of g.bglit[x] for light l); par_launch_fill then
-// copies them into the lit plane. `lights`, `d_lights` as above.
+// copies them into the lit plane. `lights`, `d_lights`, `radii`, `d_radii` as above.
 hipError_t par_launch_bglights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,
-                               const par_lights_dyn* d_lights, hipStream_t stream);
+                               const par_lights_dyn* d_lights, const par_light_radii* radii,
+                               const par_light_radii* d_radii, hipStream_t stream);
 
 // Sharded frames: tiles between a frame block and packed slots, and the background colour for whole rows.
 hipError_t par_launch_tiles_copy(bool pack, const int32_t* d_tiles, int n, int W, int H, int B, int row_begin, int row_end,

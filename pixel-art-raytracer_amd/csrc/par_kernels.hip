@@ -32,6 +32,7 @@
 #include "par_internal.h"
 #include "par_fastdiv.h"
 #include "par_strips.h"
+#include "par_lightbox.h"
 
 #include <limits.h>
 
@@ -2252,6 +2253,15 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_both_kernel(par_grid_
 //      par_raytracer.h (par_set_lights). Each walk is done once per column and light.
 // Two instantiations: the lights as a kernel argument (direct frames), or read from device memory once per workgroup
 // into LDS (a captured graph, whose copy node uploads them before the frame): frame_lights.
+// Each of them again in a RANGED form (PAR_LIGHTS_RANGED, the contract beside par_set_light_model), which takes the
+// lights' radii as one more argument (frame_radii) and differs in two places:
+//   A. a (start bin, light) pair is not walked when no pixel in range of the light can start in that bin: by the bin
+//      alone, then by what the column's slot records can show in it (par_lightbox.h). It is marked as a recorded
+//      walk of zero records, and the pairs that are left are dealt to the wavefronts;
+//   B. per pixel and light the range test comes first -- out of range: no slab tests, no lane walk, no bit, no ray
+//      counted -- and a ranged light's diffuse term is weighted by 1 - len / r. The per-pixel test alone decides a
+//      pixel: the cull only skips walks whose records no pixel in range would read.
+// The unbounded instantiations have no such argument, LDS or code (`if constexpr`).
 // ------------------------------------------------------------------------------------------------------------
 constexpr int PAR_LIGHT_NB = 64;      // occupied bins of a column whose walks are recorded (the others: lane walks)
 constexpr int PAR_LIGHT_WALK = 1024;  // occluder records of all walks of a column (16 KiB)
@@ -2285,11 +2295,45 @@ __device__ __forceinline__ const par_lights_dyn& frame_lights(const par_lights_d
     return sl;
 }
 
-// LightsArg: par_lights_dyn (direct frames) or const par_lights_dyn* (graph replay), see frame_lights.
-template <class LightsArg>
+// The radii a RANGED light kernel reads, as frame_lights hands out the lights: its kernel argument, or the device
+// memory behind the graph's lights, read once per workgroup into LDS. The unbounded kernels have none.
+struct NoRadii {};
+__device__ __forceinline__ NoRadii frame_radii() { return NoRadii{}; }
+__device__ __forceinline__ const par_light_radii& frame_radii(const par_light_radii& radii) { return radii; }
+__device__ __forceinline__ const par_light_radii& frame_radii(const par_light_radii* src) {
+    __shared__ par_light_radii sr;
+    constexpr int N = (int)(sizeof(par_light_radii) / sizeof(int32_t));
+    if ((int)threadIdx.x < N) reinterpret_cast<int32_t*>(&sr)[threadIdx.x] = reinterpret_cast<const int32_t*>(src)[threadIdx.x];
+    __syncthreads();
+    return sr;
+}
+
+// The L1 length of light - world as light_dir forms it (alt:712-714, spr:28-35): three differences of integers and
+// their sum, exact in fp32 for every view the library accepts.
+__device__ __forceinline__ float light_l1(const par_frame_dyn& l, int x, int y, int z) {
+    const float dx = (float)(l.lx - x), dy = (float)(l.ly - y), dz = (float)(l.lz - z);
+    return __builtin_fabsf(dx) + __builtin_fabsf(dy) + __builtin_fabsf(dz);
+}
+
+// The (start bin, light) pairs of a column that survive the range cull (RANGED light kernel only).
+struct LightLive {
+    int32_t n_live;
+    int16_t live[PAR_LIGHT_NB * PAR_MAX_LIGHTS];  // indices into woff / wcnt, in no particular order
+};
+__device__ __forceinline__ LightLive& light_live() {
+    __shared__ LightLive lv;
+    return lv;
+}
+
+// LightsArg: par_lights_dyn (direct frames) or const par_lights_dyn* (graph replay), see frame_lights. Radii: nothing
+// (unbounded lights), or par_light_radii / const par_light_radii* in the same way (the RANGED form), see frame_radii.
+template <class LightsArg, class... Radii>
 __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_grid_dev g, par_render_args a,
-                                                                            LightsArg lights_arg) {
+                                                                            LightsArg lights_arg, Radii... radii_arg) {
+    constexpr bool RANGED = sizeof...(Radii) != 0;
+    static_assert(sizeof...(Radii) <= 1, "one radii argument");
     __shared__ LightCol sh;
+    [[maybe_unused]] const auto& radii = frame_radii(radii_arg...);
     const par_lights_dyn& lights = frame_lights(lights_arg);
     const int lane = (int)threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
@@ -2308,6 +2352,7 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
         if (threadIdx.x == 0) {
             sh.n_nb = 0;
             sh.walk_used = 0;
+            if constexpr (RANGED) light_live().n_live = 0;
         }
         for (int z = (int)threadIdx.x; z < g.gz; z += (int)blockDim.x) sh.zslot[z] = -1;
         __syncthreads();
@@ -2322,7 +2367,55 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
         }
         __syncthreads();
         const int n_rec_nb = min(sh.n_nb, PAR_LIGHT_NB);
-        for (int p = wave; p < n_rec_nb * n_lights; p += PAR_WAVE_NW) {
+        int n_walks = n_rec_nb * n_lights;
+        if constexpr (RANGED) {
+            // the range cull, a pair per thread: a culled pair is a recorded walk of no records, the others queue up
+            LightLive& lv = light_live();
+            const int n_pairs = n_walks;
+            for (int p = (int)threadIdx.x; p < n_pairs; p += (int)blockDim.x) {
+                const int i = p / n_lights, l = p - i * n_lights;
+                const par_frame_dyn& dyn = lights.l[l];
+                const int radius = radii.r[l];
+                bool culled = false;
+                if (radius > 0) {
+                    const par_light_slab bin = par_light_slab_of(a.B, H, bx, by, sh.nb_bz[i]);
+                    culled = par_light_slab_l1(bin, dyn.lx, dyn.ly, dyn.lz) >= radius;
+                    // the bin is within reach: is any part of it that a slot record of the column can show? (Every
+                    // record is in a listed bin only while the column has no more occupied bins than the list holds.)
+                    if (!culled && sh.n_nb <= PAR_LIGHT_NB) {
+                        culled = true;
+                        for (int j = 0; j < n_rec_nb && culled; j++) {
+                            const int b = col_base + sh.nb_bz[j];
+                            const int cnt = a.count[b];
+                            for (int k = 0; k < cnt; k++) {
+                                const par_slot e = a.slots[(size_t)b * PAR_SLOTS + k];
+                                par_light_slab piece;
+                                if (par_light_slab_clip(bin, e.px, e.py, e.pz, e.ex, e.ey, e.ez, radii.depth_min,
+                                                        radii.depth_max, &piece) &&
+                                    par_light_slab_l1(piece, dyn.lx, dyn.ly, dyn.lz) < radius) {
+                                    culled = false;
+                                }
+                            }
+                        }
+                    }
+                }
+                if (culled) {
+                    sh.woff[p] = 0;
+                    sh.wcnt[p] = 0;
+                } else {
+                    lv.live[atomicAdd(&lv.n_live, 1)] = (int16_t)p;
+                }
+            }
+            __syncthreads();
+            n_walks = lv.n_live;
+            if ((a.flags & PAR_RENDER_COUNT_RAYS) && a.ray_counter && threadIdx.x == 0 && n_pairs > 0) {
+                atomicAdd(a.ray_counter + 1, (unsigned long long)n_walks);
+                atomicAdd(a.ray_counter + 2, (unsigned long long)(n_pairs - n_walks));
+            }
+        }
+        for (int q = wave; q < n_walks; q += PAR_WAVE_NW) {
+            int p = q;
+            if constexpr (RANGED) p = light_live().live[q];
             const int i = p / n_lights, l = p - i * n_lights;
             par_slot* stage = sh.stage[wave];
             const int n_rec = wave_walk(g, a.count, a.slots, lights.l[l], bx, by, sh.nb_bz[i], stage);
@@ -2409,6 +2502,7 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
             float nx = 0.f, ny = 0.f, nz = 0.f, bright = ambient;
             uint32_t rgba = 0, lit_mask = 0;
             int pal_index = PAR_PALIDX_BACKGROUND;
+            [[maybe_unused]] int n_rays = 0;  // RANGED: the lights this lane's pixel is in range of, or that are unbounded
             if (hit) {
                 const par_texel ti = a.texinfo[p_tex];  // normal (alt:349-350) + palette colour (alt:352-354)
                 nx = ti.nx; ny = ti.ny; nz = ti.nz;
@@ -2424,6 +2518,19 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
                 float s = 0.f;
                 for (int l = 0; l < n_lights; l++) {
                     const par_frame_dyn& dyn = lights.l[l];
+                    float weight = 1.f;
+                    bool ranged = false;
+                    if constexpr (RANGED) {
+                        const int radius = radii.r[l];  // (wave-uniform)
+                        ranged = radius > 0;
+                        if (ranged) {
+                            const float len = light_l1(dyn, px_col, p_y, p_z), fr = (float)radius;
+                            const bool in_range = len < fr;
+                            if (!in_range) continue;  // no ray towards this light, no bit, nothing added
+                            weight = 1.f - len / fr;
+                        }
+                        n_rays++;
+                    }
                     const LightDir d = light_dir(dyn, px_col, p_y, p_z);
                     const float inv_x = d.ix, inv_y = d.iy, inv_z = d.iz;
                     const float dif = diffuse(d, nx, ny, nz);
@@ -2443,13 +2550,19 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
                                                inv_y, inv_z);
                     }
                     if (lit) {
-                        s = s + dif;
+                        s = ranged ? s + dif * weight : s + dif;  // (product rounded, then the addition)
                         lit_mask |= 1u << l;
                     }
                 }
                 bright = std_min(1.f, s + ambient);
             }
-            if ((a.flags & PAR_RENDER_COUNT_RAYS) && a.ray_counter) {
+            if constexpr (RANGED) {  // the (covered pixel, light) pairs in range or unbounded
+                if ((a.flags & PAR_RENDER_COUNT_RAYS) && a.ray_counter) {
+                    int total = 0;  // (a lane's count fits four bits)
+                    for (int b = 0; b < 4; b++) total += __popcll(__ballot((n_rays >> b) & 1)) << b;
+                    if (lane == 0 && total) atomicAdd(a.ray_counter, (unsigned long long)total);
+                }
+            } else if ((a.flags & PAR_RENDER_COUNT_RAYS) && a.ray_counter) {
                 const unsigned long long m = __ballot(valid && hit);
                 if (lane == 0 && m) atomicAdd(a.ray_counter, (unsigned long long)__popcll(m) * (unsigned)n_lights);
             }
@@ -2468,15 +2581,24 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
 
 // The background rays of a frame with several lights (bgline_kernel's, once per light): bit l of bglit[x] is the
 // shadow ray of a background pixel of screen column x towards light l, traced per lane as the reference writes it.
-template <class LightsArg>
-__global__ __launch_bounds__(256) void bglights_kernel(par_grid_dev g, par_render_args a, LightsArg lights_arg) {
-    const par_lights_dyn& lights = frame_lights(lights_arg);  // (every thread meets its barrier before any returns)
+// The RANGED form (Radii as for render_lights_kernel): a light with a radius leaves its bit 0, untraced, where (x, 0, 0)
+// is out of its range.
+template <class LightsArg, class... Radii>
+__global__ __launch_bounds__(256) void bglights_kernel(par_grid_dev g, par_render_args a, LightsArg lights_arg,
+                                                       Radii... radii_arg) {
+    constexpr bool RANGED = sizeof...(Radii) != 0;
+    [[maybe_unused]] const auto& radii = frame_radii(radii_arg...);  // (every thread meets the barriers before any returns)
+    const par_lights_dyn& lights = frame_lights(lights_arg);
     const int x = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (x >= a.W) return;
     const BgRay ray = bg_ray(a, x);
     uint32_t mask = 0;
     for (int l = 0; l < lights.n; l++) {
         const par_frame_dyn& dyn = lights.l[l];
+        if constexpr (RANGED) {
+            const int radius = radii.r[l];
+            if (radius > 0 && !(light_l1(dyn, x, 0, 0) < (float)radius)) continue;
+        }
         const LightDir d = light_dir(dyn, x, 0, 0);
         if (lane_shadow_walk(g, a.count, a.slots, ray.bx, ray.sy, 0, dyn, 0, ray.ox, 0, 0, d.ix, d.iy, d.iz)) {
             mask |= 1u << l;
@@ -2871,11 +2993,18 @@ hipError_t par_launch_render_overflow(const par_grid_dev& g, const par_render_ar
 // One workgroup per column the bound allows in the rendered rows, at most 65536 (the workgroups then stride over the
 // column list). `d_lights` non-null: a captured graph's kernels read the lights from there, else `lights`.
 hipError_t par_launch_render_lights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,
-                                    const par_lights_dyn* d_lights, int64_t column_bound, hipStream_t stream) {
+                                    const par_lights_dyn* d_lights, const par_light_radii* radii,
+                                    const par_light_radii* d_radii, int64_t column_bound, hipStream_t stream) {
     const int64_t n = std::min(columns_in_rows(g, a, column_bound), (int64_t)65536);
     if (n <= 0) return hipSuccess;
     const dim3 grid((unsigned)n), block(PAR_WAVE_NW * 64);
-    if (d_lights) {
+    if (radii && d_lights) {
+        hipLaunchKernelGGL((render_lights_kernel<const par_lights_dyn*, const par_light_radii*>), grid, block, 0, stream,
+                           g, a, d_lights, d_radii);
+    } else if (radii) {
+        hipLaunchKernelGGL((render_lights_kernel<par_lights_dyn, par_light_radii>), grid, block, 0, stream, g, a, lights,
+                           *radii);
+    } else if (d_lights) {
         hipLaunchKernelGGL(render_lights_kernel<const par_lights_dyn*>, grid, block, 0, stream, g, a, d_lights);
     } else {
         hipLaunchKernelGGL(render_lights_kernel<par_lights_dyn>, grid, block, 0, stream, g, a, lights);
@@ -2884,9 +3013,16 @@ hipError_t par_launch_render_lights(const par_grid_dev& g, const par_render_args
 }
 
 hipError_t par_launch_bglights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,
-                               const par_lights_dyn* d_lights, hipStream_t stream) {
+                               const par_lights_dyn* d_lights, const par_light_radii* radii,
+                               const par_light_radii* d_radii, hipStream_t stream) {
     const dim3 grid((unsigned)((a.W + 255) / 256)), block(256);
-    if (d_lights) {
+    if (radii && d_lights) {
+        hipLaunchKernelGGL((bglights_kernel<const par_lights_dyn*, const par_light_radii*>), grid, block, 0, stream, g, a,
+                           d_lights, d_radii);
+    } else if (radii) {
+        hipLaunchKernelGGL((bglights_kernel<par_lights_dyn, par_light_radii>), grid, block, 0, stream, g, a, lights,
+                           *radii);
+    } else if (d_lights) {
         hipLaunchKernelGGL(bglights_kernel<const par_lights_dyn*>, grid, block, 0, stream, g, a, d_lights);
     } else {
         hipLaunchKernelGGL(bglights_kernel<par_lights_dyn>, grid, block, 0, stream, g, a, lights);

@@ -6,8 +6,9 @@
 // shows the frame rate without an interpreter in the submit path.
 //
 //   par_pipeline [--size S] [--prims N] [--frames F] [--inflight K] [--threads T] [--moving] [--check] [--flags X]
-//                [--stamps F0] [--block K]
+//                [--stamps F0] [--block K] [--radius R]
 //
+// --radius R (> 0): the light is ranged (PAR_LIGHTS_RANGED, par_set_light_model) with that radius.
 // --flags X: render flags for every frame (par_raytracer.h; the library rejects undefined bits).
 // --stamps F0 (with PAR_DEBUG_STAMPS=1 in the environment): the K frames from F0 on note the GPU's 100 MHz clock at
 // every workgroup's start and end; afterwards the span of each of their kernels is printed (a timeline of the
@@ -66,7 +67,7 @@ int main(int argc, char** argv) {
     int block = 0;
     int size = 4096, prims = 1024, frames = 2000, inflight = 4;
     bool moving = false, check = false;
-    int stamps_from = -1, threads = 1;
+    int stamps_from = -1, threads = 1, radius = 0;
     unsigned all_flags = 0;
     std::string scene = "synthetic";
     for (int i = 1; i < argc; i++) {
@@ -81,6 +82,7 @@ int main(int argc, char** argv) {
         else if (a == "--stamps") next(stamps_from);
         else if (a == "--threads") next(threads);
         else if (a == "--block") next(block);
+        else if (a == "--radius") next(radius);
         else if (a == "--scene") { if (i + 1 < argc) scene = argv[++i]; }
         else if (a == "--flags") { int v = 0; next(v); all_flags = (unsigned)v; }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
@@ -107,6 +109,7 @@ int main(int argc, char** argv) {
         aabbs.resize((size_t)prims);
         par_scene_synthetic(prims, W, H, L, 12345, aabbs.data(), &light);
     }
+    if (radius > 0) light.radius = (int16_t)std::min(radius, 32767);
     prims = (int)aabbs.size();
     size = W;
     params.width = W; params.height = H; params.length = L;
@@ -124,6 +127,7 @@ int main(int argc, char** argv) {
         PAR_OK_(s.ctx, par_set_sprites(s.ctx, &sprite, 1));
         PAR_OK_(s.ctx, par_set_entities(s.ctx, aabbs.data(), nullptr, prims));
         PAR_OK_(s.ctx, par_set_light(s.ctx, &light));
+        if (radius > 0) PAR_OK_(s.ctx, par_set_light_model(s.ctx, PAR_LIGHTS_RANGED));
         HIP_OK(hipMalloc(&s.fb, npix * sizeof(par_color)));
         HIP_OK(hipMalloc(&s.pal, npix));
         s.out.fb = s.fb;

@@ -2,7 +2,13 @@
 view with 1024 primitives: one frame alone (par_render_device_timed, the span of its launches, median) and four frames
 in flight (par_render_device_slots, wall time per frame). Also N = 1 forced through the light kernel (test hook
 lights_path) and through the overflow kernel on every column (force_generic), the two paths whose walks it replaces.
-Prints one JSON line.   python tools/lights.py [frames]"""
+Prints one JSON line.   python tools/lights.py [frames]
+
+With --radius F every light is ranged (PAR_LIGHTS_RANGED, par_set_light_model) with radius F x the view's width; with
+--torches F light 0 stays a sun (radius 0) and the other N - 1 are such torches. Then N = 2, 4, 8 are timed, in the
+same table, each with the (start bin, light) pairs the light kernel walked and culled in one frame.
+   python tools/lights.py [frames] [--radius F | --torches F] [--scene graybox_480x320 | synthetic_4096_1024]"""
+import argparse
 import importlib
 import json
 import os
@@ -24,17 +30,28 @@ FRACTIONS = [(5 / 8, 1 / 2, 1 / 4), (1 / 8, 3 / 4, 1 / 16), (15 / 16, 1 / 16, 7 
              (1 / 4, 1 / 4, 3 / 4), (3 / 4, 5 / 8, 1 / 8), (1 / 16, 1 / 8, 1 / 2), (7 / 8, 7 / 8, 15 / 16)]
 
 
-def lights_for(params, n):
+def lights_for(params, n, radius=None, sun=False):
+    """`radius` (a fraction of the view's width): ranged lights; `sun`: light 0 keeps radius 0."""
     a = np.zeros(n, dtype=T.LIGHT)
     for i, (fx, fy, fz) in enumerate(FRACTIONS[:n]):
         a[i]["x"], a[i]["y"], a[i]["z"] = int(params.width * fx), int(params.height * fy), int(params.length * fz)
-        a[i]["radius"] = 10
+        a[i]["radius"] = 10 if radius is None else (0 if sun and i == 0 else min(32767, max(1, int(params.width * radius))))
     return a
 
 
 def configure(r, lights, mode):
+    r.set_light_model(par.LIGHTS_RANGED if mode == "ranged" else par.LIGHTS_UNBOUNDED)
     r.set_lights(lights)
     r.set_test_hooks(lights_path=(mode == "kernel"), force_generic=(mode == "generic"))
+
+
+def pair_counts(params, aabbs, sprite, lights):
+    """(walked, culled) pairs of one ranged frame."""
+    with par.Renderer(params, 0) as r:
+        r.set_scene(aabbs, sprite, lights[0:1])
+        configure(r, lights, "ranged")
+        r.render(("fb",), flags=par.RENDER_COUNT_RAYS)
+        return r.light_walks()
 
 
 def alone_us(params, aabbs, sprite, lights, mode, frames):
@@ -74,7 +91,14 @@ def inflight_us(params, aabbs, sprite, lights, mode, frames):
 
 
 def main():
-    frames = int(sys.argv[1]) if len(sys.argv) > 1 else 40
+    ap = argparse.ArgumentParser()
+    ap.add_argument("frames", nargs="?", type=int, default=40)
+    ap.add_argument("--radius", type=float, help="every light ranged, radius = this fraction of the view's width")
+    ap.add_argument("--torches", type=float, help="one sun and N - 1 torches of that radius")
+    ap.add_argument("--scene", help="one scene only")
+    args = ap.parse_args()
+    frames = args.frames
+    radius = args.radius if args.radius is not None else args.torches
     sprite = par.tile_floor()
     scenes = {}
     p = T.default_params()
@@ -82,8 +106,21 @@ def main():
     p = T.default_params(4096, 4096, 4096)
     scenes["synthetic_4096_1024"] = (p, par.scene_synthetic(1024, 4096, 4096, 4096, 12345)[0])
     out = {"tool": "lights", "frames": frames, "us_per_frame": {}}
+    if radius is not None:
+        out["radius" if args.radius is not None else "torches"] = radius
     for name, (params, aabbs) in scenes.items():
+        if args.scene and name != args.scene:
+            continue
         res = {}
+        if radius is not None:
+            for n in (2, 4, 8):
+                lights = lights_for(params, n, radius, sun=args.radius is None)
+                walked, culled = pair_counts(params, aabbs, sprite, lights)
+                res[f"n{n}"] = {"alone": alone_us(params, aabbs, sprite, lights, "ranged", frames),
+                                "inflight4": inflight_us(params, aabbs, sprite, lights, "ranged", frames),
+                                "pairs_walked": walked, "pairs_culled": culled}
+            out["us_per_frame"][name] = res
+            continue
         for n in (1, 2, 4, 8):
             lights = lights_for(params, n)
             res[f"n{n}"] = {"alone": alone_us(params, aabbs, sprite, lights, "auto", frames),
