@@ -176,6 +176,33 @@ enum { PAR_LIGHTS_UNBOUNDED = 0, PAR_LIGHTS_RANGED = 1 };
  *   With every r_l <= 0 a ranged frame equals the unbounded frame, byte for byte on every plane. */
 int par_set_light_model(par_context* ctx, int model);
 
+/* The lights' colours. `tints` != NULL with 1 <= n <= PAR_MAX_LIGHTS makes the context TINTED: light l < n gets tints[l],
+ * the lights l >= n are white ({1, 1, 1}); tints go by the light's index, whatever the light count is or becomes, and
+ * the array may be reused when the call returns. `tints` == NULL with n == 0 makes the context UNTINTED again, the state
+ * of a new context, in which everything above holds as it stands. PAR_ERR_INVALID_ARG, before any device work and with
+ * nothing changed, for a null context, `tints` and n disagreeing about being empty, n outside [0, PAR_MAX_LIGHTS], and
+ * any component that is not finite or is negative. Components above 1 are allowed (a bright light; the min below clamps).
+ * On a tinted context everything par_set_lights and par_set_light_model say holds, with this change for a covered pixel.
+ * Let t_l be the term the untinted sum adds for light l: d_l under PAR_LIGHTS_UNBOUNDED or for a light with radius <= 0,
+ * d_l * w_l (rounded) for a ranged light in range. Then, in ascending l, for the lit lights that are in range or
+ * unbounded only:
+ *     s_r = s_r + t_l * tint_l.r;  s_g = s_g + t_l * tint_l.g;  s_b = s_b + t_l * tint_l.b;
+ *           (each product rounded to fp32, then the addition, no fma)
+ *     b_c = std::min(1.f, s_c + ambient)                  for c = r, g, b   (`ambient` stays white)
+ *     fb.c = (unsigned char)((float)color.c * b_c)        per channel, truncating as spr:8-16; alpha passes through
+ *     brightness plane = std::max(std::max(b_r, b_g), b_b)
+ *   The lit plane, the G-buffer, the palette index, background pixels, shadow_rays and the pairs the ranged kernel walks
+ *   and culls do not depend on the tints at all: a black light {0, 0, 0} still traces, sets its bit and counts its rays.
+ *   A frame takes the light kernel whatever the light count and model, as a ranged context's does. par_graph_capture
+ *   on a tinted context, and par_graph_launch of a one-light graph on one, return PAR_ERR_UNSUPPORTED.
+ *   par_graph_capture_lights captures the state the context has; a call that CHANGES the state (tinted <-> untinted)
+ *   drops the captured graphs as a change of the light model does (PAR_ERR_NOT_READY from the stage and launch calls
+ *   afterwards); a call that only changes the tints' values keeps them, and the new values reach the next
+ *   par_graph_launch as positions and radii do (there is no stage call for tints).
+ *   With every tint {1, 1, 1} a tinted frame equals the untinted frame, byte for byte on every plane: t * 1.f == t, so
+ *   the three sums are the untinted sum and the three factors the untinted brightness. */
+int par_set_light_tints(par_context* ctx, const par_light_tint* tints, int n);
+
 /* --- render: replaces alt:690-760 ----------------------------------------------------------------------------- */
 
 /* One frame into caller-owned HOST buffers: bin, trace, shade, copy back, synchronise. */

@@ -65,6 +65,10 @@ typedef struct par_light {
     int16_t radius;
 } par_light;
 
+/* The colour of a light (par_set_light_tints, par_raytracer.h; nothing in the reference): what its term of a covered
+ * pixel's sum is multiplied by, channel by channel. White is {1, 1, 1}; a component above 1 makes a bright light. */
+typedef struct par_light_tint { float r, g, b; } par_light_tint;
+
 /* `Ray`, alt:30-33 (20 bytes: fp32 inverse direction + short origin, 2 bytes tail padding). */
 typedef struct par_ray {
     float inv_x, inv_y, inv_z;

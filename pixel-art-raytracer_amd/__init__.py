@@ -16,8 +16,8 @@ import sys
 import numpy as np
 
 from . import types as T
-from .types import (AABB, COLOR, LIGHT, PIXEL, SPRITE, FrameStats, Outputs, Params, default_params, make_aabbs,
-                    make_light, ptr)
+from .types import (AABB, COLOR, LIGHT, LIGHT_TINT, PIXEL, SPRITE, FrameStats, Outputs, Params, default_params,
+                    make_aabbs, make_light, make_tints, ptr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libpar_raytracer.so")
@@ -40,7 +40,7 @@ ABI_SYMBOLS = (
     "par_sprite_tile_floor", "par_scene_graybox", "par_scene_synthetic", "par_debug_line", "par_debug_units",
     "par_render_device_slots", "par_row_block", "par_scene_tiles", "par_tiles_pack", "par_tiles_unpack",
     "par_background_fill", "par_tiles_assemble", "par_scene_tile_map", "par_set_lights", "par_graph_capture_lights",
-    "par_graph_stage_lights", "par_set_light_model",
+    "par_graph_stage_lights", "par_set_light_model", "par_set_light_tints",
 )
 MAX_LIGHTS = 8  # PAR_MAX_LIGHTS
 LIGHTS_UNBOUNDED, LIGHTS_RANGED = 0, 1  # par_set_light_model
@@ -103,6 +103,7 @@ def lib():
         L.par_set_light.argtypes = [vp, vp]
         L.par_set_lights.argtypes = [vp, vp, i32]
         L.par_set_light_model.argtypes = [vp, i32]
+        L.par_set_light_tints.argtypes = [vp, vp, i32]
         L.par_render.argtypes = [vp, vp, C.c_uint]
         L.par_render_rows.argtypes = [vp, i32, i32, vp, C.c_uint]
         L.par_render_device.argtypes = [vp, vp, i32, i32, vp, C.c_uint]
@@ -277,6 +278,17 @@ class Renderer:
         radius > 0 reaches the pixels whose L1 distance to it is below the radius and fades out towards it; a radius
         <= 0 leaves a light unbounded. A different model drops captured graphs."""
         self._check(lib().par_set_light_model(self._ctx, int(model)))
+
+    def set_light_tints(self, tints):
+        """The lights' colours (par_set_light_tints): a LIGHT_TINT array (types.make_tints) of 1 .. MAX_LIGHTS entries, by
+        light index, white for the lights beyond it; a lit light's term is multiplied by its tint channel by channel.
+        None makes the renderer untinted again (a new renderer). A change between the two states drops captured graphs;
+        new values alone reach a captured graph's next launch."""
+        if tints is None:
+            self._check(lib().par_set_light_tints(self._ctx, None, 0))
+            return
+        tints = np.ascontiguousarray(tints, dtype=LIGHT_TINT)
+        self._check(lib().par_set_light_tints(self._ctx, ptr(tints), len(tints)))
 
     def set_scene(self, aabbs, sprites, light, sprite_ids=None):
         self.set_sprites(sprites)

@@ -5,6 +5,7 @@
 // frame = bin + trace + shade (alt:690-760) per render call. There is no CPU rendering path in this library.
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <new>
 #include <cstdio>
 #include <cstdlib>
@@ -17,14 +18,15 @@
 #include "par_internal.h"
 
 // The staged lights of a captured graph: par_lights_dyn, then the lights' radii (read by the ranged light kernels
-// alone), padded to a whole number of 64-byte lines; the graph's copy node copies the whole block. A one-light graph's
-// kernels read their par_frame_dyn from lights.l[0].
+// alone) and their tints (read by the tinted ones alone), padded to a whole number of 64-byte lines; the graph's copy
+// node copies the whole block. A one-light graph's kernels read their par_frame_dyn from lights.l[0].
 struct par_lights_block {
     par_lights_dyn lights;
     par_light_radii radii;
-    int32_t pad_[(256 - sizeof(par_lights_dyn) - sizeof(par_light_radii)) / sizeof(int32_t)];
+    par_light_tints tints;
+    int32_t pad_[(384 - sizeof(par_lights_dyn) - sizeof(par_light_radii) - sizeof(par_light_tints)) / sizeof(int32_t)];
 };
-static_assert(sizeof(par_lights_block) == 256, "lights staging block");
+static_assert(sizeof(par_lights_block) == 384, "lights staging block");
 
 struct par_context {
     par_params params{};
@@ -39,6 +41,8 @@ struct par_context {
     int n_lights = 0;                    // 0 until a light is set
     int depth_min = 0, depth_max = 0;    // least and largest texel depth of the sprite table (par_set_sprites)
     int light_model = PAR_LIGHTS_UNBOUNDED;  // par_set_light_model; PAR_LIGHTS_RANGED always takes the light kernel
+    bool tinted = false;                 // par_set_light_tints; a tinted context always takes the light kernel
+    par_light_tints tints{};             // by light index (white beyond those the call named); read while `tinted`
     int set = 0;  // head/count/node set the NEXT frame uses
     hipStream_t last_stream = nullptr;  // stream of the most recent asynchronous render (scene updates wait for it)
     bool has_last_stream = false;
@@ -78,7 +82,8 @@ struct par_context {
     hipStream_t update_stream = nullptr;
     // The captured kernels read the frame's lights from d_lights (a one-light graph's from the first light alone).
     bool graph_lights = false;  // which kernels were captured: false one-light (par_graph_capture), true light path
-                                // (then of the light model the context had, which only changes with the graphs dropped)
+                                // (then of the light model and the tinted state the context had, which only change
+                                // with the graphs dropped)
     par_lights_block* d_lights = nullptr;
 
     bool timed_tiles = false, timed_overflow = false, timed_both = false;  // the last timed frame launched these kernels
@@ -388,9 +393,12 @@ int check_device_error(par_context* ctx) {
     return fail(ctx, PAR_ERR_DEVICE, what + "a frame rendered since the last check is not valid");
 }
 
-// A frame takes the light kernel when it has several lights, or ranged ones (or the test hook asks for it with one).
+// A frame takes the light kernel when it has several lights, or ranged or tinted ones (or the test hook asks for it with
+// one).
 bool ranged(const par_context* c) { return c->light_model == PAR_LIGHTS_RANGED; }
-bool lights_path(const par_context* c) { return c->n_lights > 1 || ranged(c) || (c->hooks & PAR_HOOK_LIGHTS_PATH); }
+bool lights_path(const par_context* c) {
+    return c->n_lights > 1 || ranged(c) || c->tinted || (c->hooks & PAR_HOOK_LIGHTS_PATH);
+}
 
 par_lights_dyn make_lights_dyn(const par_context* c) {
     par_lights_dyn lights{};
@@ -412,6 +420,7 @@ par_light_radii make_light_radii(const par_context* c) {
 void stage_lights(par_context* c, int s) {
     c->pin_lights[s]->lights = make_lights_dyn(c);
     c->pin_lights[s]->radii = make_light_radii(c);
+    c->pin_lights[s]->tints = c->tints;
 }
 
 // The hash build: small scenes in one launch, large ones in two (and frames that keep their kernels `apart`, and the
@@ -435,7 +444,8 @@ int enqueue_build(par_context* ctx, hipStream_t stream, const par_bin_args& b, i
 // ms_launch[2]; the other render launches it does not have are 0. In graph mode (par_graph_capture_lights) the
 // launches are sized by what the graph accepts (par_book::graph) and the kernels read the lights from d_lights, which
 // the graph's copy node fills before them: one graph serves any count of lights. A ranged context (PAR_LIGHTS_RANGED)
-// launches the ranged kernels, with the radii beside the lights.
+// launches the ranged kernels, with the radii beside the lights; a tinted one (par_set_light_tints) the tinted light
+// kernel, with the tints behind them.
 int enqueue_lights_frame(par_context* ctx, hipStream_t stream, const par_bin_args& b, const par_render_args& r,
                          const par_bound& bound, bool graph_mode, bool apart, hipEvent_t* ev) {
     const par_lights_dyn lights = make_lights_dyn(ctx);
@@ -443,6 +453,8 @@ int enqueue_lights_frame(par_context* ctx, hipStream_t stream, const par_bin_arg
     const par_light_radii radii_v = make_light_radii(ctx);
     const par_light_radii* radii = ranged(ctx) ? &radii_v : nullptr;
     const par_light_radii* d_radii = graph_mode ? &ctx->d_lights->radii : nullptr;
+    const par_light_tints* tints = ctx->tinted ? &ctx->tints : nullptr;
+    const par_light_tints* d_tints = graph_mode ? &ctx->d_lights->tints : nullptr;
     const int rc = enqueue_build(ctx, stream, b, bound.pairs, &r, nullptr, apart);
     if (rc != PAR_OK) return rc;
     if (ev) {
@@ -454,7 +466,7 @@ int enqueue_lights_frame(par_context* ctx, hipStream_t stream, const par_bin_arg
     }
     PAR_HIP(par_launch_fill(ctx->grid, r, stream));
     if (ev) PAR_HIP(hipEventRecord(ev[EV_FILLED], stream));
-    PAR_HIP(par_launch_render_lights(ctx->grid, r, lights, d_lights, radii, d_radii, bound.cols, stream));
+    PAR_HIP(par_launch_render_lights(ctx->grid, r, lights, d_lights, radii, d_radii, tints, d_tints, bound.cols, stream));
     if (ev) {
         PAR_HIP(hipEventRecord(ev[EV_ITEMS], stream));
         PAR_HIP(hipEventRecord(ev[EV_RENDERED], stream));
@@ -922,6 +934,35 @@ static int par_set_light_model_impl(par_context* ctx, int model) {
     return PAR_OK;
 }
 
+static int par_set_light_tints_impl(par_context* ctx, const par_light_tint* tints, int n) {
+    if (!ctx) return PAR_ERR_INVALID_ARG;
+    if (n < 0 || n > PAR_MAX_LIGHTS || (tints == nullptr) != (n == 0)) {
+        return fail(ctx, PAR_ERR_INVALID_ARG, "light tints: NULL with 0, or 1 <= n <= PAR_MAX_LIGHTS");
+    }
+    for (int l = 0; l < n; l++) {
+        for (const float v : {tints[l].r, tints[l].g, tints[l].b}) {
+            if (!std::isfinite(v) || v < 0.f) {
+                return fail(ctx, PAR_ERR_INVALID_ARG, "light tints: every component must be finite and not negative");
+            }
+        }
+    }
+    const bool tinted = n > 0;
+    if (tinted != ctx->tinted) {
+        PAR_HIP(hipSetDevice(ctx->device));
+        PAR_HIP(hipDeviceSynchronize());
+        drop_graphs(ctx);  // (a captured graph bakes the kernels of the state it was captured in)
+        ctx->tinted = tinted;
+    }
+    // (a graph captured in this state reads the values from its staging area, which par_graph_launch rewrites)
+    for (int l = 0; l < PAR_MAX_LIGHTS; l++) {
+        const par_light_tint t = l < n ? tints[l] : par_light_tint{1.f, 1.f, 1.f};
+        ctx->tints.t[l][0] = t.r;
+        ctx->tints.t[l][1] = t.g;
+        ctx->tints.t[l][2] = t.b;
+    }
+    return PAR_OK;
+}
+
 static int par_set_light_impl(par_context* ctx, const par_light* light) {
     if (!ctx || !light) return fail(ctx, PAR_ERR_INVALID_ARG, "light");
     return par_set_lights_impl(ctx, light, 1);
@@ -989,6 +1030,9 @@ static int graph_capture(par_context* ctx, void* stream_v, int row_begin, int ro
     if (rc != PAR_OK) return rc;
     if (!lights_kind && ranged(ctx)) {
         return fail(ctx, PAR_ERR_UNSUPPORTED, "a frame with ranged lights cannot be captured (par_graph_capture_lights)");
+    }
+    if (!lights_kind && ctx->tinted) {
+        return fail(ctx, PAR_ERR_UNSUPPORTED, "a frame with tinted lights cannot be captured (par_graph_capture_lights)");
     }
     if (!lights_kind && lights_path(ctx)) {
         return fail(ctx, PAR_ERR_UNSUPPORTED, "a frame with several lights cannot be captured (par_graph_capture_lights)");
@@ -1075,6 +1119,9 @@ static int par_graph_launch_impl(par_context* ctx, void* stream) {
     }
     if (ranged(ctx) && !ctx->graph_lights) {
         return fail(ctx, PAR_ERR_UNSUPPORTED, "a frame with ranged lights has no one-light graph (par_graph_capture_lights)");
+    }
+    if (ctx->tinted && !ctx->graph_lights) {
+        return fail(ctx, PAR_ERR_UNSUPPORTED, "a frame with tinted lights has no one-light graph (par_graph_capture_lights)");
     }
     const int s = ctx->set;
     if (!ctx->graph_exec[s]) return fail(ctx, PAR_ERR_NOT_READY, "no captured graph for this grid set");
@@ -1351,6 +1398,9 @@ int par_set_lights(par_context* ctx, const par_light* lights, int n) {
 }
 int par_set_light_model(par_context* ctx, int model) {
     return guarded(ctx, [&] { return par_set_light_model_impl(ctx, model); });
+}
+int par_set_light_tints(par_context* ctx, const par_light_tint* tints, int n) {
+    return guarded(ctx, [&] { return par_set_light_tints_impl(ctx, tints, n); });
 }
 int par_render(par_context* ctx, const par_outputs* host_out, unsigned flags) {
     return guarded(ctx, [&] { return par_render_impl(ctx, host_out, flags); });

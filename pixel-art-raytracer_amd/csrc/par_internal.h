@@ -129,6 +129,13 @@ struct par_light_radii {
     int32_t depth_min, depth_max;  // least and largest texel depth of the sprite table (the range cull, par_lightbox.h)
 };
 
+// The colours of those lights on a tinted context (par_set_light_tints; white for the lights it names none for), which
+// only the tinted instantiations of the light kernel take, as the radii travel: one more kernel argument, or, in graph
+// mode, device memory right behind the graph's radii (the same copy node uploads all three).
+struct par_light_tints {
+    float t[PAR_MAX_LIGHTS][3];  // r, g, b
+};
+
 // Render flags that make the render launch use its instrumented variant (ray counting and the time stamps, bit 29);
 // a production frame has neither and runs kernels compiled without them.
 constexpr uint32_t PAR_DEBUG_FLAGS = PAR_RENDER_COUNT_RAYS | (1u << 29);
@@ -279,10 +286,12 @@ hipError_t par_launch_render_overflow(const par_grid_dev& g, const par_render_ar
 // lights from that device memory (a copy node of the graph fills it before them), once per workgroup, so one graph
 // serves any count of lights. `radii` null: the unbounded kernels; else the ranged ones (PAR_LIGHTS_RANGED), which take
 // the radii as an argument too or, with `d_lights`, read them from `d_radii`. Under PAR_RENDER_COUNT_RAYS the ranged
-// light kernel also adds the (start bin, light) pairs it walked and culled to a.ray_counter[1] and [2].
+// light kernel also adds the (start bin, light) pairs it walked and culled to a.ray_counter[1] and [2]. `tints` null:
+// the untinted kernels; else the tinted ones (par_set_light_tints), which take the tints in the same way (`d_tints`).
 hipError_t par_launch_render_lights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,
                                     const par_lights_dyn* d_lights, const par_light_radii* radii,
-                                    const par_light_radii* d_radii, int64_t column_bound, hipStream_t stream);
+                                    const par_light_radii* d_radii, const par_light_tints* tints,
+                                    const par_light_tints* d_tints, int64_t column_bound, hipStream_t stream);
 // The background rays of such a frame (one per x and light, bit l of g.bglit[x] for light l); par_launch_fill then
 // copies them into the lit plane. `lights`, `d_lights`, `radii`, `d_radii` as above.
 hipError_t par_launch_bglights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,

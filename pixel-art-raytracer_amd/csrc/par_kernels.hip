@@ -392,6 +392,13 @@ __device__ __forceinline__ uint32_t color_scale(uint32_t c, float v) {
     const uint32_t b = (uint32_t)(uint8_t)((float)((c >> 16) & 0xFF) * v);
     return r | (g << 8) | (b << 16) | (c & 0xFF000000u);
 }
+// The same with a factor of its own per channel (the tinted light kernel, par_set_light_tints).
+__device__ __forceinline__ uint32_t color_scale(uint32_t c, float vr, float vg, float vb) {
+    const uint32_t r = (uint32_t)(uint8_t)((float)(c & 0xFF) * vr);
+    const uint32_t g = (uint32_t)(uint8_t)((float)((c >> 8) & 0xFF) * vg);
+    const uint32_t b = (uint32_t)(uint8_t)((float)((c >> 16) & 0xFF) * vb);
+    return r | (g << 8) | (b << 16) | (c & 0xFF000000u);
+}
 
 // Vector<float>::normalize, spr:28-35 — divides by the L1 length (abs(x) + abs(y)) + abs(z) — and the inverse
 // direction 1 / n (alt:717-719), through the short sequences of par_fastdiv.h when every
@@ -2262,6 +2269,12 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_both_kernel(par_grid_
 //      counted -- and a ranged light's diffuse term is weighted by 1 - len / r. The per-pixel test alone decides a
 //      pixel: the cull only skips walks whose records no pixel in range would read.
 // The unbounded instantiations have no such argument, LDS or code (`if constexpr`).
+// And each of the four again in a TINTED form (par_set_light_tints, the contract beside it), which takes the lights'
+// colours as its last argument (frame_tints) and differs in B alone: three running sums instead of one, a lit light's
+// term times its tint's three components, and a factor per channel for the quantise. A light's three components are
+// read inside the light loop, wave-uniform as its radius is: from the kernarg segment in direct frames (scalar loads
+// at a dynamic offset; the ranged by-value form has no SGPRs to hold all 24 in), from LDS in the graph form. The
+// untinted instantiations have none of it.
 // ------------------------------------------------------------------------------------------------------------
 constexpr int PAR_LIGHT_NB = 64;      // occupied bins of a column whose walks are recorded (the others: lane walks)
 constexpr int PAR_LIGHT_WALK = 1024;  // occluder records of all walks of a column (16 KiB)
@@ -2308,6 +2321,45 @@ __device__ __forceinline__ const par_light_radii& frame_radii(const par_light_ra
     return sr;
 }
 
+// The same with the kernel's other extra behind the radii (the tints, which frame_tints hands out), or with the tints
+// alone (an unbounded, tinted kernel).
+__device__ __forceinline__ NoRadii frame_radii(const par_light_tints&) { return NoRadii{}; }
+__device__ __forceinline__ NoRadii frame_radii(const par_light_tints*) { return NoRadii{}; }
+template <class R, class Tn>
+__device__ __forceinline__ const par_light_radii& frame_radii(const R& radii, const Tn&) {
+    return frame_radii(radii);
+}
+
+// The tints a TINTED light kernel reads, the last of its extras: its kernel argument, or the device memory behind the
+// graph's radii, read once per workgroup into LDS. The untinted kernels have none.
+struct NoTints {};
+__device__ __forceinline__ NoTints frame_tints() { return NoTints{}; }
+template <class First, class... Rest>
+__device__ __forceinline__ decltype(auto) frame_tints(const First& first, const Rest&... rest) {
+    if constexpr (std::is_same_v<First, par_light_tints>) {
+        return (first);
+    } else if constexpr (std::is_same_v<First, const par_light_tints*>) {
+        __shared__ par_light_tints st;
+        constexpr int N = (int)(sizeof(par_light_tints) / sizeof(float));
+        if ((int)threadIdx.x < N) reinterpret_cast<float*>(&st)[threadIdx.x] = reinterpret_cast<const float*>(first)[threadIdx.x];
+        __syncthreads();
+        return (const_cast<const par_light_tints&>(st));
+    } else {
+        return frame_tints(rest...);
+    }
+}
+// A value per colour channel in the TINTED light kernel; nothing at all in the others.
+template <bool TINTED>
+struct LightRgb {};
+template <>
+struct LightRgb<true> {
+    float r = 0.f, g = 0.f, b = 0.f;
+};
+template <class T>
+constexpr bool is_light_radii = std::is_same_v<T, par_light_radii> || std::is_same_v<T, const par_light_radii*>;
+template <class T>
+constexpr bool is_light_tints = std::is_same_v<T, par_light_tints> || std::is_same_v<T, const par_light_tints*>;
+
 // The L1 length of light - world as light_dir forms it (alt:712-714, spr:28-35): three differences of integers and
 // their sum, exact in fp32 for every view the library accepts.
 __device__ __forceinline__ float light_l1(const par_frame_dyn& l, int x, int y, int z) {
@@ -2326,14 +2378,17 @@ __device__ __forceinline__ LightLive& light_live() {
 }
 
 // LightsArg: par_lights_dyn (direct frames) or const par_lights_dyn* (graph replay), see frame_lights. Radii: nothing
-// (unbounded lights), or par_light_radii / const par_light_radii* in the same way (the RANGED form), see frame_radii.
-template <class LightsArg, class... Radii>
+// (unbounded lights), or par_light_radii / const par_light_radii* in the same way (the RANGED form), see frame_radii;
+// then nothing (white lights), or par_light_tints / const par_light_tints* (the TINTED form), see frame_tints.
+template <class LightsArg, class... Extras>
 __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_grid_dev g, par_render_args a,
-                                                                            LightsArg lights_arg, Radii... radii_arg) {
-    constexpr bool RANGED = sizeof...(Radii) != 0;
-    static_assert(sizeof...(Radii) <= 1, "one radii argument");
+                                                                            LightsArg lights_arg, Extras... extras_arg) {
+    constexpr bool RANGED = (is_light_radii<Extras> || ...);
+    constexpr bool TINTED = (is_light_tints<Extras> || ...);
+    static_assert(sizeof...(Extras) == (RANGED ? 1 : 0) + (TINTED ? 1 : 0), "the radii, then the tints, one of each at most");
     __shared__ LightCol sh;
-    [[maybe_unused]] const auto& radii = frame_radii(radii_arg...);
+    [[maybe_unused]] const auto& radii = frame_radii(extras_arg...);
+    [[maybe_unused]] const auto& tints = frame_tints(extras_arg...);
     const par_lights_dyn& lights = frame_lights(lights_arg);
     const int lane = (int)threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
@@ -2500,6 +2555,7 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
             }
             // shading, alt:704-758, one shadow ray per light
             float nx = 0.f, ny = 0.f, nz = 0.f, bright = ambient;
+            [[maybe_unused]] LightRgb<TINTED> factor;  // TINTED: the brightness per channel
             uint32_t rgba = 0, lit_mask = 0;
             int pal_index = PAR_PALIDX_BACKGROUND;
             [[maybe_unused]] int n_rays = 0;  // RANGED: the lights this lane's pixel is in range of, or that are unbounded
@@ -2516,6 +2572,7 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
                 const int ox = (int)(int16_t)px_col, oy = (int)(int16_t)p_y, oz = (int)(int16_t)p_z;  // alt:720-722
                 const int zs = (sz >= 0 && sz < g.gz) ? (int)sh.zslot[sz] : -1;
                 float s = 0.f;
+                [[maybe_unused]] LightRgb<TINTED> sum;  // TINTED: the sum per channel
                 for (int l = 0; l < n_lights; l++) {
                     const par_frame_dyn& dyn = lights.l[l];
                     float weight = 1.f;
@@ -2549,12 +2606,28 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
                         lit = lane_shadow_walk(g, a.count, a.slots, bx, by, sz, dyn, p_entity, ox, oy, oz, inv_x,
                                                inv_y, inv_z);
                     }
-                    if (lit) {
+                    if constexpr (TINTED) {
+                        if (lit) {
+                            const float term = ranged ? dif * weight : dif;  // (what the untinted sum would add)
+                            const float* tint = tints.t[l];                    // (wave-uniform, read here: see above)
+                            sum.r = sum.r + term * tint[0];                   // (each product rounded, then the addition)
+                            sum.g = sum.g + term * tint[1];
+                            sum.b = sum.b + term * tint[2];
+                            lit_mask |= 1u << l;
+                        }
+                    } else if (lit) {
                         s = ranged ? s + dif * weight : s + dif;  // (product rounded, then the addition)
                         lit_mask |= 1u << l;
                     }
                 }
-                bright = std_min(1.f, s + ambient);
+                if constexpr (TINTED) {
+                    factor.r = std_min(1.f, sum.r + ambient);
+                    factor.g = std_min(1.f, sum.g + ambient);
+                    factor.b = std_min(1.f, sum.b + ambient);
+                    bright = std_max(std_max(factor.r, factor.g), factor.b);
+                } else {
+                    bright = std_min(1.f, s + ambient);
+                }
             }
             if constexpr (RANGED) {  // the (covered pixel, light) pairs in range or unbounded
                 if ((a.flags & PAR_RENDER_COUNT_RAYS) && a.ray_counter) {
@@ -2569,7 +2642,11 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
             // quantise + store, alt:735, 757-758 (uncovered pixels keep what the fill wrote)
             if (valid && hit) {
                 const size_t o = (size_t)(row - a.row_begin) * W + px_col;
-                if (a.out.fb) reinterpret_cast<uint32_t*>(a.out.fb)[o] = color_scale(rgba, bright);
+                if constexpr (TINTED) {
+                    if (a.out.fb) reinterpret_cast<uint32_t*>(a.out.fb)[o] = color_scale(rgba, factor.r, factor.g, factor.b);
+                } else {
+                    if (a.out.fb) reinterpret_cast<uint32_t*>(a.out.fb)[o] = color_scale(rgba, bright);
+                }
                 if (a.out.palidx) a.out.palidx[o] = (uint8_t)pal_index;
                 if (a.out.brightness) a.out.brightness[o] = bright;
                 if (a.out.lit) a.out.lit[o] = (uint8_t)lit_mask;
@@ -2994,11 +3071,24 @@ hipError_t par_launch_render_overflow(const par_grid_dev& g, const par_render_ar
 // column list). `d_lights` non-null: a captured graph's kernels read the lights from there, else `lights`.
 hipError_t par_launch_render_lights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,
                                     const par_lights_dyn* d_lights, const par_light_radii* radii,
-                                    const par_light_radii* d_radii, int64_t column_bound, hipStream_t stream) {
+                                    const par_light_radii* d_radii, const par_light_tints* tints,
+                                    const par_light_tints* d_tints, int64_t column_bound, hipStream_t stream) {
     const int64_t n = std::min(columns_in_rows(g, a, column_bound), (int64_t)65536);
     if (n <= 0) return hipSuccess;
     const dim3 grid((unsigned)n), block(PAR_WAVE_NW * 64);
-    if (radii && d_lights) {
+    if (tints && radii && d_lights) {
+        hipLaunchKernelGGL((render_lights_kernel<const par_lights_dyn*, const par_light_radii*, const par_light_tints*>),
+                           grid, block, 0, stream, g, a, d_lights, d_radii, d_tints);
+    } else if (tints && radii) {
+        hipLaunchKernelGGL((render_lights_kernel<par_lights_dyn, par_light_radii, par_light_tints>), grid, block, 0, stream,
+                           g, a, lights, *radii, *tints);
+    } else if (tints && d_lights) {
+        hipLaunchKernelGGL((render_lights_kernel<const par_lights_dyn*, const par_light_tints*>), grid, block, 0, stream,
+                           g, a, d_lights, d_tints);
+    } else if (tints) {
+        hipLaunchKernelGGL((render_lights_kernel<par_lights_dyn, par_light_tints>), grid, block, 0, stream, g, a, lights,
+                           *tints);
+    } else if (radii && d_lights) {
         hipLaunchKernelGGL((render_lights_kernel<const par_lights_dyn*, const par_light_radii*>), grid, block, 0, stream,
                            g, a, d_lights, d_radii);
     } else if (radii) {

@@ -23,11 +23,13 @@ SPRITE = np.dtype([("color", "<i4", (SPRITE_TEXELS,)), ("depth", "<i4", (SPRITE_
 AABB = np.dtype([("px", "<i2"), ("py", "<i2"), ("pz", "<i2"), ("ex", "<i2"), ("ey", "<i2"), ("ez", "<i2"),
                  ("pad", "<i2", (2,))])
 LIGHT = np.dtype([("x", "<i2"), ("y", "<i2"), ("z", "<i2"), ("radius", "<i2")])
+LIGHT_TINT = np.dtype([("r", "<f4"), ("g", "<f4"), ("b", "<f4")])  # par_light_tint
 RAY = np.dtype([("inv_x", "<f4"), ("inv_y", "<f4"), ("inv_z", "<f4"), ("ox", "<i2"), ("oy", "<i2"), ("oz", "<i2"),
                 ("pad", "<i2")])
 
 assert COLOR.itemsize == 4 and VEC3.itemsize == 12 and PIXEL.itemsize == 28
 assert SPRITE.itemsize == 16000 and AABB.itemsize == 16 and LIGHT.itemsize == 8 and RAY.itemsize == 20
+assert LIGHT_TINT.itemsize == 12
 
 
 class Color(C.Structure):
@@ -77,6 +79,15 @@ def make_light(x, y, z, radius=10):
     l = np.zeros(1, dtype=LIGHT)
     l["x"], l["y"], l["z"], l["radius"] = x, y, z, radius
     return l
+
+
+def make_tints(rows):
+    """LIGHT_TINT array from an iterable of (r, g, b), one per light (par_set_light_tints; white is (1, 1, 1))."""
+    rows = list(rows)
+    t = np.zeros(len(rows), dtype=LIGHT_TINT)
+    for i, rgb in enumerate(rows):
+        t[i]["r"], t[i]["g"], t[i]["b"] = rgb
+    return t
 
 
 def make_aabbs(rows):

@@ -7,7 +7,10 @@ Prints one JSON line.   python tools/lights.py [frames]
 With --radius F every light is ranged (PAR_LIGHTS_RANGED, par_set_light_model) with radius F x the view's width; with
 --torches F light 0 stays a sun (radius 0) and the other N - 1 are such torches. Then N = 2, 4, 8 are timed, in the
 same table, each with the (start bin, light) pairs the light kernel walked and culled in one frame.
-   python tools/lights.py [frames] [--radius F | --torches F] [--scene graybox_480x320 | synthetic_4096_1024]"""
+With --tints every light has a colour (par_set_light_tints, the eight non-white tints below), alone or beside --radius /
+--torches: the same table through the tinted light kernels (N = 1 takes the light kernel too; the two N = 1 hook rows
+are left out).
+   python tools/lights.py [frames] [--radius F | --torches F] [--tints] [--scene graybox_480x320 | synthetic_4096_1024]"""
 import argparse
 import importlib
 import json
@@ -28,6 +31,9 @@ pipeline = importlib.import_module("pixel-art-raytracer_amd.pipeline")
 
 FRACTIONS = [(5 / 8, 1 / 2, 1 / 4), (1 / 8, 3 / 4, 1 / 16), (15 / 16, 1 / 16, 7 / 8), (1 / 2, 3 / 8, 1 / 2),
              (1 / 4, 1 / 4, 3 / 4), (3 / 4, 5 / 8, 1 / 8), (1 / 16, 1 / 8, 1 / 2), (7 / 8, 7 / 8, 15 / 16)]
+# --tints: a warm torch, a cold moon, components above 1, a zero component; none white, none black
+TINTS = [(1, .5, .125), (.25, .5, 1.5), (2, 1.5, 1), (0, 1, .5), (.5, 1, .25), (1.5, 0, .75), (.125, .125, 1), (3, .5, 0)]
+TINTED = False  # (main sets it)
 
 
 def lights_for(params, n, radius=None, sun=False):
@@ -42,6 +48,7 @@ def lights_for(params, n, radius=None, sun=False):
 def configure(r, lights, mode):
     r.set_light_model(par.LIGHTS_RANGED if mode == "ranged" else par.LIGHTS_UNBOUNDED)
     r.set_lights(lights)
+    r.set_light_tints(T.make_tints(TINTS[:len(lights)]) if TINTED else None)
     r.set_test_hooks(lights_path=(mode == "kernel"), force_generic=(mode == "generic"))
 
 
@@ -95,8 +102,11 @@ def main():
     ap.add_argument("frames", nargs="?", type=int, default=40)
     ap.add_argument("--radius", type=float, help="every light ranged, radius = this fraction of the view's width")
     ap.add_argument("--torches", type=float, help="one sun and N - 1 torches of that radius")
+    ap.add_argument("--tints", action="store_true", help="every light tinted (par_set_light_tints)")
     ap.add_argument("--scene", help="one scene only")
     args = ap.parse_args()
+    global TINTED
+    TINTED = args.tints
     frames = args.frames
     radius = args.radius if args.radius is not None else args.torches
     sprite = par.tile_floor()
@@ -106,6 +116,8 @@ def main():
     p = T.default_params(4096, 4096, 4096)
     scenes["synthetic_4096_1024"] = (p, par.scene_synthetic(1024, 4096, 4096, 4096, 12345)[0])
     out = {"tool": "lights", "frames": frames, "us_per_frame": {}}
+    if args.tints:
+        out["tints"] = True
     if radius is not None:
         out["radius" if args.radius is not None else "torches"] = radius
     for name, (params, aabbs) in scenes.items():
@@ -126,7 +138,7 @@ def main():
             res[f"n{n}"] = {"alone": alone_us(params, aabbs, sprite, lights, "auto", frames),
                             "inflight4": inflight_us(params, aabbs, sprite, lights, "auto", frames)}
         lights = lights_for(params, 1)
-        for mode in ("kernel", "generic"):
+        for mode in () if args.tints else ("kernel", "generic"):
             res[f"n1_{mode}"] = {"alone": alone_us(params, aabbs, sprite, lights, mode, frames),
                                  "inflight4": inflight_us(params, aabbs, sprite, lights, mode, frames)}
         out["us_per_frame"][name] = res
