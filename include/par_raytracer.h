@@ -227,6 +227,44 @@ int par_render_device_slots(par_context* const* ctxs, void* const* streams, cons
 int par_render_device_timed(par_context* ctx, void* stream, int row_begin, int row_end,
                             const par_outputs* device_out, unsigned flags, par_frame_stats* stats);
 
+/* Relit frames: re-shade a frame from its G-buffer when only the lights changed (the reference's own keys move
+ * lights[0] while the world stands still, alt:641-681; its shading loop, alt:703-758, is a pass over the G-buffer).
+ * No hash build and no primary pass: the covered pixels are shaded again under the lights, the light model and the
+ * tints the context holds at the call.
+ * Retained frame. A context has one once par_render, par_render_rows, par_render_device, par_render_device_timed,
+ * par_pick (its one row) or par_render_device_slots (per slot context) has returned PAR_OK: the rows [r0, r1) of that
+ * frame, and what its hash build left on the device. Nothing new is stored. Every later call that enqueues a hash
+ * build replaces it. The context has none after par_set_sprites, par_set_entities[_ref_layout],
+ * par_update_aabbs[_async], par_graph_capture[_lights], par_graph_stage[_lights], par_graph_launch, or a
+ * PAR_ERR_DEVICE report. par_set_light, par_set_lights, par_set_light_model, par_set_light_tints, par_get_stats and
+ * par_read_grid keep it, and so does a relit frame: relit frames can follow one another.
+ * `gbuf` is the G-buffer plane of the retained frame, device memory addressing (row_begin, 0) as every plane does; it
+ * is only read. device_out->fb, ->brightness and ->lit are written, each nullable; they may be the very buffers the
+ * retained frame wrote. ->gbuf and ->palidx must be NULL: they do not depend on lights, the caller keeps the ones it
+ * has. On every requested plane a relit frame equals, byte for byte, what par_render_device would write now for the
+ * same scene, rows and flags (1 to PAR_MAX_LIGHTS lights, both light models, tinted or not; one white unbounded light
+ * too, whose full frame takes another path), provided `gbuf` holds what that render would put in its gbuf plane.
+ * A pixel is covered iff its 28-byte texel differs from the background texel (normal 0, colour {bg, bg, bg, 0}, y, z
+ * and entity 0); a covered pixel whose texel equals it has a zero normal and gets the background's colour either way.
+ * Background pixels get the fill's colour, `ambient`, and, when rays are asked for (PAR_RENDER_TRACE_BACKGROUND or a
+ * lit plane), the background bits of a frame with these lights.
+ * Checked in this order, before any device work (a refused call changes nothing): PAR_ERR_INVALID_ARG for a null
+ * context, `gbuf` or outputs, a non-null out->gbuf or out->palidx, undefined flag bits, a bad row range;
+ * PAR_ERR_NOT_READY without sprites, entities or a light, without a retained frame, for rows not inside [r0, r1), and,
+ * for par_relight_rows, when the retained frame is not a par_render / par_render_rows frame with a gbuf plane.
+ * PAR_RENDER_COUNT_RAYS counts what the light kernel would count for that frame; PAR_RENDER_PIPELINED and
+ * PAR_RENDER_TIMED_AS_LAUNCHED are accepted and change nothing. A relit frame does not flip the grid set and leaves
+ * par_get_stats' entities, insertions and column counts as the retained frame left them.
+ * Ordering: enqueue a relit frame on the retained frame's stream, or order the two yourself; the library does not
+ * check it. The kernel stays inside its arrays whatever the texels hold.
+ * Left out on purpose: no graph capture of relit frames, no timed variant, no par_render_device_slots counterpart. */
+/* device buffers, asynchronous on `stream`, no sync */
+int par_relight_device(par_context* ctx, void* stream, int row_begin, int row_end, const par_pixel* gbuf,
+                       const par_outputs* device_out, unsigned flags);
+/* host buffers, synchronous; reads the context's own device copy of the gbuf plane of the last par_render /
+ * par_render_rows */
+int par_relight_rows(par_context* ctx, int row_begin, int row_end, const par_outputs* host_out, unsigned flags);
+
 /* hipGraph path (BASELINE config 5): capture {pinned-host AABB/light upload -> build -> fill -> render} once, replay
  * per frame. `par_graph_stage` writes the next frame's AABBs/light into the pinned staging area the graph copies
  * from; it fails with PAR_ERR_UNSUPPORTED when the staged scene needs larger launch grids than were captured (about

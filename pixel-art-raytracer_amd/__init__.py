@@ -40,7 +40,7 @@ ABI_SYMBOLS = (
     "par_sprite_tile_floor", "par_scene_graybox", "par_scene_synthetic", "par_debug_line", "par_debug_units",
     "par_render_device_slots", "par_row_block", "par_scene_tiles", "par_tiles_pack", "par_tiles_unpack",
     "par_background_fill", "par_tiles_assemble", "par_scene_tile_map", "par_set_lights", "par_graph_capture_lights",
-    "par_graph_stage_lights", "par_set_light_model", "par_set_light_tints",
+    "par_graph_stage_lights", "par_set_light_model", "par_set_light_tints", "par_relight_device", "par_relight_rows",
 )
 MAX_LIGHTS = 8  # PAR_MAX_LIGHTS
 LIGHTS_UNBOUNDED, LIGHTS_RANGED = 0, 1  # par_set_light_model
@@ -108,6 +108,8 @@ def lib():
         L.par_render_rows.argtypes = [vp, i32, i32, vp, C.c_uint]
         L.par_render_device.argtypes = [vp, vp, i32, i32, vp, C.c_uint]
         L.par_render_device_timed.argtypes = [vp, vp, i32, i32, vp, C.c_uint, vp]
+        L.par_relight_device.argtypes = [vp, vp, i32, i32, vp, vp, C.c_uint]
+        L.par_relight_rows.argtypes = [vp, i32, i32, vp, C.c_uint]
         L.par_graph_capture.argtypes = [vp, vp, i32, i32, vp, C.c_uint]
         L.par_graph_stage.argtypes = [vp, vp, i32, i32, vp]
         L.par_graph_launch.argtypes = [vp, vp]
@@ -324,6 +326,25 @@ class Renderer:
             return st
         self._check(lib().par_render_device(self._ctx, C.c_void_p(stream), r0, r1, C.byref(o), flags))
         return None
+
+    def relight(self, planes=("fb",), rows=None, flags=0):
+        """The last render() again under the lights, light model and tints of now (par_relight_rows): no hash build, no
+        primary pass. That render must have had a "gbuf" plane (the renderer keeps its device copy) and cover `rows`;
+        planes out of "fb", "brightness", "lit". Returns {plane: flat row-major array}."""
+        r0, r1 = rows or (0, self.height)
+        n = (r1 - r0) * self.width
+        out = {k: np.zeros(n, dtype=_PLANE_DTYPE[k]) for k in planes}
+        o = Outputs(*[out[k].ctypes.data if k in out else None for k in _PLANES])
+        self._check(lib().par_relight_rows(self._ctx, r0, r1, C.byref(o), flags))
+        return out
+
+    def relight_device(self, gbuf_ptr, device_ptrs, rows=None, flags=0, stream=0):
+        """Asynchronous relit frame (par_relight_device): `gbuf_ptr` is the device pointer of the retained frame's gbuf
+        plane at (row_begin, 0); `device_ptrs` maps "fb", "brightness", "lit" to device pointers as render_device
+        takes them (no "gbuf" or "palidx": they do not depend on lights). Enqueue it on the retained frame's stream."""
+        r0, r1 = rows or (0, self.height)
+        o = Outputs(*[device_ptrs.get(k) for k in _PLANES])
+        self._check(lib().par_relight_device(self._ctx, C.c_void_p(stream), r0, r1, C.c_void_p(gbuf_ptr), C.byref(o), flags))
 
     def graph_capture(self, device_ptrs, rows=None, flags=0, stream=0):
         r0, r1 = rows or (0, self.height)

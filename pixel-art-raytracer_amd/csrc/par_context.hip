@@ -44,6 +44,14 @@ struct par_context {
     bool tinted = false;                 // par_set_light_tints; a tinted context always takes the light kernel
     par_light_tints tints{};             // by light index (white beyond those the call named); read while `tinted`
     int set = 0;  // head/count/node set the NEXT frame uses
+    // The retained frame (par_relight_device, the contract beside it): the rows of the last frame whose hash build is
+    // still what the device holds, its grid set, and whether it was a par_render / par_render_rows frame with a gbuf
+    // plane (which d_out[1] then still holds: par_relight_rows). Nothing of the frame itself is stored.
+    struct {
+        bool valid = false;
+        int r0 = 0, r1 = 0, set = 0;
+        bool host_gbuf = false;
+    } kept;
     hipStream_t last_stream = nullptr;  // stream of the most recent asynchronous render (scene updates wait for it)
     bool has_last_stream = false;
 
@@ -148,6 +156,17 @@ int guarded(par_context* ctx, F&& body) noexcept {
         return fail(ctx, PAR_ERR_HIP, "unexpected C++ exception");
     }
 }
+
+// The retained frame: `set` is the grid set the frame that just returned PAR_OK was built in; and its end (a hash build
+// was enqueued or the scene changed, see par_raytracer.h).
+void retain_frame(par_context* c, int row_begin, int row_end, int set, bool host_gbuf) {
+    c->kept.valid = true;
+    c->kept.r0 = row_begin;
+    c->kept.r1 = row_end;
+    c->kept.set = set;
+    c->kept.host_gbuf = host_gbuf;
+}
+void drop_retained(par_context* c) { c->kept.valid = false; }
 
 int hip_fail(par_context* c, hipError_t e, const char* what) {
     return fail(c, e == hipErrorOutOfMemory ? PAR_ERR_OOM : PAR_ERR_HIP,
@@ -383,6 +402,7 @@ int check_device_error(par_context* ctx) {
     PAR_HIP(hipMemcpy(&word, ctx->grid.counters + PAR_CNT_ERROR, sizeof(word), hipMemcpyDeviceToHost));
     if (word == 0) return PAR_OK;
     PAR_HIP(hipMemset(ctx->grid.counters + PAR_CNT_ERROR, 0, sizeof(word)));
+    drop_retained(ctx);
     std::string what;
     if (word & PAR_DEVERR_BARRIER) {
         what += "the hash build's barrier timed out (a build workgroup never arrived); ";
@@ -481,6 +501,7 @@ int enqueue_lights_frame(par_context* ctx, hipStream_t stream, const par_bin_arg
 // Enqueue one frame (alt:690-760) on `stream` using grid set `set`.
 int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, int row_end, const par_outputs& out,
                   unsigned flags, bool graph_mode, hipEvent_t* ev) {
+    drop_retained(ctx);  // (a hash build follows; the entry point retains the new frame once it has returned PAR_OK)
     par_outputs outs = out;
     if ((flags & PAR_RENDER_TRACE_BACKGROUND) && !outs.lit) {
         // every ray is to be traced but the caller wants no lit plane: the results still go to memory (a scratch
@@ -595,7 +616,9 @@ int render_to_host(par_context* ctx, int row_begin, int row_end, const par_outpu
         if (host[i]) PAR_HIP(hipMemcpyAsync(host[i], dev[i], n * kPlaneElem[i], hipMemcpyDeviceToHost, ctx->stream));
     }
     PAR_HIP(hipStreamSynchronize(ctx->stream));
-    return check_device_error(ctx);
+    rc = check_device_error(ctx);
+    if (rc == PAR_OK) retain_frame(ctx, row_begin, row_end, ctx->set ^ 1, host_out->gbuf != nullptr);
+    return rc;
 }
 
 // The context's fixed device buffers: par_create allocates those of more than 0 bytes and sets every byte of those
@@ -751,6 +774,7 @@ static int par_set_sprites_impl(par_context* ctx, const par_sprite* sprites, int
     PAR_HIP(hipSetDevice(ctx->device));
     PAR_HIP(hipDeviceSynchronize());
     drop_graphs(ctx);  // (a captured graph bakes the table's pointers)
+    drop_retained(ctx);
     ctx->n_sprites = 0;
     PAR_HIP(reallocate(&ctx->d_sprites, (size_t)n_sprites));
     PAR_HIP(hipMemcpy(ctx->d_sprites, sprites, (size_t)n_sprites * sizeof(par_sprite), hipMemcpyHostToDevice));
@@ -796,6 +820,7 @@ static int par_set_entities_impl(par_context* ctx, const par_aabb* aabbs, const 
     PAR_HIP(hipSetDevice(ctx->device));
     PAR_HIP(hipDeviceSynchronize());
     drop_graphs(ctx);
+    drop_retained(ctx);
     // (pools and lists by what the extents allow too: they then hold wherever the entities move)
     const int rc = ensure_room(ctx, ctx->book.plan(par_change::SET, aabbs, 0, n).need);
     if (rc != PAR_OK) return rc;
@@ -860,6 +885,7 @@ static int par_update_aabbs_impl(par_context* ctx, const par_aabb* aabbs, int fi
     if (!ctx) return PAR_ERR_INVALID_ARG;
     int rc = check_update(ctx, aabbs, first, n, false);
     if (rc != PAR_OK) return rc;
+    drop_retained(ctx);
     const par_bound need = ctx->book.plan(par_change::UPDATE, aabbs, first, n).need;
     PAR_HIP(hipSetDevice(ctx->device));
     rc = ensure_room(ctx, need);
@@ -882,6 +908,7 @@ static int par_update_aabbs_async_impl(par_context* ctx, const par_aabb* aabbs, 
     const int rc = check_update(ctx, aabbs, first, n, false);
     if (rc != PAR_OK) return rc;
     hipStream_t stream = (hipStream_t)stream_v;
+    drop_retained(ctx);
     // No cull and range arithmetic here (it cost a moving scene more host time per frame than its launches): the
     // book keeps the extents alone (EXTENTS_ONLY) until a blocking call refreshes it, and the frame's launches are
     // sized by them and include the one for the overflow list whatever the columns hold.
@@ -987,6 +1014,7 @@ static int par_render_device_impl(par_context* ctx, void* stream, int row_begin,
     ctx->last_flags = flags;
     ctx->last_stream = (hipStream_t)stream;
     ctx->has_last_stream = true;
+    retain_frame(ctx, row_begin, row_end, ctx->set ^ 1, false);
     return PAR_OK;
 }
 
@@ -1016,7 +1044,101 @@ static int par_render_device_timed_impl(par_context* ctx, void* stream, int row_
         if (!ctx->timed_tiles) ctx->stats.ms_launch[3] = 0.f;  // (an empty bracket still measures the events themselves)
         if (!ctx->timed_overflow) ctx->stats.ms_launch[4] = 0.f;
     }
-    if (stats) return par_get_stats(ctx, stats);
+    rc = stats ? par_get_stats(ctx, stats) : check_device_error(ctx);
+    if (rc == PAR_OK) retain_frame(ctx, row_begin, row_end, ctx->set ^ 1, false);
+    return rc;
+}
+
+// What both relight calls check, in the order par_raytracer.h gives, before any device work. `host`: par_relight_rows.
+static int relight_prologue(par_context* ctx, bool gbuf_given, const par_outputs* out, int row_begin, int row_end,
+                            unsigned flags, bool host) {
+    if (!ctx || !gbuf_given || !out) return fail(ctx, PAR_ERR_INVALID_ARG, "null argument");
+    if (out->gbuf || out->palidx) {
+        return fail(ctx, PAR_ERR_INVALID_ARG, "a relit frame writes no gbuf or palidx plane: they do not depend on lights");
+    }
+    if (flags & ~PAR_ACCEPTED_FLAGS) return fail(ctx, PAR_ERR_INVALID_ARG, "undefined render flag bits");
+    if (row_begin < 0 || row_end > ctx->params.height || row_begin >= row_end) {
+        return fail(ctx, PAR_ERR_INVALID_ARG, "rows must satisfy 0 <= row_begin < row_end <= height");
+    }
+    if (ctx->n_sprites <= 0) return fail(ctx, PAR_ERR_NOT_READY, "par_set_sprites has not been called");
+    if (!ctx->have_entities) return fail(ctx, PAR_ERR_NOT_READY, "par_set_entities has not been called");
+    if (ctx->n_lights <= 0) return fail(ctx, PAR_ERR_NOT_READY, "par_set_light has not been called");
+    if (!ctx->kept.valid) return fail(ctx, PAR_ERR_NOT_READY, "no retained frame: render one first");
+    if (row_begin < ctx->kept.r0 || row_end > ctx->kept.r1) {
+        return fail(ctx, PAR_ERR_NOT_READY, "rows outside the retained frame's");
+    }
+    if (host && !ctx->kept.host_gbuf) {
+        return fail(ctx, PAR_ERR_NOT_READY, "the retained frame is not a par_render / par_render_rows frame with a gbuf plane");
+    }
+    PAR_HIP(hipSetDevice(ctx->device));
+    return PAR_OK;
+}
+
+// A relit frame on `stream`: the background rays when they are wanted, the background fill, and the relight form of the
+// light kernel over the retained frame's column list, under the lights the context holds now. No hash build, no flip
+// of the grid set; the retained frame stays.
+static int enqueue_relight(par_context* ctx, hipStream_t stream, int row_begin, int row_end, const par_pixel* gbuf,
+                           const par_outputs& out, unsigned flags) {
+    par_outputs outs = out;
+    if ((flags & PAR_RENDER_TRACE_BACKGROUND) && !outs.lit) {  // (as enqueue_frame: the rays' results go to a scratch plane)
+        const size_t need = (size_t)(row_end - row_begin) * ctx->params.width;
+        if (ctx->scratch_lit_bytes < need) PAR_HIP(grow(&ctx->d_scratch_lit, &ctx->scratch_lit_bytes, need));
+        outs.lit = ctx->d_scratch_lit;
+    }
+    const par_render_args r = make_render_args(ctx, ctx->kept.set, row_begin, row_end, outs, flags, false);
+    const par_lights_dyn lights = make_lights_dyn(ctx);
+    const par_light_radii radii_v = make_light_radii(ctx);
+    const par_light_radii* radii = ranged(ctx) ? &radii_v : nullptr;
+    const par_light_tints* tints = ctx->tinted ? &ctx->tints : nullptr;
+    if (flags & PAR_RENDER_COUNT_RAYS) {
+        PAR_HIP(hipMemsetAsync(ctx->d_ray_counter, 0, 3 * sizeof(unsigned long long), stream));
+    }
+    if (r.trace_bg) PAR_HIP(par_launch_bglights(ctx->grid, r, lights, nullptr, radii, nullptr, stream));
+    PAR_HIP(par_launch_fill(ctx->grid, r, stream));
+    // the column list is the retained frame's: bounded as its launch was, by its rows
+    const int B = ctx->params.bin_size;
+    const int64_t kept_cols = (int64_t)ctx->gx * ((ctx->kept.r1 - 1) / B - ctx->kept.r0 / B + 1);
+    const int64_t cols = std::min(ctx->book.frame_bounds(false).cols, kept_cols);
+    PAR_HIP(par_launch_relight(ctx->grid, r, gbuf, lights, radii, tints, cols, stream));
+    ctx->last_flags = flags;
+    return PAR_OK;
+}
+
+static int par_relight_device_impl(par_context* ctx, void* stream, int row_begin, int row_end, const par_pixel* gbuf,
+                                   const par_outputs* device_out, unsigned flags) {
+    int rc = relight_prologue(ctx, gbuf != nullptr, device_out, row_begin, row_end, flags, false);
+    if (rc != PAR_OK) return rc;
+    rc = enqueue_relight(ctx, (hipStream_t)stream, row_begin, row_end, gbuf, *device_out, flags);
+    if (rc != PAR_OK) return rc;
+    ctx->last_stream = (hipStream_t)stream;
+    ctx->has_last_stream = true;
+    return PAR_OK;
+}
+
+static int par_relight_rows_impl(par_context* ctx, int row_begin, int row_end, const par_outputs* host_out, unsigned flags) {
+    int rc = relight_prologue(ctx, true, host_out, row_begin, row_end, flags, true);
+    if (rc != PAR_OK) return rc;
+    // fb, brightness, lit: the context's device planes, addressing (row_begin, 0); the gbuf plane stays as the
+    // retained frame left it, addressing that frame's first row
+    const int plane[3] = {0, 3, 4};
+    void* host[3] = {host_out->fb, host_out->brightness, host_out->lit};
+    const size_t n = (size_t)(row_end - row_begin) * ctx->params.width;
+    void* dev[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < 3; i++) {
+        if (!host[i]) continue;
+        const int k = plane[i];
+        const size_t bytes = n * kPlaneElem[k];
+        if (ctx->d_out_bytes[k] < bytes) PAR_HIP(grow(&ctx->d_out[k], &ctx->d_out_bytes[k], bytes));
+        dev[i] = ctx->d_out[k];
+    }
+    const par_outputs d{(par_color*)dev[0], nullptr, nullptr, (float*)dev[1], (uint8_t*)dev[2]};
+    const par_pixel* gbuf = (const par_pixel*)ctx->d_out[1] + (size_t)(row_begin - ctx->kept.r0) * ctx->params.width;
+    rc = enqueue_relight(ctx, ctx->stream, row_begin, row_end, gbuf, d, flags);
+    if (rc != PAR_OK) return rc;
+    for (int i = 0; i < 3; i++) {
+        if (host[i]) PAR_HIP(hipMemcpyAsync(host[i], dev[i], n * kPlaneElem[plane[i]], hipMemcpyDeviceToHost, ctx->stream));
+    }
+    PAR_HIP(hipStreamSynchronize(ctx->stream));
     return check_device_error(ctx);
 }
 
@@ -1039,6 +1161,7 @@ static int graph_capture(par_context* ctx, void* stream_v, int row_begin, int ro
     }
     PAR_HIP(hipDeviceSynchronize());
     drop_graphs(ctx);
+    drop_retained(ctx);
     rc = ensure_room(ctx, ctx->book.capture());
     if (rc != PAR_OK) return rc;
     for (int s = 0; s < 2; s++) {
@@ -1102,6 +1225,7 @@ static int graph_stage(par_context* ctx, const par_aabb* aabbs, int first, int n
         return fail(ctx, PAR_ERR_UNSUPPORTED, "staged frame exceeds what the captured graph was sized for; capture again");
     }
     ctx->book.commit();
+    drop_retained(ctx);
     mark_staged(ctx, first, n);  // (the staging areas are brought up to date by par_graph_launch)
     if (n_lights > 0) set_lights(ctx, lights, n_lights, keep_count ? ctx->n_lights : n_lights);
     return PAR_OK;
@@ -1142,6 +1266,7 @@ static int par_graph_launch_impl(par_context* ctx, void* stream) {
     if (ctx->ev_update_pending && ctx->update_stream != (hipStream_t)stream) {
         PAR_HIP(hipStreamWaitEvent((hipStream_t)stream, ctx->ev_update, 0));
     }
+    drop_retained(ctx);
     PAR_HIP(hipGraphLaunch(ctx->graph_exec[s], (hipStream_t)stream));
     PAR_HIP(hipEventRecord(ctx->ev_graph[s], (hipStream_t)stream));
     ctx->ev_graph_pending[s] = true;
@@ -1159,6 +1284,7 @@ static int par_pick_impl(par_context* ctx, int x, int y, par_pixel* out) {
     par_outputs o{nullptr, row.data(), nullptr, nullptr, nullptr};
     int rc = render_to_host(ctx, y, y + 1, &o, 0);
     if (rc != PAR_OK) return rc;
+    ctx->kept.host_gbuf = false;  // (its one row is retained, for par_relight_device alone)
     *out = row[(size_t)x];  // `mouse_pixel`, alt:380-382
     return PAR_OK;
 }
@@ -1413,6 +1539,13 @@ int par_render_device(par_context* ctx, void* stream, int row_begin, int row_end
 }
 int par_render_device_timed(par_context* ctx, void* stream, int row_begin, int row_end, const par_outputs* device_out, unsigned flags, par_frame_stats* stats) {
     return guarded(ctx, [&] { return par_render_device_timed_impl(ctx, stream, row_begin, row_end, device_out, flags, stats); });
+}
+int par_relight_device(par_context* ctx, void* stream, int row_begin, int row_end, const par_pixel* gbuf,
+                       const par_outputs* device_out, unsigned flags) {
+    return guarded(ctx, [&] { return par_relight_device_impl(ctx, stream, row_begin, row_end, gbuf, device_out, flags); });
+}
+int par_relight_rows(par_context* ctx, int row_begin, int row_end, const par_outputs* host_out, unsigned flags) {
+    return guarded(ctx, [&] { return par_relight_rows_impl(ctx, row_begin, row_end, host_out, flags); });
 }
 int par_graph_launch(par_context* ctx, void* stream) {
     return guarded(ctx, [&] { return par_graph_launch_impl(ctx, stream); });

@@ -292,6 +292,14 @@ hipError_t par_launch_render_lights(const par_grid_dev& g, const par_render_args
                                     const par_lights_dyn* d_lights, const par_light_radii* radii,
                                     const par_light_radii* d_radii, const par_light_tints* tints,
                                     const par_light_tints* d_tints, int64_t column_bound, hipStream_t stream);
+// A relit frame (par_relight_device): the relight form of the light kernel over the column list the retained frame's
+// hash build left, reading that frame's G-buffer plane `gbuf` (device memory, addressing (a.row_begin, 0)) where the
+// kernel above runs its primary pass. `a.count` is the retained frame's set; a.out.gbuf and a.out.palidx are not
+// written. Lights, radii and tints by value (there is no graph form); `column_bound` bounds the retained frame's
+// columns.
+hipError_t par_launch_relight(const par_grid_dev& g, const par_render_args& a, const par_pixel* gbuf,
+                              const par_lights_dyn& lights, const par_light_radii* radii, const par_light_tints* tints,
+                              int64_t column_bound, hipStream_t stream);
 // The background rays of such a frame (one per x and light, bit l of g.bglit[x] for light l); par_launch_fill then
 // copies them into the lit plane. `lights`, `d_lights`, `radii`, `d_radii` as above.
 hipError_t par_launch_bglights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,

@@ -2275,6 +2275,11 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_both_kernel(par_grid_
 // read inside the light loop, wave-uniform as its radius is: from the kernarg segment in direct frames (scalar loads
 // at a dynamic offset; the ranged by-value form has no SGPRs to hold all 24 in), from LDS in the graph form. The
 // untinted instantiations have none of it.
+// And the four by-value forms again in a RELIGHT form (par_relight_device, the contract beside it), whose last extra
+// is the G-buffer plane of the retained frame (RelightSrc). It runs over the column list and the hash that frame's
+// build left, skips the columns outside the relit rows, does phase A as above under the lights of now, and in phase B
+// reads its pixel's texel (gbuf_texel) where the others run the primary pass; then the same light loop. It stores fb,
+// brightness and lit only. The other instantiations have none of it.
 // ------------------------------------------------------------------------------------------------------------
 constexpr int PAR_LIGHT_NB = 64;      // occupied bins of a column whose walks are recorded (the others: lane walks)
 constexpr int PAR_LIGHT_WALK = 1024;  // occluder records of all walks of a column (16 KiB)
@@ -2377,6 +2382,54 @@ __device__ __forceinline__ LightLive& light_live() {
     return lv;
 }
 
+// The relight form's last extra (par_relight_device): the G-buffer plane of the retained frame, device memory that
+// addresses (a.row_begin, 0). frame_radii and frame_tints look past it.
+struct RelightSrc {
+    const par_pixel* gbuf;
+};
+__device__ __forceinline__ NoRadii frame_radii(const RelightSrc&) { return NoRadii{}; }
+__device__ __forceinline__ NoRadii frame_radii(const par_light_tints&, const RelightSrc&) { return NoRadii{}; }
+template <class R, class Tn>
+__device__ __forceinline__ const par_light_radii& frame_radii(const R& radii, const Tn&, const RelightSrc&) {
+    return frame_radii(radii);
+}
+template <class First, class... Rest>
+__device__ __forceinline__ const RelightSrc& relight_src(const First& first, const Rest&... rest) {
+    if constexpr (sizeof...(Rest) == 0) {
+        return first;
+    } else {
+        return relight_src(rest...);
+    }
+}
+
+// The same pixel as a relit frame gets it: the G-buffer texel the primary pass of the retained frame left, seven dwords
+// per lane; a row of a tile is contiguous, so the wavefront's loads cover whole cache lines between them. Covered: the
+// texel differs from the background texel of fill_generic_kernel.
+struct GbufTexel {
+    bool covered;
+    float nx, ny, nz;
+    uint32_t rgba;
+    int y, z, entity;
+};
+__device__ __forceinline__ GbufTexel gbuf_texel(const par_render_args& a, const par_pixel* gbuf, bool valid, int row,
+                                                int px_col) {
+    GbufTexel t{false, 0.f, 0.f, 0.f, 0u, 0, 0, 0};
+    if (valid) {
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(gbuf + ((size_t)(row - a.row_begin) * a.W + px_col));
+        const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4], w5 = w[5], w6 = w[6];
+        const uint32_t gray = (uint8_t)a.background;
+        t.covered = (w0 | w1 | w2 | (w3 ^ (gray | (gray << 8) | (gray << 16))) | w4 | w5 | w6) != 0;
+        t.nx = __uint_as_float(w0);
+        t.ny = __uint_as_float(w1);
+        t.nz = __uint_as_float(w2);
+        t.rgba = w3;
+        t.y = (int)w4;
+        t.z = (int)w5;
+        t.entity = (int)w6;
+    }
+    return t;
+}
+
 // LightsArg: par_lights_dyn (direct frames) or const par_lights_dyn* (graph replay), see frame_lights. Radii: nothing
 // (unbounded lights), or par_light_radii / const par_light_radii* in the same way (the RANGED form), see frame_radii;
 // then nothing (white lights), or par_light_tints / const par_light_tints* (the TINTED form), see frame_tints.
@@ -2385,7 +2438,9 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
                                                                             LightsArg lights_arg, Extras... extras_arg) {
     constexpr bool RANGED = (is_light_radii<Extras> || ...);
     constexpr bool TINTED = (is_light_tints<Extras> || ...);
-    static_assert(sizeof...(Extras) == (RANGED ? 1 : 0) + (TINTED ? 1 : 0), "the radii, then the tints, one of each at most");
+    constexpr bool RELIGHT = (std::is_same_v<Extras, RelightSrc> || ...);
+    static_assert(sizeof...(Extras) == (RANGED ? 1 : 0) + (TINTED ? 1 : 0) + (RELIGHT ? 1 : 0),
+                  "the radii, then the tints, then the G-buffer of a relit frame, one of each at most");
     __shared__ LightCol sh;
     [[maybe_unused]] const auto& radii = frame_radii(extras_arg...);
     [[maybe_unused]] const auto& tints = frame_tints(extras_arg...);
@@ -2402,6 +2457,9 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
         const int col = g.col_list[ci];
         const int bx = col / g.gy, by = col - bx * g.gy;
         const int col_base = flat_index(g.gy, g.gz, bx, by, 0);
+        if constexpr (RELIGHT) {
+            if (by < a.by_lo || by > a.by_hi) continue;  // (a column of the retained rows, not of the relit ones)
+        }
         // ---- A: occupied bins, then the walks ---------------------------------------------------------------
         __syncthreads();  // (the previous column's pixels are done with the LDS)
         if (threadIdx.x == 0) {
@@ -2504,10 +2562,17 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
             const int pyy = rm.row(pidx);
             const int px_col = c0 + (pidx - pyy * rw), row = ry0 + pyy;
             const bool valid = pidx < area;
-            // primary ray, alt:271-397: the column's bins as they lie in the hash (render_chunk<GENERIC>)
+            // primary ray, alt:271-397: from the hash, or (RELIGHT) what it left in the G-buffer
             bool hit = false;
             int p_entity = 0, p_y = 0, p_z = 0, p_tex = 0;
-            {
+            [[maybe_unused]] GbufTexel texel;
+            if constexpr (RELIGHT) {
+                texel = gbuf_texel(a, relight_src(extras_arg...).gbuf, valid, row, px_col);
+                hit = texel.covered;
+                p_entity = texel.entity;
+                p_y = texel.y;
+                p_z = texel.z;
+            } else {  // the column's bins as they lie in the hash (render_chunk<GENERIC>); kept in place: DESIGN 8c
                 const int world_j = (int)(int16_t)(H - row);  // alt:280
                 int adjacent = 0;                             // alt:282
                 int closest = INT_MIN;                        // alt:289
@@ -2560,12 +2625,17 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
             int pal_index = PAR_PALIDX_BACKGROUND;
             [[maybe_unused]] int n_rays = 0;  // RANGED: the lights this lane's pixel is in range of, or that are unbounded
             if (hit) {
-                const par_texel ti = a.texinfo[p_tex];  // normal (alt:349-350) + palette colour (alt:352-354)
-                nx = ti.nx; ny = ti.ny; nz = ti.nz;
-                rgba = ti.rgba;
-                if (a.out.palidx) {
-                    const int sid = p_tex / PAR_SPRITE_TEXELS;
-                    pal_index = a.sprites[sid].color[p_tex - sid * PAR_SPRITE_TEXELS];
+                if constexpr (RELIGHT) {
+                    nx = texel.nx; ny = texel.ny; nz = texel.nz;
+                    rgba = texel.rgba;
+                } else {
+                    const par_texel ti = a.texinfo[p_tex];  // normal (alt:349-350) + palette colour (alt:352-354)
+                    nx = ti.nx; ny = ti.ny; nz = ti.nz;
+                    rgba = ti.rgba;
+                    if (a.out.palidx) {
+                        const int sid = p_tex / PAR_SPRITE_TEXELS;
+                        pal_index = a.sprites[sid].color[p_tex - sid * PAR_SPRITE_TEXELS];
+                    }
                 }
                 // the start bin (alt:724-727): its row is this column's (render_chunk), its depth bin(z)
                 const int sz = div_bin(p_z, a.magic_b);
@@ -2647,10 +2717,14 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
                 } else {
                     if (a.out.fb) reinterpret_cast<uint32_t*>(a.out.fb)[o] = color_scale(rgba, bright);
                 }
-                if (a.out.palidx) a.out.palidx[o] = (uint8_t)pal_index;
+                if constexpr (!RELIGHT) {
+                    if (a.out.palidx) a.out.palidx[o] = (uint8_t)pal_index;
+                }
                 if (a.out.brightness) a.out.brightness[o] = bright;
                 if (a.out.lit) a.out.lit[o] = (uint8_t)lit_mask;
-                if (a.out.gbuf) a.out.gbuf[o] = gbuf_pixel(nx, ny, nz, rgba, p_y, p_z, p_entity);
+                if constexpr (!RELIGHT) {
+                    if (a.out.gbuf) a.out.gbuf[o] = gbuf_pixel(nx, ny, nz, rgba, p_y, p_z, p_entity);
+                }
             }
         }
     }
@@ -3098,6 +3172,30 @@ hipError_t par_launch_render_lights(const par_grid_dev& g, const par_render_args
         hipLaunchKernelGGL(render_lights_kernel<const par_lights_dyn*>, grid, block, 0, stream, g, a, d_lights);
     } else {
         hipLaunchKernelGGL(render_lights_kernel<par_lights_dyn>, grid, block, 0, stream, g, a, lights);
+    }
+    return hipGetLastError();
+}
+
+// One workgroup per column of the RETAINED frame's list that `column_bound` allows (the caller bounds it by that
+// frame's rows, which may be more than a's), at most 65536.
+hipError_t par_launch_relight(const par_grid_dev& g, const par_render_args& a, const par_pixel* gbuf,
+                              const par_lights_dyn& lights, const par_light_radii* radii, const par_light_tints* tints,
+                              int64_t column_bound, hipStream_t stream) {
+    const int64_t n = std::min(column_bound, (int64_t)65536);
+    if (n <= 0) return hipSuccess;
+    const dim3 grid((unsigned)n), block(PAR_WAVE_NW * 64);
+    const RelightSrc src{gbuf};
+    if (tints && radii) {
+        hipLaunchKernelGGL((render_lights_kernel<par_lights_dyn, par_light_radii, par_light_tints, RelightSrc>), grid, block,
+                           0, stream, g, a, lights, *radii, *tints, src);
+    } else if (tints) {
+        hipLaunchKernelGGL((render_lights_kernel<par_lights_dyn, par_light_tints, RelightSrc>), grid, block, 0, stream, g, a,
+                           lights, *tints, src);
+    } else if (radii) {
+        hipLaunchKernelGGL((render_lights_kernel<par_lights_dyn, par_light_radii, RelightSrc>), grid, block, 0, stream, g, a,
+                           lights, *radii, src);
+    } else {
+        hipLaunchKernelGGL((render_lights_kernel<par_lights_dyn, RelightSrc>), grid, block, 0, stream, g, a, lights, src);
     }
     return hipGetLastError();
 }

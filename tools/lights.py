@@ -10,8 +10,15 @@ same table, each with the (start bin, light) pairs the light kernel walked and c
 With --tints every light has a colour (par_set_light_tints, the eight non-white tints below), alone or beside --radius /
 --torches: the same table through the tinted light kernels (N = 1 takes the light kernel too; the two N = 1 hook rows
 are left out).
-   python tools/lights.py [frames] [--radius F | --torches F] [--tints] [--scene graybox_480x320 | synthetic_4096_1024]"""
+With --relight (alone or beside --radius / --torches / --tints) full frames and relit frames (par_relight_device) of
+the same lights are timed in turn, full, relit, full, relit, for N = 1, 2, 4, 8: "alone" is the span of the frame's
+launches between two events on its stream (the full frame's also as par_render_device_timed gives it, as in the other
+tables), "inflight4" is wall time per frame with four contexts, each with its retained frame, on four streams, relit
+round robin. Full frames write fb and palidx, relit frames fb; the G-buffer they read is written once, before.
+   python tools/lights.py [frames] [--radius F | --torches F] [--tints] [--relight]
+                          [--scene graybox_480x320 | synthetic_4096_1024]"""
 import argparse
+import ctypes
 import importlib
 import json
 import os
@@ -97,12 +104,107 @@ def inflight_us(params, aabbs, sprite, lights, mode, frames):
         pipe.close()
 
 
+def bracket_us(stream, frames, enqueue):
+    """Median span of `enqueue()`'s launches on `stream`, one frame at a time, between two events."""
+    spans = []
+    for i in range(frames + 3):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        enqueue()
+        e1.record(stream)
+        e1.synchronize()
+        if i >= 3:
+            spans.append(1000.0 * e0.elapsed_time(e1))
+    return round(statistics.median(spans), 1)
+
+
+def relight_call(r, stream, gbuf, fb):
+    """par_relight_device of the whole view into `fb`, its arguments built once."""
+    out = T.Outputs(fb.data_ptr(), None, None, None, None)
+    args = (r._ctx, ctypes.c_void_p(stream.cuda_stream), 0, r.height, ctypes.c_void_p(gbuf.data_ptr()), ctypes.byref(out), 0)
+    fn = par.lib().par_relight_device
+
+    def call():
+        rc = fn(*args)
+        if rc != 0:
+            raise par.ParError(rc, par.lib().par_last_error(r._ctx).decode())
+    call.keep = out
+    return call
+
+
+def relight_alone(params, aabbs, sprite, lights, mode, frames, rounds=2):
+    n_px = params.width * params.height
+    with par.Renderer(params, 0) as r:
+        r.set_scene(aabbs, sprite, lights[0:1])
+        configure(r, lights, mode)
+        stream = torch.cuda.Stream()
+        fb = torch.zeros(n_px * 4, dtype=torch.uint8, device="cuda")
+        pal = torch.zeros(n_px, dtype=torch.uint8, device="cuda")
+        gbuf = torch.zeros(n_px * 28, dtype=torch.uint8, device="cuda")
+        ptrs = {"fb": fb.data_ptr(), "palidx": pal.data_ptr()}
+        r.render_device(dict(ptrs, gbuf=gbuf.data_ptr()), stream=stream.cuda_stream)
+        stream.synchronize()
+        relit = relight_call(r, stream, gbuf, fb)
+        res = {"full_timed": [], "full": [], "relit": []}
+        for _ in range(rounds):
+            spans = []
+            for i in range(frames + 3):
+                st = r.render_device(ptrs, timed=True, flags=par.RENDER_TIMED_AS_LAUNCHED, stream=stream.cuda_stream)
+                if i >= 3:
+                    spans.append(1000.0 * sum(v for v in st.ms_launch if v > 0))
+            res["full_timed"].append(round(statistics.median(spans), 1))
+            res["full"].append(bracket_us(stream, frames, lambda: r.render_device(ptrs, stream=stream.cuda_stream)))
+            res["relit"].append(bracket_us(stream, frames, relit))
+        r.stats()  # PAR_ERR_DEVICE raises
+        return res
+
+
+def relight_inflight(params, aabbs, sprite, lights, mode, frames, rounds=2):
+    n_px = params.width * params.height
+    pipe = pipeline.FramePipeline(params, aabbs, sprite, lights[0:1], depth=4)
+    try:
+        calls = []
+        for s in pipe.slots:
+            configure(s.renderer, lights, mode)
+            gbuf = torch.zeros(n_px * 28, dtype=torch.uint8, device="cuda")
+            s.renderer.render_device(dict(s.ptrs, gbuf=gbuf.data_ptr()), stream=s.stream.cuda_stream)
+            calls.append(relight_call(s.renderer, s.stream, gbuf, s.buffers["fb"]))
+        pipe.synchronize()
+
+        def full(n):
+            pipe.submit_many(0, n)
+
+        def relit(n):
+            for f in range(n):
+                calls[f % 4]()
+
+        res = {"full": [], "relit": []}
+        for _ in range(rounds):
+            for name, submit in (("full", full), ("relit", relit)):
+                submit(8)
+                pipe.synchronize()
+                best = None
+                for _ in range(3):
+                    t0 = time.perf_counter()
+                    submit(frames)
+                    pipe.synchronize()
+                    us = (time.perf_counter() - t0) * 1e6 / frames
+                    best = us if best is None else min(best, us)
+                res[name].append(round(best, 1))
+        for s in pipe.slots:
+            s.renderer.stats()  # PAR_ERR_DEVICE raises
+        return res
+    finally:
+        pipe.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("frames", nargs="?", type=int, default=40)
     ap.add_argument("--radius", type=float, help="every light ranged, radius = this fraction of the view's width")
     ap.add_argument("--torches", type=float, help="one sun and N - 1 torches of that radius")
     ap.add_argument("--tints", action="store_true", help="every light tinted (par_set_light_tints)")
+    ap.add_argument("--relight", action="store_true", help="full frames against relit frames (par_relight_device)")
     ap.add_argument("--scene", help="one scene only")
     args = ap.parse_args()
     global TINTED
@@ -118,12 +220,22 @@ def main():
     out = {"tool": "lights", "frames": frames, "us_per_frame": {}}
     if args.tints:
         out["tints"] = True
+    if args.relight:
+        out["relight"] = True
     if radius is not None:
         out["radius" if args.radius is not None else "torches"] = radius
     for name, (params, aabbs) in scenes.items():
         if args.scene and name != args.scene:
             continue
         res = {}
+        if args.relight:
+            for n in (1, 2, 4, 8):
+                lights = lights_for(params, n, radius, sun=radius is not None and args.radius is None)
+                mode = "ranged" if radius is not None else "auto"
+                res[f"n{n}"] = {"alone": relight_alone(params, aabbs, sprite, lights, mode, frames),
+                                "inflight4": relight_inflight(params, aabbs, sprite, lights, mode, frames)}
+            out["us_per_frame"][name] = res
+            continue
         if radius is not None:
             for n in (2, 4, 8):
                 lights = lights_for(params, n, radius, sun=args.radius is None)
