@@ -7,6 +7,7 @@ import os
 import re
 import subprocess
 
+import numpy as np
 import pytest
 
 import light_range as LR
@@ -106,17 +107,30 @@ def nearest(points, light):
 
 
 @pytest.fixture(scope="module")
-def header_answers(tmp_path_factory):
+def lightbox_exe(tmp_path_factory):
     exe = tmp_path_factory.mktemp("lightbox") / "lightbox_check"
     p = subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", "-I", CSRC,
                         os.path.join(ROOT, "tests", "lightbox_check.cpp"), "-o", str(exe)], capture_output=True, text=True)
     assert p.returncode == 0, p.stderr
-    args = [str(v) for c in CASES for v in (*c[:5], *c[5], *c[7], *c[8])]
-    out = subprocess.run([str(exe)] + args, capture_output=True, text=True, timeout=60)
+    return str(exe)
+
+
+def case_values(c):
+    """The sixteen integers of a case, in the order lightbox_check takes them."""
+    return [int(v) for v in (*c[:5], *c[5], *c[7], *c[8])]
+
+
+def answers_of(out, n):
     assert out.returncode == 0, out.stderr
     rows = [tuple(int(v) for v in line.split()) for line in out.stdout.splitlines()]
-    assert len(rows) == len(CASES)
+    assert len(rows) == n
     return rows
+
+
+@pytest.fixture(scope="module")
+def header_answers(lightbox_exe):
+    args = [str(v) for c in CASES for v in case_values(c)]
+    return answers_of(subprocess.run([lightbox_exe] + args, capture_output=True, text=True, timeout=60), len(CASES))
 
 
 @pytest.mark.parametrize("k", range(len(CASES)))
@@ -154,3 +168,88 @@ def test_the_cases_cover_what_they_should():
     # a culled pair next to a kept one for the same light: the radius decides
     assert LR.pair_culled(40, 320, 6, 2, 2, (250, 150, 90), 1) is False  # the light is inside: distance 0 < 1
     assert LR.pair_culled(40, 320, 0, 0, 0, (-50, 120, -30), 100) and not LR.pair_culled(40, 320, 0, 0, 0, (-50, 120, -30), 300)
+
+
+# ---- the same, over a random sample -----------------------------------------------------------------------------
+
+RANDOM_SEED, RANDOM_CASES = 20261017, 3000
+RANDOM_BINS = [1, 2, 3, 5, 8, 12]  # (the enumeration of a case has B * B * B positions, twice that for bz = 0)
+
+
+def random_cases():
+    """Cases in the layout of CASES: small bins, view heights from B to 6 B + 5 (most of them no multiple of B), every
+    bin row up to the clipped last one, depth bin 0 in a third of them, lights from -3 B to 3 B beyond the view on each
+    axis (a fifth of them in the slab or just beside it), a slot record of any extent the hash holds (ex <= 20,
+    ey + ez <= 40) placed around the bin, and sprite depths that are negative, single-valued or wider than the bin."""
+    rng = np.random.default_rng(RANDOM_SEED)
+    cases = []
+    for _ in range(RANDOM_CASES):
+        B = int(rng.choice(RANDOM_BINS))
+        H = int(rng.integers(B, 6 * B + 6))
+        last = (H - 1) // B
+        by = last if rng.random() < 0.25 else int(rng.integers(0, last + 1))
+        bx = int(rng.integers(0, 6))
+        bz = 0 if rng.random() < 1 / 3 else int(rng.integers(0, 6))
+        light = (int(rng.integers(-3 * B, 9 * B + 1)), int(rng.integers(-3 * B, H + 3 * B + 1)),
+                 int(rng.integers(-3 * B, 9 * B + 1)))
+        r = int(rng.integers(1, 12 * B + 1))
+        ex = int(rng.integers(0, 21))
+        ey = int(rng.integers(0, 41))
+        ez = int(rng.integers(0, 41 - ey))
+        x0, x1, s0, s1, z0, z1 = LR.light_slab(B, H, bx, by, bz)
+        if rng.random() < 0.2:  # a light in the slab or just beside it
+            lz = int(rng.integers(z0 - 2, z1 + 3))
+            light = (int(rng.integers(x0 - 2, x1 + 3)), int(rng.integers(s0 - 2, s1 + 3)) - lz, lz)
+        dmin = int(rng.integers(-3 * B - 5, 21))
+        dmax = dmin + (0 if rng.random() < 0.2 else int(rng.integers(0, 3 * B + 21)))
+        px = x0 + int(rng.integers(-ex - 2, B + 3))
+        pz = int(rng.integers(z0 - dmax - 3, z1 - dmin + 4))
+        py = int(rng.integers(s0 - ey - ez - 3, s1 + 3)) - pz
+        cases.append((B, H, bx, by, bz, light, r, (px, py, pz, ex, ey, ez), (dmin, dmax)))
+    return cases
+
+
+def test_cull_slab_against_brute_force_over_a_random_sample(lightbox_exe):
+    cases = random_cases()
+    text = "\n".join(" ".join(str(v) for v in case_values(c)) for c in cases) + "\n"
+    answers = answers_of(subprocess.run([lightbox_exe], input=text, capture_output=True, text=True, timeout=60), len(cases))
+    seen = {"an empty piece": 0, "a non-empty piece": 0, "a bin at distance 0": 0, "a piece at distance 0": 0,
+            "bz = 0 and the light at negative z": 0, "a clipped last bin row": 0, "a view height that is no multiple of B": 0,
+            "a negative least depth": 0, "a single depth": 0, "depths wider than the bin": 0,
+            "a bin within reach whose record is not": 0}
+    for c, answer in zip(cases, answers):
+        B, H, bx, by, bz, light, r, rec, depths = c
+        slab = LR.light_slab(B, H, bx, by, bz)
+        l1 = LR.slab_l1(slab, *light)
+        piece = LR.slab_clip(slab, rec, *depths)
+        l1_piece = -1 if piece is None else LR.slab_l1(piece, *light)
+        # the header's functions and the Python restatement agree on the slab, its distance, the piece and its distance
+        assert answer == (*slab, l1, *(piece or (0,) * 6), l1_piece), c
+        # ... and both with the enumeration
+        points = list(bin_positions(B, H, bx, by, bz))
+        assert (min(p[0] for p in points), max(p[0] for p in points), min(p[1] + p[2] for p in points),
+                max(p[1] + p[2] for p in points), min(p[2] for p in points), max(p[2] for p in points)) == slab, c
+        assert l1 == nearest(points, light), c
+        shown = list(record_positions(B, H, bx, by, bz, rec, depths))
+        assert (piece is None) == (not shown), c
+        if piece is not None:
+            assert (min(p[0] for p in shown), max(p[0] for p in shown), min(p[1] + p[2] for p in shown),
+                    max(p[1] + p[2] for p in shown), min(p[2] for p in shown), max(p[2] for p in shown)) == piece, c
+            assert l1_piece == nearest(shown, light), c
+        assert LR.pair_culled(B, H, bx, by, bz, light, r) == (not l1 < r), c
+        in_range_rec = piece is not None and l1_piece < r
+        assert LR.pair_culled(B, H, bx, by, bz, light, r, [rec], depths) == (not (l1 < r and in_range_rec)), c
+        seen["an empty piece"] += piece is None
+        seen["a non-empty piece"] += piece is not None
+        seen["a bin at distance 0"] += l1 == 0
+        seen["a piece at distance 0"] += l1_piece == 0
+        seen["bz = 0 and the light at negative z"] += bz == 0 and light[2] < 0
+        seen["a clipped last bin row"] += by == (H - 1) // B and H % B != 0
+        seen["a view height that is no multiple of B"] += H % B != 0
+        seen["a negative least depth"] += depths[0] < 0
+        seen["a single depth"] += depths[0] == depths[1]
+        seen["depths wider than the bin"] += depths[1] - depths[0] >= B
+        seen["a bin within reach whose record is not"] += l1 < r and (piece is None or l1_piece >= r)
+    print(f"{len(cases)} random cases: {seen}")
+    for what, n in seen.items():
+        assert n > 0, f"the sample has no case with {what}"
