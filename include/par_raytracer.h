@@ -268,7 +268,14 @@ int par_relight_rows(par_context* ctx, int row_begin, int row_end, const par_out
 /* hipGraph path (BASELINE config 5): capture {pinned-host AABB/light upload -> build -> fill -> render} once, replay
  * per frame. `par_graph_stage` writes the next frame's AABBs/light into the pinned staging area the graph copies
  * from; it fails with PAR_ERR_UNSUPPORTED when the staged scene needs larger launch grids than were captured (about
- * twice the bin insertions of the captured frame): capture again then. */
+ * twice the bin insertions of the captured frame): capture again then. The staged AABBs are the context's scene from
+ * then on: a frame that is not a graph's (par_render*, par_pick) uploads them itself before it renders, on its own
+ * stream; as for any two frames on different streams, the caller orders it after a graph still in flight on another.
+ * A capture with PAR_RENDER_TRACE_BACKGROUND and no lit plane keeps the rays' results in a plane of the context that
+ * a capture cannot allocate: it returns PAR_ERR_NOT_READY unless a frame that is not a graph's was rendered or relit
+ * with that flag, without a lit plane and with at least as many rows before. This check comes after every other one,
+ * when the capture has begun: like any capture that fails then, it leaves no graph and no retained frame. A scene
+ * without entities (par_set_entities with n == 0) is captured, staged and launched like any other. */
 /* A context with more than one light (par_set_lights) cannot be captured: PAR_ERR_UNSUPPORTED. Two kinds of graph:
  * par_graph_capture's (the one-light path: the kernels of par_render_device with one light) and
  * par_graph_capture_lights's (the light path). Capturing either drops the graphs captured before; so does

@@ -79,10 +79,14 @@ struct par_context {
     // rewritten only after the event recorded behind set s's last launch. `stage_lo/hi`: entities changed since the
     // area last matched the host mirror.
     par_aabb* pin_aabbs[2] = {nullptr, nullptr};
+    int pin_aabbs_capacity[2] = {0, 0};  // entities each holds: they grow with aabb_capacity when a graph is captured
     par_lights_block* pin_lights[2] = {nullptr, nullptr};
     hipEvent_t ev_graph[2] = {nullptr, nullptr};
     bool ev_graph_pending[2] = {false, false};
     int stage_lo[2] = {0, 0}, stage_hi[2] = {0, 0};
+    // Entities par_graph_stage changed that d_aabbs does not hold yet: the next graph launch uploads the whole scene; a
+    // frame that is not a graph's uploads them itself first (its launches are sized by the staged scene).
+    int dev_lo = 0, dev_hi = 0;
     par_aabb* pin_update = nullptr;   // staging of par_update_aabbs_async
     int pin_update_capacity = 0;
     hipEvent_t ev_update = nullptr;   // its last copy
@@ -517,6 +521,11 @@ int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, 
     if (ctx->ev_update_pending && ctx->update_stream != stream && !graph_mode) {
         PAR_HIP(hipStreamWaitEvent(stream, ctx->ev_update, 0));
     }
+    if (ctx->dev_hi > ctx->dev_lo && !graph_mode) {  // staged for a graph, but this frame is none
+        PAR_HIP(hipMemcpyAsync(ctx->d_aabbs + ctx->dev_lo, ctx->book.aabbs.data() + ctx->dev_lo,
+                               (size_t)(ctx->dev_hi - ctx->dev_lo) * sizeof(par_aabb), hipMemcpyHostToDevice, stream));
+        ctx->dev_lo = ctx->dev_hi = 0;
+    }
     const par_bin_args b = make_bin_args(ctx, set, row_begin, row_end, flags);
     par_render_args r = make_render_args(ctx, set, row_begin, row_end, outs, flags, graph_mode);
     // (a timed frame keeps its kernels apart unless it is asked to time the launches as a production frame makes them)
@@ -833,6 +842,7 @@ static int par_set_entities_impl(par_context* ctx, const par_aabb* aabbs, const 
         PAR_HIP(hipMemcpy(ctx->d_sprite_ids, sprite_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     ctx->book.commit();
+    ctx->dev_lo = ctx->dev_hi = 0;
     ctx->n_entities = n;
     ctx->max_sprite_id = max_id;
     ctx->have_entities = true;
@@ -1165,8 +1175,9 @@ static int graph_capture(par_context* ctx, void* stream_v, int row_begin, int ro
     rc = ensure_room(ctx, ctx->book.capture());
     if (rc != PAR_OK) return rc;
     for (int s = 0; s < 2; s++) {
-        if (!ctx->pin_aabbs[s]) {
-            PAR_HIP(hipHostMalloc(&ctx->pin_aabbs[s], (size_t)std::max(ctx->aabb_capacity, 1) * sizeof(par_aabb), hipHostMallocDefault));
+        // (par_set_entities may have brought more entities since the last capture; no graph reads the area now)
+        if (ctx->pin_aabbs_capacity[s] < std::max(ctx->aabb_capacity, 1)) {
+            PAR_HIP(grow(&ctx->pin_aabbs[s], &ctx->pin_aabbs_capacity[s], std::max(ctx->aabb_capacity, 1), true));
         }
         if (!ctx->pin_lights[s]) PAR_HIP(hipHostMalloc(&ctx->pin_lights[s], sizeof(par_lights_block), hipHostMallocDefault));
         if (!ctx->ev_graph[s]) PAR_HIP(hipEventCreateWithFlags(&ctx->ev_graph[s], hipEventDisableTiming));
@@ -1181,8 +1192,11 @@ static int graph_capture(par_context* ctx, void* stream_v, int row_begin, int ro
     // ahead of every kernel of the frame).
     for (int s = 0; s < 2; s++) {
         PAR_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-        hipError_t e = hipMemcpyAsync(ctx->d_aabbs, ctx->pin_aabbs[s], (size_t)ctx->n_entities * sizeof(par_aabb),
-                                      hipMemcpyHostToDevice, stream);
+        hipError_t e = hipSuccess;
+        if (ctx->n_entities > 0) {  // (a copy of no bytes is no graph node: hipErrorInvalidValue)
+            e = hipMemcpyAsync(ctx->d_aabbs, ctx->pin_aabbs[s], (size_t)ctx->n_entities * sizeof(par_aabb),
+                               hipMemcpyHostToDevice, stream);
+        }
         if (e == hipSuccess) {
             e = hipMemcpyAsync(ctx->d_lights, ctx->pin_lights[s], sizeof(par_lights_block), hipMemcpyHostToDevice, stream);
         }
@@ -1227,6 +1241,11 @@ static int graph_stage(par_context* ctx, const par_aabb* aabbs, int first, int n
     ctx->book.commit();
     drop_retained(ctx);
     mark_staged(ctx, first, n);  // (the staging areas are brought up to date by par_graph_launch)
+    if (n > 0) {
+        const bool none = ctx->dev_hi <= ctx->dev_lo;
+        ctx->dev_lo = none ? first : std::min(ctx->dev_lo, first);
+        ctx->dev_hi = none ? first + n : std::max(ctx->dev_hi, first + n);
+    }
     if (n_lights > 0) set_lights(ctx, lights, n_lights, keep_count ? ctx->n_lights : n_lights);
     return PAR_OK;
 }
@@ -1268,6 +1287,7 @@ static int par_graph_launch_impl(par_context* ctx, void* stream) {
     }
     drop_retained(ctx);
     PAR_HIP(hipGraphLaunch(ctx->graph_exec[s], (hipStream_t)stream));
+    ctx->dev_lo = ctx->dev_hi = 0;  // (the graph's first node copies the whole scene)
     PAR_HIP(hipEventRecord(ctx->ev_graph[s], (hipStream_t)stream));
     ctx->ev_graph_pending[s] = true;
     ctx->set ^= 1;
