@@ -371,6 +371,48 @@ int par_tiles_assemble(const par_params* params, void* stream, const int32_t* d_
                        par_color* frame, int row_begin, int row_end);
 int par_scene_tile_map(const par_params* params, const int32_t* tiles, int n, int32_t* map, int capacity);
 
+/* --- palette output: a frame quantised to a fixed palette (nothing in the reference, which presents RGBA8) --------
+ * Several lights, ranged and tinted lights give a frame thousands of colours; an indexed-colour display, a GIF or a
+ * sprite sheet wants an index plane over a fixed, art-directed palette. These calls are a pass over a frame's `fb`
+ * plane, whatever made it (one light, the light path, a relit frame, a graph's, a frame assembled from row blocks).
+ * They take no context: retained frames, graphs and statistics are not involved and do not change.
+ * `fb`, `fb_out` and `index_out` address the element of (row_begin, column 0), as every plane does, and hold
+ * (row_end - row_begin) * width elements, dense and row-major; `palette` holds n_colors entries,
+ * 1 <= n_colors <= PAR_MAX_PALETTE. For the pixel {r, g, b, a} at column x and ABSOLUTE frame row y (row_begin + its
+ * row in the block, so a row block of a sharded frame dithers exactly as the whole frame does), in integers:
+ *     t   = B4[y & 3][x & 3],  B4 = {{0, 8, 2, 10}, {12, 4, 14, 6}, {3, 11, 1, 9}, {15, 7, 13, 5}}  (ordered dither)
+ *     off = floor(((2 * t - 15) * spread) / 32)     (towards minus infinity; spread == 0 gives 0 everywhere)
+ *     c'  = min(255, max(0, c + off))               for c = r, g, b
+ *     d_p = |r' - P[p].red| + |g' - P[p].green| + |b' - P[p].blue|   (L1, the metric of the reference's normalize;
+ *                                                    the alpha of the pixel and of the entries takes no part)
+ *     k   = the p with the smallest d_p, the lowest p among equals
+ *     index_out = (uint8_t)k                        when index_out is not NULL
+ *     fb_out    = {P[k].red, P[k].green, P[k].blue, a}   when fb_out is not NULL (the pixel's own alpha)
+ * Every pixel of the rows is processed, the background too. fb_out == fb (in place) is allowed; any other overlap of
+ * the arrays is undefined. PAR_ERR_INVALID_ARG, before any device work and with nothing written (no GPU is needed
+ * to get it), for a null `params`, palette or `fb`, both outputs null, n_colors outside [1, PAR_MAX_PALETTE], spread
+ * outside [0, 255], params->width <= 0, or rows that are not 0 <= row_begin < row_end <= params->height.
+ * Left out on purpose: no palette made from the image's content (median cut, k-means: the caller's art direction), no
+ * error-diffusion dithering (sequential by nature), no metric other than L1, no fusing into the render kernels, and no
+ * graph-capture helper (the device call is capturable as any stream-ordered launch is). */
+/* device pointers (`d_palette` too), asynchronous on `stream` (a hipStream_t), no sync: in a frame loop it goes on the
+ * frame's own stream, after the render or relight call */
+int par_quantize_device(const par_params* params, void* stream, const par_color* d_palette, int n_colors, int spread,
+                        const par_color* fb, int row_begin, int row_end, par_color* fb_out, uint8_t* index_out);
+/* host pointers, synchronous, everything on HIP device `device` (-1: the current device, as par_create): allocates,
+ * copies, launches, synchronises, copies back and frees; PAR_ERR_NO_DEVICE / PAR_ERR_OOM / PAR_ERR_HIP as par_create */
+int par_quantize_host(const par_params* params, int device, const par_color* palette, int n_colors, int spread,
+                      const par_color* fb, int row_begin, int row_end, par_color* fb_out, uint8_t* index_out);
+/* The natural output palette of a scene: every sprite-palette entry at `levels` brightness bands from ambient to
+ * full, then the background. Host arithmetic in integers, no GPU needed. With a = (int)(ambient * 255.f), for p in
+ * [0, palette_size) and k in [0, levels): s = a + ((255 - a) * k) / (levels - 1) and entry p * levels + k is
+ * {(red * s) / 255, (green * s) / 255, (blue * s) / 255, palette[p].alpha} (truncating divisions); the last entry is
+ * the colour par_background_fill writes, {ch, ch, ch, 0} with ch = (uint8_t)((float)background * ambient). Returns the
+ * entry count palette_size * levels + 1 (writes at most `capacity` entries), or a negative par_status: a null `params`
+ * or `out`, capacity < 0, levels outside [2, 255], a count above PAR_MAX_PALETTE, an ambient outside [0, 1] or a
+ * palette_size outside [1, PAR_MAX_PALETTE]. */
+int par_palette_ramp(const par_params* params, int levels, par_color* out, int capacity);
+
 /* Debug overlay of alt:763-772 (Bresenham line from the picked pixel to the light) drawn into a host frame. */
 void par_debug_line(const par_params* params, const par_pixel* pick, int mouse_x, const par_light* light,
                     par_color* fb);

@@ -41,6 +41,7 @@ ABI_SYMBOLS = (
     "par_render_device_slots", "par_row_block", "par_scene_tiles", "par_tiles_pack", "par_tiles_unpack",
     "par_background_fill", "par_tiles_assemble", "par_scene_tile_map", "par_set_lights", "par_graph_capture_lights",
     "par_graph_stage_lights", "par_set_light_model", "par_set_light_tints", "par_relight_device", "par_relight_rows",
+    "par_quantize_device", "par_quantize_host", "par_palette_ramp",
 )
 MAX_LIGHTS = 8  # PAR_MAX_LIGHTS
 LIGHTS_UNBOUNDED, LIGHTS_RANGED = 0, 1  # par_set_light_model
@@ -132,6 +133,9 @@ def lib():
         L.par_background_fill.argtypes = [vp, vp, vp, i32]
         L.par_tiles_assemble.argtypes = [vp, vp, vp, vp, vp, i32, i32]
         L.par_scene_tile_map.argtypes = [vp, vp, i32, vp, i32]
+        L.par_quantize_device.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, vp, vp]
+        L.par_quantize_host.argtypes = [vp, i32, vp, i32, i32, vp, i32, i32, vp, vp]
+        L.par_palette_ramp.argtypes = [vp, i32, vp, i32]
         L.par_debug_read_stamps.argtypes = [vp, vp, C.c_size_t]
         L.par_debug_set_hooks.argtypes = [vp, C.c_uint, i32]
         L.par_debug_read_light_walks.argtypes = [vp, vp]
@@ -471,3 +475,50 @@ def background_fill(params, rows_ptr, n_rows, stream=0):
     rc = lib().par_background_fill(C.byref(params), C.c_void_p(stream), C.c_void_p(rows_ptr), n_rows)
     if rc != PAR_OK:
         raise ParError(rc, "par_background_fill")
+
+
+# ---- palette output ----------------------------------------------------------------------------------------------
+
+def quantize(params, d_palette, n_colors, fb, rows, fb_out=None, index_out=None, spread=0, stream=0):
+    """Device pointers (ints): rows [rows[0], rows[1]) of the frame block at `fb` quantised to the n_colors entries at
+    d_palette (par_quantize_device: L1-nearest entry, lowest index among equals, 4x4 ordered dither of strength
+    `spread`) into the index plane at index_out and / or the RGBA plane at fb_out (fb_out == fb: in place).
+    Asynchronous on `stream`."""
+    rc = lib().par_quantize_device(C.byref(params), C.c_void_p(stream), C.c_void_p(d_palette), n_colors, spread,
+                                   C.c_void_p(fb), rows[0], rows[1], C.c_void_p(fb_out), C.c_void_p(index_out))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_quantize_device")
+
+
+def quantize_host(params, palette, fb, rows=None, spread=0, planes=("index",), device=-1):
+    """The same on host arrays (par_quantize_host): `palette` and `fb` are COLOR arrays, fb the rows `rows` (default:
+    the whole frame). Returns {"index": uint8 array, "fb": COLOR array} for the planes asked for."""
+    r0, r1 = rows or (0, params.height)
+    palette = np.ascontiguousarray(palette, dtype=COLOR).reshape(-1)
+    fb = np.ascontiguousarray(fb, dtype=COLOR).reshape(-1)
+    n = (r1 - r0) * params.width
+    if len(fb) != n:
+        raise ValueError(f"quantize_host: fb holds {len(fb)} pixels, rows {r0}..{r1} of width {params.width} hold {n}")
+    unknown = set(planes) - {"index", "fb"}
+    if unknown:
+        raise ValueError(f"quantize_host: unknown planes {sorted(unknown)}")
+    out = {}
+    if "index" in planes:
+        out["index"] = np.zeros(n, dtype=np.uint8)
+    if "fb" in planes:
+        out["fb"] = np.zeros(n, dtype=COLOR)
+    rc = lib().par_quantize_host(C.byref(params), device, ptr(palette), len(palette), spread, ptr(fb), r0, r1,
+                                 ptr(out.get("fb")), ptr(out.get("index")))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_quantize_host")
+    return out
+
+
+def palette_ramp(params, levels):
+    """The natural output palette of a scene (par_palette_ramp): every sprite-palette entry at `levels` brightness bands
+    from ambient to full, then the background; a COLOR array of palette_size * levels + 1 entries."""
+    out = np.zeros(T.MAX_PALETTE, dtype=COLOR)
+    n = lib().par_palette_ramp(C.byref(params), levels, ptr(out), len(out))
+    if n < 0:
+        raise ParError(-n, "par_palette_ramp")
+    return out[:n].copy()

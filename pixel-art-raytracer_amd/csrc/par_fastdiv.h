@@ -33,4 +33,24 @@ __device__ __forceinline__ float par_fast_rcp(float t) {
     return (at > 0.0f && at < __builtin_inff()) ? y1 : y;
 }
 
+// n / d for a wave-uniform divisor the host knows at launch: one v_mul_hi_u32 and one shift, exact for every
+// n < 2^31 and 1 <= d < 2^31. With l = ceil(log2 d) and mul = ceil(2^(31 + l) / d) = (2^(31 + l) + e) / d, 0 <= e < d:
+// n * mul / 2^(31 + l) = n / d + n * e / (d * 2^(31 + l)), and the second term is below 1 / d because n < 2^31 and
+// e < d <= 2^l, so the floor is floor(n / d). mul < 2^32 because d > 2^(l - 1). d == 1 has no such mul: mul == 0
+// stands for "the quotient is n".
+struct par_udiv31 {
+    uint32_t mul, shift;
+};
+
+inline par_udiv31 par_udiv31_make(uint32_t d) {
+    if (d <= 1) return par_udiv31{0, 0};
+    uint32_t l = 0;
+    while ((1ull << l) < d) l++;
+    return par_udiv31{(uint32_t)(((1ull << (31 + l)) + d - 1) / d), l - 1};
+}
+
+__device__ __forceinline__ uint32_t par_udiv31_quotient(uint32_t n, par_udiv31 by) {
+    return by.mul ? __umulhi(n, by.mul) >> by.shift : n;
+}
+
 #endif

@@ -7,12 +7,18 @@
 // alt:815-817.
 //
 //   par_demo [--keys RRRRUUUUhhhhjjPP] [--frames N] [--out DIR] [--gif FILE] [--debug-line] [--as-sdl] [--size W H L]
+//            [--palette-levels K] [--dither S]
 //
 // --gif writes the frames as one animated GIF89a (100 ms per frame like the reference's gif.gif); a frame's colours
 // are palette entries times a brightness, at most a few hundred distinct values, so each frame gets an exact local
 // colour table (frames with more than 256 colours fall back to a 3-3-2 bit table). --as-sdl shows the frame as the
 // reference's window does: its SDL_PIXELFORMAT_RGB888 texture reads the struct's `red` byte as blue on little-endian
 // machines (alt:613, 772: the debug line comes out blue).
+//
+// --palette-levels K (with --gif) quantises every frame of the GIF on the GPU (par_quantize_host) to the scene's own
+// palette, par_palette_ramp(params, K): each sprite-palette entry at K brightness bands, then the background. That
+// palette is every frame's local colour table and the index plane is written as it comes back; --dither S (0..255) adds
+// the ordered dither. The PPM frames of --out stay unquantised.
 //
 // Letters: R L U D P N = right, left, up, down, page-up, page-down; a k j u h o as in the reference. Frame 0 gets no
 // key; frame k applies key k-1 (cycling when --frames exceeds the script).
@@ -109,6 +115,21 @@ class GifWriter {
             }
         }
         table.resize(256 * 3, 0);
+        image(pix, table, delay_cs);
+    }
+    // an index plane over a fixed palette of at most 256 entries: the palette, padded to 256, is the local colour table
+    void frame(const std::vector<unsigned char>& index, const std::vector<par_color>& palette, int delay_cs) {
+        std::vector<unsigned char> table;
+        for (const par_color& c : palette) { table.push_back(c.red); table.push_back(c.green); table.push_back(c.blue); }
+        table.resize(256 * 3, 0);
+        image(index, table, delay_cs);
+    }
+    void close() {
+        if (f_) { std::fputc(0x3B, f_); std::fclose(f_); f_ = nullptr; }
+    }
+
+  private:
+    void image(const std::vector<unsigned char>& pix, const std::vector<unsigned char>& table, int delay_cs) {
         const unsigned char gce[] = {0x21, 0xF9, 4, 0, (unsigned char)(delay_cs & 0xFF), (unsigned char)(delay_cs >> 8), 0, 0};
         std::fwrite(gce, 1, sizeof(gce), f_);
         std::fputc(0x2C, f_);
@@ -117,11 +138,6 @@ class GifWriter {
         std::fwrite(table.data(), 1, table.size(), f_);
         lzw(pix);
     }
-    void close() {
-        if (f_) { std::fputc(0x3B, f_); std::fclose(f_); f_ = nullptr; }
-    }
-
-  private:
     void put16(int v) { std::fputc(v & 0xFF, f_); std::fputc((v >> 8) & 0xFF, f_); }
     void emit(unsigned code, int bits) {
         acc_ |= (uint64_t)code << nacc_;
@@ -178,7 +194,7 @@ class GifWriter {
 
 int main(int argc, char** argv) {
     std::string keys = "RRRRUUUUhhhhjjPP", out_dir, gif_path;
-    int frames = -1, W = 480, H = 320, L = 320;
+    int frames = -1, W = 480, H = 320, L = 320, palette_levels = 0, dither = 0;
     bool debug_line = false, as_sdl = false;
     for (int i = 1; i < argc; i++) {
         if (!std::strcmp(argv[i], "--keys") && i + 1 < argc) keys = argv[++i];
@@ -187,6 +203,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--gif") && i + 1 < argc) gif_path = argv[++i];
         else if (!std::strcmp(argv[i], "--debug-line")) debug_line = true;
         else if (!std::strcmp(argv[i], "--as-sdl")) as_sdl = true;
+        else if (!std::strcmp(argv[i], "--palette-levels") && i + 1 < argc) palette_levels = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--dither") && i + 1 < argc) dither = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--size") && i + 3 < argc) { W = std::atoi(argv[++i]); H = std::atoi(argv[++i]); L = std::atoi(argv[++i]); }
         else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
@@ -216,6 +234,16 @@ int main(int argc, char** argv) {
     std::vector<par_color> fb((size_t)W * H);
     std::vector<par_pixel> gbuf((size_t)W * H);
     std::vector<unsigned char> rgb((size_t)W * H * 3);
+    // --palette-levels: the GIF's frames are index planes over the scene's ramp
+    std::vector<par_color> ramp;
+    std::vector<unsigned char> index;
+    if (palette_levels != 0 && !gif_path.empty()) {
+        ramp.resize(PAR_MAX_PALETTE);
+        const int n_ramp = par_palette_ramp(&params, palette_levels, ramp.data(), (int)ramp.size());
+        if (n_ramp < 0) { std::fprintf(stderr, "--palette-levels %d: %s\n", palette_levels, par_status_string(-n_ramp)); return 2; }
+        ramp.resize((size_t)n_ramp);
+        index.resize((size_t)W * H);
+    }
     GifWriter gif;
     if (!gif_path.empty() && !gif.open(gif_path, W, H)) { std::fprintf(stderr, "cannot write %s\n", gif_path.c_str()); return 1; }
     const int mouse_x = 0, mouse_y = 0;  // the reference's mouse position before any motion event (alt:133-134)
@@ -243,7 +271,13 @@ int main(int argc, char** argv) {
             std::snprintf(name, sizeof(name), "/frame_%03d.ppm", f);
             if (!write_ppm(out_dir + name, fb.data(), W, H)) { std::fprintf(stderr, "cannot write %s%s\n", out_dir.c_str(), name); return 1; }
         }
-        if (!gif_path.empty()) {
+        if (!ramp.empty()) {
+            if ((rc = par_quantize_host(&params, 0, ramp.data(), (int)ramp.size(), dither, fb.data(), 0, H, nullptr, index.data())) != PAR_OK) {
+                std::fprintf(stderr, "par_quantize_host: %s\n", par_status_string(rc));
+                return 1;
+            }
+            gif.frame(index, ramp, 10);
+        } else if (!gif_path.empty()) {
             for (size_t i = 0; i < fb.size(); i++) { rgb[i * 3] = fb[i].red; rgb[i * 3 + 1] = fb[i].green; rgb[i * 3 + 2] = fb[i].blue; }
             gif.frame(rgb, 10);  // 100 ms per frame, as the reference's gif.gif
         }
