@@ -17,17 +17,6 @@
 #include "par_book.h"
 #include "par_internal.h"
 
-// The staged lights of a captured graph: par_lights_dyn, then the lights' radii (read by the ranged light kernels
-// alone) and their tints (read by the tinted ones alone), padded to a whole number of 64-byte lines; the graph's copy
-// node copies the whole block. A one-light graph's kernels read their par_frame_dyn from lights.l[0].
-struct par_lights_block {
-    par_lights_dyn lights;
-    par_light_radii radii;
-    par_light_tints tints;
-    int32_t pad_[(384 - sizeof(par_lights_dyn) - sizeof(par_light_radii) - sizeof(par_light_tints)) / sizeof(int32_t)];
-};
-static_assert(sizeof(par_lights_block) == 384, "lights staging block");
-
 struct par_context {
     par_params params{};
     int device = 0;
@@ -424,28 +413,30 @@ bool lights_path(const par_context* c) {
     return c->n_lights > 1 || ranged(c) || c->tinted || (c->hooks & PAR_HOOK_LIGHTS_PATH);
 }
 
-par_lights_dyn make_lights_dyn(const par_context* c) {
-    par_lights_dyn lights{};
-    lights.n = c->n_lights;
-    for (int l = 0; l < c->n_lights; l++) lights.l[l] = make_dyn(c, c->lights[l]);
-    return lights;
+// The context's lights as they are now: positions and bins, radii (<= 0: unbounded; the lights the context does not have
+// read as that) and tints.
+par_lights_block make_lights_block(const par_context* c) {
+    par_lights_block b{};
+    b.lights.n = c->n_lights;
+    for (int l = 0; l < c->n_lights; l++) {
+        b.lights.l[l] = make_dyn(c, c->lights[l]);
+        b.radii.r[l] = c->lights[l].radius;
+    }
+    b.radii.depth_min = c->depth_min;
+    b.radii.depth_max = c->depth_max;
+    b.tints = c->tints;
+    return b;
 }
 
-// Their radii for the ranged light kernels (<= 0: unbounded; the lights the context does not have read as that).
-par_light_radii make_light_radii(const par_context* c) {
-    par_light_radii radii{};
-    for (int l = 0; l < c->n_lights; l++) radii.r[l] = c->lights[l].radius;
-    radii.depth_min = c->depth_min;
-    radii.depth_max = c->depth_max;
-    return radii;
+// What the light kernels of a frame enqueued now read: a ranged context (PAR_LIGHTS_RANGED) takes the ranged kernels, a
+// tinted one (par_set_light_tints) the tinted light kernel, and in graph mode they read the lights from d_lights, which
+// the graph's copy node fills before them.
+par_light_state make_light_state(const par_context* c, bool graph_mode) {
+    return {make_lights_block(c), ranged(c), c->tinted, graph_mode ? c->d_lights : nullptr};
 }
 
 // Staging area `s` of the captured graphs: the context's lights as they are now.
-void stage_lights(par_context* c, int s) {
-    c->pin_lights[s]->lights = make_lights_dyn(c);
-    c->pin_lights[s]->radii = make_light_radii(c);
-    c->pin_lights[s]->tints = c->tints;
-}
+void stage_lights(par_context* c, int s) { *c->pin_lights[s] = make_lights_block(c); }
 
 // The hash build: small scenes in one launch, large ones in two (and frames that keep their kernels `apart`, and the
 // test hook). `fa`, `fill`: the share of the background fill that rides along, if any.
@@ -472,25 +463,17 @@ int enqueue_build(par_context* ctx, hipStream_t stream, const par_bin_args& b, i
 // kernel, with the tints behind them.
 int enqueue_lights_frame(par_context* ctx, hipStream_t stream, const par_bin_args& b, const par_render_args& r,
                          const par_bound& bound, bool graph_mode, bool apart, hipEvent_t* ev) {
-    const par_lights_dyn lights = make_lights_dyn(ctx);
-    const par_lights_dyn* d_lights = graph_mode ? &ctx->d_lights->lights : nullptr;
-    const par_light_radii radii_v = make_light_radii(ctx);
-    const par_light_radii* radii = ranged(ctx) ? &radii_v : nullptr;
-    const par_light_radii* d_radii = graph_mode ? &ctx->d_lights->radii : nullptr;
-    const par_light_tints* tints = ctx->tinted ? &ctx->tints : nullptr;
-    const par_light_tints* d_tints = graph_mode ? &ctx->d_lights->tints : nullptr;
+    const par_light_state lights = make_light_state(ctx, graph_mode);
     const int rc = enqueue_build(ctx, stream, b, bound.pairs, &r, nullptr, apart);
     if (rc != PAR_OK) return rc;
     if (ev) {
         PAR_HIP(hipEventRecord(ev[EV_BUILT], stream));
         PAR_HIP(hipEventRecord(ev[EV_COLUMNS], stream));
     }
-    if (r.trace_bg) {
-        PAR_HIP(par_launch_bglights(ctx->grid, r, lights, d_lights, radii, d_radii, stream));
-    }
+    if (r.trace_bg) PAR_HIP(par_launch_bglights(ctx->grid, r, lights, stream));
     PAR_HIP(par_launch_fill(ctx->grid, r, stream));
     if (ev) PAR_HIP(hipEventRecord(ev[EV_FILLED], stream));
-    PAR_HIP(par_launch_render_lights(ctx->grid, r, lights, d_lights, radii, d_radii, tints, d_tints, bound.cols, stream));
+    PAR_HIP(par_launch_render_lights(ctx->grid, r, lights, bound.cols, stream));
     if (ev) {
         PAR_HIP(hipEventRecord(ev[EV_ITEMS], stream));
         PAR_HIP(hipEventRecord(ev[EV_RENDERED], stream));
@@ -1096,20 +1079,17 @@ static int enqueue_relight(par_context* ctx, hipStream_t stream, int row_begin, 
         outs.lit = ctx->d_scratch_lit;
     }
     const par_render_args r = make_render_args(ctx, ctx->kept.set, row_begin, row_end, outs, flags, false);
-    const par_lights_dyn lights = make_lights_dyn(ctx);
-    const par_light_radii radii_v = make_light_radii(ctx);
-    const par_light_radii* radii = ranged(ctx) ? &radii_v : nullptr;
-    const par_light_tints* tints = ctx->tinted ? &ctx->tints : nullptr;
+    const par_light_state lights = make_light_state(ctx, false);
     if (flags & PAR_RENDER_COUNT_RAYS) {
         PAR_HIP(hipMemsetAsync(ctx->d_ray_counter, 0, 3 * sizeof(unsigned long long), stream));
     }
-    if (r.trace_bg) PAR_HIP(par_launch_bglights(ctx->grid, r, lights, nullptr, radii, nullptr, stream));
+    if (r.trace_bg) PAR_HIP(par_launch_bglights(ctx->grid, r, lights, stream));
     PAR_HIP(par_launch_fill(ctx->grid, r, stream));
     // the column list is the retained frame's: bounded as its launch was, by its rows
     const int B = ctx->params.bin_size;
     const int64_t kept_cols = (int64_t)ctx->gx * ((ctx->kept.r1 - 1) / B - ctx->kept.r0 / B + 1);
     const int64_t cols = std::min(ctx->book.frame_bounds(false).cols, kept_cols);
-    PAR_HIP(par_launch_relight(ctx->grid, r, gbuf, lights, radii, tints, cols, stream));
+    PAR_HIP(par_launch_relight(ctx->grid, r, gbuf, lights, cols, stream));
     ctx->last_flags = flags;
     return PAR_OK;
 }

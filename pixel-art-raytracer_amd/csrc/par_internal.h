@@ -136,6 +136,25 @@ struct par_light_tints {
     float t[PAR_MAX_LIGHTS][3];  // r, g, b
 };
 
+// The three together, as the light path stages them for a captured graph, padded to a whole number of 64-byte lines;
+// the graph's copy node copies the whole block. A one-light graph's kernels read their par_frame_dyn from lights.l[0].
+struct par_lights_block {
+    par_lights_dyn lights;
+    par_light_radii radii;
+    par_light_tints tints;
+    int32_t pad_[(384 - sizeof(par_lights_dyn) - sizeof(par_light_radii) - sizeof(par_light_tints)) / sizeof(int32_t)];
+};
+static_assert(sizeof(par_lights_block) == 384, "lights staging block");
+
+// What a frame's light kernels read, and so which of them run: the context's lights as they are now, whether the ranged
+// and the tinted forms are wanted, and, for a captured graph's kernels (the graph form), the device block they read
+// &dev->lights, &dev->radii and &dev->tints from instead of `block`.
+struct par_light_state {
+    par_lights_block block;
+    bool ranged, tinted;
+    const par_lights_block* dev;  // null: the by-value forms
+};
+
 // Render flags that make the render launch use its instrumented variant (ray counting and the time stamps, bit 29);
 // a production frame has neither and runs kernels compiled without them.
 constexpr uint32_t PAR_DEBUG_FLAGS = PAR_RENDER_COUNT_RAYS | (1u << 29);
@@ -282,29 +301,21 @@ hipError_t par_launch_render_overflow(const par_grid_dev& g, const par_render_ar
 // A frame with several lights (or one, forced by a test hook): after the hash build, every occupied column of col_list
 // in one launch of render_lights_kernel (`column_bound` as for par_launch_columns). The column, item, tile and overflow
 // kernels do not run.
-// The kernels take `lights` as a kernel argument, or, when `d_lights` is not null (a captured graph), read the frame's
-// lights from that device memory (a copy node of the graph fills it before them), once per workgroup, so one graph
-// serves any count of lights. `radii` null: the unbounded kernels; else the ranged ones (PAR_LIGHTS_RANGED), which take
-// the radii as an argument too or, with `d_lights`, read them from `d_radii`. Under PAR_RENDER_COUNT_RAYS the ranged
-// light kernel also adds the (start bin, light) pairs it walked and culled to a.ray_counter[1] and [2]. `tints` null:
-// the untinted kernels; else the tinted ones (par_set_light_tints), which take the tints in the same way (`d_tints`).
-hipError_t par_launch_render_lights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,
-                                    const par_lights_dyn* d_lights, const par_light_radii* radii,
-                                    const par_light_radii* d_radii, const par_light_tints* tints,
-                                    const par_light_tints* d_tints, int64_t column_bound, hipStream_t stream);
+// `s`: the frame's light state (par_light_state), which names the kernels' form. Under PAR_RENDER_COUNT_RAYS the ranged
+// light kernel also adds the (start bin, light) pairs it walked and culled to a.ray_counter[1] and [2].
+hipError_t par_launch_render_lights(const par_grid_dev& g, const par_render_args& a, const par_light_state& s,
+                                    int64_t column_bound, hipStream_t stream);
 // A relit frame (par_relight_device): the relight form of the light kernel over the column list the retained frame's
 // hash build left, reading that frame's G-buffer plane `gbuf` (device memory, addressing (a.row_begin, 0)) where the
 // kernel above runs its primary pass. `a.count` is the retained frame's set; a.out.gbuf and a.out.palidx are not
-// written. Lights, radii and tints by value (there is no graph form); `column_bound` bounds the retained frame's
-// columns.
+// written. The light state by value (there is no graph form: s.dev is not read); `column_bound` bounds the retained
+// frame's columns.
 hipError_t par_launch_relight(const par_grid_dev& g, const par_render_args& a, const par_pixel* gbuf,
-                              const par_lights_dyn& lights, const par_light_radii* radii, const par_light_tints* tints,
-                              int64_t column_bound, hipStream_t stream);
+                              const par_light_state& s, int64_t column_bound, hipStream_t stream);
 // The background rays of such a frame (one per x and light, bit l of g.bglit[x] for light l); par_launch_fill then
-// copies them into the lit plane. `lights`, `d_lights`, `radii`, `d_radii` as above.
-hipError_t par_launch_bglights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,
-                               const par_lights_dyn* d_lights, const par_light_radii* radii,
-                               const par_light_radii* d_radii, hipStream_t stream);
+// copies them into the lit plane. `s` as above (the tints are not read).
+hipError_t par_launch_bglights(const par_grid_dev& g, const par_render_args& a, const par_light_state& s,
+                               hipStream_t stream);
 
 // Sharded frames: tiles between a frame block and packed slots, and the background colour for whole rows.
 hipError_t par_launch_tiles_copy(bool pack, const int32_t* d_tiles, int n, int W, int H, int B, int row_begin, int row_end,

@@ -37,6 +37,7 @@
 #include <limits.h>
 
 #include <algorithm>
+#include <tuple>
 #include <type_traits>
 
 namespace {
@@ -2258,28 +2259,27 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_both_kernel(par_grid_
 //      then per light the slab tests of the recorded walk of the pixel's start bin, or lane_shadow_walk where there is
 //      none (the start bin holds no primitive, or its walk did not fit), and the shading of the contract in
 //      par_raytracer.h (par_set_lights). Each walk is done once per column and light.
-// Two instantiations: the lights as a kernel argument (direct frames), or read from device memory once per workgroup
-// into LDS (a captured graph, whose copy node uploads them before the frame): frame_lights.
-// Each of them again in a RANGED form (PAR_LIGHTS_RANGED, the contract beside par_set_light_model), which takes the
-// lights' radii as one more argument (frame_radii) and differs in two places:
-//   A. a (start bin, light) pair is not walked when no pixel in range of the light can start in that bin: by the bin
-//      alone, then by what the column's slot records can show in it (par_lightbox.h). It is marked as a recorded
-//      walk of zero records, and the pairs that are left are dealt to the wavefronts;
-//   B. per pixel and light the range test comes first -- out of range: no slab tests, no lane walk, no bit, no ray
-//      counted -- and a ranged light's diffuse term is weighted by 1 - len / r. The per-pixel test alone decides a
-//      pixel: the cull only skips walks whose records no pixel in range would read.
-// The unbounded instantiations have no such argument, LDS or code (`if constexpr`).
-// And each of the four again in a TINTED form (par_set_light_tints, the contract beside it), which takes the lights'
-// colours as its last argument (frame_tints) and differs in B alone: three running sums instead of one, a lit light's
-// term times its tint's three components, and a factor per channel for the quantise. A light's three components are
-// read inside the light loop, wave-uniform as its radius is: from the kernarg segment in direct frames (scalar loads
-// at a dynamic offset; the ranged by-value form has no SGPRs to hold all 24 in), from LDS in the graph form. The
-// untinted instantiations have none of it.
-// And the four by-value forms again in a RELIGHT form (par_relight_device, the contract beside it), whose last extra
-// is the G-buffer plane of the retained frame (RelightSrc). It runs over the column list and the hash that frame's
-// build left, skips the columns outside the relit rows, does phase A as above under the lights of now, and in phase B
-// reads its pixel's texel (gbuf_texel) where the others run the primary pass; then the same light loop. It stores fb,
-// brightness and lit only. The other instantiations have none of it.
+// Four booleans name the form (they shape the arguments behind g and a: LightArgs, below; `if constexpr` the code):
+//   GRAPH    argument: pointers instead of values. LDS: a copy of what they point to, read once per workgroup
+//            (frame_state). Code: none besides. A captured graph, whose copy node uploads the lights before the frame.
+//   RANGED   argument: the lights' radii (PAR_LIGHTS_RANGED, the contract beside par_set_light_model). LDS: LightLive.
+//            A: a (start bin, light) pair is not walked when no pixel in range of the light can start in that bin: by
+//            the bin alone, then by what the column's slot records can show in it (par_lightbox.h). It is marked as a
+//            recorded walk of zero records, and the pairs that are left are dealt to the wavefronts.
+//            B: per pixel and light the range test comes first -- out of range: no slab tests, no lane walk, no bit, no
+//            ray counted -- and a ranged light's diffuse term is weighted by 1 - len / r. The per-pixel test alone
+//            decides a pixel: the cull only skips walks whose records no pixel in range would read.
+//   TINTED   argument: the lights' colours (par_set_light_tints, the contract beside it). LDS: none of its own.
+//            B alone: three running sums instead of one, a lit light's term times its tint's three components, and a
+//            factor per channel for the quantise. A light's three components are read inside the light loop,
+//            wave-uniform as its radius is: from the kernarg segment in direct frames (scalar loads at a dynamic
+//            offset; the ranged by-value form has no SGPRs to hold all 24 in), from LDS in the graph form.
+//   RELIGHT  argument: the G-buffer plane of the retained frame (par_relight_device, the contract beside it). LDS:
+//            none. It runs over the column list and the hash that frame's build left, skips the columns outside the
+//            relit rows, does phase A as above under the lights of now, and in phase B reads its pixel's texel
+//            (gbuf_texel) where the others run the primary pass; then the same light loop. It stores fb, brightness
+//            and lit only. By value alone: there is no relit graph form.
+// A form without a boolean has none of its argument, LDS or code.
 // ------------------------------------------------------------------------------------------------------------
 constexpr int PAR_LIGHT_NB = 64;      // occupied bins of a column whose walks are recorded (the others: lane walks)
 constexpr int PAR_LIGHT_WALK = 1024;  // occluder records of all walks of a column (16 KiB)
@@ -2295,63 +2295,52 @@ struct LightCol {  // LDS of one workgroup of render_lights_kernel
 };
 static_assert(PAR_LIGHT_WALK <= 32767 && PAR_MAX_LIGHTS <= 8, "int16 walk offsets, one lit bit per light");
 
-// The lights a light kernel reads: its kernel argument (direct frames), or the frame's lights in device memory, where
-// the copy node of a captured graph leaves them, read once per workgroup into LDS (one dword per thread, then one
-// barrier). There n is clamped to [1, PAR_MAX_LIGHTS]: the kernel's LDS arrays are sized by it.
-__device__ __forceinline__ const par_lights_dyn& frame_lights(const par_lights_dyn& lights) { return lights; }
-__device__ __forceinline__ const par_lights_dyn& frame_lights(const par_lights_dyn* src) {
-    __shared__ par_lights_dyn sl;
-    constexpr int N = (int)(sizeof(par_lights_dyn) / sizeof(int32_t));
-    static_assert(sizeof(par_lights_dyn) % sizeof(int32_t) == 0 && N <= 256, "one dword per thread of a workgroup");
+// What a light kernel reads of the frame's light state, behind g and a: the lights, then the radii (RANGED), the tints
+// (TINTED) and the retained frame's G-buffer plane (RELIGHT; device memory that addresses (a.row_begin, 0)) of the forms
+// that have them -- by value (direct frames), or, GRAPH, as pointers to the device memory where the copy node of a
+// captured graph leaves them. An argument each (in one struct they would be other code: the by-value forms index the
+// radii and the tints from a base address of their own), so the list is a pack, and this its type.
+template <bool GRAPH, class T>
+using LightArg = std::conditional_t<GRAPH, const T*, T>;
+template <bool PRESENT, class T>
+using LightArgIf = std::conditional_t<PRESENT, std::tuple<T>, std::tuple<>>;
+template <bool GRAPH, bool RANGED, bool TINTED, bool RELIGHT>
+using LightArgs = decltype(std::tuple_cat(std::tuple<LightArg<GRAPH, par_lights_dyn>>{},
+                                          LightArgIf<RANGED, LightArg<GRAPH, par_light_radii>>{},
+                                          LightArgIf<TINTED, LightArg<GRAPH, par_light_tints>>{},
+                                          LightArgIf<RELIGHT, const par_pixel*>{}));
+
+// A piece of the light state as the kernel reads it: the kernel argument itself, or what it points to, read once per
+// workgroup into LDS (one dword per thread, then one barrier). There the lights' n is clamped to
+// [1, PAR_MAX_LIGHTS]: the kernel's LDS arrays are sized by it.
+template <class T>
+__device__ __forceinline__ const T& frame_state(const T& arg) {
+    return arg;
+}
+template <class T>
+__device__ __forceinline__ const T& frame_state(const T* src) {
+    __shared__ T s;
+    constexpr int N = (int)(sizeof(T) / sizeof(int32_t));
+    static_assert(sizeof(T) % sizeof(int32_t) == 0 && N <= 256, "one dword per thread of a workgroup");
     const int t = (int)threadIdx.x;
-    if (t == 0) {
-        sl.n = min(max(src->n, 1), PAR_MAX_LIGHTS);
-    } else if (t < N) {
-        reinterpret_cast<int32_t*>(&sl)[t] = reinterpret_cast<const int32_t*>(src)[t];
-    }
-    __syncthreads();
-    return sl;
-}
-
-// The radii a RANGED light kernel reads, as frame_lights hands out the lights: its kernel argument, or the device
-// memory behind the graph's lights, read once per workgroup into LDS. The unbounded kernels have none.
-struct NoRadii {};
-__device__ __forceinline__ NoRadii frame_radii() { return NoRadii{}; }
-__device__ __forceinline__ const par_light_radii& frame_radii(const par_light_radii& radii) { return radii; }
-__device__ __forceinline__ const par_light_radii& frame_radii(const par_light_radii* src) {
-    __shared__ par_light_radii sr;
-    constexpr int N = (int)(sizeof(par_light_radii) / sizeof(int32_t));
-    if ((int)threadIdx.x < N) reinterpret_cast<int32_t*>(&sr)[threadIdx.x] = reinterpret_cast<const int32_t*>(src)[threadIdx.x];
-    __syncthreads();
-    return sr;
-}
-
-// The same with the kernel's other extra behind the radii (the tints, which frame_tints hands out), or with the tints
-// alone (an unbounded, tinted kernel).
-__device__ __forceinline__ NoRadii frame_radii(const par_light_tints&) { return NoRadii{}; }
-__device__ __forceinline__ NoRadii frame_radii(const par_light_tints*) { return NoRadii{}; }
-template <class R, class Tn>
-__device__ __forceinline__ const par_light_radii& frame_radii(const R& radii, const Tn&) {
-    return frame_radii(radii);
-}
-
-// The tints a TINTED light kernel reads, the last of its extras: its kernel argument, or the device memory behind the
-// graph's radii, read once per workgroup into LDS. The untinted kernels have none.
-struct NoTints {};
-__device__ __forceinline__ NoTints frame_tints() { return NoTints{}; }
-template <class First, class... Rest>
-__device__ __forceinline__ decltype(auto) frame_tints(const First& first, const Rest&... rest) {
-    if constexpr (std::is_same_v<First, par_light_tints>) {
-        return (first);
-    } else if constexpr (std::is_same_v<First, const par_light_tints*>) {
-        __shared__ par_light_tints st;
-        constexpr int N = (int)(sizeof(par_light_tints) / sizeof(float));
-        if ((int)threadIdx.x < N) reinterpret_cast<float*>(&st)[threadIdx.x] = reinterpret_cast<const float*>(first)[threadIdx.x];
-        __syncthreads();
-        return (const_cast<const par_light_tints&>(st));
+    if constexpr (std::is_same_v<T, par_lights_dyn>) {
+        if (t == 0) {
+            s.n = min(max(src->n, 1), PAR_MAX_LIGHTS);
+        } else if (t < N) {
+            reinterpret_cast<int32_t*>(&s)[t] = reinterpret_cast<const int32_t*>(src)[t];
+        }
     } else {
-        return frame_tints(rest...);
+        if (t < N) reinterpret_cast<int32_t*>(&s)[t] = reinterpret_cast<const int32_t*>(src)[t];
     }
+    __syncthreads();
+    return s;
+}
+// Argument I of a light kernel's pack as the kernel reads it; I < 0, the form has none: nothing at all.
+struct NoLightArg {};
+template <int I, class... Args>
+__device__ __forceinline__ decltype(auto) frame_arg(const Args&... args) {
+    if constexpr (I < 0) return NoLightArg{};
+    else return frame_state(std::get<I>(std::tie(args...)));
 }
 // A value per colour channel in the TINTED light kernel; nothing at all in the others.
 template <bool TINTED>
@@ -2360,10 +2349,6 @@ template <>
 struct LightRgb<true> {
     float r = 0.f, g = 0.f, b = 0.f;
 };
-template <class T>
-constexpr bool is_light_radii = std::is_same_v<T, par_light_radii> || std::is_same_v<T, const par_light_radii*>;
-template <class T>
-constexpr bool is_light_tints = std::is_same_v<T, par_light_tints> || std::is_same_v<T, const par_light_tints*>;
 
 // The L1 length of light - world as light_dir forms it (alt:712-714, spr:28-35): three differences of integers and
 // their sum, exact in fp32 for every view the library accepts.
@@ -2380,26 +2365,6 @@ struct LightLive {
 __device__ __forceinline__ LightLive& light_live() {
     __shared__ LightLive lv;
     return lv;
-}
-
-// The relight form's last extra (par_relight_device): the G-buffer plane of the retained frame, device memory that
-// addresses (a.row_begin, 0). frame_radii and frame_tints look past it.
-struct RelightSrc {
-    const par_pixel* gbuf;
-};
-__device__ __forceinline__ NoRadii frame_radii(const RelightSrc&) { return NoRadii{}; }
-__device__ __forceinline__ NoRadii frame_radii(const par_light_tints&, const RelightSrc&) { return NoRadii{}; }
-template <class R, class Tn>
-__device__ __forceinline__ const par_light_radii& frame_radii(const R& radii, const Tn&, const RelightSrc&) {
-    return frame_radii(radii);
-}
-template <class First, class... Rest>
-__device__ __forceinline__ const RelightSrc& relight_src(const First& first, const Rest&... rest) {
-    if constexpr (sizeof...(Rest) == 0) {
-        return first;
-    } else {
-        return relight_src(rest...);
-    }
 }
 
 // The same pixel as a relit frame gets it: the G-buffer texel the primary pass of the retained frame left, seven dwords
@@ -2430,21 +2395,14 @@ __device__ __forceinline__ GbufTexel gbuf_texel(const par_render_args& a, const 
     return t;
 }
 
-// LightsArg: par_lights_dyn (direct frames) or const par_lights_dyn* (graph replay), see frame_lights. Radii: nothing
-// (unbounded lights), or par_light_radii / const par_light_radii* in the same way (the RANGED form), see frame_radii;
-// then nothing (white lights), or par_light_tints / const par_light_tints* (the TINTED form), see frame_tints.
-template <class LightsArg, class... Extras>
-__global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_grid_dev g, par_render_args a,
-                                                                            LightsArg lights_arg, Extras... extras_arg) {
-    constexpr bool RANGED = (is_light_radii<Extras> || ...);
-    constexpr bool TINTED = (is_light_tints<Extras> || ...);
-    constexpr bool RELIGHT = (std::is_same_v<Extras, RelightSrc> || ...);
-    static_assert(sizeof...(Extras) == (RANGED ? 1 : 0) + (TINTED ? 1 : 0) + (RELIGHT ? 1 : 0),
-                  "the radii, then the tints, then the G-buffer of a relit frame, one of each at most");
+template <bool GRAPH, bool RANGED, bool TINTED, bool RELIGHT, class... Args>
+__global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_grid_dev g, par_render_args a, Args... args) {
+    static_assert(!(RELIGHT && GRAPH), "a relit frame takes its lights by value");
+    static_assert(std::is_same_v<std::tuple<Args...>, LightArgs<GRAPH, RANGED, TINTED, RELIGHT>>, "see LightArgs");
     __shared__ LightCol sh;
-    [[maybe_unused]] const auto& radii = frame_radii(extras_arg...);
-    [[maybe_unused]] const auto& tints = frame_tints(extras_arg...);
-    const par_lights_dyn& lights = frame_lights(lights_arg);
+    [[maybe_unused]] const auto& radii = frame_arg<RANGED ? 1 : -1>(args...);
+    [[maybe_unused]] const auto& tints = frame_arg<TINTED ? 1 + RANGED : -1>(args...);
+    const par_lights_dyn& lights = frame_arg<0>(args...);
     const int lane = (int)threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int n_lights = lights.n;
@@ -2567,7 +2525,8 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
             int p_entity = 0, p_y = 0, p_z = 0, p_tex = 0;
             [[maybe_unused]] GbufTexel texel;
             if constexpr (RELIGHT) {
-                texel = gbuf_texel(a, relight_src(extras_arg...).gbuf, valid, row, px_col);
+                const par_pixel* gbuf = std::get<sizeof...(Args) - 1>(std::tie(args...));  // (the last argument)
+                texel = gbuf_texel(a, gbuf, valid, row, px_col);
                 hit = texel.covered;
                 p_entity = texel.entity;
                 p_y = texel.y;
@@ -2732,14 +2691,12 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
 
 // The background rays of a frame with several lights (bgline_kernel's, once per light): bit l of bglit[x] is the
 // shadow ray of a background pixel of screen column x towards light l, traced per lane as the reference writes it.
-// The RANGED form (Radii as for render_lights_kernel): a light with a radius leaves its bit 0, untraced, where (x, 0, 0)
-// is out of its range.
-template <class LightsArg, class... Radii>
-__global__ __launch_bounds__(256) void bglights_kernel(par_grid_dev g, par_render_args a, LightsArg lights_arg,
-                                                       Radii... radii_arg) {
-    constexpr bool RANGED = sizeof...(Radii) != 0;
-    [[maybe_unused]] const auto& radii = frame_radii(radii_arg...);  // (every thread meets the barriers before any returns)
-    const par_lights_dyn& lights = frame_lights(lights_arg);
+// The RANGED form: a light with a radius leaves its bit 0, untraced, where (x, 0, 0) is out of its range.
+template <bool GRAPH, bool RANGED, class... Args>
+__global__ __launch_bounds__(256) void bglights_kernel(par_grid_dev g, par_render_args a, Args... args) {
+    static_assert(std::is_same_v<std::tuple<Args...>, LightArgs<GRAPH, RANGED, false, false>>, "see LightArgs");
+    [[maybe_unused]] const auto& radii = frame_arg<RANGED ? 1 : -1>(args...);  // (every thread meets the barriers before any returns)
+    const par_lights_dyn& lights = frame_arg<0>(args...);
     const int x = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (x >= a.W) return;
     const BgRay ray = bg_ray(a, x);
@@ -3141,80 +3098,84 @@ hipError_t par_launch_render_overflow(const par_grid_dev& g, const par_render_ar
     return hipGetLastError();
 }
 
+// The light kernels' arguments of the form <GRAPH, RANGED, TINTED, RELIGHT> from the frame's light state.
+template <bool GRAPH, bool RANGED, bool TINTED, bool RELIGHT = false>
+static LightArgs<GRAPH, RANGED, TINTED, RELIGHT> light_args(const par_light_state& s, const par_pixel* gbuf = nullptr) {
+    const auto member = [&](auto par_lights_block::*m) {
+        if constexpr (GRAPH) return &(s.dev->*m);
+        else return s.block.*m;
+    };
+    const auto when = [](auto present, auto arg) {
+        if constexpr (present()) return std::make_tuple(arg);
+        else return std::tuple<>{};
+    };
+    return std::tuple_cat(std::make_tuple(member(&par_lights_block::lights)),
+                          when(std::bool_constant<RANGED>{}, member(&par_lights_block::radii)),
+                          when(std::bool_constant<TINTED>{}, member(&par_lights_block::tints)),
+                          when(std::bool_constant<RELIGHT>{}, gbuf));
+}
+
+// f(std::bool_constant of each of `bools`...): the run-time form of a light launch as template arguments.
+template <class F>
+static void with_form(F&& f) {
+    f();
+}
+template <class F, class... Bools>
+static void with_form(F&& f, bool first, Bools... rest) {
+    if (first) with_form([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+    else with_form([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
+
 // One workgroup per column the bound allows in the rendered rows, at most 65536 (the workgroups then stride over the
-// column list). `d_lights` non-null: a captured graph's kernels read the lights from there, else `lights`.
-hipError_t par_launch_render_lights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,
-                                    const par_lights_dyn* d_lights, const par_light_radii* radii,
-                                    const par_light_radii* d_radii, const par_light_tints* tints,
-                                    const par_light_tints* d_tints, int64_t column_bound, hipStream_t stream) {
+// column list).
+hipError_t par_launch_render_lights(const par_grid_dev& g, const par_render_args& a, const par_light_state& s,
+                                    int64_t column_bound, hipStream_t stream) {
     const int64_t n = std::min(columns_in_rows(g, a, column_bound), (int64_t)65536);
     if (n <= 0) return hipSuccess;
     const dim3 grid((unsigned)n), block(PAR_WAVE_NW * 64);
-    if (tints && radii && d_lights) {
-        hipLaunchKernelGGL((render_lights_kernel<const par_lights_dyn*, const par_light_radii*, const par_light_tints*>),
-                           grid, block, 0, stream, g, a, d_lights, d_radii, d_tints);
-    } else if (tints && radii) {
-        hipLaunchKernelGGL((render_lights_kernel<par_lights_dyn, par_light_radii, par_light_tints>), grid, block, 0, stream,
-                           g, a, lights, *radii, *tints);
-    } else if (tints && d_lights) {
-        hipLaunchKernelGGL((render_lights_kernel<const par_lights_dyn*, const par_light_tints*>), grid, block, 0, stream,
-                           g, a, d_lights, d_tints);
-    } else if (tints) {
-        hipLaunchKernelGGL((render_lights_kernel<par_lights_dyn, par_light_tints>), grid, block, 0, stream, g, a, lights,
-                           *tints);
-    } else if (radii && d_lights) {
-        hipLaunchKernelGGL((render_lights_kernel<const par_lights_dyn*, const par_light_radii*>), grid, block, 0, stream,
-                           g, a, d_lights, d_radii);
-    } else if (radii) {
-        hipLaunchKernelGGL((render_lights_kernel<par_lights_dyn, par_light_radii>), grid, block, 0, stream, g, a, lights,
-                           *radii);
-    } else if (d_lights) {
-        hipLaunchKernelGGL(render_lights_kernel<const par_lights_dyn*>, grid, block, 0, stream, g, a, d_lights);
-    } else {
-        hipLaunchKernelGGL(render_lights_kernel<par_lights_dyn>, grid, block, 0, stream, g, a, lights);
-    }
+    with_form(
+        [&](auto graph, auto ranged, auto tinted) {
+            std::apply(
+                [&](auto... la) {
+                    hipLaunchKernelGGL((render_lights_kernel<graph(), ranged(), tinted(), false>), grid, block, 0, stream,
+                                       g, a, la...);
+                },
+                light_args<graph(), ranged(), tinted()>(s));
+        },
+        s.dev != nullptr, s.ranged, s.tinted);
     return hipGetLastError();
 }
 
 // One workgroup per column of the RETAINED frame's list that `column_bound` allows (the caller bounds it by that
 // frame's rows, which may be more than a's), at most 65536.
 hipError_t par_launch_relight(const par_grid_dev& g, const par_render_args& a, const par_pixel* gbuf,
-                              const par_lights_dyn& lights, const par_light_radii* radii, const par_light_tints* tints,
-                              int64_t column_bound, hipStream_t stream) {
+                              const par_light_state& s, int64_t column_bound, hipStream_t stream) {
     const int64_t n = std::min(column_bound, (int64_t)65536);
     if (n <= 0) return hipSuccess;
     const dim3 grid((unsigned)n), block(PAR_WAVE_NW * 64);
-    const RelightSrc src{gbuf};
-    if (tints && radii) {
-        hipLaunchKernelGGL((render_lights_kernel<par_lights_dyn, par_light_radii, par_light_tints, RelightSrc>), grid, block,
-                           0, stream, g, a, lights, *radii, *tints, src);
-    } else if (tints) {
-        hipLaunchKernelGGL((render_lights_kernel<par_lights_dyn, par_light_tints, RelightSrc>), grid, block, 0, stream, g, a,
-                           lights, *tints, src);
-    } else if (radii) {
-        hipLaunchKernelGGL((render_lights_kernel<par_lights_dyn, par_light_radii, RelightSrc>), grid, block, 0, stream, g, a,
-                           lights, *radii, src);
-    } else {
-        hipLaunchKernelGGL((render_lights_kernel<par_lights_dyn, RelightSrc>), grid, block, 0, stream, g, a, lights, src);
-    }
+    with_form(
+        [&](auto ranged, auto tinted) {
+            std::apply(
+                [&](auto... la) {
+                    hipLaunchKernelGGL((render_lights_kernel<false, ranged(), tinted(), true>), grid, block, 0, stream, g,
+                                       a, la...);
+                },
+                light_args<false, ranged(), tinted(), true>(s, gbuf));
+        },
+        s.ranged, s.tinted);
     return hipGetLastError();
 }
 
-hipError_t par_launch_bglights(const par_grid_dev& g, const par_render_args& a, const par_lights_dyn& lights,
-                               const par_lights_dyn* d_lights, const par_light_radii* radii,
-                               const par_light_radii* d_radii, hipStream_t stream) {
+hipError_t par_launch_bglights(const par_grid_dev& g, const par_render_args& a, const par_light_state& s,
+                               hipStream_t stream) {
     const dim3 grid((unsigned)((a.W + 255) / 256)), block(256);
-    if (radii && d_lights) {
-        hipLaunchKernelGGL((bglights_kernel<const par_lights_dyn*, const par_light_radii*>), grid, block, 0, stream, g, a,
-                           d_lights, d_radii);
-    } else if (radii) {
-        hipLaunchKernelGGL((bglights_kernel<par_lights_dyn, par_light_radii>), grid, block, 0, stream, g, a, lights,
-                           *radii);
-    } else if (d_lights) {
-        hipLaunchKernelGGL(bglights_kernel<const par_lights_dyn*>, grid, block, 0, stream, g, a, d_lights);
-    } else {
-        hipLaunchKernelGGL(bglights_kernel<par_lights_dyn>, grid, block, 0, stream, g, a, lights);
-    }
+    with_form(
+        [&](auto graph, auto ranged) {
+            std::apply(
+                [&](auto... la) { hipLaunchKernelGGL((bglights_kernel<graph(), ranged()>), grid, block, 0, stream, g, a, la...); },
+                light_args<graph(), ranged(), false>(s));
+        },
+        s.dev != nullptr, s.ranged);
     return hipGetLastError();
 }
 

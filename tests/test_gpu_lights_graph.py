@@ -32,6 +32,8 @@ class Planes:
         self.planes = planes
         self.bufs = {k: torch.zeros(n * BYTES[k], dtype=torch.uint8, device="cuda") for k in planes}
         self.ptrs = {k: b.data_ptr() for k, b in self.bufs.items()}
+        # (the fills ran on the current stream; the tests render on streams of their own, which do not wait for it)
+        torch.cuda.current_stream().synchronize()
 
     def host(self, T):
         dt = {"fb": T.COLOR, "gbuf": T.PIXEL, "palidx": np.uint8, "brightness": np.float32, "lit": np.uint8}
