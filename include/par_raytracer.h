@@ -371,6 +371,63 @@ int par_tiles_assemble(const par_params* params, void* stream, const int32_t* d_
                        par_color* frame, int row_begin, int row_end);
 int par_scene_tile_map(const par_params* params, const int32_t* tiles, int n, int32_t* map, int capacity);
 
+/* --- outlines: silhouettes and creases drawn from the G-buffer (nothing in the reference) ------------------------
+ * The post-process pixel-art renderers use most: a dark line where one object ends in front of another or in front of
+ * the background, a highlight where a box's top face meets its front face. Everything it needs is in the G-buffer
+ * plane of a frame, whatever made it. These calls are a pass over finished planes and take no context: retained
+ * frames, graphs and statistics are not involved and do not change. In a frame loop the call goes directly before
+ * palette output: render or relight, then outline, then quantise, so that the darkened and lightened colours snap to
+ * the palette with everything else.
+ * Planes and ranges. `gbuf` addresses (gbuf_row_begin, column 0) and holds rows [g0, g1) = [gbuf_row_begin,
+ * gbuf_row_end); it is only read. `fb`, `fb_out` and `edge_out` address (row_begin, 0) and hold rows [r0, r1) =
+ * [row_begin, row_end), dense and row-major as every plane is. Required: 0 <= g0 <= r0 < r1 <= g1 <= height. The extra
+ * G-buffer rows are the halo: a caller that shades a row block passes a G-buffer plane with one more row on each side
+ * that exists in the frame (par_render_device renders any row range), and the block then equals those rows of the
+ * whole frame's result, byte for byte. A neighbour row outside [g0, g1) is treated exactly like a row outside the frame.
+ * For the pixel at column x and absolute row y, with texel T read as seven little-endian 32-bit words w0..w6,
+ * everything in integers:
+ *     cov(T)  = T differs from the background texel (normal words 0, colour {bg, bg, bg, 0}, y, z and entity 0: the
+ *               definition of par_relight_device)
+ *     key(T)  = w4 - w5, that is y - z, in wrapping uint32 (a larger key is nearer to the viewer)
+ *     d(T, N) = (int32_t)(key(T) - key(N)), the subtraction wrapping
+ *     neighbours: left (x-1), right (x+1), up (y-1), down (y+1); one is present iff its column lies in [0, width) and
+ *               its row in [max(0, g0), min(height, g1)); an absent neighbour contributes nothing
+ *     silhouette: T is covered, and some present neighbour N either is not covered or has N.entity != T.entity with
+ *               d(T, N) >= depth_step (depth_step >= 1 puts the line on the nearer object only, one pixel wide;
+ *               background pixels are never outlined)
+ *     crease: T is covered and is not a silhouette; the right or the down neighbour N is present and covered, does not
+ *               meet the silhouette condition against T (not: T.entity != N.entity with d(N, T) >= depth_step), and
+ *               its three normal words differ from T's bit for bit (-0 differs from +0; no float compare). Only right
+ *               and down are looked at: the line is one pixel wide and lies on the last pixel of the upper or left
+ *               face, which is a box's top edge
+ *     class   = 2 for a silhouette, else 1 for a crease, else 0
+ *     edge_out = (uint8_t)class                      when edge_out is not NULL
+ *     fb_out  = {min(255, (r * s) >> 8), min(255, (g * s) >> 8), min(255, (b * s) >> 8), a} of the pixel's fb value
+ *               when fb_out is not NULL, with s = silhouette_scale for class 2, crease_scale for class 1, 256 for class 0
+ * fb_out == fb (in place) is allowed: the call reads only a pixel's own fb value; any other overlap of the arrays is
+ * undefined. `fb` may be NULL only when fb_out is NULL. PAR_ERR_INVALID_ARG, before any device work and with nothing
+ * written (no GPU is needed to get it), for a null `params`, `style` or `gbuf`, both outputs null, fb_out without fb,
+ * params->width <= 0, depth_step < 1, a scale outside [0, 1024], or row ranges that break the inequality above. The
+ * kernel stays inside its arrays whatever the texels hold. The pointers have their types' alignment (4 bytes for
+ * par_pixel and par_color, any byte for edge_out); planes on 16-byte (edge_out: 4-byte) boundaries of a frame whose
+ * width is a multiple of 4 take the kernel's wider accesses, every other placement gives the same bytes.
+ * Left out on purpose: no 8-neighbourhood, no lines thicker than one pixel, no outline colour other than a scaled pixel
+ * colour, no fusing into the render or quantise kernels, and no graph-capture helper (the device call is capturable as
+ * any stream-ordered launch is). */
+/* device pointers, asynchronous on `stream` (a hipStream_t), no sync: on the frame's own stream, after the render or
+ * relight call and before par_quantize_device */
+int par_outline_device(const par_params* params, void* stream, const par_outline_style* style,
+                       const par_pixel* gbuf, int gbuf_row_begin, int gbuf_row_end,
+                       const par_color* fb, int row_begin, int row_end,
+                       par_color* fb_out, uint8_t* edge_out);
+/* host pointers, synchronous, everything on HIP device `device` (-1: the current device, as par_create): allocates,
+ * copies, launches, synchronises, copies back and frees; PAR_ERR_NO_DEVICE / PAR_ERR_OOM / PAR_ERR_HIP as
+ * par_quantize_host */
+int par_outline_host(const par_params* params, int device, const par_outline_style* style,
+                     const par_pixel* gbuf, int gbuf_row_begin, int gbuf_row_end,
+                     const par_color* fb, int row_begin, int row_end,
+                     par_color* fb_out, uint8_t* edge_out);
+
 /* --- palette output: a frame quantised to a fixed palette (nothing in the reference, which presents RGBA8) --------
  * Several lights, ranged and tinted lights give a frame thousands of colours; an indexed-colour display, a GIF or a
  * sprite sheet wants an index plane over a fixed, art-directed palette. These calls are a pass over a frame's `fb`

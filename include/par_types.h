@@ -69,6 +69,15 @@ typedef struct par_light {
  * pixel's sum is multiplied by, channel by channel. White is {1, 1, 1}; a component above 1 makes a bright light. */
 typedef struct par_light_tint { float r, g, b; } par_light_tint;
 
+/* How par_outline_device (par_raytracer.h; nothing in the reference) draws a frame's outlines: the depth difference from
+ * which an edge between two entities is a silhouette, and the 8.8 fixed-point factors a silhouette's and a crease's red,
+ * green and blue are multiplied by (256 leaves a colour as it is, below darkens, above lightens). */
+typedef struct par_outline_style {
+    int32_t depth_step;        /* >= 1 */
+    int32_t silhouette_scale;  /* 0..1024, 256 = unchanged */
+    int32_t crease_scale;      /* 0..1024, 256 = unchanged */
+} par_outline_style;
+
 /* `Ray`, alt:30-33 (20 bytes: fp32 inverse direction + short origin, 2 bytes tail padding). */
 typedef struct par_ray {
     float inv_x, inv_y, inv_z;

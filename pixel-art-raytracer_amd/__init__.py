@@ -16,8 +16,8 @@ import sys
 import numpy as np
 
 from . import types as T
-from .types import (AABB, COLOR, LIGHT, LIGHT_TINT, PIXEL, SPRITE, FrameStats, Outputs, Params, default_params,
-                    make_aabbs, make_light, make_tints, ptr)
+from .types import (AABB, COLOR, LIGHT, LIGHT_TINT, OUTLINE_STYLE, PIXEL, SPRITE, FrameStats, Outputs, Params,
+                    default_params, make_aabbs, make_light, make_outline_style, make_tints, ptr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libpar_raytracer.so")
@@ -41,7 +41,7 @@ ABI_SYMBOLS = (
     "par_render_device_slots", "par_row_block", "par_scene_tiles", "par_tiles_pack", "par_tiles_unpack",
     "par_background_fill", "par_tiles_assemble", "par_scene_tile_map", "par_set_lights", "par_graph_capture_lights",
     "par_graph_stage_lights", "par_set_light_model", "par_set_light_tints", "par_relight_device", "par_relight_rows",
-    "par_quantize_device", "par_quantize_host", "par_palette_ramp",
+    "par_quantize_device", "par_quantize_host", "par_palette_ramp", "par_outline_device", "par_outline_host",
 )
 MAX_LIGHTS = 8  # PAR_MAX_LIGHTS
 LIGHTS_UNBOUNDED, LIGHTS_RANGED = 0, 1  # par_set_light_model
@@ -136,6 +136,8 @@ def lib():
         L.par_quantize_device.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, vp, vp]
         L.par_quantize_host.argtypes = [vp, i32, vp, i32, i32, vp, i32, i32, vp, vp]
         L.par_palette_ramp.argtypes = [vp, i32, vp, i32]
+        L.par_outline_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, i32, vp, vp]
+        L.par_outline_host.argtypes = [vp, i32, vp, vp, i32, i32, vp, i32, i32, vp, vp]
         L.par_debug_read_stamps.argtypes = [vp, vp, C.c_size_t]
         L.par_debug_set_hooks.argtypes = [vp, C.c_uint, i32]
         L.par_debug_read_light_walks.argtypes = [vp, vp]
@@ -475,6 +477,54 @@ def background_fill(params, rows_ptr, n_rows, stream=0):
     rc = lib().par_background_fill(C.byref(params), C.c_void_p(stream), C.c_void_p(rows_ptr), n_rows)
     if rc != PAR_OK:
         raise ParError(rc, "par_background_fill")
+
+
+# ---- outlines ----------------------------------------------------------------------------------------------------
+
+def outline(params, style, gbuf, gbuf_rows, fb, rows, fb_out=None, edge_out=None, stream=0):
+    """Device pointers (ints): silhouettes and creases of rows [rows[0], rows[1]) drawn from the G-buffer block at
+    `gbuf`, which holds rows [gbuf_rows[0], gbuf_rows[1]) (par_outline_device: the rows beyond `rows` are the halo a row
+    block needs to equal the whole frame). `style` is an OUTLINE_STYLE array (types.make_outline_style). The class plane
+    (2 silhouette, 1 crease, 0 neither) goes to edge_out and / or the frame block at `fb` with the lines' colours scaled
+    to fb_out (fb_out == fb: in place; fb may be None without fb_out). Asynchronous on `stream`: in a frame loop after
+    the render or relight call and before quantize."""
+    style = np.ascontiguousarray(style, dtype=OUTLINE_STYLE).reshape(-1)
+    rc = lib().par_outline_device(C.byref(params), C.c_void_p(stream), ptr(style), C.c_void_p(gbuf), gbuf_rows[0],
+                                  gbuf_rows[1], C.c_void_p(fb), rows[0], rows[1], C.c_void_p(fb_out),
+                                  C.c_void_p(edge_out))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_outline_device")
+
+
+def outline_host(params, style, gbuf, fb=None, rows=None, gbuf_rows=None, planes=("edge",), device=-1):
+    """The same on host arrays (par_outline_host): `gbuf` is a PIXEL array holding rows `gbuf_rows` (default: `rows`),
+    `fb` a COLOR array holding rows `rows` (default: the whole frame; needed for the "fb" plane only). Returns
+    {"edge": uint8 array, "fb": COLOR array} for the planes asked for."""
+    r0, r1 = rows or (0, params.height)
+    g0, g1 = gbuf_rows or (r0, r1)
+    style = np.ascontiguousarray(style, dtype=OUTLINE_STYLE).reshape(-1)
+    gbuf = np.ascontiguousarray(gbuf, dtype=PIXEL).reshape(-1)
+    n = (r1 - r0) * params.width
+    if len(gbuf) != (g1 - g0) * params.width:
+        raise ValueError(f"outline_host: gbuf holds {len(gbuf)} texels, rows {g0}..{g1} of width {params.width} hold "
+                         f"{(g1 - g0) * params.width}")
+    unknown = set(planes) - {"edge", "fb"}
+    if unknown:
+        raise ValueError(f"outline_host: unknown planes {sorted(unknown)}")
+    if fb is not None:
+        fb = np.ascontiguousarray(fb, dtype=COLOR).reshape(-1)
+        if len(fb) != n:
+            raise ValueError(f"outline_host: fb holds {len(fb)} pixels, rows {r0}..{r1} of width {params.width} hold {n}")
+    out = {}
+    if "edge" in planes:
+        out["edge"] = np.zeros(n, dtype=np.uint8)
+    if "fb" in planes:
+        out["fb"] = np.zeros(n, dtype=COLOR)
+    rc = lib().par_outline_host(C.byref(params), device, ptr(style), ptr(gbuf), g0, g1, ptr(fb), r0, r1,
+                                ptr(out.get("fb")), ptr(out.get("edge")))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_outline_host")
+    return out
 
 
 # ---- palette output ----------------------------------------------------------------------------------------------

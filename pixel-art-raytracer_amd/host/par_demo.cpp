@@ -7,7 +7,7 @@
 // alt:815-817.
 //
 //   par_demo [--keys RRRRUUUUhhhhjjPP] [--frames N] [--out DIR] [--gif FILE] [--debug-line] [--as-sdl] [--size W H L]
-//            [--palette-levels K] [--dither S]
+//            [--palette-levels K] [--dither S] [--outline S,C,D]
 //
 // --gif writes the frames as one animated GIF89a (100 ms per frame like the reference's gif.gif); a frame's colours
 // are palette entries times a brightness, at most a few hundred distinct values, so each frame gets an exact local
@@ -19,6 +19,11 @@
 // palette, par_palette_ramp(params, K): each sprite-palette entry at K brightness bands, then the background. That
 // palette is every frame's local colour table and the index plane is written as it comes back; --dither S (0..255) adds
 // the ordered dither. The PPM frames of --out stay unquantised.
+//
+// --outline S,C,D draws every frame's outlines on the GPU (par_outline_host) from the frame's own G-buffer: silhouettes
+// scaled by S / 256, creases by C / 256, a silhouette between two entities from a depth difference of D (128,320,4 is a
+// dark line and a light top edge). The frame is outlined as soon as it is rendered: before the debug line, before
+// --palette-levels quantises it and before it is written as PPM or GIF.
 //
 // Letters: R L U D P N = right, left, up, down, page-up, page-down; a k j u h o as in the reference. Frame 0 gets no
 // key; frame k applies key k-1 (cycling when --frames exceeds the script).
@@ -195,7 +200,8 @@ class GifWriter {
 int main(int argc, char** argv) {
     std::string keys = "RRRRUUUUhhhhjjPP", out_dir, gif_path;
     int frames = -1, W = 480, H = 320, L = 320, palette_levels = 0, dither = 0;
-    bool debug_line = false, as_sdl = false;
+    bool debug_line = false, as_sdl = false, outline = false;
+    par_outline_style outline_style{4, 256, 256};
     for (int i = 1; i < argc; i++) {
         if (!std::strcmp(argv[i], "--keys") && i + 1 < argc) keys = argv[++i];
         else if (!std::strcmp(argv[i], "--frames") && i + 1 < argc) frames = std::atoi(argv[++i]);
@@ -205,6 +211,12 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--as-sdl")) as_sdl = true;
         else if (!std::strcmp(argv[i], "--palette-levels") && i + 1 < argc) palette_levels = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--dither") && i + 1 < argc) dither = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--outline") && i + 1 < argc) {
+            int s = 0, c = 0, d = 0;
+            if (std::sscanf(argv[++i], "%d,%d,%d", &s, &c, &d) != 3) { std::fprintf(stderr, "--outline wants S,C,D, got %s\n", argv[i]); return 2; }
+            outline_style = par_outline_style{d, s, c};
+            outline = true;
+        }
         else if (!std::strcmp(argv[i], "--size") && i + 3 < argc) { W = std::atoi(argv[++i]); H = std::atoi(argv[++i]); L = std::atoi(argv[++i]); }
         else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
@@ -260,6 +272,10 @@ int main(int argc, char** argv) {
             return 1;
         }
         const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (outline && (rc = par_outline_host(&params, 0, &outline_style, gbuf.data(), 0, H, fb.data(), 0, H, fb.data(), nullptr)) != PAR_OK) {
+            std::fprintf(stderr, "par_outline_host: %s\n", par_status_string(rc));
+            return rc == PAR_ERR_INVALID_ARG ? 2 : 1;
+        }
         if (debug_line) par_debug_line(&params, &gbuf[(size_t)mouse_y * W + mouse_x], mouse_x, &light, fb.data());
         std::printf("frame %d: %.3fms  player <%d, %d, %d>  light <%d, %d, %d>\n", f, ms, aabbs[0].px, aabbs[0].py,
                     aabbs[0].pz, light.x, light.y, light.z);  // alt:815-817 prints the frame time

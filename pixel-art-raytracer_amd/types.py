@@ -24,12 +24,13 @@ AABB = np.dtype([("px", "<i2"), ("py", "<i2"), ("pz", "<i2"), ("ex", "<i2"), ("e
                  ("pad", "<i2", (2,))])
 LIGHT = np.dtype([("x", "<i2"), ("y", "<i2"), ("z", "<i2"), ("radius", "<i2")])
 LIGHT_TINT = np.dtype([("r", "<f4"), ("g", "<f4"), ("b", "<f4")])  # par_light_tint
+OUTLINE_STYLE = np.dtype([("depth_step", "<i4"), ("silhouette_scale", "<i4"), ("crease_scale", "<i4")])  # par_outline_style
 RAY = np.dtype([("inv_x", "<f4"), ("inv_y", "<f4"), ("inv_z", "<f4"), ("ox", "<i2"), ("oy", "<i2"), ("oz", "<i2"),
                 ("pad", "<i2")])
 
 assert COLOR.itemsize == 4 and VEC3.itemsize == 12 and PIXEL.itemsize == 28
 assert SPRITE.itemsize == 16000 and AABB.itemsize == 16 and LIGHT.itemsize == 8 and RAY.itemsize == 20
-assert LIGHT_TINT.itemsize == 12
+assert LIGHT_TINT.itemsize == 12 and OUTLINE_STYLE.itemsize == 12
 
 
 class Color(C.Structure):
@@ -88,6 +89,14 @@ def make_tints(rows):
     for i, rgb in enumerate(rows):
         t[i]["r"], t[i]["g"], t[i]["b"] = rgb
     return t
+
+
+def make_outline_style(depth_step=4, silhouette_scale=128, crease_scale=320):
+    """1-element OUTLINE_STYLE array (par_outline_device): the depth difference from which an edge between two entities
+    is a silhouette, and the 8.8 fixed-point factors of a silhouette's and a crease's colour (256 = unchanged)."""
+    s = np.zeros(1, dtype=OUTLINE_STYLE)
+    s["depth_step"], s["silhouette_scale"], s["crease_scale"] = depth_step, silhouette_scale, crease_scale
+    return s
 
 
 def make_aabbs(rows):
