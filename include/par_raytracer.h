@@ -470,6 +470,52 @@ int par_quantize_host(const par_params* params, int device, const par_color* pal
  * palette_size outside [1, PAR_MAX_PALETTE]. */
 int par_palette_ramp(const par_params* params, int levels, par_color* out, int capacity);
 
+/* --- present: a frame or an index plane scaled onto a surface (the reference's present, alt:774-788) ---------------
+ * The last step of a frame loop: render or relight, then outline, then quantise, then present. The reference copies its
+ * frame row by row into a locked SDL texture, honouring the texture's pitch (alt:776-780); the texture is
+ * SDL_PIXELFORMAT_RGB888, which shows a par_color's red byte as blue. These calls do that on the device and at an integer
+ * scale, nearest neighbour, and they turn an index plane (par_quantize_device's) back into colour through a palette:
+ * presenting one index plane with a rotated palette frame after frame is palette cycling, with no render and no
+ * quantise. They are a pass over finished planes and take no context: retained frames, graphs and statistics are not
+ * involved and do not change. Everything is in integers; sx = desc->scale_x, sy = desc->scale_y.
+ * Sources. Exactly one of `fb` and `index` is non-null. Each addresses (row_begin, column 0) and holds rows [r0, r1) =
+ * [row_begin, row_end), dense and row-major as every plane is. With `index`, the palette holds n_colors entries,
+ * 1 <= n_colors <= PAR_MAX_PALETTE; with `fb`, the palette must be NULL and n_colors 0.
+ * Output. `out` addresses output row r0 * sy, byte 0, and holds output rows [r0 * sy, r1 * sy) of W' = width * sx pixels
+ * each, desc->pitch bytes from row to row. For the output pixel (X, Y), 0 <= X < W' and r0 * sy <= Y < r1 * sy:
+ *     s = the source element at column X / sx and absolute row Y / sy (truncating divisions)
+ *     c = fb[s]                                     with an fb source
+ *     c = palette[min(index[s], n_colors - 1)]      with an index source: all four bytes, the entry's alpha included
+ *         (the clamp defines the out-of-range index, PAR_PALIDX_BACKGROUND among them, and keeps the kernel inside the
+ *         palette whatever the plane holds)
+ *     under PAR_PRESENT_BGRA the red and blue bytes of c are exchanged
+ *     the 4 bytes of c go to (char*)out + (Y - r0 * sy) * pitch + 4 * X
+ * The bytes of a row from 4 * W' up to pitch are NOT written (a letterboxed or larger surface: the caller offsets
+ * `out`); that holds for the host form's `out` too, which is copied back with a pitched copy. A row block's output is,
+ * by the formula, those output rows of the whole frame's: no halo is needed. No overlap of `out` with a source is
+ * defined. `fb`, the palette and `out` must be 4-byte aligned; `index` may sit on any byte. `out` on a 16-byte boundary
+ * with a pitch that is a multiple of 16 takes the kernel's wider stores; every other placement gives the same bytes.
+ * PAR_ERR_INVALID_ARG, before any device work and with nothing written (no GPU is needed to get it), for a null
+ * `params`, `desc` or `out`; both sources or neither; an index source without a palette or with n_colors outside
+ * [1, PAR_MAX_PALETTE]; an fb source with a palette or n_colors != 0; params->width <= 0; rows that are not
+ * 0 <= r0 < r1 <= params->height; a scale outside [1, PAR_MAX_SCALE]; an order that is neither of the two; a pitch that
+ * is not a multiple of 4 or is below 4 * width * sx (formed in 64 bits: a product that does not fit an int32 is thereby
+ * refused).
+ * Left out on purpose: no filtering other than nearest, no fractional scale, no scaled INDEX output, no fusing into the
+ * quantise kernel, no 24-bit or 16-bit surface formats, and no graph-capture helper (the device call is capturable as
+ * any stream-ordered launch is). */
+/* device pointers (`d_palette` too), asynchronous on `stream` (a hipStream_t), no sync: on the frame's own stream, after
+ * the last call that writes the source */
+int par_present_device(const par_params* params, void* stream, const par_present_desc* desc,
+                       const par_color* fb, const uint8_t* index, const par_color* d_palette, int n_colors,
+                       int row_begin, int row_end, void* out);
+/* host pointers, synchronous, everything on HIP device `device` (-1: the current device, as par_create): allocates,
+ * copies, launches, synchronises, copies back and frees; PAR_ERR_NO_DEVICE / PAR_ERR_OOM / PAR_ERR_HIP as
+ * par_quantize_host */
+int par_present_host(const par_params* params, int device, const par_present_desc* desc,
+                     const par_color* fb, const uint8_t* index, const par_color* palette, int n_colors,
+                     int row_begin, int row_end, void* out);
+
 /* Debug overlay of alt:763-772 (Bresenham line from the picked pixel to the light) drawn into a host frame. */
 void par_debug_line(const par_params* params, const par_pixel* pick, int mouse_x, const par_light* light,
                     par_color* fb);

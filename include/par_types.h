@@ -78,6 +78,17 @@ typedef struct par_outline_style {
     int32_t crease_scale;      /* 0..1024, 256 = unchanged */
 } par_outline_style;
 
+/* How par_present_device (par_raytracer.h) puts a frame or an index plane on a surface: nearest neighbour at an integer
+ * scale, in the surface's byte order and row pitch (the reference's present, alt:774-788, at scale 1). */
+#define PAR_MAX_SCALE 16
+enum { PAR_PRESENT_RGBA = 0, PAR_PRESENT_BGRA = 1 };
+typedef struct par_present_desc {
+    int32_t scale_x, scale_y; /* 1..PAR_MAX_SCALE each; they may differ (pixel-aspect correction) */
+    int32_t pitch;            /* bytes from one output row to the next: a multiple of 4, >= 4 * width * scale_x */
+    int32_t order;            /* PAR_PRESENT_RGBA: bytes red, green, blue, alpha as par_color;
+                                 PAR_PRESENT_BGRA: red and blue exchanged (an SDL RGB888 / ARGB8888 surface) */
+} par_present_desc;           /* 16 bytes */
+
 /* `Ray`, alt:30-33 (20 bytes: fp32 inverse direction + short origin, 2 bytes tail padding). */
 typedef struct par_ray {
     float inv_x, inv_y, inv_z;

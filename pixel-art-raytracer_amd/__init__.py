@@ -16,8 +16,9 @@ import sys
 import numpy as np
 
 from . import types as T
-from .types import (AABB, COLOR, LIGHT, LIGHT_TINT, OUTLINE_STYLE, PIXEL, SPRITE, FrameStats, Outputs, Params,
-                    default_params, make_aabbs, make_light, make_outline_style, make_tints, ptr)
+from .types import (AABB, COLOR, LIGHT, LIGHT_TINT, MAX_SCALE, OUTLINE_STYLE, PIXEL, PRESENT_BGRA, PRESENT_DESC,
+                    PRESENT_RGBA, SPRITE, FrameStats, Outputs, Params, default_params, make_aabbs, make_light,
+                    make_outline_style, make_present_desc, make_tints, ptr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libpar_raytracer.so")
@@ -42,6 +43,7 @@ ABI_SYMBOLS = (
     "par_background_fill", "par_tiles_assemble", "par_scene_tile_map", "par_set_lights", "par_graph_capture_lights",
     "par_graph_stage_lights", "par_set_light_model", "par_set_light_tints", "par_relight_device", "par_relight_rows",
     "par_quantize_device", "par_quantize_host", "par_palette_ramp", "par_outline_device", "par_outline_host",
+    "par_present_device", "par_present_host",
 )
 MAX_LIGHTS = 8  # PAR_MAX_LIGHTS
 LIGHTS_UNBOUNDED, LIGHTS_RANGED = 0, 1  # par_set_light_model
@@ -138,6 +140,8 @@ def lib():
         L.par_palette_ramp.argtypes = [vp, i32, vp, i32]
         L.par_outline_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, i32, vp, vp]
         L.par_outline_host.argtypes = [vp, i32, vp, vp, i32, i32, vp, i32, i32, vp, vp]
+        L.par_present_device.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
+        L.par_present_host.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, vp]
         L.par_debug_read_stamps.argtypes = [vp, vp, C.c_size_t]
         L.par_debug_set_hooks.argtypes = [vp, C.c_uint, i32]
         L.par_debug_read_light_walks.argtypes = [vp, vp]
@@ -572,3 +576,44 @@ def palette_ramp(params, levels):
     if n < 0:
         raise ParError(-n, "par_palette_ramp")
     return out[:n].copy()
+
+
+# ---- present -----------------------------------------------------------------------------------------------------
+
+def present(params, desc, out, rows, fb=None, index=None, d_palette=None, n_colors=0, stream=0):
+    """Device pointers (ints): rows [rows[0], rows[1]) of the frame block at `fb`, or of the index plane at `index` through
+    the n_colors palette entries at d_palette, scaled onto the surface at `out` (par_present_device: nearest neighbour at
+    the integer scales, byte order and pitch of `desc`, a PRESENT_DESC array from types.make_present_desc; `out`
+    addresses output row rows[0] * scale_y). Asynchronous on `stream`: the last call of a frame loop."""
+    desc = np.ascontiguousarray(desc, dtype=PRESENT_DESC).reshape(-1)
+    rc = lib().par_present_device(C.byref(params), C.c_void_p(stream), ptr(desc), C.c_void_p(fb), C.c_void_p(index),
+                                  C.c_void_p(d_palette), n_colors, rows[0], rows[1], C.c_void_p(out))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_present_device")
+
+
+def present_host(params, desc, rows=None, fb=None, index=None, palette=None, device=-1):
+    """The same on host arrays (par_present_host): `fb` a COLOR array or `index` a uint8 array holding rows `rows`
+    (default: the whole frame), `palette` a COLOR array with `index`. Returns the surface's rows as a
+    (rows * scale_y, pitch) uint8 array; the bytes of a row beyond 4 * width * scale_x are not written (zeros here)."""
+    r0, r1 = rows or (0, params.height)
+    desc = np.ascontiguousarray(desc, dtype=PRESENT_DESC).reshape(-1)
+    n = (r1 - r0) * params.width
+    if fb is not None:
+        fb = np.ascontiguousarray(fb, dtype=COLOR).reshape(-1)
+    if index is not None:
+        index = np.ascontiguousarray(index, dtype=np.uint8).reshape(-1)
+    for name, plane in (("fb", fb), ("index", index)):
+        if plane is not None and len(plane) != n:
+            raise ValueError(f"present_host: {name} holds {len(plane)} elements, rows {r0}..{r1} of width {params.width} "
+                             f"hold {n}")
+    n_colors = 0
+    if palette is not None:
+        palette = np.ascontiguousarray(palette, dtype=COLOR).reshape(-1)
+        n_colors = len(palette)
+    out = np.zeros((max(0, r1 - r0) * max(0, int(desc["scale_y"][0])), max(0, int(desc["pitch"][0]))), dtype=np.uint8)
+    rc = lib().par_present_host(C.byref(params), device, ptr(desc), ptr(fb), ptr(index), ptr(palette), n_colors, r0, r1,
+                                out.ctypes.data_as(C.c_void_p))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_present_host")
+    return out

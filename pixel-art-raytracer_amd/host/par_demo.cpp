@@ -7,7 +7,7 @@
 // alt:815-817.
 //
 //   par_demo [--keys RRRRUUUUhhhhjjPP] [--frames N] [--out DIR] [--gif FILE] [--debug-line] [--as-sdl] [--size W H L]
-//            [--palette-levels K] [--dither S] [--outline S,C,D]
+//            [--palette-levels K] [--dither S] [--outline S,C,D] [--scale SX[,SY]]
 //
 // --gif writes the frames as one animated GIF89a (100 ms per frame like the reference's gif.gif); a frame's colours
 // are palette entries times a brightness, at most a few hundred distinct values, so each frame gets an exact local
@@ -24,6 +24,10 @@
 // scaled by S / 256, creases by C / 256, a silhouette between two entities from a depth difference of D (128,320,4 is a
 // dark line and a light top edge). The frame is outlined as soon as it is rendered: before the debug line, before
 // --palette-levels quantises it and before it is written as PPM or GIF.
+//
+// --scale SX[,SY] (with --out; each 1..16, SY defaults to SX) writes the PPM frames at W * SX x H * SY: the frame as it
+// stands when it is written (after the outline, the debug line and --as-sdl's exchange) put on a surface of that size on
+// the GPU (par_present_host, nearest neighbour, tight pitch, RGBA order). GIFs stay at view size.
 //
 // Letters: R L U D P N = right, left, up, down, page-up, page-down; a k j u h o as in the reference. Frame 0 gets no
 // key; frame k applies key k-1 (cycling when --frames exceeds the script).
@@ -201,6 +205,7 @@ int main(int argc, char** argv) {
     std::string keys = "RRRRUUUUhhhhjjPP", out_dir, gif_path;
     int frames = -1, W = 480, H = 320, L = 320, palette_levels = 0, dither = 0;
     bool debug_line = false, as_sdl = false, outline = false;
+    int scale_x = 0, scale_y = 0;  // 0: no --scale
     par_outline_style outline_style{4, 256, 256};
     for (int i = 1; i < argc; i++) {
         if (!std::strcmp(argv[i], "--keys") && i + 1 < argc) keys = argv[++i];
@@ -216,6 +221,16 @@ int main(int argc, char** argv) {
             if (std::sscanf(argv[++i], "%d,%d,%d", &s, &c, &d) != 3) { std::fprintf(stderr, "--outline wants S,C,D, got %s\n", argv[i]); return 2; }
             outline_style = par_outline_style{d, s, c};
             outline = true;
+        }
+        else if (!std::strcmp(argv[i], "--scale") && i + 1 < argc) {
+            char tail = 0;
+            const int got = std::sscanf(argv[++i], "%d,%d%c", &scale_x, &scale_y, &tail);
+            if (got == 1) scale_y = scale_x;
+            if ((got != 1 && got != 2) || (got == 1 && std::strchr(argv[i], ',')) || scale_x < 1 || scale_x > PAR_MAX_SCALE ||
+                scale_y < 1 || scale_y > PAR_MAX_SCALE) {
+                std::fprintf(stderr, "--scale wants SX[,SY], each 1..%d, got %s\n", PAR_MAX_SCALE, argv[i]);
+                return 2;
+            }
         }
         else if (!std::strcmp(argv[i], "--size") && i + 3 < argc) { W = std::atoi(argv[++i]); H = std::atoi(argv[++i]); L = std::atoi(argv[++i]); }
         else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
@@ -246,6 +261,8 @@ int main(int argc, char** argv) {
     std::vector<par_color> fb((size_t)W * H);
     std::vector<par_pixel> gbuf((size_t)W * H);
     std::vector<unsigned char> rgb((size_t)W * H * 3);
+    std::vector<par_color> surface;  // --scale: the frame as the PPM shows it
+    if (scale_x > 0 && !out_dir.empty()) surface.resize((size_t)W * scale_x * H * scale_y);
     // --palette-levels: the GIF's frames are index planes over the scene's ramp
     std::vector<par_color> ramp;
     std::vector<unsigned char> index;
@@ -285,7 +302,17 @@ int main(int argc, char** argv) {
         if (!out_dir.empty()) {
             char name[64];
             std::snprintf(name, sizeof(name), "/frame_%03d.ppm", f);
-            if (!write_ppm(out_dir + name, fb.data(), W, H)) { std::fprintf(stderr, "cannot write %s%s\n", out_dir.c_str(), name); return 1; }
+            const par_color* shown = fb.data();
+            if (!surface.empty()) {
+                const par_present_desc desc{scale_x, scale_y, 4 * W * scale_x, PAR_PRESENT_RGBA};
+                if ((rc = par_present_host(&params, 0, &desc, fb.data(), nullptr, nullptr, 0, 0, H, surface.data())) != PAR_OK) {
+                    std::fprintf(stderr, "par_present_host: %s\n", par_status_string(rc));
+                    return rc == PAR_ERR_INVALID_ARG ? 2 : 1;
+                }
+                shown = surface.data();
+            }
+            const int sw = surface.empty() ? W : W * scale_x, sh = surface.empty() ? H : H * scale_y;
+            if (!write_ppm(out_dir + name, shown, sw, sh)) { std::fprintf(stderr, "cannot write %s%s\n", out_dir.c_str(), name); return 1; }
         }
         if (!ramp.empty()) {
             if ((rc = par_quantize_host(&params, 0, ramp.data(), (int)ramp.size(), dither, fb.data(), 0, H, nullptr, index.data())) != PAR_OK) {

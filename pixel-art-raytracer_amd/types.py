@@ -14,6 +14,8 @@ SPRITE_TEXELS = SPRITE_W * SPRITE_H
 SLOTS = 8
 MAX_PALETTE = 256
 PALIDX_BACKGROUND = 0xFF
+MAX_SCALE = 16
+PRESENT_RGBA, PRESENT_BGRA = 0, 1
 
 COLOR = np.dtype([("red", "u1"), ("green", "u1"), ("blue", "u1"), ("alpha", "u1")])
 VEC3 = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")])
@@ -25,12 +27,13 @@ AABB = np.dtype([("px", "<i2"), ("py", "<i2"), ("pz", "<i2"), ("ex", "<i2"), ("e
 LIGHT = np.dtype([("x", "<i2"), ("y", "<i2"), ("z", "<i2"), ("radius", "<i2")])
 LIGHT_TINT = np.dtype([("r", "<f4"), ("g", "<f4"), ("b", "<f4")])  # par_light_tint
 OUTLINE_STYLE = np.dtype([("depth_step", "<i4"), ("silhouette_scale", "<i4"), ("crease_scale", "<i4")])  # par_outline_style
+PRESENT_DESC = np.dtype([("scale_x", "<i4"), ("scale_y", "<i4"), ("pitch", "<i4"), ("order", "<i4")])  # par_present_desc
 RAY = np.dtype([("inv_x", "<f4"), ("inv_y", "<f4"), ("inv_z", "<f4"), ("ox", "<i2"), ("oy", "<i2"), ("oz", "<i2"),
                 ("pad", "<i2")])
 
 assert COLOR.itemsize == 4 and VEC3.itemsize == 12 and PIXEL.itemsize == 28
 assert SPRITE.itemsize == 16000 and AABB.itemsize == 16 and LIGHT.itemsize == 8 and RAY.itemsize == 20
-assert LIGHT_TINT.itemsize == 12 and OUTLINE_STYLE.itemsize == 12
+assert LIGHT_TINT.itemsize == 12 and OUTLINE_STYLE.itemsize == 12 and PRESENT_DESC.itemsize == 16
 
 
 class Color(C.Structure):
@@ -97,6 +100,19 @@ def make_outline_style(depth_step=4, silhouette_scale=128, crease_scale=320):
     s = np.zeros(1, dtype=OUTLINE_STYLE)
     s["depth_step"], s["silhouette_scale"], s["crease_scale"] = depth_step, silhouette_scale, crease_scale
     return s
+
+
+def make_present_desc(scale_x=1, scale_y=None, pitch=None, order=PRESENT_RGBA, width=None):
+    """1-element PRESENT_DESC array (par_present_device): the integer scales (scale_y defaults to scale_x), the bytes
+    from one output row to the next (default: tight, 4 * width * scale_x, which needs `width`) and the byte order."""
+    scale_y = scale_x if scale_y is None else scale_y
+    if pitch is None:
+        if width is None:
+            raise ValueError("make_present_desc: give pitch, or width for a tight pitch")
+        pitch = 4 * width * scale_x
+    d = np.zeros(1, dtype=PRESENT_DESC)
+    d["scale_x"], d["scale_y"], d["pitch"], d["order"] = scale_x, scale_y, pitch, order
+    return d
 
 
 def make_aabbs(rows):
