@@ -516,6 +516,57 @@ int par_present_host(const par_params* params, int device, const par_present_des
                      const par_color* fb, const uint8_t* index, const par_color* palette, int n_colors,
                      int row_begin, int row_end, void* out);
 
+/* --- finish: outline, quantise and present a frame in one launch (nothing in the reference) ----------------------
+ * The tail of a frame loop as one call: render or relight, then finish. It takes the G-buffer and `fb` in and writes the
+ * scaled surface; the outlined frame and the index plane that the three calls above pass from one to the next are never
+ * written (the index plane only when asked for). It is a pass over finished planes and takes no context: retained
+ * frames, graphs and statistics are not involved and do not change. The contract is the three contracts above and
+ * nothing else, and it holds byte for byte.
+ * Stage 1, outlines, runs iff `style` is not NULL; `style` and `gbuf` are both given or both NULL. A = the fb_out of
+ * par_outline_device(params, style, gbuf, g0, g1, fb, r0, r1) with [g0, g1) = [gbuf_row_begin, gbuf_row_end) and
+ * [r0, r1) = [row_begin, row_end): the halo rule is that call's, 0 <= g0 <= r0 < r1 <= g1 <= height, a neighbour row
+ * outside [g0, g1) being absent. Without a style A = fb, and gbuf_row_begin and gbuf_row_end are not read.
+ * Stage 2, quantise, runs iff `d_palette` (`palette`) is not NULL; then 1 <= n_colors <= PAR_MAX_PALETTE and
+ * 0 <= spread <= 255. I = the index_out of par_quantize_device on A, the dither on the absolute row and column.
+ * `index_out` is nullable and gets I (rows [r0, r1), dense): it is what a later par_present_device needs for palette
+ * cycling. Without a palette n_colors and spread must be 0 and index_out NULL.
+ * Stage 3, present. With a palette `out` is what par_present_device(index = I, d_palette, n_colors) writes: all four
+ * bytes of the entry, its alpha included (I < n_colors always: the clamp never acts). Without a palette `out` is what
+ * par_present_device(fb = A) writes. Scale, order, pitch, the unwritten gap bytes [4 * W', pitch) and the addressing of
+ * `out` (output row r0 * sy, byte 0) are that call's.
+ * At least one of stages 1 and 2 must run: neither is PAR_ERR_INVALID_ARG, because that call is par_present_device.
+ * With a G-buffer halo a row block's surface (and index plane) equals those output rows of the whole frame's.
+ * PAR_ERR_INVALID_ARG, before any device work and with nothing written (no GPU is needed to get it), for a null
+ * `params`, `desc`, `fb` or `out`; the pairings above broken; and every range check of the three calls on the arguments
+ * in use: the style's fields and the row inequality with a style, 0 <= r0 < r1 <= height without one, n_colors and
+ * spread with a palette, a scale outside [1, PAR_MAX_SCALE], an order that is neither of the two, a pitch that is not a
+ * multiple of 4 or is below 4 * width * sx (formed in 64 bits), params->width <= 0.
+ * No overlap of `out` or `index_out` with any input is defined; `fb` and `gbuf` are only read. `gbuf`, `fb`, the palette
+ * and `out` must be 4-byte aligned, `index_out` may sit on any byte; `out` on a 16-byte boundary with a pitch that is a
+ * multiple of 16, and `index_out` on a 4-byte boundary of a frame whose width is a multiple of 4, take the kernel's wider
+ * stores, every other placement gives the same bytes. The kernel stays inside its arrays whatever the texels and pixels
+ * hold.
+ * Left out on purpose: no fb_out or edge_out planes (a caller who wants the intermediates has the three calls), no second
+ * palette for the present stage, no fusing into the render or light kernels, no graph-capture helper (the device call is
+ * capturable as any stream-ordered launch is), and no change to what the three calls above do. */
+/* device pointers (`d_palette` too), asynchronous on `stream` (a hipStream_t), no sync: on the frame's own stream, after
+ * the render or relight call */
+int par_finish_device(const par_params* params, void* stream,
+                      const par_outline_style* style, const par_pixel* gbuf, int gbuf_row_begin, int gbuf_row_end,
+                      const par_color* d_palette, int n_colors, int spread,
+                      const par_present_desc* desc,
+                      const par_color* fb, int row_begin, int row_end,
+                      void* out, uint8_t* index_out);
+/* host pointers, synchronous, everything on HIP device `device` (-1: the current device, as par_create): allocates,
+ * copies, launches, synchronises, copies back (`out` with a pitched copy: the caller's gap bytes stay) and frees;
+ * PAR_ERR_NO_DEVICE / PAR_ERR_OOM / PAR_ERR_HIP as par_present_host */
+int par_finish_host(const par_params* params, int device,
+                    const par_outline_style* style, const par_pixel* gbuf, int gbuf_row_begin, int gbuf_row_end,
+                    const par_color* palette, int n_colors, int spread,
+                    const par_present_desc* desc,
+                    const par_color* fb, int row_begin, int row_end,
+                    void* out, uint8_t* index_out);
+
 /* Debug overlay of alt:763-772 (Bresenham line from the picked pixel to the light) drawn into a host frame. */
 void par_debug_line(const par_params* params, const par_pixel* pick, int mouse_x, const par_light* light,
                     par_color* fb);

@@ -43,7 +43,7 @@ ABI_SYMBOLS = (
     "par_background_fill", "par_tiles_assemble", "par_scene_tile_map", "par_set_lights", "par_graph_capture_lights",
     "par_graph_stage_lights", "par_set_light_model", "par_set_light_tints", "par_relight_device", "par_relight_rows",
     "par_quantize_device", "par_quantize_host", "par_palette_ramp", "par_outline_device", "par_outline_host",
-    "par_present_device", "par_present_host",
+    "par_present_device", "par_present_host", "par_finish_device", "par_finish_host",
 )
 MAX_LIGHTS = 8  # PAR_MAX_LIGHTS
 LIGHTS_UNBOUNDED, LIGHTS_RANGED = 0, 1  # par_set_light_model
@@ -142,6 +142,8 @@ def lib():
         L.par_outline_host.argtypes = [vp, i32, vp, vp, i32, i32, vp, i32, i32, vp, vp]
         L.par_present_device.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
         L.par_present_host.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, vp]
+        L.par_finish_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, i32, vp, vp]
+        L.par_finish_host.argtypes = [vp, i32, vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, i32, vp, vp]
         L.par_debug_read_stamps.argtypes = [vp, vp, C.c_size_t]
         L.par_debug_set_hooks.argtypes = [vp, C.c_uint, i32]
         L.par_debug_read_light_walks.argtypes = [vp, vp]
@@ -617,3 +619,56 @@ def present_host(params, desc, rows=None, fb=None, index=None, palette=None, dev
     if rc != PAR_OK:
         raise ParError(rc, "par_present_host")
     return out
+
+
+# ---- finish ------------------------------------------------------------------------------------------------------
+
+def finish(params, desc, out, rows, fb, style=None, gbuf=None, gbuf_rows=None, d_palette=None, n_colors=0, spread=0,
+           index_out=None, stream=0):
+    """Device pointers (ints): outline, quantize and present in one launch (par_finish_device). Rows [rows[0], rows[1]) of
+    the frame block at `fb` are outlined from the G-buffer block at `gbuf` (rows `gbuf_rows`, default `rows`) when `style`
+    (an OUTLINE_STYLE array) is given, quantised to the n_colors entries at d_palette with dither `spread` when d_palette
+    is given (the index plane to index_out when asked for), and scaled onto the surface at `out` as `desc` (a PRESENT_DESC
+    array) says. At least one of style and d_palette. Asynchronous on `stream`: the call after render or relight."""
+    desc = np.ascontiguousarray(desc, dtype=PRESENT_DESC).reshape(-1)
+    if style is not None:
+        style = np.ascontiguousarray(style, dtype=OUTLINE_STYLE).reshape(-1)
+    g0, g1 = gbuf_rows or rows
+    rc = lib().par_finish_device(C.byref(params), C.c_void_p(stream), ptr(style), C.c_void_p(gbuf), g0, g1,
+                                 C.c_void_p(d_palette), n_colors, spread, ptr(desc), C.c_void_p(fb), rows[0], rows[1],
+                                 C.c_void_p(out), C.c_void_p(index_out))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_finish_device")
+
+
+def finish_host(params, desc, fb, rows=None, style=None, gbuf=None, gbuf_rows=None, palette=None, spread=0,
+                want_index=False, device=-1):
+    """The same on host arrays (par_finish_host): `fb` a COLOR array holding rows `rows` (default: the whole frame), `gbuf`
+    a PIXEL array holding rows `gbuf_rows` (default: `rows`) with `style`, `palette` a COLOR array. Returns the surface's
+    rows as a (rows * scale_y, pitch) uint8 array as present_host does (zeros in the gap bytes), or (surface, index plane)
+    with want_index."""
+    r0, r1 = rows or (0, params.height)
+    g0, g1 = gbuf_rows or (r0, r1)
+    desc = np.ascontiguousarray(desc, dtype=PRESENT_DESC).reshape(-1)
+    n = (r1 - r0) * params.width
+    fb = np.ascontiguousarray(fb, dtype=COLOR).reshape(-1)
+    if len(fb) != n:
+        raise ValueError(f"finish_host: fb holds {len(fb)} pixels, rows {r0}..{r1} of width {params.width} hold {n}")
+    if style is not None:
+        style = np.ascontiguousarray(style, dtype=OUTLINE_STYLE).reshape(-1)
+    if gbuf is not None:
+        gbuf = np.ascontiguousarray(gbuf, dtype=PIXEL).reshape(-1)
+        if len(gbuf) != (g1 - g0) * params.width:
+            raise ValueError(f"finish_host: gbuf holds {len(gbuf)} texels, rows {g0}..{g1} of width {params.width} hold "
+                             f"{(g1 - g0) * params.width}")
+    n_colors = 0
+    if palette is not None:
+        palette = np.ascontiguousarray(palette, dtype=COLOR).reshape(-1)
+        n_colors = len(palette)
+    out = np.zeros((max(0, r1 - r0) * max(0, int(desc["scale_y"][0])), max(0, int(desc["pitch"][0]))), dtype=np.uint8)
+    index = np.zeros(n, dtype=np.uint8) if want_index else None
+    rc = lib().par_finish_host(C.byref(params), device, ptr(style), ptr(gbuf), g0, g1, ptr(palette), n_colors, spread,
+                               ptr(desc), ptr(fb), r0, r1, out.ctypes.data_as(C.c_void_p), ptr(index))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_finish_host")
+    return (out, index) if want_index else out

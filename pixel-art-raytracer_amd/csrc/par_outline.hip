@@ -25,6 +25,7 @@
 #include <cstdint>
 #include <cstring>
 
+#include "par_post.h"
 #include "par_raytracer.h"
 
 namespace {
@@ -60,41 +61,6 @@ struct OutlineArgs {
     uint32_t background;  // w3 of the background texel
     int depth_step, silhouette_scale, crease_scale;
 };
-
-// What a pixel's class needs of a texel.
-struct Texel {
-    bool covered;
-    uint32_t key, entity, n0, n1, n2;
-};
-
-__device__ __forceinline__ Texel texel_at(const uint32_t* w, uint32_t background) {
-    const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4], w5 = w[5], w6 = w[6];
-    Texel t;
-    t.covered = (w0 | w1 | w2 | (w3 ^ background) | w4 | w5 | w6) != 0;
-    t.key = w4 - w5;
-    t.entity = w6;
-    t.n0 = w0; t.n1 = w1; t.n2 = w2;
-    return t;
-}
-
-// (bitwise operators on purpose in these two: nothing here is worth a branch)
-// `t` (covered) meets the silhouette condition against its present neighbour `n`
-__device__ __forceinline__ int silhouette_against(const Texel& t, const Texel& n, int depth_step) {
-    return (int)!n.covered | ((int)(n.entity != t.entity) & (int)((int32_t)(t.key - n.key) >= depth_step));
-}
-
-// the right or down neighbour `n` of `t` (covered) makes `t` a crease
-__device__ __forceinline__ int crease_with(const Texel& t, const Texel& n, int present, int depth_step) {
-    return present & (int)n.covered & (1 ^ silhouette_against(n, t, depth_step)) &
-           (int)(((n.n0 ^ t.n0) | (n.n1 ^ t.n1) | (n.n2 ^ t.n2)) != 0u);
-}
-
-__device__ __forceinline__ uint32_t scaled(uint32_t px, int s) {
-    const uint32_t r = std::min(255u, ((px & 0xFFu) * (uint32_t)s) >> 8);
-    const uint32_t g = std::min(255u, (((px >> 8) & 0xFFu) * (uint32_t)s) >> 8);
-    const uint32_t b = std::min(255u, (((px >> 16) & 0xFFu) * (uint32_t)s) >> 8);
-    return r | (g << 8) | (b << 16) | (px & 0xFF000000u);
-}
 
 // The shift (0..3 dwords) of staged row `j` of the tile at column tx0, absolute row r: with it the LDS index of a
 // texel's dword is congruent, modulo 4, to its dword address in memory (7 = -1 modulo 4).

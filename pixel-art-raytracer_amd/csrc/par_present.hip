@@ -18,6 +18,7 @@
 #include <cstring>
 
 #include "par_fastdiv.h"
+#include "par_post.h"
 #include "par_raytracer.h"
 
 namespace {
@@ -28,11 +29,6 @@ constexpr int PRESENT_THREADS = 256;
 // Output pixels of one row of one launch, summed over its source rows (the groups' padding included): flat group
 // indices and both divisions stay below 2^31 (par_udiv31).
 constexpr uint32_t PRESENT_MAX_PX = 0x7FFFFFF0u;
-
-// red and blue of a par_color read as one little-endian word exchanged
-__device__ __forceinline__ uint32_t exchanged(uint32_t c) {
-    return (c & 0xFF00FF00u) | ((c & 0xFFu) << 16) | ((c >> 16) & 0xFFu);
-}
 
 // INDEXED: `src` is an index plane (bytes) and `palette` its palette; else `src` is a frame (words). VEC: `out` and
 // `pitch` are multiples of 16. `wide_src` (VEC, a frame, sx == 1, `src` on a 16-byte boundary, width a multiple of 4):

@@ -17,6 +17,7 @@
 #include <cstring>
 
 #include "par_fastdiv.h"
+#include "par_post.h"
 #include "par_raytracer.h"
 
 namespace {
@@ -24,32 +25,8 @@ namespace {
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int QUANT_THREADS = 256;
-constexpr uint32_t QUANT_RGB = 0x00FFFFFFu;  // red, green, blue of a par_color read as one little-endian word
 // Pixels of one launch: flat indices and the division by the width stay below 2^31 (par_udiv31).
 constexpr uint32_t QUANT_MAX_PX = 0x7FFFFFF0u;
-
-// The 4x4 Bayer matrix of the contract, B4[y & 3][x & 3], as sixteen nibbles: entry (y, x) at bit 4 * (4 * y + x).
-constexpr int BAYER4[4][4] = {{0, 8, 2, 10}, {12, 4, 14, 6}, {3, 11, 1, 9}, {15, 7, 13, 5}};
-constexpr uint64_t bayer_nibbles() {
-    uint64_t v = 0;
-    for (int y = 0; y < 4; y++) {
-        for (int x = 0; x < 4; x++) v |= (uint64_t)BAYER4[y][x] << (4 * (4 * y + x));
-    }
-    return v;
-}
-constexpr uint64_t BAYER_NIBBLES = bayer_nibbles();
-
-// c' = min(255, max(0, c + off)) on the three colour channels; the alpha byte of the result is 0.
-__device__ __forceinline__ uint32_t dithered(uint32_t px, uint32_t x, uint32_t y, int spread) {
-    const int t = (int)((BAYER_NIBBLES >> (((y & 3u) << 4) | ((x & 3u) << 2))) & 15u);
-    const int off = ((2 * t - 15) * spread) >> 5;  // floor: an arithmetic shift rounds towards minus infinity
-    const int r = std::min(255, std::max(0, (int)(px & 0xFFu) + off));
-    const int g = std::min(255, std::max(0, (int)((px >> 8) & 0xFFu) + off));
-    const int b = std::min(255, std::max(0, (int)((px >> 16) & 0xFFu) + off));
-    return (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16);
-}
-
-__device__ __forceinline__ uint32_t min3u(uint32_t a, uint32_t b, uint32_t c) { return std::min(std::min(a, b), c); }
 
 template <bool DITHER, bool VEC>
 __global__ __launch_bounds__(QUANT_THREADS) void quantize_kernel(const uint32_t* fb, uint32_t* fb_out, uint8_t* index_out,

@@ -7,7 +7,7 @@
 // alt:815-817.
 //
 //   par_demo [--keys RRRRUUUUhhhhjjPP] [--frames N] [--out DIR] [--gif FILE] [--debug-line] [--as-sdl] [--size W H L]
-//            [--palette-levels K] [--dither S] [--outline S,C,D] [--scale SX[,SY]]
+//            [--palette-levels K] [--dither S] [--outline S,C,D] [--scale SX[,SY]] [--finish]
 //
 // --gif writes the frames as one animated GIF89a (100 ms per frame like the reference's gif.gif); a frame's colours
 // are palette entries times a brightness, at most a few hundred distinct values, so each frame gets an exact local
@@ -28,6 +28,12 @@
 // --scale SX[,SY] (with --out; each 1..16, SY defaults to SX) writes the PPM frames at W * SX x H * SY: the frame as it
 // stands when it is written (after the outline, the debug line and --as-sdl's exchange) put on a surface of that size on
 // the GPU (par_present_host, nearest neighbour, tight pitch, RGBA order). GIFs stay at view size.
+//
+// --finish (with --out, and with --outline or --palette-levels or both) makes every frame's PPM the surface of ONE
+// par_finish_host call in place of the separate host calls: the style of --outline, the ramp of --palette-levels and
+// --dither, the scale of --scale (default 1), tight pitch, RGBA order. With a ramp the PPM shows the ramp's colours, and
+// the frame of --gif is that call's index plane; without a ramp the frame of --gif is the outlined frame at scale 1.
+// --debug-line and --as-sdl act between the stages and are refused together with it.
 //
 // Letters: R L U D P N = right, left, up, down, page-up, page-down; a k j u h o as in the reference. Frame 0 gets no
 // key; frame k applies key k-1 (cycling when --frames exceeds the script).
@@ -204,7 +210,7 @@ class GifWriter {
 int main(int argc, char** argv) {
     std::string keys = "RRRRUUUUhhhhjjPP", out_dir, gif_path;
     int frames = -1, W = 480, H = 320, L = 320, palette_levels = 0, dither = 0;
-    bool debug_line = false, as_sdl = false, outline = false;
+    bool debug_line = false, as_sdl = false, outline = false, finish = false;
     int scale_x = 0, scale_y = 0;  // 0: no --scale
     par_outline_style outline_style{4, 256, 256};
     for (int i = 1; i < argc; i++) {
@@ -214,6 +220,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--gif") && i + 1 < argc) gif_path = argv[++i];
         else if (!std::strcmp(argv[i], "--debug-line")) debug_line = true;
         else if (!std::strcmp(argv[i], "--as-sdl")) as_sdl = true;
+        else if (!std::strcmp(argv[i], "--finish")) finish = true;
         else if (!std::strcmp(argv[i], "--palette-levels") && i + 1 < argc) palette_levels = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--dither") && i + 1 < argc) dither = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--outline") && i + 1 < argc) {
@@ -236,6 +243,12 @@ int main(int argc, char** argv) {
         else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
     if (frames < 0) frames = (int)keys.size() + 1;
+    if (finish) {
+        if (out_dir.empty()) { std::fprintf(stderr, "--finish wants --out\n"); return 2; }
+        if (!outline && palette_levels == 0) { std::fprintf(stderr, "--finish wants --outline or --palette-levels: without both it is --scale\n"); return 2; }
+        if (debug_line || as_sdl) { std::fprintf(stderr, "--finish cannot go with --debug-line or --as-sdl: they act between its stages\n"); return 2; }
+        if (scale_x == 0) scale_x = scale_y = 1;
+    }
 
     par_params params;
     par_default_params(&params);
@@ -262,11 +275,12 @@ int main(int argc, char** argv) {
     std::vector<par_pixel> gbuf((size_t)W * H);
     std::vector<unsigned char> rgb((size_t)W * H * 3);
     std::vector<par_color> surface;  // --scale: the frame as the PPM shows it
+    std::vector<par_color> view;     // --finish with --gif, no ramp, a scale other than 1: the outlined frame at view size
     if (scale_x > 0 && !out_dir.empty()) surface.resize((size_t)W * scale_x * H * scale_y);
     // --palette-levels: the GIF's frames are index planes over the scene's ramp
     std::vector<par_color> ramp;
     std::vector<unsigned char> index;
-    if (palette_levels != 0 && !gif_path.empty()) {
+    if (palette_levels != 0 && (finish || !gif_path.empty())) {
         ramp.resize(PAR_MAX_PALETTE);
         const int n_ramp = par_palette_ramp(&params, palette_levels, ramp.data(), (int)ramp.size());
         if (n_ramp < 0) { std::fprintf(stderr, "--palette-levels %d: %s\n", palette_levels, par_status_string(-n_ramp)); return 2; }
@@ -289,13 +303,45 @@ int main(int argc, char** argv) {
             return 1;
         }
         const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        std::printf("frame %d: %.3fms  player <%d, %d, %d>  light <%d, %d, %d>\n", f, ms, aabbs[0].px, aabbs[0].py,
+                    aabbs[0].pz, light.x, light.y, light.z);  // alt:815-817 prints the frame time
+        if (finish) {
+            const par_outline_style* style = outline ? &outline_style : nullptr;
+            const par_pixel* g = outline ? gbuf.data() : nullptr;
+            const par_color* pal = ramp.empty() ? nullptr : ramp.data();
+            const par_present_desc desc{scale_x, scale_y, 4 * W * scale_x, PAR_PRESENT_RGBA};
+            if ((rc = par_finish_host(&params, 0, style, g, 0, H, pal, (int)ramp.size(), pal ? dither : 0, &desc, fb.data(), 0, H,
+                                      surface.data(), pal ? index.data() : nullptr)) != PAR_OK) {
+                std::fprintf(stderr, "par_finish_host: %s\n", par_status_string(rc));
+                return rc == PAR_ERR_INVALID_ARG ? 2 : 1;
+            }
+            char name[64];
+            std::snprintf(name, sizeof(name), "/frame_%03d.ppm", f);
+            if (!write_ppm(out_dir + name, surface.data(), W * scale_x, H * scale_y)) { std::fprintf(stderr, "cannot write %s%s\n", out_dir.c_str(), name); return 1; }
+            if (pal && !gif_path.empty()) {
+                gif.frame(index, ramp, 10);
+            } else if (!gif_path.empty()) {
+                // the outlined frame at view size: the surface itself at scale 1, else one more call at scale 1
+                const par_color* shown = surface.data();
+                if (scale_x != 1 || scale_y != 1) {
+                    const par_present_desc one{1, 1, 4 * W, PAR_PRESENT_RGBA};
+                    view.resize(fb.size());
+                    if ((rc = par_finish_host(&params, 0, style, g, 0, H, nullptr, 0, 0, &one, fb.data(), 0, H, view.data(), nullptr)) != PAR_OK) {
+                        std::fprintf(stderr, "par_finish_host: %s\n", par_status_string(rc));
+                        return 1;
+                    }
+                    shown = view.data();
+                }
+                for (size_t i = 0; i < fb.size(); i++) { rgb[i * 3] = shown[i].red; rgb[i * 3 + 1] = shown[i].green; rgb[i * 3 + 2] = shown[i].blue; }
+                gif.frame(rgb, 10);
+            }
+            continue;
+        }
         if (outline && (rc = par_outline_host(&params, 0, &outline_style, gbuf.data(), 0, H, fb.data(), 0, H, fb.data(), nullptr)) != PAR_OK) {
             std::fprintf(stderr, "par_outline_host: %s\n", par_status_string(rc));
             return rc == PAR_ERR_INVALID_ARG ? 2 : 1;
         }
         if (debug_line) par_debug_line(&params, &gbuf[(size_t)mouse_y * W + mouse_x], mouse_x, &light, fb.data());
-        std::printf("frame %d: %.3fms  player <%d, %d, %d>  light <%d, %d, %d>\n", f, ms, aabbs[0].px, aabbs[0].py,
-                    aabbs[0].pz, light.x, light.y, light.z);  // alt:815-817 prints the frame time
         if (as_sdl) {
             for (auto& c : fb) std::swap(c.red, c.blue);
         }
