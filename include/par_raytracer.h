@@ -371,6 +371,76 @@ int par_tiles_assemble(const par_params* params, void* stream, const int32_t* d_
                        par_color* frame, int row_begin, int row_end);
 int par_scene_tile_map(const par_params* params, const int32_t* tiles, int n, int32_t* map, int capacity);
 
+/* --- changed tiles: copying back only the tiles that differ from the last frame (nothing in the reference) --------
+ * A frame on the device costs tens of microseconds; the same frame copied to the host costs milliseconds, and in a
+ * frame loop almost nothing on screen changes from one frame to the next. These calls compare two finished `fb` planes
+ * tile by tile on the device, pack the tiles that differ by a count that never leaves the device, fetch them with one
+ * small and one proportional copy, and apply them to the host's copy of the frame. Like the other passes over finished
+ * planes they take no context: retained frames, graphs and statistics are not involved and do not change, and the
+ * planes may come from a render, a relit frame, a graph's frame, an outlined or quantised frame, or a row block of a
+ * sharded frame. par_scene_tiles cannot stand in for the comparison: it is a superset computed from the geometry and
+ * knows nothing of lights, outlines or palette output, which change pixels without moving an AABB.
+ * In everything below B = params->bin_size, gx = ceil(width / B), gy = ceil(height / B); params->length, the ambient,
+ * the background and the palette are not read. Tile (bx, by) covers columns [bx * B, min((bx + 1) * B, width)) and rows
+ * [by * B, min((by + 1) * B, height)); a tile word is bx | by << 16, a slot is B x B pixels, row-major, as
+ * par_tiles_pack has them.
+ * The property that ties the four calls together: take a host frame that equals `a` on the rows [r0, r1). When
+ * count <= capacity, par_tiles_changed_device(a, b) -> par_tiles_pack_counted on b -> par_tiles_fetch ->
+ * par_tiles_apply_host turns that frame into `b` on those rows and leaves every other row alone.
+ * Left out on purpose: no comparison of planes other than 4-byte fb planes (index planes and the G-buffer are a later
+ * step), no tolerance or "nearly equal", no bounding rectangle, no copy of b over a (a swap chain already holds the
+ * previous frame in its other slot), no device-side apply (par_tiles_unpack is that), no graph-capture helper (the two
+ * device calls are capturable as any stream-ordered launch is), and no change to par_render's own copy. */
+
+/* Which tiles differ. Device pointers, asynchronous on `stream` (a hipStream_t): no synchronisation, no allocation, no
+ * copy to the host. `a` and `b` each address (row_begin, column 0) and hold rows [r0, r1) = [row_begin, row_end), dense
+ * and row-major; both are only read, and a == b is allowed (count 0). A tile is IN THE BLOCK iff its rows intersect
+ * [r0, r1). A tile is CHANGED iff it is in the block and some pixel differs between a and b as a 32-bit word (the alpha
+ * byte counts), among the pixels whose column is in the tile and whose row is in both the tile and the block.
+ *     d_map   gx * gy entries, every one written: d_map[bx + by * gx] is the tile's rank among the changed tiles in
+ *             ascending (by, bx) order -- its slot in a packed buffer -- or -1 when the tile is unchanged or not in the
+ *             block (the format par_tiles_assemble reads). The rank is written whatever `capacity` is. d_map doubles as
+ *             the call's work array, which is why it may not be NULL.
+ *     d_tiles d_tiles[i] = bx | by << 16 of the changed tile of rank i, for i < min(count, capacity); the entries from
+ *             there on are not written. May be NULL when capacity is 0.
+ *     d_count d_count[0] = the number of changed tiles, which may exceed `capacity`.
+ * The output is a function of the two planes alone: it does not depend on the order in which workgroups run (ordering
+ * is by kernel boundaries; no flag is polled and no global atomic is used).
+ * PAR_ERR_INVALID_ARG, before any device work and with nothing written (no GPU is needed to get it), for a null
+ * `params`, `a`, `b`, `d_map` or `d_count`, capacity < 0, a null d_tiles with capacity > 0, width <= 0 or height <= 0,
+ * a bin size outside [8, 160] (as par_tiles_pack), or rows that are not 0 <= r0 < r1 <= height; PAR_ERR_UNSUPPORTED,
+ * as early, for gx or gy above 1024 (par_create's bound; the tile word depends on it). The pointers have their types'
+ * alignment; planes on 16-byte boundaries with width % 4 == 0 and B % 4 == 0 take wider loads, every other placement
+ * gives the same result. The loads are bounded by the block's rows and the view's width whatever the planes hold. */
+int par_tiles_changed_device(const par_params* params, void* stream, const par_color* a, const par_color* b,
+                             int row_begin, int row_end, int32_t* d_map, int32_t* d_tiles, int capacity,
+                             int32_t* d_count);
+/* par_tiles_pack by a count that stays on the device. Device pointers, asynchronous on `stream`. With m =
+ * min(max(d_count[0], 0), capacity) read on the device, the result is what par_tiles_pack(params, stream, d_tiles, m,
+ * fb_block, row_begin, row_end, packed) writes, byte for byte: slot pixels outside the block's rows or beyond the view's
+ * edge are not written, and slots from m on are not written. A list entry with bx >= gx or by >= gy is skipped, so the
+ * kernel stays inside the frame whatever the list holds. capacity == 0 launches nothing. The argument checks are
+ * par_tiles_pack's (PAR_ERR_INVALID_ARG for a null `params`, width or height <= 0, a bin size outside [8, 160], null
+ * d_tiles, fb_block or packed with capacity > 0, or rows that are not 0 <= row_begin <= row_end <= height), plus a null
+ * d_count and capacity < 0. */
+int par_tiles_pack_counted(const par_params* params, void* stream, const int32_t* d_tiles, const int32_t* d_count,
+                           int capacity, const par_color* fb_block, int row_begin, int row_end, par_color* packed);
+/* The only call of the four that waits for the device: synchronises `stream` and copies d_count[0] to *count. If
+ * 0 <= *count <= capacity then *n = *count, and *n tile words and *n * B * B pixels are copied into the host arrays
+ * `tiles` and `packed` (pageable or pinned). Otherwise *n = 0 and nothing more is copied: the list is incomplete, and
+ * the caller copies the frame instead. PAR_OK either way. A copy that fails returns PAR_ERR_HIP, a missing device
+ * PAR_ERR_NO_DEVICE; PAR_ERR_INVALID_ARG, before any device work, for a null pointer, capacity < 0, width or
+ * height <= 0 or a bin size outside [8, 160]. */
+int par_tiles_fetch(const par_params* params, void* stream, const int32_t* d_count, const int32_t* d_tiles,
+                    const par_color* d_packed, int capacity, int32_t* tiles, par_color* packed, int* n, int* count);
+/* Host arithmetic, no GPU needed. `frame` addresses row 0 of a whole host frame. For each i < n, the pixels of slot i
+ * whose row lies in both the tile and [row_begin, row_end) and whose column lies in the tile go to their place in
+ * `frame`; nothing else is written. PAR_ERR_INVALID_ARG, after every entry is checked and before anything is written,
+ * for a null `params`, null tiles, packed or frame with n > 0, n < 0, rows that are not 0 <= row_begin < row_end <=
+ * height, width or height <= 0, a bin size outside [8, 160], or any entry with bx >= gx or by >= gy. */
+int par_tiles_apply_host(const par_params* params, const int32_t* tiles, int n, const par_color* packed,
+                         int row_begin, int row_end, par_color* frame);
+
 /* --- outlines: silhouettes and creases drawn from the G-buffer (nothing in the reference) ------------------------
  * The post-process pixel-art renderers use most: a dark line where one object ends in front of another or in front of
  * the background, a highlight where a box's top face meets its front face. Everything it needs is in the G-buffer

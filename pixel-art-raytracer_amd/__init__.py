@@ -43,7 +43,8 @@ ABI_SYMBOLS = (
     "par_background_fill", "par_tiles_assemble", "par_scene_tile_map", "par_set_lights", "par_graph_capture_lights",
     "par_graph_stage_lights", "par_set_light_model", "par_set_light_tints", "par_relight_device", "par_relight_rows",
     "par_quantize_device", "par_quantize_host", "par_palette_ramp", "par_outline_device", "par_outline_host",
-    "par_present_device", "par_present_host", "par_finish_device", "par_finish_host",
+    "par_present_device", "par_present_host", "par_finish_device", "par_finish_host", "par_tiles_changed_device",
+    "par_tiles_pack_counted", "par_tiles_fetch", "par_tiles_apply_host",
 )
 MAX_LIGHTS = 8  # PAR_MAX_LIGHTS
 LIGHTS_UNBOUNDED, LIGHTS_RANGED = 0, 1  # par_set_light_model
@@ -135,6 +136,10 @@ def lib():
         L.par_background_fill.argtypes = [vp, vp, vp, i32]
         L.par_tiles_assemble.argtypes = [vp, vp, vp, vp, vp, i32, i32]
         L.par_scene_tile_map.argtypes = [vp, vp, i32, vp, i32]
+        L.par_tiles_changed_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, i32, vp]
+        L.par_tiles_pack_counted.argtypes = [vp, vp, vp, vp, i32, vp, i32, i32, vp]
+        L.par_tiles_fetch.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+        L.par_tiles_apply_host.argtypes = [vp, vp, i32, vp, i32, i32, vp]
         L.par_quantize_device.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, vp, vp]
         L.par_quantize_host.argtypes = [vp, i32, vp, i32, i32, vp, i32, i32, vp, vp]
         L.par_palette_ramp.argtypes = [vp, i32, vp, i32]
@@ -483,6 +488,53 @@ def background_fill(params, rows_ptr, n_rows, stream=0):
     rc = lib().par_background_fill(C.byref(params), C.c_void_p(stream), C.c_void_p(rows_ptr), n_rows)
     if rc != PAR_OK:
         raise ParError(rc, "par_background_fill")
+
+
+# ---- changed tiles -----------------------------------------------------------------------------------------------
+
+def tiles_changed(params, a, b, rows, d_map, d_tiles, capacity, d_count, stream=0):
+    """Device pointers (ints): the tiles of the frame block `rows` that differ between the planes at `a` and `b`
+    (par_tiles_changed_device, asynchronous): ranks or -1 into d_map (grid-x * grid-y entries), the first `capacity`
+    tile words into d_tiles, the total into d_count[0]."""
+    rc = lib().par_tiles_changed_device(C.byref(params), C.c_void_p(stream), C.c_void_p(a), C.c_void_p(b), rows[0],
+                                        rows[1], C.c_void_p(d_map), C.c_void_p(d_tiles), capacity, C.c_void_p(d_count))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_tiles_changed_device")
+
+
+def tiles_pack_counted(params, d_tiles, d_count, capacity, fb_block, rows, packed, stream=0):
+    """Device pointers (ints): tiles_pack with n = min(max(d_count[0], 0), capacity) read on the device (asynchronous)."""
+    rc = lib().par_tiles_pack_counted(C.byref(params), C.c_void_p(stream), C.c_void_p(d_tiles), C.c_void_p(d_count),
+                                      capacity, C.c_void_p(fb_block), rows[0], rows[1], C.c_void_p(packed))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_tiles_pack_counted")
+
+
+def tiles_fetch(params, d_count, d_tiles, d_packed, capacity, tiles, packed, stream=0):
+    """Waits for `stream`, then copies the count and, when it is within `capacity`, that many tile words and slots from
+    the device pointers (ints) into the host arrays `tiles` (int32) and `packed` (COLOR), pageable or pinned
+    (par_tiles_fetch). Returns (n, count): n == count when the list is complete, else n == 0 and nothing was copied."""
+    n, count = C.c_int(0), C.c_int(0)
+    rc = lib().par_tiles_fetch(C.byref(params), C.c_void_p(stream), C.c_void_p(d_count), C.c_void_p(d_tiles),
+                               C.c_void_p(d_packed), capacity, _host_ptr(tiles), _host_ptr(packed), C.byref(n),
+                               C.byref(count))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_tiles_fetch")
+    return n.value, count.value
+
+
+def tiles_apply_host(params, tiles, n, packed, rows, frame):
+    """Host arrays (or host addresses as ints): slots packed[0, n) of the tiles tiles[0, n) to their place in the whole
+    host frame `frame`, on the rows `rows` only (par_tiles_apply_host: host arithmetic, no GPU needed)."""
+    rc = lib().par_tiles_apply_host(C.byref(params), _host_ptr(tiles), n, _host_ptr(packed), rows[0], rows[1],
+                                    _host_ptr(frame))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_tiles_apply_host")
+
+
+def _host_ptr(a):
+    """A host array, or a host address as an int (pinned staging)."""
+    return C.c_void_p(a) if isinstance(a, int) else ptr(a)
 
 
 # ---- outlines ----------------------------------------------------------------------------------------------------
