@@ -387,8 +387,8 @@ int par_scene_tile_map(const par_params* params, const int32_t* tiles, int n, in
  * The property that ties the four calls together: take a host frame that equals `a` on the rows [r0, r1). When
  * count <= capacity, par_tiles_changed_device(a, b) -> par_tiles_pack_counted on b -> par_tiles_fetch ->
  * par_tiles_apply_host turns that frame into `b` on those rows and leaves every other row alone.
- * Left out on purpose: no comparison of planes other than 4-byte fb planes (index planes and the G-buffer are a later
- * step), no tolerance or "nearly equal", no bounding rectangle, no copy of b over a (a swap chain already holds the
+ * Left out on purpose: no comparison of planes other than 4-byte fb planes (index planes and the G-buffer have the
+ * par_plane_tiles_* calls further down), no tolerance or "nearly equal", no bounding rectangle, no copy of b over a (a swap chain already holds the
  * previous frame in its other slot), no device-side apply (par_tiles_unpack is that), no graph-capture helper (the two
  * device calls are capturable as any stream-ordered launch is), and no change to par_render's own copy. */
 
@@ -440,6 +440,108 @@ int par_tiles_fetch(const par_params* params, void* stream, const int32_t* d_cou
  * height, width or height <= 0, a bin size outside [8, 160], or any entry with bx >= gx or by >= gy. */
 int par_tiles_apply_host(const par_params* params, const int32_t* tiles, int n, const par_color* packed,
                          int row_begin, int row_end, par_color* frame);
+
+/* --- plane tiles: the tile calls for planes of 1-, 4- and 28-byte elements (nothing in the reference) ------------
+ * The calls above move `fb` planes. The plane a frame loop most wants on the host is often another one: the index
+ * plane of par_quantize_device or par_finish_device (1 byte a pixel, a quarter of the copy), or the G-buffer a host picks
+ * from. A tile of any plane is a run of B * E bytes per row, so these seven calls are par_tiles_pack, par_tiles_unpack,
+ * par_tiles_assemble, par_tiles_changed_device, par_tiles_pack_counted, par_tiles_fetch and par_tiles_apply_host with
+ * "pixel" read as "element of E = elem_bytes bytes". E is 1 (`palidx`, `lit`, index_out of par_quantize_device,
+ * edge_out of par_outline_device), 4 (`fb`, `brightness`) or 28 (`gbuf`); any other value is PAR_ERR_INVALID_ARG.
+ * In everything below B = params->bin_size, gx = ceil(width / B), gy = ceil(height / B); params->length (except where
+ * par_plane_tiles_assemble checks it), the ambient, the background and the palette are not read. Tile (bx, by) covers
+ * columns [bx * B, min((bx + 1) * B, width)) and rows [by * B, min((by + 1) * B, height)); a tile word is bx | by << 16.
+ * A PLANE is dense and row-major, width * E bytes a row, and addresses (row_begin, column 0) unless a call says row 0.
+ * A SLOT is B * B * E bytes: slot i starts at byte i * B * B * E of a packed buffer, and element (ry, cx) of it is at
+ * byte (ry * B + cx) * E of the slot. Planes and packed buffers are void* with the alignment of their element: any
+ * byte for E = 1, 4 bytes for E = 4 and E = 28. The width and B may be odd; slots of an odd B start on odd bytes.
+ * The kernels move units of 16, 8, 4 or 1 bytes, the largest that divides width * E, B * E and every address involved,
+ * so that a unit never spans two tiles; every placement gives the same bytes. With E = 4 (and `fill` set to the
+ * background colour for assemble) every output equals the 4-byte call's, byte for byte.
+ * The property that ties the changed-tiles four together holds here as there: take a host plane that equals `a` on the
+ * rows [r0, r1). When count <= capacity, par_plane_tiles_changed_device(a, b) -> par_plane_tiles_pack_counted on b ->
+ * par_plane_tiles_fetch -> par_plane_tiles_apply_host turns it into `b` on those rows and leaves every other row alone.
+ * Left out on purpose: no union of several planes' changes in one call (a caller with `fb` and `palidx` calls twice),
+ * no element sizes other than the three, no rerouting of the eight 4-byte calls through these kernels, no change to
+ * par_ranks or to the benchmark, and no demo flag. */
+
+/* Which tiles differ. Device pointers, asynchronous on `stream` (a hipStream_t): no synchronisation, no allocation, no
+ * copy to the host. `a` and `b` each address (row_begin, column 0) and hold rows [r0, r1) = [row_begin, row_end); both
+ * are only read, and a == b is allowed (count 0). A tile is IN THE BLOCK iff its rows intersect [r0, r1). A tile is
+ * CHANGED iff it is in the block and some byte differs between a and b among the elements whose column is in the tile
+ * and whose row is in both the tile and the block.
+ *     d_map   gx * gy entries, every one written: d_map[bx + by * gx] is the tile's rank among the changed tiles in
+ *             ascending (by, bx) order -- its slot in a packed buffer -- or -1 when the tile is unchanged or not in the
+ *             block (the format par_plane_tiles_assemble reads). The rank is written whatever `capacity` is. d_map
+ *             doubles as the call's work array, which is why it may not be NULL.
+ *     d_tiles d_tiles[i] = bx | by << 16 of the changed tile of rank i, for i < min(count, capacity); the entries from
+ *             there on are not written. May be NULL when capacity is 0.
+ *     d_count d_count[0] = the number of changed tiles, which may exceed `capacity`.
+ * The output is a function of the two planes alone: it does not depend on the order in which workgroups run (ordering
+ * is by kernel boundaries; no flag is polled and no global atomic is used).
+ * PAR_ERR_INVALID_ARG, before any device work and with nothing written (no GPU is needed to get it), for an elem_bytes
+ * other than 1, 4 or 28, a null `params`, `a`, `b`, `d_map` or `d_count`, capacity < 0, a null d_tiles with capacity > 0,
+ * width <= 0 or height <= 0, a bin size outside [8, 160], or rows that are not 0 <= r0 < r1 <= height;
+ * PAR_ERR_UNSUPPORTED, as early, for gx or gy above 1024. The loads are bounded by the block's rows and the view's width
+ * whatever the planes hold. */
+int par_plane_tiles_changed_device(const par_params* params, void* stream, int elem_bytes, const void* a, const void* b,
+                                   int row_begin, int row_end, int32_t* d_map, int32_t* d_tiles, int capacity,
+                                   int32_t* d_count);
+/* Copy tiles d_tiles[0, n) (device array) out of a plane block -- rows [row_begin, row_end) of the plane, stored at
+ * `block` -- into `packed`: n slots. Slot bytes outside the block's rows or beyond the view's right / bottom edge are
+ * not written, and slots from n on are not written. A list entry with bx >= gx or by outside [0, gy) is skipped, so the
+ * kernel stays inside the block whatever the list holds. Asynchronous on `stream`; device pointers; n == 0 launches
+ * nothing. PAR_ERR_INVALID_ARG, before any device work, for an elem_bytes other than 1, 4 or 28, a null `params`, width
+ * or height <= 0, a bin size outside [8, 160], n < 0, null d_tiles, block or packed with n > 0, or rows that are not
+ * 0 <= row_begin <= row_end <= height. */
+int par_plane_tiles_pack(const par_params* params, void* stream, int elem_bytes, const int32_t* d_tiles, int n,
+                         const void* block, int row_begin, int row_end, void* packed);
+/* par_plane_tiles_pack by a count that stays on the device. Device pointers, asynchronous on `stream`. With m =
+ * min(max(d_count[0], 0), capacity) read on the device, the result is what par_plane_tiles_pack(params, stream,
+ * elem_bytes, d_tiles, m, block, row_begin, row_end, packed) writes, byte for byte: slot bytes outside the block's rows
+ * or beyond the view's edge are not written, slots from m on are not written, and a list entry with bx >= gx or by
+ * outside [0, gy) is skipped. capacity == 0 launches nothing. PAR_ERR_INVALID_ARG, before any device work, for an
+ * elem_bytes other than 1, 4 or 28, a null `params`, width or height <= 0, a bin size outside [8, 160], a null d_count,
+ * capacity < 0, null d_tiles, block or packed with capacity > 0, or rows that are not 0 <= row_begin <= row_end <=
+ * height. */
+int par_plane_tiles_pack_counted(const par_params* params, void* stream, int elem_bytes, const int32_t* d_tiles,
+                                 const int32_t* d_count, int capacity, const void* block, int row_begin, int row_end,
+                                 void* packed);
+/* The inverse of par_plane_tiles_pack on a whole plane (`frame` addresses row 0): the elements of slot i that lie in
+ * the view go to their place in `frame`, for i < n; nothing else is written. A list entry with bx >= gx or by outside
+ * [0, gy) is skipped, so the kernel stays inside the frame whatever the list holds. Asynchronous on `stream`; device
+ * pointers. PAR_ERR_INVALID_ARG, before any device work, for an elem_bytes other than 1, 4 or 28, a null `params`, width
+ * or height <= 0, a bin size outside [8, 160], n < 0, or null d_tiles, packed or frame with n > 0. */
+int par_plane_tiles_unpack(const par_params* params, void* stream, int elem_bytes, const int32_t* d_tiles, int n,
+                           const void* packed, void* frame);
+/* Rows [row_begin, row_end) of `frame` (`frame` addresses row 0) are written exactly once: a packed tile's element
+ * where `d_map` (device array of gx * gy entries: bx + by * gx -> slot in `packed`, negative = none; what
+ * par_plane_tiles_changed_device and par_scene_tile_map write) names a slot >= 0, the E bytes at the HOST pointer `fill`
+ * elsewhere. `fill` is read during the call and may be reused on return (it travels to the kernel by value). For the
+ * palidx plane the fill is the byte PAR_PALIDX_BACKGROUND; params->ambient and background are not read. A map entry >=
+ * the number of slots the caller allocated is the caller's error. Asynchronous on `stream`; row_begin == row_end launches
+ * nothing. PAR_ERR_INVALID_ARG, before any device work, for an elem_bytes other than 1, 4 or 28, a null `params`, width,
+ * height, length or bin size <= 0, a null d_map, packed, fill or frame, or rows that are not 0 <= row_begin <= row_end <=
+ * height. */
+int par_plane_tiles_assemble(const par_params* params, void* stream, int elem_bytes, const int32_t* d_map,
+                             const void* packed, const void* fill, void* frame, int row_begin, int row_end);
+/* The only call of the seven that waits for the device: synchronises `stream` and copies d_count[0] to *count. If
+ * 0 <= *count <= capacity then *n = *count, and *n tile words and *n * B * B * E bytes of slots are copied into the host
+ * arrays `tiles` and `packed` (pageable or pinned). Otherwise *n = 0 and nothing more is copied: the list is incomplete,
+ * and the caller copies the plane instead. PAR_OK either way. A copy that fails returns PAR_ERR_HIP, a missing device
+ * PAR_ERR_NO_DEVICE; PAR_ERR_INVALID_ARG, before any device work, for an elem_bytes other than 1, 4 or 28, a null pointer,
+ * capacity < 0, width or height <= 0 or a bin size outside [8, 160]. */
+int par_plane_tiles_fetch(const par_params* params, void* stream, int elem_bytes, const int32_t* d_count,
+                          const int32_t* d_tiles, const void* d_packed, int capacity, int32_t* tiles, void* packed, int* n,
+                          int* count);
+/* Host arithmetic, no GPU needed. `frame` addresses row 0 of a whole host plane. For each i < n, the elements of slot i
+ * whose row lies in both the tile and [row_begin, row_end) and whose column lies in the tile go to their place in
+ * `frame`; nothing else is written. PAR_ERR_INVALID_ARG, after every entry is checked and before anything is written,
+ * for an elem_bytes other than 1, 4 or 28, a null `params`, null tiles, packed or frame with n > 0, n < 0, rows that are
+ * not 0 <= row_begin < row_end <= height, width or height <= 0, a bin size outside [8, 160], or any entry with bx >= gx or
+ * by outside [0, gy). */
+int par_plane_tiles_apply_host(const par_params* params, int elem_bytes, const int32_t* tiles, int n, const void* packed,
+                               int row_begin, int row_end, void* frame);
 
 /* --- outlines: silhouettes and creases drawn from the G-buffer (nothing in the reference) ------------------------
  * The post-process pixel-art renderers use most: a dark line where one object ends in front of another or in front of

@@ -44,7 +44,9 @@ ABI_SYMBOLS = (
     "par_graph_stage_lights", "par_set_light_model", "par_set_light_tints", "par_relight_device", "par_relight_rows",
     "par_quantize_device", "par_quantize_host", "par_palette_ramp", "par_outline_device", "par_outline_host",
     "par_present_device", "par_present_host", "par_finish_device", "par_finish_host", "par_tiles_changed_device",
-    "par_tiles_pack_counted", "par_tiles_fetch", "par_tiles_apply_host",
+    "par_tiles_pack_counted", "par_tiles_fetch", "par_tiles_apply_host", "par_plane_tiles_changed_device",
+    "par_plane_tiles_pack", "par_plane_tiles_pack_counted", "par_plane_tiles_unpack", "par_plane_tiles_assemble",
+    "par_plane_tiles_fetch", "par_plane_tiles_apply_host",
 )
 MAX_LIGHTS = 8  # PAR_MAX_LIGHTS
 LIGHTS_UNBOUNDED, LIGHTS_RANGED = 0, 1  # par_set_light_model
@@ -140,6 +142,13 @@ def lib():
         L.par_tiles_pack_counted.argtypes = [vp, vp, vp, vp, i32, vp, i32, i32, vp]
         L.par_tiles_fetch.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
         L.par_tiles_apply_host.argtypes = [vp, vp, i32, vp, i32, i32, vp]
+        L.par_plane_tiles_changed_device.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp, i32, vp]
+        L.par_plane_tiles_pack.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, vp]
+        L.par_plane_tiles_pack_counted.argtypes = [vp, vp, i32, vp, vp, i32, vp, i32, i32, vp]
+        L.par_plane_tiles_unpack.argtypes = [vp, vp, i32, vp, i32, vp, vp]
+        L.par_plane_tiles_assemble.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, i32]
+        L.par_plane_tiles_fetch.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]
+        L.par_plane_tiles_apply_host.argtypes = [vp, i32, vp, i32, vp, i32, i32, vp]
         L.par_quantize_device.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, vp, vp]
         L.par_quantize_host.argtypes = [vp, i32, vp, i32, i32, vp, i32, i32, vp, vp]
         L.par_palette_ramp.argtypes = [vp, i32, vp, i32]
@@ -535,6 +544,78 @@ def tiles_apply_host(params, tiles, n, packed, rows, frame):
 def _host_ptr(a):
     """A host array, or a host address as an int (pinned staging)."""
     return C.c_void_p(a) if isinstance(a, int) else ptr(a)
+
+
+# ---- plane tiles: the tile calls with an element size (1: palidx / lit / index / edge, 4: fb / brightness, 28: gbuf) --
+
+def plane_tiles_changed(params, elem_bytes, a, b, rows, d_map, d_tiles, capacity, d_count, stream=0):
+    """Device pointers (ints): tiles_changed on planes of `elem_bytes`-byte elements (par_plane_tiles_changed_device,
+    asynchronous)."""
+    rc = lib().par_plane_tiles_changed_device(C.byref(params), C.c_void_p(stream), elem_bytes, C.c_void_p(a), C.c_void_p(b),
+                                              rows[0], rows[1], C.c_void_p(d_map), C.c_void_p(d_tiles), capacity,
+                                              C.c_void_p(d_count))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_plane_tiles_changed_device")
+
+
+def plane_tiles_pack(params, elem_bytes, d_tiles, n, block, rows, packed, stream=0):
+    """Device pointers (ints): tiles d_tiles[0, n) of the plane block `rows` at `block` -> packed slots of
+    bin_size * bin_size * elem_bytes bytes (par_plane_tiles_pack, asynchronous)."""
+    rc = lib().par_plane_tiles_pack(C.byref(params), C.c_void_p(stream), elem_bytes, C.c_void_p(d_tiles), n,
+                                    C.c_void_p(block), rows[0], rows[1], C.c_void_p(packed))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_plane_tiles_pack")
+
+
+def plane_tiles_pack_counted(params, elem_bytes, d_tiles, d_count, capacity, block, rows, packed, stream=0):
+    """Device pointers (ints): plane_tiles_pack with n = min(max(d_count[0], 0), capacity) read on the device
+    (par_plane_tiles_pack_counted, asynchronous)."""
+    rc = lib().par_plane_tiles_pack_counted(C.byref(params), C.c_void_p(stream), elem_bytes, C.c_void_p(d_tiles),
+                                            C.c_void_p(d_count), capacity, C.c_void_p(block), rows[0], rows[1],
+                                            C.c_void_p(packed))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_plane_tiles_pack_counted")
+
+
+def plane_tiles_unpack(params, elem_bytes, d_tiles, n, packed, frame, stream=0):
+    """Device pointers (ints): slots -> their place in the whole plane at `frame` (par_plane_tiles_unpack, asynchronous)."""
+    rc = lib().par_plane_tiles_unpack(C.byref(params), C.c_void_p(stream), elem_bytes, C.c_void_p(d_tiles), n,
+                                      C.c_void_p(packed), C.c_void_p(frame))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_plane_tiles_unpack")
+
+
+def plane_tiles_assemble(params, elem_bytes, d_map, packed, fill, frame, rows, stream=0):
+    """Device pointers (ints) and `fill`, the `elem_bytes` bytes of the element that goes where the map names no slot:
+    rows [rows[0], rows[1]) of the plane at `frame` (row 0) in one pass (par_plane_tiles_assemble, asynchronous)."""
+    fill = bytes(fill)
+    if len(fill) != elem_bytes:
+        raise ParError(1, f"par_plane_tiles_assemble: a fill of {len(fill)} bytes for elements of {elem_bytes}")
+    rc = lib().par_plane_tiles_assemble(C.byref(params), C.c_void_p(stream), elem_bytes, C.c_void_p(d_map),
+                                        C.c_void_p(packed), C.c_char_p(fill), C.c_void_p(frame), rows[0], rows[1])
+    if rc != PAR_OK:
+        raise ParError(rc, "par_plane_tiles_assemble")
+
+
+def plane_tiles_fetch(params, elem_bytes, d_count, d_tiles, d_packed, capacity, tiles, packed, stream=0):
+    """tiles_fetch with slots of bin_size * bin_size * elem_bytes bytes (par_plane_tiles_fetch): waits for `stream`.
+    Returns (n, count): n == count when the list is complete, else n == 0 and nothing was copied."""
+    n, count = C.c_int(0), C.c_int(0)
+    rc = lib().par_plane_tiles_fetch(C.byref(params), C.c_void_p(stream), elem_bytes, C.c_void_p(d_count),
+                                     C.c_void_p(d_tiles), C.c_void_p(d_packed), capacity, _host_ptr(tiles),
+                                     _host_ptr(packed), C.byref(n), C.byref(count))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_plane_tiles_fetch")
+    return n.value, count.value
+
+
+def plane_tiles_apply_host(params, elem_bytes, tiles, n, packed, rows, frame):
+    """Host arrays (or host addresses as ints): tiles_apply_host on a plane of `elem_bytes`-byte elements
+    (par_plane_tiles_apply_host: host arithmetic, no GPU needed)."""
+    rc = lib().par_plane_tiles_apply_host(C.byref(params), elem_bytes, _host_ptr(tiles), n, _host_ptr(packed), rows[0],
+                                          rows[1], _host_ptr(frame))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_plane_tiles_apply_host")
 
 
 # ---- outlines ----------------------------------------------------------------------------------------------------

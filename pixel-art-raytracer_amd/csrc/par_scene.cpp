@@ -263,6 +263,38 @@ int par_tiles_apply_host(const par_params* p, const int32_t* tiles, int n, const
     return PAR_OK;
 }
 
+// Plane tiles, the host end: par_tiles_apply_host with elements of elem_bytes bytes, in bytes throughout.
+int par_plane_tiles_apply_host(const par_params* p, int elem_bytes, const int32_t* tiles, int n, const void* packed,
+                               int row_begin, int row_end, void* frame) {
+    if (!p || (elem_bytes != 1 && elem_bytes != 4 && elem_bytes != 28) || n < 0 || (n > 0 && (!tiles || !packed || !frame)) ||
+        p->width <= 0 || p->height <= 0 || p->bin_size < 8 || p->bin_size > 160 || row_begin < 0 || row_begin >= row_end ||
+        row_end > p->height) {
+        return PAR_ERR_INVALID_ARG;
+    }
+    const int W = p->width, H = p->height, B = p->bin_size;
+    const int gx = (W + B - 1) / B, gy = (H + B - 1) / B;
+    for (int i = 0; i < n; i++) {
+        const int bx = tiles[i] & 0xFFFF, by = tiles[i] >> 16;
+        if (bx >= gx || by < 0 || by >= gy) return PAR_ERR_INVALID_ARG;
+    }
+    const size_t E = (size_t)elem_bytes;
+    const unsigned char* slots = static_cast<const unsigned char*>(packed);
+    unsigned char* out = static_cast<unsigned char*>(frame);
+    for (int i = 0; i < n; i++) {
+        const int c0 = (tiles[i] & 0xFFFF) * B, r0 = (tiles[i] >> 16) * B;
+        const int tw = B < W - c0 ? B : W - c0;
+        const int lo = r0 > row_begin ? r0 : row_begin;
+        int hi = r0 + B < H ? r0 + B : H;
+        if (row_end < hi) hi = row_end;
+        const unsigned char* slot = slots + (size_t)i * (size_t)(B * B) * E;
+        for (int row = lo; row < hi; row++) {
+            std::memcpy(out + ((size_t)row * (size_t)W + (size_t)c0) * E, slot + (size_t)(row - r0) * (size_t)B * E,
+                        (size_t)tw * E);
+        }
+    }
+    return PAR_OK;
+}
+
 void par_row_block(int rank, int ranks, int height, int bin_size, int* begin, int* end) {
     if (ranks < 1) ranks = 1;
     if (bin_size < 1) bin_size = 1;

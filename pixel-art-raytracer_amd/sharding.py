@@ -114,24 +114,38 @@ class TileGather:
     `in_place`: the root renders its own block straight into its rows of the assembled frame (`root_block()`), packs
     and copies nothing of its own, and writes every OTHER row exactly once, tile or background, in one pass
     (par_tiles_assemble) -- the root is the rank with the most to do, and this takes a launch and a third of the
-    bytes off it."""
+    bytes off it.
 
-    def __init__(self, params, aabbs, device, world=None, rank=None, dst=0, group=None, in_place=False):
-        from . import scene_tiles
+    `elem_bytes`, `fill`: the plane that travels need not be `fb`. With an element size of 1 (palidx, lit, an index or
+    edge plane) or 28 (the G-buffer), or with an explicit `fill` of `elem_bytes` bytes, the par_plane_tiles_* calls pack
+    and assemble it, and `fill` is the element the root writes where no tile lands (for the palidx plane
+    bytes([PAR_PALIDX_BACKGROUND])). The defaults are the `fb` plane and the background colour, through the calls above."""
+
+    def __init__(self, params, aabbs, device, world=None, rank=None, dst=0, group=None, in_place=False, elem_bytes=4,
+                 fill=None):
+        if elem_bytes not in (1, 4, 28):
+            raise ValueError(f"TileGather: elements of {elem_bytes} bytes (1, 4 or 28)")
+        if fill is None and elem_bytes != 4:
+            raise ValueError("TileGather: a plane other than fb needs its fill element")
+        if fill is not None and len(bytes(fill)) != elem_bytes:
+            raise ValueError(f"TileGather: a fill of {len(bytes(fill))} bytes for elements of {elem_bytes}")
+        self.elem_bytes = elem_bytes
+        self.fill = None if fill is None else bytes(fill)
+        self.plane_calls = fill is not None  # else: the 4-byte calls and the background colour, as ever
         self.group = group
         self.world = dist.get_world_size(group) if world is None else world
         self.rank = dist.get_rank(group) if rank is None else rank
         self.dst = dst
         self.params = params
         self.device = torch.device(device)
-        self.slot_bytes = params.bin_size * params.bin_size * 4
+        self.slot_bytes = params.bin_size * params.bin_size * elem_bytes
         self.in_place = in_place
         self.frame = None
         self.inbox = None
         self.d_map = None
         self.set_scene(aabbs)
         if self.rank == dst:
-            self.frame = torch.zeros(params.height * params.width * 4, dtype=torch.uint8, device=self.device)
+            self.frame = torch.zeros(params.height * params.width * elem_bytes, dtype=torch.uint8, device=self.device)
 
     def set_scene(self, aabbs):
         """(Re)derive the tile list and its split over the ranks from the scene (same call on every rank)."""
@@ -156,6 +170,11 @@ class TileGather:
                 own[(own >= f) & (own < e)] = -1  # (the root's own tiles are already in place)
                 self.tile_map = own
                 self.d_map = torch.from_numpy(own).to(self.device)
+            elif self.plane_calls:
+                from . import scene_tile_map
+                # (no fill call for planes: the whole frame is assembled in one pass, from every tile of the list)
+                self.tile_map = scene_tile_map(p, self.tiles)
+                self.d_map = torch.from_numpy(self.tile_map).to(self.device)
 
     @property
     def max_rows(self):
@@ -164,8 +183,8 @@ class TileGather:
     def root_block(self):
         """in_place, root: its own rows of the assembled frame -- what it renders its block into."""
         b, e = self.blocks[self.rank]
-        w4 = self.params.width * 4
-        return self.frame[b * w4:e * w4]
+        row = self.params.width * self.elem_bytes
+        return self.frame[b * row:e * row]
 
     def bytes_sent(self, rank=None):
         r = self.rank if rank is None else rank
@@ -177,7 +196,7 @@ class TileGather:
 
     def block_buffer(self):
         """A buffer for this rank's row block (the largest block's size, as FrameGather's)."""
-        return torch.zeros(self.max_rows * self.params.width * 4, dtype=torch.uint8, device=self.device)
+        return torch.zeros(self.max_rows * self.params.width * self.elem_bytes, dtype=torch.uint8, device=self.device)
 
     # ---- the three steps of a frame --------------------------------------------------------------------------
     def pack(self, block, packed, stream=0):
@@ -186,11 +205,16 @@ class TileGather:
         if n == 0 or (self.in_place and self.rank == self.dst):
             return
         rows = self.blocks[self.rank]
-        if block.is_cuda:
+        if block.is_cuda and self.plane_calls:
+            from . import plane_tiles_pack
+            plane_tiles_pack(self.params, self.elem_bytes, self.d_tiles.data_ptr() + 4 * first, n, block.data_ptr(), rows,
+                             packed.data_ptr(), stream)
+        elif block.is_cuda:
             from . import tiles_pack
             tiles_pack(self.params, self.d_tiles.data_ptr() + 4 * first, n, block.data_ptr(), rows, packed.data_ptr(), stream)
         else:
-            _tiles_copy_cpu(self.params, self.tiles[first:first + n], block, rows, packed, pack=True)
+            _tiles_copy_cpu(self.params, self.tiles[first:first + n], block, rows, packed, pack=True,
+                            elem_bytes=self.elem_bytes)
 
     def exchange(self, packed, async_op=False):
         """Runs to `dst`. Returns a work handle (wait() before assemble()). On the root the own run is copied into
@@ -237,6 +261,8 @@ class TileGather:
         if self.rank != self.dst:
             return
         p = self.params
+        if self.plane_calls:
+            return self._assemble_plane(stream)
         if self.in_place:
             b, e = self.blocks[self.rank]
             others = [(0, b), (e, p.height)]
@@ -270,6 +296,34 @@ class TileGather:
             _tiles_copy_cpu(p, self.tiles, self.frame, (0, p.height), self.inbox, pack=False)
 
 
+    def _assemble_plane(self, stream):
+        """assemble() for a plane with its own fill: every row the root did not produce itself (in_place) or every row
+        is written once, a tile's element or the fill."""
+        p, eb = self.params, self.elem_bytes
+        if self.in_place:
+            b, e = self.blocks[self.rank]
+            spans = [(0, b), (e, p.height)]
+            runs = [r for r in range(self.world) if r != self.rank]
+        else:
+            spans = [(0, p.height)]
+            runs = list(range(self.world))
+        if self.frame.is_cuda:
+            from . import plane_tiles_assemble
+            for rows in spans:
+                if rows[1] > rows[0]:
+                    plane_tiles_assemble(p, eb, self.d_map.data_ptr(), self.inbox.data_ptr(), self.fill,
+                                         self.frame.data_ptr(), rows, stream)
+            return
+        element = torch.tensor(list(self.fill), dtype=torch.uint8)
+        row = p.width * eb
+        for lo, hi in spans:
+            self.frame[lo * row:hi * row].view(-1, eb)[:] = element
+        for r in runs:
+            if self.counts[r]:
+                _tiles_copy_cpu(p, self.tiles[self.first[r]:self.end[r]], self.frame, (0, p.height),
+                                self.inbox[self.first[r] * self.slot_bytes:], pack=False, elem_bytes=eb)
+
+
 class _Works:
     def __init__(self, works):
         self.works = works
@@ -280,12 +334,12 @@ class _Works:
         return True
 
 
-def _tiles_copy_cpu(params, tiles, frame_block, rows, packed, pack):
-    """par_tiles_pack / par_tiles_unpack on host tensors (the CPU tests of the N > 1 path): frame_block holds rows
-    [rows[0], rows[1]) of the frame, packed the slots."""
+def _tiles_copy_cpu(params, tiles, frame_block, rows, packed, pack, elem_bytes=4):
+    """par_tiles_pack / par_tiles_unpack, or their par_plane_tiles_* counterparts, on host tensors of bytes (the CPU tests
+    of the N > 1 path): frame_block holds rows [rows[0], rows[1]) of the plane, packed the slots."""
     B, W, H = params.bin_size, params.width, params.height
-    fb = frame_block.view(torch.int32)[:(rows[1] - rows[0]) * W].view(rows[1] - rows[0], W)
-    slots = packed.view(torch.int32)[:len(tiles) * B * B].view(len(tiles), B, B)
+    fb = frame_block[:(rows[1] - rows[0]) * W * elem_bytes].view(rows[1] - rows[0], W, elem_bytes)
+    slots = packed[:len(tiles) * B * B * elem_bytes].view(len(tiles), B, B, elem_bytes)
     for i, t in enumerate(tiles):
         bx, by = int(t) & 0xFFFF, int(t) >> 16
         c0, r0 = bx * B, by * B

@@ -1,0 +1,503 @@
+"""GPU tests of the plane-tile calls (par_plane_tiles_*) and of FrameDelta with an element size: maps, lists, counts,
+slots and assembled planes byte for byte against the contract restated in numpy (tests/plane_tiles.py; tests/
+test_plane_tiles_cpu.py holds it to per-element loops without a GPU), at the three element sizes. Every device buffer a
+call reads or writes lies in a guard-filled tensor whose guard bytes are compared after the call, so a store out of range
+shows as a failed comparison; the inputs are checked unchanged. The frames (plane_tiles.FRAMES) are the smallest at which
+each mechanism of the kernels can go wrong -- among them every access unit and the shapes at which a wider unit would
+span two tiles -- each run whole and as a row block; the planes of a block are rows [r0, r1) of whole planes, so the rows
+just outside the block lie right beside the memory a call may read."""
+import importlib
+
+import numpy as np
+import pytest
+
+import plane_tiles as P
+import quantize as Q
+from test_gpu_quantize import GUARD, Carved
+
+pytestmark = pytest.mark.gpu
+
+GUARD_WORD = GUARD * 0x01010101
+CASES = [(w, h, b, e) for w, h, b in P.FRAMES for e in P.SIZES]
+PLACED = [(w, h, b, e) for w, h, b in (P.FRAMES[1], P.FRAMES[6], P.FRAMES[7]) for e in P.SIZES]
+OFFSETS = {1: (0, 1, 2, 3, 16), 4: (0, 4, 8, 12), 28: (0, 4, 8, 12)}
+
+
+def params_of(T, w, h, b):
+    return T.default_params(w, h, h, b)
+
+
+def sync():
+    import torch
+    torch.cuda.synchronize()
+
+
+class Plane:
+    """A whole plane of e-byte elements on the device, `shift` bytes past a 16-byte boundary."""
+
+    def __init__(self, params, e, content, shift=0):
+        self.host = np.ascontiguousarray(content, dtype=np.uint8)
+        assert len(self.host) == params.width * params.height * e
+        self.dev = Carved(len(self.host), shift, self.host)
+        self.row = params.width * e
+
+    def at(self, rows):
+        return self.dev.ptr + rows[0] * self.row
+
+    def read(self):
+        return self.dev.host(np.uint8)
+
+    def unchanged(self):
+        return self.read().tobytes() == self.host.tobytes() and self.dev.guards_intact()
+
+
+def some_flips(rng, a, e, share):
+    """`a` with one byte of about `share` of its elements changed."""
+    cur = a.copy()
+    which = np.nonzero(rng.random(len(a) // e) < share)[0]
+    cur[which * e + rng.integers(0, e, len(which))] ^= np.uint8(0x40)
+    return cur
+
+
+def run_changed(par, params, e, pa, pb, rows, capacity, null_tiles=False, same=False):
+    """One par_plane_tiles_changed_device call: (map, the list plane of `capacity` words, count, the device planes)."""
+    gx, gy = P.grid(params)
+    d_map, d_count = Carved(4 * gx * gy, 0), Carved(4, 0)
+    d_tiles = None if null_tiles else Carved(4 * capacity, 0)
+    sync()
+    par.plane_tiles_changed(params, e, pa.at(rows), pa.at(rows) if same else pb.at(rows), rows, d_map.ptr,
+                            None if d_tiles is None else d_tiles.ptr, capacity, d_count.ptr)
+    sync()
+    assert d_map.guards_intact() and d_count.guards_intact() and (d_tiles is None or d_tiles.guards_intact())
+    assert pa.unchanged() and pb.unchanged(), "an input was written"
+    tiles = np.zeros(0, dtype=np.int32) if d_tiles is None else d_tiles.host(np.int32)
+    return d_map.host(np.int32), tiles, int(d_count.host(np.int32)[0]), (d_map, d_tiles, d_count)
+
+
+def check_changed(got, exp, capacity, tag):
+    map_, tiles, count = got[:3]
+    e_map, e_tiles, e_count = exp
+    assert count == e_count, f"{tag}: count {count}, expected {e_count}"
+    bad = np.nonzero(map_ != e_map)[0]
+    assert len(bad) == 0, f"{tag}: the map differs at {len(bad)} tiles, first {bad[:4]}"
+    m = min(e_count, capacity)
+    assert tiles[:m].tobytes() == e_tiles[:m].tobytes(), f"{tag}: the list differs"
+    assert (tiles[m:].view(np.uint32) == GUARD_WORD).all(), f"{tag}: list entries from min(count, capacity) on were written"
+
+
+def cut_of(params, e, rows):
+    return slice(rows[0] * params.width * e, rows[1] * params.width * e)
+
+
+# ---- 1. map, list and count against the model -----------------------------------------------------------------------
+
+@pytest.mark.parametrize("w,h,b,e", CASES)
+def test_flips_against_the_model(par, T, w, h, b, e):
+    params = params_of(T, w, h, b)
+    gx, gy = P.grid(params)
+    a = P.random_plane(np.random.default_rng(w + h + e), w * h * e)
+    pa = Plane(params, e, a)
+    for rows in P.both_blocks(h):
+        P.check_flips(params, e, rows)
+        inside, outside = P.flips(params, e, rows)
+        cut = cut_of(params, e, rows)
+        cur = P.flipped(params, e, a, inside + outside)
+        exp = P.changed(params, e, a[cut], cur[cut], rows)
+        assert exp[2] == len({(x // b, y // b) for x, y, _, _, _ in inside})
+        check_changed(run_changed(par, params, e, pa, Plane(params, e, cur), rows, gx * gy), exp, gx * gy, f"rows {rows}")
+        if outside:  # a flip in a row just outside the block does not flag a tile
+            got = run_changed(par, params, e, pa, Plane(params, e, P.flipped(params, e, a, outside)), rows, gx * gy)
+            assert got[2] == 0 and (got[0] == -1).all() and (got[1].view(np.uint32) == GUARD_WORD).all()
+        same = run_changed(par, params, e, Plane(params, e, cur), pa, rows, gx * gy, same=True)
+        assert same[2] == 0 and (same[0] == -1).all() and (same[1].view(np.uint32) == GUARD_WORD).all()
+
+
+# ---- 2. placements -----------------------------------------------------------------------------------------------------
+
+def run_pack(par, params, e, tiles, block_ptr, rows, shift, counted=None, n=None):
+    """par_plane_tiles_pack (or the counted pack with the device count `counted`) of the device list `tiles` into a
+    guard-filled buffer of len(list) slots at `shift`: the buffer's bytes."""
+    n_slots = tiles.nbytes // 4
+    out = Carved(n_slots * params.bin_size ** 2 * e, shift)
+    sync()
+    if counted is None:
+        par.plane_tiles_pack(params, e, tiles.ptr, n_slots if n is None else n, block_ptr, rows, out.ptr)
+    else:
+        par.plane_tiles_pack_counted(params, e, tiles.ptr, counted.ptr, n_slots, block_ptr, rows, out.ptr)
+    sync()
+    assert out.guards_intact() and tiles.guards_intact()
+    return out.host(np.uint8)
+
+
+def run_unpack(par, params, e, tiles, slots, frame0, shifts=(0, 0)):
+    d_slots, frame = Carved(len(slots), shifts[0], slots), Plane(params, e, frame0, shifts[1])
+    sync()
+    par.plane_tiles_unpack(params, e, tiles.ptr, tiles.nbytes // 4, d_slots.ptr, frame.dev.ptr)
+    sync()
+    assert frame.dev.guards_intact() and d_slots.guards_intact() and d_slots.host(np.uint8).tobytes() == slots.tobytes()
+    return frame.read()
+
+
+def run_assemble(par, params, e, map_, slots, fill, frame0, rows, shifts=(0, 0)):
+    d_map, d_slots = Carved(map_.nbytes, 0, map_), Carved(len(slots), shifts[0], slots)
+    frame = Plane(params, e, frame0, shifts[1])
+    sync()
+    par.plane_tiles_assemble(params, e, d_map.ptr, d_slots.ptr, fill, frame.dev.ptr, rows)
+    sync()
+    assert frame.dev.guards_intact() and d_slots.guards_intact() and d_map.guards_intact()
+    assert d_slots.host(np.uint8).tobytes() == slots.tobytes() and d_map.host(np.int32).tobytes() == map_.tobytes()
+    return frame.read()
+
+
+def some_map(rng, params, n_slots):
+    gx, gy = P.grid(params)
+    map_ = np.full(gx * gy, -1, dtype=np.int32)
+    map_[rng.permutation(gx * gy)[:n_slots]] = rng.permutation(n_slots).astype(np.int32)
+    return map_
+
+
+def fill_of(e):
+    return bytes(range(0xB1, 0xB1 + e))
+
+
+@pytest.mark.parametrize("w,h,b,e", PLACED)
+def test_placements(par, T, w, h, b, e):
+    """Planes and slot buffers at every listed byte offset past a 16-byte boundary, independently: the same outputs,
+    whichever access unit the placement allows."""
+    params = params_of(T, w, h, b)
+    gx, gy = P.grid(params)
+    rng = np.random.default_rng(2 * w + h + e)
+    a = P.random_plane(rng, w * h * e)
+    guard_plane = np.full(w * h * e, GUARD, dtype=np.uint8)
+    for rows in P.both_blocks(h):
+        inside, outside = P.flips(params, e, rows)
+        cut = cut_of(params, e, rows)
+        cur = P.flipped(params, e, a, inside + outside)
+        exp = P.changed(params, e, a[cut], cur[cut], rows)
+        d_list = Carved(4 * exp[2], 0, exp[1])
+        packed = P.pack(params, e, exp[1], cur[cut], rows, GUARD)
+        slots = P.random_plane(rng, exp[2] * b * b * e)
+        unpacked = P.unpack(params, e, exp[1], slots, a)
+        map_ = some_map(rng, params, exp[2])
+        assembled = P.assemble(params, e, map_, slots, fill_of(e), guard_plane, rows)
+        for s0 in OFFSETS[e]:
+            p0 = Plane(params, e, a, s0)
+            for s1 in OFFSETS[e]:
+                tag = f"rows {rows} placements {s0}, {s1}"
+                p1 = Plane(params, e, cur, s1)
+                check_changed(run_changed(par, params, e, p0, p1, rows, gx * gy), exp, gx * gy, tag)
+                assert run_pack(par, params, e, d_list, p1.at(rows), rows, s0).tobytes() == packed.tobytes(), tag
+                assert run_unpack(par, params, e, d_list, slots, a, (s0, s1)).tobytes() == unpacked.tobytes(), tag
+                got = run_assemble(par, params, e, map_, slots, fill_of(e), guard_plane, rows, (s0, s1))
+                assert got.tobytes() == assembled.tobytes(), tag
+
+
+# ---- 3. capacity -------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("w,h,b,e", [(w, h, b, e) for w, h, b in (P.FRAMES[3], P.FRAMES[5]) for e in P.SIZES])
+def test_capacity(par, T, w, h, b, e):
+    params = params_of(T, w, h, b)
+    gx, gy = P.grid(params)
+    rng = np.random.default_rng(3 * w + h + e)
+    a = P.random_plane(rng, w * h * e)
+    cur = some_flips(rng, a, e, 0.02)
+    pa, pb = Plane(params, e, a), Plane(params, e, cur)
+    for rows in P.both_blocks(h):
+        cut = cut_of(params, e, rows)
+        exp = P.changed(params, e, a[cut], cur[cut], rows)
+        count = exp[2]
+        assert 2 < count < gx * gy
+        for capacity in (0, 1, count - 1, count, gx * gy):
+            check_changed(run_changed(par, params, e, pa, pb, rows, capacity), exp, capacity,
+                          f"rows {rows} capacity {capacity}")
+        check_changed(run_changed(par, params, e, pa, pb, rows, 0, null_tiles=True), exp, 0, f"rows {rows} null list")
+
+
+# ---- 4. the packs ------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("w,h,b,e", CASES)
+def test_pack_and_counted_pack(par, T, w, h, b, e):
+    params = params_of(T, w, h, b)
+    gx, gy = P.grid(params)
+    rng = np.random.default_rng(5 * w + h + e)
+    a = P.random_plane(rng, w * h * e)
+    cur = P.random_plane(rng, w * h * e) if gx * gy <= 64 else some_flips(rng, a, e, 0.01)
+    pa, pb = Plane(params, e, a), Plane(params, e, cur)
+    slot = b * b * e
+    for rows in P.both_blocks(h):
+        cut = cut_of(params, e, rows)
+        _, e_tiles, count = P.changed(params, e, a[cut], cur[cut], rows)
+        assert count >= 1
+        for capacity in sorted({gx * gy, count, max(count - 1, 1)}):
+            m = min(count, capacity)
+            _, tiles, got_count, (d_map, d_tiles, d_count) = run_changed(par, params, e, pa, pb, rows, capacity)
+            assert got_count == count and tiles[:m].tobytes() == e_tiles[:m].tobytes()
+            exp = np.full(capacity * slot, GUARD, dtype=np.uint8)
+            exp[:m * slot] = P.pack(params, e, e_tiles[:m], cur[cut], rows, GUARD)
+            counted = run_pack(par, params, e, d_tiles, pb.at(rows), rows, 0, counted=d_count)
+            plain = run_pack(par, params, e, d_tiles, pb.at(rows), rows, 0, n=m)
+            assert counted.tobytes() == exp.tobytes(), f"rows {rows} capacity {capacity}: the counted pack"
+            assert plain.tobytes() == exp.tobytes(), f"rows {rows} capacity {capacity}: the pack"
+            assert pb.unchanged() and d_count.guards_intact()
+        # a garbage negative count packs nothing; a count beyond the capacity is clamped to it
+        d_list = Carved(4 * count, 0, e_tiles)
+        full = P.pack(params, e, e_tiles, cur[cut], rows, GUARD)
+        for n_dev, exp in ((-12345, np.full(count * slot, GUARD, dtype=np.uint8)), (count + 7, full)):
+            d_n = Carved(4, 0, np.array([n_dev], dtype=np.int32))
+            got = run_pack(par, params, e, d_list, pb.at(rows), rows, 0, counted=d_n)
+            assert got.tobytes() == exp.tobytes() and d_n.guards_intact(), f"rows {rows}: a device count of {n_dev}"
+        # list entries outside the grid are skipped: their slots stay as they were, the others are packed
+        listed = e_tiles.copy()
+        listed[0] = gx | (int(listed[0]) >> 16) << 16
+        if count > 2:
+            listed[count // 2] = (int(listed[count // 2]) & 0xFFFF) | gy << 16
+        if count > 1:
+            listed[count - 1] = -1
+        d_list, d_n = Carved(4 * count, 0, listed), Carved(4, 0, np.array([count], dtype=np.int32))
+        exp = P.pack(params, e, listed, cur[cut], rows, GUARD)
+        assert (exp[:slot] == GUARD).all() and (count == 1 or (exp[(count - 1) * slot:] == GUARD).all())
+        assert run_pack(par, params, e, d_list, pb.at(rows), rows, 0, counted=d_n).tobytes() == exp.tobytes()
+        assert run_pack(par, params, e, d_list, pb.at(rows), rows, 0).tobytes() == exp.tobytes()
+        assert pb.unchanged()
+
+
+# ---- 5. unpack and assemble --------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("w,h,b,e", CASES)
+def test_unpack_and_assemble(par, T, w, h, b, e):
+    params = params_of(T, w, h, b)
+    gx, gy = P.grid(params)
+    rng = np.random.default_rng(7 * w + h + e)
+    a = P.random_plane(rng, w * h * e)
+    where = np.sort(rng.permutation(gx * gy)[:max(1, gx * gy // 2)])
+    tiles = ((where % gx) | ((where // gx) << 16)).astype(np.int32)
+    slots = P.random_plane(rng, len(tiles) * b * b * e)
+    got = run_unpack(par, params, e, Carved(tiles.nbytes, 0, tiles), slots, a)
+    assert got.tobytes() == P.unpack(params, e, tiles, slots, a).tobytes(), "unpack"
+    # entries outside the grid are skipped and the others land
+    listed = tiles.copy()
+    listed[0] = gx | (int(listed[0]) >> 16) << 16
+    listed[-1] = (int(listed[-1]) & 0xFFFF) | gy << 16 if len(listed) > 1 else listed[-1]
+    if len(listed) > 2:
+        listed[1] = -1
+    got = run_unpack(par, params, e, Carved(listed.nbytes, 0, listed), slots, a)
+    assert got.tobytes() == P.unpack(params, e, listed, slots, a).tobytes(), "unpack with entries outside the grid"
+    # assemble writes the block's rows, each once, and nothing else: the other rows keep the guard
+    guard_plane = np.full(w * h * e, GUARD, dtype=np.uint8)
+    for rows in P.both_blocks(h):
+        for map_ in (some_map(rng, params, len(tiles)), np.full(gx * gy, -1, dtype=np.int32)):
+            got = run_assemble(par, params, e, map_, slots, fill_of(e), guard_plane, rows)
+            exp = P.assemble(params, e, map_, slots, fill_of(e), guard_plane, rows)
+            assert got.tobytes() == exp.tobytes(), f"assemble rows {rows}"
+            rest = np.ones(w * h * e, dtype=bool)
+            rest[cut_of(params, e, rows)] = False
+            assert (got[rest] == GUARD).all()
+
+
+# ---- 6. round trip -----------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("w,h,b,e", CASES)
+def test_round_trip(par, T, w, h, b, e):
+    import torch
+    params = params_of(T, w, h, b)
+    gx, gy = P.grid(params)
+    rng = np.random.default_rng(6 * w + h + e)
+    a = P.random_plane(rng, w * h * e)
+    pa = Plane(params, e, a)
+    for rows in P.both_blocks(h):
+        cut = cut_of(params, e, rows)
+        inside, outside = P.flips(params, e, rows)
+        cur = P.flipped(params, e, a, inside + outside)
+        cur[cut] = some_flips(rng, cur[cut], e, 0.01)
+        count = P.changed(params, e, a[cut], cur[cut], rows)[2]
+        assert count >= 1
+        pb = Plane(params, e, cur)
+        for capacity in (gx * gy, count, count - 1):
+            _, _, _, (d_map, d_tiles, d_count) = run_changed(par, params, e, pa, pb, rows, capacity)
+            d_packed = Carved(b * b * e * capacity, 0)
+            stream = torch.cuda.Stream()
+            # the fetch is what waits: the pack is enqueued on a stream of its own and not waited for
+            par.plane_tiles_pack_counted(params, e, d_tiles.ptr, d_count.ptr, capacity, pb.at(rows), rows, d_packed.ptr,
+                                         stream=stream.cuda_stream)
+            tiles = np.full(capacity, GUARD_WORD, dtype=np.uint32).view(np.int32)
+            packed = np.full(capacity * b * b * e, GUARD, dtype=np.uint8)
+            n, got_count = par.plane_tiles_fetch(params, e, d_count.ptr, d_tiles.ptr, d_packed.ptr, capacity, tiles,
+                                                 packed, stream=stream.cuda_stream)
+            assert got_count == count
+            if capacity < count:
+                assert n == 0, "an incomplete list is not fetched"
+                assert (tiles.view(np.uint32) == GUARD_WORD).all() and (packed == GUARD).all(), "something was copied"
+                continue
+            assert n == count
+            assert (tiles[n:].view(np.uint32) == GUARD_WORD).all() and (packed[n * b * b * e:] == GUARD).all()
+            frame = a.copy()
+            par.plane_tiles_apply_host(params, e, tiles, n, packed, rows, frame)
+            assert frame[cut].tobytes() == cur[cut].tobytes(), f"rows {rows} capacity {capacity}: the block is not b"
+            rest = np.ones(w * h * e, dtype=bool)
+            rest[cut] = False
+            assert frame[rest].tobytes() == a[rest].tobytes(), f"rows {rows}: rows outside the block were written"
+            assert pb.unchanged() and d_packed.guards_intact()
+
+
+# ---- 7. 4-byte elements equal the existing calls -----------------------------------------------------------------------
+
+@pytest.mark.parametrize("w,h,b", P.FRAMES)
+def test_4_bytes_equal_the_existing_calls(par, T, w, h, b):
+    """Every output of the seven calls at E = 4 (with the background colour as the fill) equals the output of
+    par_tiles_changed_device, par_tiles_pack, par_tiles_pack_counted, par_tiles_unpack, par_tiles_assemble, par_tiles_fetch
+    and par_tiles_apply_host on the same inputs, byte for byte, guard bytes of partly written buffers included."""
+    params = params_of(T, w, h, b)
+    gx, gy = P.grid(params)
+    n_tiles, slot = gx * gy, 4 * b * b
+    rng = np.random.default_rng(8 * w + h)
+    a = P.random_plane(rng, w * h * 4)
+    cur = some_flips(rng, a, 4, 0.01 if n_tiles > 64 else 0.2)
+    pa, pb = Plane(params, 4, a), Plane(params, 4, cur)
+    ch = int(float(params.background) * float(params.ambient))
+    fill = bytes([ch, ch, ch, 0])
+    for rows in P.both_blocks(h):
+        out = {}
+        for which in ("old", "new"):
+            new = which == "new"
+            size = (4,) if new else ()
+            call = lambda name: getattr(par, ("plane_" if new else "") + name)
+            d_map, d_count, d_tiles = Carved(4 * n_tiles, 0), Carved(4, 0), Carved(4 * n_tiles, 0)
+            counted, plain = Carved(n_tiles * slot, 0), Carved(n_tiles * slot, 0)
+            frame_u, frame_a = Plane(params, 4, a), Plane(params, 4, a)
+            sync()
+            call("tiles_changed")(params, *size, pa.at(rows), pb.at(rows), rows, d_map.ptr, d_tiles.ptr, n_tiles, d_count.ptr)
+            call("tiles_pack_counted")(params, *size, d_tiles.ptr, d_count.ptr, n_tiles, pb.at(rows), rows, counted.ptr)
+            sync()
+            count = int(d_count.host(np.int32)[0])
+            assert count >= 1
+            call("tiles_pack")(params, *size, d_tiles.ptr, count, pb.at(rows), rows, plain.ptr)
+            call("tiles_unpack")(params, *size, d_tiles.ptr, count, counted.ptr, frame_u.dev.ptr)
+            if new:
+                par.plane_tiles_assemble(params, 4, d_map.ptr, counted.ptr, fill, frame_a.dev.ptr, rows)
+            else:
+                par.tiles_assemble(params, d_map.ptr, counted.ptr, frame_a.dev.ptr, rows)
+            tiles = np.full(n_tiles, GUARD_WORD, dtype=np.uint32).view(np.int32)
+            packed = np.full(n_tiles * slot, GUARD, dtype=np.uint8)
+            fetched = call("tiles_fetch")(params, *size, d_count.ptr, d_tiles.ptr, counted.ptr, n_tiles, tiles,
+                                          packed if new else packed.view(T.COLOR))
+            host = a.copy()
+            call("tiles_apply_host")(params, *size, tiles, fetched[0], packed if new else packed.view(T.COLOR), rows,
+                                     host if new else host.view(T.COLOR))
+            sync()
+            for c in (d_map, d_count, d_tiles, counted, plain, frame_u.dev, frame_a.dev):
+                assert c.guards_intact()
+            out[which] = dict(map=d_map.host(np.uint8), count=d_count.host(np.uint8), tiles=d_tiles.host(np.uint8),
+                              counted=counted.host(np.uint8), plain=plain.host(np.uint8), unpacked=frame_u.read(),
+                              assembled=frame_a.read(), fetched=np.array(fetched), h_tiles=tiles.view(np.uint8),
+                              h_packed=packed, applied=host)
+        for k in out["old"]:
+            assert out["old"][k].tobytes() == out["new"][k].tobytes(), f"rows {rows}: {k} differs from the existing call"
+        assert out["new"]["applied"][cut_of(params, 4, rows)].tobytes() == cur[cut_of(params, 4, rows)].tobytes()
+
+
+# ---- 8. real planes ----------------------------------------------------------------------------------------------------
+
+def test_real_planes(par, T, oracle):
+    """One renderer at 96 x 64 x 64 with bins of 16, a few entities moving over six frames, two output sets swapped frame
+    by frame. FrameDelta keeps host copies of palidx (1 byte), gbuf (28 bytes) and fb (4 bytes, the existing calls) side by
+    side; after every frame each equals the device plane and the oracle's plane. One frame runs with a capacity of 1, so
+    that the whole-block copy runs. The same loop then runs on the index plane that par_finish_device writes through a
+    par_palette_ramp palette."""
+    import torch
+    FD = importlib.import_module("pixel-art-raytracer_amd.delta")
+    w, h, b = 96, 64, 16
+    params = T.default_params(w, h, 64, b)
+    gx, gy, _ = params.grid_dims()
+    light = T.make_light(60, 40, 20)
+    sprite = par.tile_floor()
+    base = T.make_aabbs([(4, 0, 8, 20, 20, 20), (40, 4, 30, 20, 20, 20), (70, 0, 12, 16, 24, 16), (20, 10, 44, 12, 12, 12)])
+    sizes = {"palidx": 1, "gbuf": 28, "fb": 4}
+    stream = torch.cuda.Stream()
+    s = stream.cuda_stream
+    sets = [{k: torch.zeros(n * w * h, dtype=torch.uint8, device="cuda") for k, n in sizes.items()} for _ in range(2)]
+    index = [torch.zeros(w * h, dtype=torch.uint8, device="cuda") for _ in range(2)]
+    surface = torch.zeros(4 * w * h, dtype=torch.uint8, device="cuda")
+    palette = par.palette_ramp(params, 4)
+    d_palette = torch.from_numpy(palette.view(np.uint8).copy()).cuda()
+    desc = T.make_present_desc(1, width=w)
+    torch.cuda.synchronize()
+
+    def scene(k):
+        moved = base.copy()
+        moved["px"][0] += 3 * k
+        moved["pz"][1] += 2 * k
+        moved["py"][3] += k
+        return moved
+
+    def ptrs(k):
+        return {name: t.data_ptr() for name, t in sets[k % 2].items()}
+
+    def finish(k):
+        par.finish(params, desc, surface.data_ptr(), (0, h), sets[k % 2]["fb"].data_ptr(), d_palette=d_palette.data_ptr(),
+                   n_colors=len(palette), spread=16, index_out=index[k % 2].data_ptr(), stream=s)
+
+    with par.Renderer(params, 0) as r:
+        r.set_scene(scene(0), sprite, light)
+        deltas = {name: FD.FrameDelta(params, elem_bytes=n) if n != 4 else FD.FrameDelta(params) for name, n in sizes.items()}
+        tiny = {name: FD.FrameDelta(params, capacity=1, elem_bytes=sizes[name]) for name in ("palidx", "gbuf")}
+        on_index, tiny_index = FD.FrameDelta(params, elem_bytes=1), FD.FrameDelta(params, capacity=1, elem_bytes=1)
+        assert deltas["palidx"].frame.dtype == np.uint8 and deltas["gbuf"].frame.dtype == T.PIXEL
+        assert deltas["fb"].frame.dtype == T.COLOR and all(len(d.frame) == w * h for d in deltas.values())
+        assert deltas["gbuf"].capacity == max(1, int(gx * gy * FD.DEFAULT_CAPACITY_SHARE))
+        r.render_device(ptrs(0), stream=s)
+        finish(0)
+        for name, d in list(deltas.items()) + [(n, t) for n, t in tiny.items()]:
+            d.first(ptrs(0)[name], s)
+        on_index.first(index[0].data_ptr(), s)
+        tiny_index.first(index[0].data_ptr(), s)
+        fallbacks = 0
+        for k in range(1, 7):
+            aabbs = scene(k)
+            r.update_aabbs(aabbs, 0)
+            expect = oracle.render(params, aabbs, sprite, light, planes=tuple(sizes))
+            r.render_device(ptrs(k), stream=s)
+            finish(k)
+            for name, d in deltas.items():
+                count, fell_back = d.update(ptrs(k - 1)[name], ptrs(k)[name], s)  # no host wait before the fetch
+                assert 0 < count <= gx * gy and fell_back == (count > d.capacity), (k, name, count)
+                assert d.frame.tobytes() == sets[k % 2][name].cpu().numpy().tobytes(), f"frame {k}: {name}: not the device's"
+                assert d.frame.tobytes() == expect[name].tobytes(), f"frame {k}: {name}: not the oracle's"
+            for name, d in tiny.items():
+                count, fell_back = d.update(ptrs(k - 1)[name], ptrs(k)[name], s)
+                fallbacks += int(fell_back)
+                assert fell_back == (count > 1) and d.frame.tobytes() == expect[name].tobytes(), f"frame {k}: {name}, capacity 1"
+            want = Q.model(params, palette, expect["fb"], None, 16)[0]
+            for d in (on_index, tiny_index):
+                count, fell_back = d.update(index[(k - 1) % 2].data_ptr(), index[k % 2].data_ptr(), s)
+                assert count > 0 and fell_back == (count > d.capacity)
+                assert d.frame.tobytes() == index[k % 2].cpu().numpy().tobytes(), f"frame {k}: the index plane"
+                assert d.frame.tobytes() == want.tobytes(), f"frame {k}: the index plane is not the model's"
+                fallbacks += int(fell_back and d is tiny_index)
+        assert fallbacks >= 3, "the whole-block copy ran on each plane with a capacity of 1"
+
+
+# ---- 9. TileGather's plane path on device tensors ----------------------------------------------------------------------
+
+@pytest.mark.parametrize("plane,e", [("palidx", 1), ("gbuf", 28)])
+def test_tile_gather_on_the_device(par, T, oracle, plane, e):
+    """A world of one rank with its tensors on the device: TileGather packs the tiles that can show a primitive out of the
+    oracle's plane with par_plane_tiles_pack and assembles the whole plane from them and the fill with
+    par_plane_tiles_assemble (the exchange of a world of one is the copy of the rank's own run into the inbox)."""
+    import torch
+    SH = importlib.import_module("pixel-art-raytracer_amd.sharding")
+    w, h, b = 96, 80, 16
+    params = T.default_params(w, h, h, b)
+    aabbs, light = par.scene_synthetic(12, w, h, h, 3)
+    want = oracle.render(params, aabbs, par.tile_floor(), light, planes=(plane,))[plane].view(np.uint8)
+    fill = bytes([T.PALIDX_BACKGROUND]) if e == 1 else P.background_texel(T)
+    g = SH.TileGather(params, aabbs, "cuda", world=1, rank=0, elem_bytes=e, fill=fill)
+    assert 0 < len(g.tiles) < np.prod(P.grid(params)) and g.counts == [len(g.tiles)]
+    block, packed = g.block_buffer(), g.packed_buffer()
+    block.copy_(torch.from_numpy(want.copy()).cuda())
+    g.frame.fill_(GUARD)
+    g.pack(block, packed)
+    g.inbox.copy_(packed)
+    g.assemble()
+    torch.cuda.synchronize()
+    assert packed.cpu().numpy().tobytes() == P.pack(params, e, g.tiles, want, (0, h), 0).tobytes()
+    assert g.frame.cpu().numpy().tobytes() == want.tobytes()
