@@ -410,8 +410,9 @@ int par_scene_tile_map(const par_params* params, const int32_t* tiles, int n, in
  * `params`, `a`, `b`, `d_map` or `d_count`, capacity < 0, a null d_tiles with capacity > 0, width <= 0 or height <= 0,
  * a bin size outside [8, 160] (as par_tiles_pack), or rows that are not 0 <= r0 < r1 <= height; PAR_ERR_UNSUPPORTED,
  * as early, for gx or gy above 1024 (par_create's bound; the tile word depends on it). The pointers have their types'
- * alignment; planes on 16-byte boundaries with width % 4 == 0 and B % 4 == 0 take wider loads, every other placement
- * gives the same result. The loads are bounded by the block's rows and the view's width whatever the planes hold. */
+ * alignment; the loads are of 16, 8 or 4 bytes, the largest that divides width * 4, B * 4 and both addresses (the rule of
+ * the plane-tile calls below, which this call shares its kernels with), and every placement gives the same result. The
+ * loads are bounded by the block's rows and the view's width whatever the planes hold. */
 int par_tiles_changed_device(const par_params* params, void* stream, const par_color* a, const par_color* b,
                              int row_begin, int row_end, int32_t* d_map, int32_t* d_tiles, int capacity,
                              int32_t* d_count);
@@ -462,8 +463,7 @@ int par_tiles_apply_host(const par_params* params, const int32_t* tiles, int n, 
  * rows [r0, r1). When count <= capacity, par_plane_tiles_changed_device(a, b) -> par_plane_tiles_pack_counted on b ->
  * par_plane_tiles_fetch -> par_plane_tiles_apply_host turns it into `b` on those rows and leaves every other row alone.
  * Left out on purpose: no union of several planes' changes in one call (a caller with `fb` and `palidx` calls twice),
- * no element sizes other than the three, no rerouting of the eight 4-byte calls through these kernels, no change to
- * par_ranks or to the benchmark, and no demo flag. */
+ * no element sizes other than the three, no change to par_ranks or to the benchmark, and no demo flag. */
 
 /* Which tiles differ. Device pointers, asynchronous on `stream` (a hipStream_t): no synchronisation, no allocation, no
  * copy to the host. `a` and `b` each address (row_begin, column 0) and hold rows [r0, r1) = [row_begin, row_end); both

@@ -1,25 +1,25 @@
-// par_delta.hip — changed tiles: which bin-sized tiles of a finished `fb` plane differ from the previous frame's
-// (par_tiles_changed_device), those tiles packed by a count that stays on the device (par_tiles_pack_counted), and the
-// one call that waits and copies them to the host (par_tiles_fetch). The contract is beside the declarations in
-// par_raytracer.h; par_tiles_apply_host, the host arithmetic that ends the chain, is in par_scene.cpp. Nothing here
-// knows a par_context, and the render kernels (par_kernels.hip) know nothing of this.
+// par_delta.hip — the tile calls on the device: bin-sized tiles of a finished plane packed into slots, unpacked and
+// assembled (sharded frames), and changed tiles: which tiles of a plane differ from the previous frame's, those tiles
+// packed by a count that stays on the device, and the one call that waits and copies them to the host. One set of
+// kernels serves both families of entry points: par_plane_tiles_* over planes of 1-, 4- and 28-byte elements (palidx /
+// lit / index / edge planes, fb / brightness, the G-buffer) and par_tiles_* over `fb` planes, which are the same calls
+// at 4 bytes. The contracts are beside the declarations in par_raytracer.h; the host arithmetic that ends the chain
+// (par_plane_tiles_apply_host, par_tiles_apply_host) is in par_scene.cpp. Nothing here knows a par_context, and the
+// render kernels (par_kernels.hip) know nothing of this.
 //
-// Ordering is by kernel boundaries alone: no flag is polled, no workgroup waits for another, and no global atomic is
-// used, so nothing a workgroup's arrival order could change reaches the result.
-//   1. tiles_flag_kernel: a workgroup owns T whole, consecutive tiles of one bin row. Its 256 threads are laid out as
-//      `rw` pieces along the row (a piece is 4 pixels = 16 bytes in the wide form, one pixel otherwise) by 256 / rw row
-//      lanes; a thread keeps its piece column, hence its tile, and ORs a ^ b down the tile's rows, four rows' loads of
-//      both planes issued before the first use. A thread that saw a difference stores 1 to its tile's word in LDS
-//      (every such store writes the same value); after the barrier the tile's 0 / 1 goes to d_map with one plain store.
-//      Every tile of the block's bin rows is written exactly once, by the one workgroup that owns it.
+// The kernels work in bytes and are described where they stand. Changed tiles are two launches, ordered by the kernel
+// boundary alone: no flag is polled, no workgroup waits for another, and no global atomic is used, so nothing a
+// workgroup's arrival order could change reaches the result.
+//   1. plane_flag_kernel: a workgroup owns whole, consecutive tiles of one bin row. Its 256 threads are laid out as `rw`
+//      access units along the row by 256 / rw row lanes; a thread keeps its unit column, hence its tile, and ORs a ^ b
+//      down the tile's rows, four rows' loads of both planes issued before the first use. A thread that saw a difference
+//      stores 1 to its tile's word in LDS (every such store writes the same value); after the barrier the tile's 0 / 1
+//      goes to d_map with one plain store. Every tile of the block's bin rows is written exactly once, by the one
+//      workgroup that owns it.
 //   2. tiles_rank_kernel: ONE workgroup turns the flags into ranks in place, RANK_ITEMS entries a round: ballots give a
 //      wave's count and a lane's place in it, the waves' counts meet in LDS, and the running base is carried in a
 //      register. Entries of bin rows outside the block are not read (the first launch did not write them) and become
-//      -1. The list and the count are written here.
-//
-// Plane tiles (par_plane_tiles_*): the same passes, and the pack, unpack and assemble of sharded frames, over planes of
-// 1-, 4- and 28-byte elements (palidx / lit / index / edge planes, fb / brightness, the G-buffer). Their kernels work in
-// bytes and are described where they stand; tiles_rank_kernel serves them unchanged, since it knows no element size.
+//      -1. The list and the count are written here. It knows no element size.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -41,71 +41,12 @@ constexpr int RANK_SUB = 4;  // entries per thread and round, RANK_THREADS apart
 constexpr int RANK_ITEMS = RANK_THREADS * RANK_SUB;
 static_assert(RANK_WAVES * RANK_SUB == 64, "one wave scans the round's wave counts, one per lane");
 
-// How 256 threads lie over the tiles a workgroup owns (flag kernel) or over one slot (counted pack): `rw` pieces along
+// How 256 threads lie over the tiles a workgroup owns (flag kernel) or over one slot (pack and unpack): `rw` units along
 // a row, `rs` rows side by side. The threads from rw * rs on idle.
 struct delta_shape {
     int tiles;  // tiles of a bin row per workgroup (flag kernel only)
     int rw, rs;
 };
-
-delta_shape flag_shape(int B, bool vec) {
-    const int per_piece = vec ? 4 : 1;
-    delta_shape s;
-    s.tiles = (vec ? 64 : DELTA_THREADS) * per_piece / B;  // the wide form keeps a row of pieces within one wave
-    if (s.tiles < 1) s.tiles = 1;
-    s.rw = s.tiles * B / per_piece;
-    s.rs = DELTA_THREADS / s.rw;
-    return s;
-}
-
-template <bool VEC>
-__global__ __launch_bounds__(DELTA_THREADS) void tiles_flag_kernel(const uint32_t* __restrict__ a,
-                                                                    const uint32_t* __restrict__ b, int W, int H, int B,
-                                                                    int gx, int row_begin, int row_end, int by_lo, int tiles,
-                                                                    int rw, int rs, int32_t* __restrict__ map) {
-    __shared__ uint32_t changed[DELTA_THREADS];
-    const int t = (int)threadIdx.x;
-    const int by = by_lo + (int)blockIdx.y, bx0 = (int)blockIdx.x * tiles;
-    const int n_tiles = min(tiles, gx - bx0);
-    changed[t] = 0u;
-    __syncthreads();
-    const int ty = t / rw, tx = t - ty * rw;
-    const int px = tx * (VEC ? 4 : 1);                    // pixel column within the workgroup's tiles
-    const int x = bx0 * B + px;                           // and in the view
-    const int rows_lo = max(by * B, row_begin), rows_hi = min(min(by * B + B, H), row_end);
-    if (ty < rs && x < W && rows_lo + ty < rows_hi) {
-        uint32_t acc = 0u;
-        for (int y = rows_lo + ty; y < rows_hi; y += FLAG_ROWS_IN_FLIGHT * rs) {
-            // a row beyond the tile's last is replaced by row y, which is in range: its difference is ORed in twice
-            size_t at[FLAG_ROWS_IN_FLIGHT];
-            for (int k = 0; k < FLAG_ROWS_IN_FLIGHT; k++) {
-                const int yk = y + k * rs < rows_hi ? y + k * rs : y;
-                at[k] = (size_t)(yk - row_begin) * (size_t)W + (size_t)x;
-            }
-            if (VEC) {
-                u32x4 va[FLAG_ROWS_IN_FLIGHT], vb[FLAG_ROWS_IN_FLIGHT];
-                for (int k = 0; k < FLAG_ROWS_IN_FLIGHT; k++) {
-                    va[k] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a + at[k]));
-                    vb[k] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(b + at[k]));
-                }
-                for (int k = 0; k < FLAG_ROWS_IN_FLIGHT; k++) {
-                    const u32x4 d = va[k] ^ vb[k];
-                    acc |= d[0] | d[1] | d[2] | d[3];
-                }
-            } else {
-                uint32_t va[FLAG_ROWS_IN_FLIGHT], vb[FLAG_ROWS_IN_FLIGHT];
-                for (int k = 0; k < FLAG_ROWS_IN_FLIGHT; k++) {
-                    va[k] = a[at[k]];
-                    vb[k] = b[at[k]];
-                }
-                for (int k = 0; k < FLAG_ROWS_IN_FLIGHT; k++) acc |= va[k] ^ vb[k];
-            }
-        }
-        if (acc != 0u) changed[px / B] = 1u;
-    }
-    __syncthreads();
-    if (t < n_tiles) map[(size_t)by * (size_t)gx + (size_t)(bx0 + t)] = (int32_t)changed[t];
-}
 
 // map[i]: 0 / 1 for the tiles of bin rows [by_lo, by_hi], anything elsewhere -> rank or -1 everywhere.
 __global__ __launch_bounds__(RANK_THREADS) void tiles_rank_kernel(int32_t* map, int gx, int n, int by_lo, int by_hi,
@@ -155,37 +96,7 @@ __global__ __launch_bounds__(RANK_THREADS) void tiles_rank_kernel(int32_t* map, 
     if (t == 0) count[0] = base;
 }
 
-// The counted pack: one workgroup per slot of `capacity`; those from min(max(count, 0), capacity) on leave after one
-// (wave-uniform) load of the count. A slot's row is B pixels in the frame and in the slot; PIECE pixels per thread.
-template <bool VEC>
-__global__ __launch_bounds__(DELTA_THREADS) void tiles_pack_counted_kernel(const int32_t* __restrict__ tiles,
-                                                                            const int32_t* __restrict__ count, int capacity,
-                                                                            int W, int H, int B, int gx, int gy,
-                                                                            int row_begin, int row_end, int rw, int rs,
-                                                                            const uint32_t* __restrict__ src,
-                                                                            uint32_t* __restrict__ dst) {
-    const int slot = (int)blockIdx.x;
-    const int m = min(max(count[0], 0), capacity);
-    if (slot >= m) return;
-    const int tile = tiles[slot];
-    const int bx = tile & 0xFFFF, by = tile >> 16;
-    if (bx >= gx || by < 0 || by >= gy) return;
-    const int t = (int)threadIdx.x;
-    const int ty = t / rw, tx = t - ty * rw;
-    const int px = tx * (VEC ? 4 : 1);
-    const int c0 = bx * B, r0 = by * B;
-    if (ty >= rs || c0 + px >= W) return;
-    const int rows_lo = max(r0, row_begin), rows_hi = min(min(r0 + B, H), row_end);
-    for (int row = r0 + ty; row < rows_hi; row += rs) {
-        if (row < rows_lo) continue;
-        const size_t in_frame = (size_t)(row - row_begin) * (size_t)W + (size_t)(c0 + px);
-        const size_t in_slot = (size_t)slot * (size_t)(B * B) + (size_t)((row - r0) * B + px);
-        if (VEC) *reinterpret_cast<u32x4*>(dst + in_slot) = *reinterpret_cast<const u32x4*>(src + in_frame);
-        else dst[in_slot] = src[in_frame];
-    }
-}
-
-// ---- plane tiles: the same passes over planes of 1-, 4- and 28-byte elements --------------------------------------
+// ---- the kernels that touch planes, over elements of 1, 4 and 28 bytes ----------------------------------------------
 // Everything is in bytes: a plane row is RB = W * E bytes, a tile's row is B * E bytes, and a kernel moves access units
 // of U bytes, U in {16, 8, 4, 1}. The host picks the largest U that divides RB and B * E and the address of every plane
 // and slot buffer involved (plane_unit), so a unit is aligned, lies inside one row and inside ONE tile; `upt` is the
@@ -210,7 +121,7 @@ __device__ inline uint32_t unit_diff(u32x2 a, u32x2 b) {
 __device__ inline uint32_t unit_diff(uint32_t a, uint32_t b) { return a ^ b; }
 __device__ inline uint32_t unit_diff(uint8_t a, uint8_t b) { return (uint32_t)(a ^ b); }
 
-// The wide units stream past the caches as the wide forms above do; dwords and bytes are plain accesses.
+// The wide units stream past the caches; dwords and bytes are plain accesses.
 template <int U>
 __device__ inline typename unit_of<U>::type unit_load(const uint8_t* p) {
     typedef typename unit_of<U>::type unit;
@@ -218,7 +129,7 @@ __device__ inline typename unit_of<U>::type unit_load(const uint8_t* p) {
     else return *reinterpret_cast<const unit*>(p);
 }
 
-// tiles_flag_kernel in bytes. A workgroup owns `tiles` whole, consecutive tiles of one bin row: `rw` units along the
+// Which tiles differ, pass 1. A workgroup owns `tiles` whole, consecutive tiles of one bin row: `rw` units along the
 // row by `rs` row lanes. Where the tiles' row holds more than 256 units (28-byte elements in large bins) the workgroup
 // owns one tile and a thread walks the row in steps of rw. Four rows of both planes are in flight before the first use.
 template <int U>
@@ -325,7 +236,7 @@ __device__ inline typename unit_of<U>::type fill_unit(const plane_fill& f, int E
     }
 }
 
-// tiles_assemble_kernel in bytes: rows [row_begin, row_end) of `frame` in one pass, a thread keeping its unit column
+// Assemble: rows [row_begin, row_end) of `frame` in one pass, each written exactly once, a thread keeping its unit column
 // (hence its tile column, its place in the tile's row and its unit of the fill) and streaming down the rows; the bin row
 // of a row through the reciprocal `magic_b` (0: the rows are too many for it to be exact, divide).
 template <int U>
@@ -386,137 +297,26 @@ bool params_ok(const par_params* p) {
     return p && p->width > 0 && p->height > 0 && p->bin_size >= PAR_MIN_BIN && p->bin_size <= PAR_MAX_BIN;
 }
 
-bool on_16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 int status_of(hipError_t e) {
     if (e == hipSuccess) return PAR_OK;
     return e == hipErrorNoDevice || e == hipErrorInvalidDevice ? PAR_ERR_NO_DEVICE : PAR_ERR_HIP;
 }
 
-// Pack or unpack `n` list entries (by the device's count where `d_count` is given) with the unit the operands allow.
-int plane_copy(bool pack, const par_params* p, hipStream_t s, int E, const int32_t* d_tiles, const int32_t* d_count, int n,
-               int row_begin, int row_end, const void* src, void* dst) {
-    if (n == 0) return PAR_OK;
+// par_tiles_pack, par_tiles_unpack and par_tiles_assemble report every HIP failure, a missing device included, as
+// PAR_ERR_HIP.
+int hip_only(int rc) { return rc == PAR_ERR_NO_DEVICE ? PAR_ERR_HIP : rc; }
+
+// ---- the six operations, once each: the argument checks both families share, then the launch; E is the element size --
+
+int plane_changed(const par_params* p, hipStream_t s, int E, const void* a, const void* b, int row_begin, int row_end,
+                  int32_t* d_map, int32_t* d_tiles, int capacity, int32_t* d_count) {
+    if (!params_ok(p) || !elem_ok(E) || !a || !b || !d_map || !d_count || capacity < 0 || (capacity > 0 && !d_tiles) ||
+        row_begin < 0 || row_begin >= row_end || row_end > p->height) {
+        return PAR_ERR_INVALID_ARG;
+    }
     const int W = p->width, H = p->height, B = p->bin_size;
     const int gx = (W + B - 1) / B, gy = (H + B - 1) / B;
-    const int u = plane_unit(W, B, E, src, dst);
-    const int upt = B * E / u;
-    const delta_shape f = plane_shape(upt, 1);  // one tile a workgroup
-    with_unit(u, [&](auto U) {
-        if (pack) {
-            hipLaunchKernelGGL((plane_copy_kernel<U(), true>), dim3((unsigned)n), dim3(DELTA_THREADS), 0, s, d_tiles, d_count,
-                               n, (size_t)W * (size_t)E, H, B, upt, gx, gy, row_begin, row_end, f.rw, f.rs,
-                               static_cast<const uint8_t*>(src), static_cast<uint8_t*>(dst));
-        } else {
-            hipLaunchKernelGGL((plane_copy_kernel<U(), false>), dim3((unsigned)n), dim3(DELTA_THREADS), 0, s, d_tiles, d_count,
-                               n, (size_t)W * (size_t)E, H, B, upt, gx, gy, row_begin, row_end, f.rw, f.rs,
-                               static_cast<const uint8_t*>(src), static_cast<uint8_t*>(dst));
-        }
-    });
-    return status_of(hipGetLastError());
-}
-
-}  // namespace
-
-extern "C" {
-
-int par_tiles_changed_device(const par_params* params, void* stream, const par_color* a, const par_color* b,
-                             int row_begin, int row_end, int32_t* d_map, int32_t* d_tiles, int capacity,
-                             int32_t* d_count) {
-    if (!params_ok(params) || !a || !b || !d_map || !d_count || capacity < 0 || (capacity > 0 && !d_tiles) ||
-        row_begin < 0 || row_begin >= row_end || row_end > params->height) {
-        return PAR_ERR_INVALID_ARG;
-    }
-    const int W = params->width, H = params->height, B = params->bin_size;
-    const int gx = (W + B - 1) / B, gy = (H + B - 1) / B;
     if (gx > PAR_MAX_GRID_DIM || gy > PAR_MAX_GRID_DIM) return PAR_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    int by_lo = row_begin / B, by_hi = (row_end - 1) / B;
-    if (a == b) {
-        by_hi = by_lo - 1;  // nothing can differ: no tile is looked at, the rank launch writes -1 and 0
-    } else {
-        const bool vec = W % 4 == 0 && B % 4 == 0 && on_16(a) && on_16(b);
-        const delta_shape f = flag_shape(B, vec);
-        const dim3 grid((unsigned)((gx + f.tiles - 1) / f.tiles), (unsigned)(by_hi - by_lo + 1));
-        const uint32_t* pa = reinterpret_cast<const uint32_t*>(a);
-        const uint32_t* pb = reinterpret_cast<const uint32_t*>(b);
-        if (vec) {
-            hipLaunchKernelGGL(tiles_flag_kernel<true>, grid, dim3(DELTA_THREADS), 0, s, pa, pb, W, H, B, gx, row_begin,
-                               row_end, by_lo, f.tiles, f.rw, f.rs, d_map);
-        } else {
-            hipLaunchKernelGGL(tiles_flag_kernel<false>, grid, dim3(DELTA_THREADS), 0, s, pa, pb, W, H, B, gx, row_begin,
-                               row_end, by_lo, f.tiles, f.rw, f.rs, d_map);
-        }
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return status_of(e);
-    }
-    hipLaunchKernelGGL(tiles_rank_kernel, dim3(1), dim3(RANK_THREADS), 0, s, d_map, gx, gx * gy, by_lo, by_hi, d_tiles,
-                       capacity, d_count);
-    return status_of(hipGetLastError());
-}
-
-int par_tiles_pack_counted(const par_params* params, void* stream, const int32_t* d_tiles, const int32_t* d_count,
-                           int capacity, const par_color* fb_block, int row_begin, int row_end, par_color* packed) {
-    if (!params_ok(params) || capacity < 0 || !d_count || (capacity > 0 && (!d_tiles || !fb_block || !packed)) ||
-        row_begin < 0 || row_end > params->height || row_begin > row_end) {
-        return PAR_ERR_INVALID_ARG;
-    }
-    if (capacity == 0) return PAR_OK;
-    const int W = params->width, H = params->height, B = params->bin_size;
-    const int gx = (W + B - 1) / B, gy = (H + B - 1) / B;
-    const bool vec = W % 4 == 0 && B % 4 == 0 && on_16(fb_block) && on_16(packed);
-    const int rw = vec ? B / 4 : B, rs = DELTA_THREADS / rw;
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(fb_block);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(packed);
-    if (vec) {
-        hipLaunchKernelGGL(tiles_pack_counted_kernel<true>, dim3((unsigned)capacity), dim3(DELTA_THREADS), 0,
-                           (hipStream_t)stream, d_tiles, d_count, capacity, W, H, B, gx, gy, row_begin, row_end, rw, rs, src,
-                           dst);
-    } else {
-        hipLaunchKernelGGL(tiles_pack_counted_kernel<false>, dim3((unsigned)capacity), dim3(DELTA_THREADS), 0,
-                           (hipStream_t)stream, d_tiles, d_count, capacity, W, H, B, gx, gy, row_begin, row_end, rw, rs, src,
-                           dst);
-    }
-    return status_of(hipGetLastError());
-}
-
-int par_tiles_fetch(const par_params* params, void* stream, const int32_t* d_count, const int32_t* d_tiles,
-                    const par_color* d_packed, int capacity, int32_t* tiles, par_color* packed, int* n, int* count) {
-    if (!params_ok(params) || capacity < 0 || !d_count || !d_tiles || !d_packed || !tiles || !packed || !n || !count) {
-        return PAR_ERR_INVALID_ARG;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PAR_ERR_NO_DEVICE;
-    hipStream_t s = (hipStream_t)stream;
-    int32_t total = 0;
-    hipError_t e = hipMemcpyAsync(&total, d_count, sizeof(total), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return status_of(e);
-    *count = total;
-    *n = 0;
-    if (total <= 0 || total > capacity) return PAR_OK;
-    const size_t slot = (size_t)params->bin_size * (size_t)params->bin_size * sizeof(par_color);
-    e = hipMemcpyAsync(tiles, d_tiles, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(packed, d_packed, (size_t)total * slot, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return status_of(e);
-    *n = total;
-    return PAR_OK;
-}
-
-// ---- plane tiles ---------------------------------------------------------------------------------------------------
-
-int par_plane_tiles_changed_device(const par_params* params, void* stream, int elem_bytes, const void* a, const void* b,
-                                   int row_begin, int row_end, int32_t* d_map, int32_t* d_tiles, int capacity,
-                                   int32_t* d_count) {
-    if (!params_ok(params) || !elem_ok(elem_bytes) || !a || !b || !d_map || !d_count || capacity < 0 ||
-        (capacity > 0 && !d_tiles) || row_begin < 0 || row_begin >= row_end || row_end > params->height) {
-        return PAR_ERR_INVALID_ARG;
-    }
-    const int W = params->width, H = params->height, B = params->bin_size, E = elem_bytes;
-    const int gx = (W + B - 1) / B, gy = (H + B - 1) / B;
-    if (gx > PAR_MAX_GRID_DIM || gy > PAR_MAX_GRID_DIM) return PAR_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
     int by_lo = row_begin / B, by_hi = (row_end - 1) / B;
     if (a == b) {
         by_hi = by_lo - 1;  // nothing can differ: no tile is looked at, the rank launch writes -1 and 0
@@ -538,45 +338,44 @@ int par_plane_tiles_changed_device(const par_params* params, void* stream, int e
     return status_of(hipGetLastError());
 }
 
-int par_plane_tiles_pack(const par_params* params, void* stream, int elem_bytes, const int32_t* d_tiles, int n,
-                         const void* block, int row_begin, int row_end, void* packed) {
-    if (!params_ok(params) || !elem_ok(elem_bytes) || n < 0 || (n > 0 && (!d_tiles || !block || !packed)) || row_begin < 0 ||
-        row_end > params->height || row_begin > row_end) {
+// Pack, counted pack and unpack: `n` list entries (by the device's count where `d_count` is given, `n` then being the
+// capacity) with the unit the operands allow. An unpack is over the rows [0, height).
+int plane_copy(bool pack, const par_params* p, hipStream_t s, int E, const int32_t* d_tiles, const int32_t* d_count, int n,
+               int row_begin, int row_end, const void* src, void* dst) {
+    if (!params_ok(p) || !elem_ok(E) || n < 0 || (n > 0 && (!d_tiles || !src || !dst)) || row_begin < 0 ||
+        row_end > p->height || row_begin > row_end) {
         return PAR_ERR_INVALID_ARG;
     }
-    return plane_copy(true, params, (hipStream_t)stream, elem_bytes, d_tiles, nullptr, n, row_begin, row_end, block, packed);
+    if (n == 0) return PAR_OK;
+    const int W = p->width, H = p->height, B = p->bin_size;
+    const int gx = (W + B - 1) / B, gy = (H + B - 1) / B;
+    const int u = plane_unit(W, B, E, src, dst);
+    const int upt = B * E / u;
+    const delta_shape f = plane_shape(upt, 1);  // one tile a workgroup
+    with_unit(u, [&](auto U) {
+        if (pack) {
+            hipLaunchKernelGGL((plane_copy_kernel<U(), true>), dim3((unsigned)n), dim3(DELTA_THREADS), 0, s, d_tiles, d_count,
+                               n, (size_t)W * (size_t)E, H, B, upt, gx, gy, row_begin, row_end, f.rw, f.rs,
+                               static_cast<const uint8_t*>(src), static_cast<uint8_t*>(dst));
+        } else {
+            hipLaunchKernelGGL((plane_copy_kernel<U(), false>), dim3((unsigned)n), dim3(DELTA_THREADS), 0, s, d_tiles, d_count,
+                               n, (size_t)W * (size_t)E, H, B, upt, gx, gy, row_begin, row_end, f.rw, f.rs,
+                               static_cast<const uint8_t*>(src), static_cast<uint8_t*>(dst));
+        }
+    });
+    return status_of(hipGetLastError());
 }
 
-int par_plane_tiles_pack_counted(const par_params* params, void* stream, int elem_bytes, const int32_t* d_tiles,
-                                 const int32_t* d_count, int capacity, const void* block, int row_begin, int row_end,
-                                 void* packed) {
-    if (!params_ok(params) || !elem_ok(elem_bytes) || capacity < 0 || !d_count ||
-        (capacity > 0 && (!d_tiles || !block || !packed)) || row_begin < 0 || row_end > params->height ||
-        row_begin > row_end) {
-        return PAR_ERR_INVALID_ARG;
-    }
-    return plane_copy(true, params, (hipStream_t)stream, elem_bytes, d_tiles, d_count, capacity, row_begin, row_end, block,
-                      packed);
-}
-
-int par_plane_tiles_unpack(const par_params* params, void* stream, int elem_bytes, const int32_t* d_tiles, int n,
-                           const void* packed, void* frame) {
-    if (!params_ok(params) || !elem_ok(elem_bytes) || n < 0 || (n > 0 && (!d_tiles || !frame || !packed))) {
-        return PAR_ERR_INVALID_ARG;
-    }
-    return plane_copy(false, params, (hipStream_t)stream, elem_bytes, d_tiles, nullptr, n, 0, params->height, packed, frame);
-}
-
-int par_plane_tiles_assemble(const par_params* params, void* stream, int elem_bytes, const int32_t* d_map,
-                             const void* packed, const void* fill, void* frame, int row_begin, int row_end) {
-    if (!params || params->bin_size <= 0 || params->width <= 0 || params->height <= 0 || params->length <= 0 ||
-        !elem_ok(elem_bytes) || !d_map || !frame || !packed || !fill || row_begin < 0 || row_end > params->height ||
-        row_begin > row_end) {
+// `fill`: E bytes on the host. The bin size is checked as par_grid_dims checks it (> 0), not against [8, 160].
+int plane_assemble(const par_params* p, hipStream_t s, int E, const int32_t* d_map, const void* packed, const void* fill,
+                   void* frame, int row_begin, int row_end) {
+    int gx;
+    if (par_grid_dims(p, &gx, nullptr, nullptr) != PAR_OK || !elem_ok(E) || !d_map || !frame || !packed || !fill ||
+        row_begin < 0 || row_end > p->height || row_begin > row_end) {
         return PAR_ERR_INVALID_ARG;
     }
     if (row_begin == row_end) return PAR_OK;
-    const int W = params->width, H = params->height, B = params->bin_size, E = elem_bytes;
-    const int gx = (W + B - 1) / B;
+    const int W = p->width, H = p->height, B = p->bin_size;
     plane_fill f;
     if (E == 28) {
         std::memcpy(f.w, fill, 28);
@@ -599,23 +398,20 @@ int par_plane_tiles_assemble(const par_params* params, void* stream, int elem_by
     by = by > rows ? rows : by;
     by = by > 65535u ? 65535u : by;
     with_unit(u, [&](auto U) {
-        hipLaunchKernelGGL(plane_assemble_kernel<U()>, dim3(bx, by), dim3(DELTA_THREADS), 0, (hipStream_t)stream, d_map, gx, RB,
-                           B, upt, E, row_begin, row_end, static_cast<const uint8_t*>(packed), static_cast<uint8_t*>(frame),
-                           f, magic_b);
+        hipLaunchKernelGGL(plane_assemble_kernel<U()>, dim3(bx, by), dim3(DELTA_THREADS), 0, s, d_map, gx, RB, B, upt, E,
+                           row_begin, row_end, static_cast<const uint8_t*>(packed), static_cast<uint8_t*>(frame), f, magic_b);
     });
     return status_of(hipGetLastError());
 }
 
-int par_plane_tiles_fetch(const par_params* params, void* stream, int elem_bytes, const int32_t* d_count,
-                          const int32_t* d_tiles, const void* d_packed, int capacity, int32_t* tiles, void* packed, int* n,
-                          int* count) {
-    if (!params_ok(params) || !elem_ok(elem_bytes) || capacity < 0 || !d_count || !d_tiles || !d_packed || !tiles ||
-        !packed || !n || !count) {
+int plane_fetch(const par_params* p, hipStream_t s, int E, const int32_t* d_count, const int32_t* d_tiles,
+                const void* d_packed, int capacity, int32_t* tiles, void* packed, int* n, int* count) {
+    if (!params_ok(p) || !elem_ok(E) || capacity < 0 || !d_count || !d_tiles || !d_packed || !tiles || !packed || !n ||
+        !count) {
         return PAR_ERR_INVALID_ARG;
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PAR_ERR_NO_DEVICE;
-    hipStream_t s = (hipStream_t)stream;
     int32_t total = 0;
     hipError_t e = hipMemcpyAsync(&total, d_count, sizeof(total), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -623,13 +419,101 @@ int par_plane_tiles_fetch(const par_params* params, void* stream, int elem_bytes
     *count = total;
     *n = 0;
     if (total <= 0 || total > capacity) return PAR_OK;
-    const size_t slot = (size_t)params->bin_size * (size_t)params->bin_size * (size_t)elem_bytes;
+    const size_t slot = (size_t)p->bin_size * (size_t)p->bin_size * (size_t)E;
     e = hipMemcpyAsync(tiles, d_tiles, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(packed, d_packed, (size_t)total * slot, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return status_of(e);
     *n = total;
     return PAR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- plane tiles: what only these calls check, then the operation ------------------------------------------------------
+
+int par_plane_tiles_changed_device(const par_params* params, void* stream, int elem_bytes, const void* a, const void* b,
+                                   int row_begin, int row_end, int32_t* d_map, int32_t* d_tiles, int capacity,
+                                   int32_t* d_count) {
+    return plane_changed(params, (hipStream_t)stream, elem_bytes, a, b, row_begin, row_end, d_map, d_tiles, capacity,
+                         d_count);
+}
+
+int par_plane_tiles_pack(const par_params* params, void* stream, int elem_bytes, const int32_t* d_tiles, int n,
+                         const void* block, int row_begin, int row_end, void* packed) {
+    return plane_copy(true, params, (hipStream_t)stream, elem_bytes, d_tiles, nullptr, n, row_begin, row_end, block, packed);
+}
+
+int par_plane_tiles_pack_counted(const par_params* params, void* stream, int elem_bytes, const int32_t* d_tiles,
+                                 const int32_t* d_count, int capacity, const void* block, int row_begin, int row_end,
+                                 void* packed) {
+    if (!d_count) return PAR_ERR_INVALID_ARG;
+    return plane_copy(true, params, (hipStream_t)stream, elem_bytes, d_tiles, d_count, capacity, row_begin, row_end, block,
+                      packed);
+}
+
+int par_plane_tiles_unpack(const par_params* params, void* stream, int elem_bytes, const int32_t* d_tiles, int n,
+                           const void* packed, void* frame) {
+    if (!params) return PAR_ERR_INVALID_ARG;
+    return plane_copy(false, params, (hipStream_t)stream, elem_bytes, d_tiles, nullptr, n, 0, params->height, packed, frame);
+}
+
+int par_plane_tiles_assemble(const par_params* params, void* stream, int elem_bytes, const int32_t* d_map,
+                             const void* packed, const void* fill, void* frame, int row_begin, int row_end) {
+    return plane_assemble(params, (hipStream_t)stream, elem_bytes, d_map, packed, fill, frame, row_begin, row_end);
+}
+
+int par_plane_tiles_fetch(const par_params* params, void* stream, int elem_bytes, const int32_t* d_count,
+                          const int32_t* d_tiles, const void* d_packed, int capacity, int32_t* tiles, void* packed, int* n,
+                          int* count) {
+    return plane_fetch(params, (hipStream_t)stream, elem_bytes, d_count, d_tiles, d_packed, capacity, tiles, packed, n,
+                       count);
+}
+
+// ---- the 4-byte calls: the same operations on `fb` planes -------------------------------------------------------------
+// Pack and unpack had a kernel of their own once, which had no test for a list entry outside the grid (bx >= gx, by
+// outside [0, gy), a negative word) but whose edge arithmetic wrote nothing for one: the skip in plane_copy_kernel gives
+// the same bytes.
+
+int par_tiles_pack(const par_params* params, void* stream, const int32_t* d_tiles, int n, const par_color* fb_block,
+                   int row_begin, int row_end, par_color* packed) {
+    return hip_only(plane_copy(true, params, (hipStream_t)stream, 4, d_tiles, nullptr, n, row_begin, row_end, fb_block,
+                               packed));
+}
+
+int par_tiles_unpack(const par_params* params, void* stream, const int32_t* d_tiles, int n, const par_color* packed,
+                     par_color* frame) {
+    if (!params) return PAR_ERR_INVALID_ARG;
+    return hip_only(plane_copy(false, params, (hipStream_t)stream, 4, d_tiles, nullptr, n, 0, params->height, packed,
+                               frame));
+}
+
+// The fill is the background, and this call alone reads the ambient.
+int par_tiles_assemble(const par_params* params, void* stream, const int32_t* d_map, const par_color* packed,
+                       par_color* frame, int row_begin, int row_end) {
+    if (!params || !(params->ambient >= 0.f && params->ambient <= 1.f)) return PAR_ERR_INVALID_ARG;
+    const uint8_t ch = (uint8_t)((float)params->background * params->ambient);  // Color{127,127,127,0} * ambient
+    const uint8_t fill[4] = {ch, ch, ch, 0};
+    return hip_only(plane_assemble(params, (hipStream_t)stream, 4, d_map, packed, fill, frame, row_begin, row_end));
+}
+
+int par_tiles_changed_device(const par_params* params, void* stream, const par_color* a, const par_color* b,
+                             int row_begin, int row_end, int32_t* d_map, int32_t* d_tiles, int capacity,
+                             int32_t* d_count) {
+    return plane_changed(params, (hipStream_t)stream, 4, a, b, row_begin, row_end, d_map, d_tiles, capacity, d_count);
+}
+
+int par_tiles_pack_counted(const par_params* params, void* stream, const int32_t* d_tiles, const int32_t* d_count,
+                           int capacity, const par_color* fb_block, int row_begin, int row_end, par_color* packed) {
+    if (!d_count) return PAR_ERR_INVALID_ARG;
+    return plane_copy(true, params, (hipStream_t)stream, 4, d_tiles, d_count, capacity, row_begin, row_end, fb_block, packed);
+}
+
+int par_tiles_fetch(const par_params* params, void* stream, const int32_t* d_count, const int32_t* d_tiles,
+                    const par_color* d_packed, int capacity, int32_t* tiles, par_color* packed, int* n, int* count) {
+    return plane_fetch(params, (hipStream_t)stream, 4, d_count, d_tiles, d_packed, capacity, tiles, packed, n, count);
 }
 
 }  // extern "C"

@@ -233,37 +233,9 @@ int par_scene_tile_map(const par_params* p, const int32_t* tiles, int n, int32_t
     return PAR_OK;
 }
 
-// Changed tiles, the host end: fetched slots -> their place in the host's copy of the frame. Every entry is checked
-// before the first pixel is written. (The bin-size bounds are par_internal.h's PAR_MIN_BIN and PAR_MAX_BIN, restated
-// because this unit is built without the HIP headers.)
-int par_tiles_apply_host(const par_params* p, const int32_t* tiles, int n, const par_color* packed, int row_begin,
-                         int row_end, par_color* frame) {
-    if (!p || n < 0 || (n > 0 && (!tiles || !packed || !frame)) || p->width <= 0 || p->height <= 0 || p->bin_size < 8 ||
-        p->bin_size > 160 || row_begin < 0 || row_begin >= row_end || row_end > p->height) {
-        return PAR_ERR_INVALID_ARG;
-    }
-    const int W = p->width, H = p->height, B = p->bin_size;
-    const int gx = (W + B - 1) / B, gy = (H + B - 1) / B;
-    for (int i = 0; i < n; i++) {
-        const int bx = tiles[i] & 0xFFFF, by = tiles[i] >> 16;
-        if (bx >= gx || by < 0 || by >= gy) return PAR_ERR_INVALID_ARG;
-    }
-    for (int i = 0; i < n; i++) {
-        const int c0 = (tiles[i] & 0xFFFF) * B, r0 = (tiles[i] >> 16) * B;
-        const int tw = B < W - c0 ? B : W - c0;
-        const int lo = r0 > row_begin ? r0 : row_begin;
-        int hi = r0 + B < H ? r0 + B : H;
-        if (row_end < hi) hi = row_end;
-        const par_color* slot = packed + (size_t)i * (size_t)(B * B);
-        for (int row = lo; row < hi; row++) {
-            std::memcpy(frame + (size_t)row * (size_t)W + (size_t)c0, slot + (size_t)(row - r0) * (size_t)B,
-                        (size_t)tw * sizeof(par_color));
-        }
-    }
-    return PAR_OK;
-}
-
-// Plane tiles, the host end: par_tiles_apply_host with elements of elem_bytes bytes, in bytes throughout.
+// Changed tiles, the host end: fetched slots -> their place in the host's copy of the plane, elements of elem_bytes
+// bytes, in bytes throughout. Every entry is checked before the first byte is written. (The bin-size bounds are
+// par_internal.h's PAR_MIN_BIN and PAR_MAX_BIN, restated because this unit is built without the HIP headers.)
 int par_plane_tiles_apply_host(const par_params* p, int elem_bytes, const int32_t* tiles, int n, const void* packed,
                                int row_begin, int row_end, void* frame) {
     if (!p || (elem_bytes != 1 && elem_bytes != 4 && elem_bytes != 28) || n < 0 || (n > 0 && (!tiles || !packed || !frame)) ||
@@ -293,6 +265,11 @@ int par_plane_tiles_apply_host(const par_params* p, int elem_bytes, const int32_
         }
     }
     return PAR_OK;
+}
+
+int par_tiles_apply_host(const par_params* p, const int32_t* tiles, int n, const par_color* packed, int row_begin,
+                         int row_end, par_color* frame) {
+    return par_plane_tiles_apply_host(p, (int)sizeof(par_color), tiles, n, packed, row_begin, row_end, frame);
 }
 
 void par_row_block(int rank, int ranks, int height, int bin_size, int* begin, int* end) {

@@ -345,7 +345,9 @@ def test_round_trip(par, T, w, h, b, e):
 def test_4_bytes_equal_the_existing_calls(par, T, w, h, b):
     """Every output of the seven calls at E = 4 (with the background colour as the fill) equals the output of
     par_tiles_changed_device, par_tiles_pack, par_tiles_pack_counted, par_tiles_unpack, par_tiles_assemble, par_tiles_fetch
-    and par_tiles_apply_host on the same inputs, byte for byte, guard bytes of partly written buffers included."""
+    and par_tiles_apply_host on the same inputs, byte for byte, guard bytes of partly written buffers included. The two
+    families run the same kernels, so every output of each is also compared with the numpy model at E = 4: map, count and
+    list, both packs, the unpacked and the assembled frame, and what the fetch and the host apply leave."""
     params = params_of(T, w, h, b)
     gx, gy = P.grid(params)
     n_tiles, slot = gx * gy, 4 * b * b
@@ -393,6 +395,21 @@ def test_4_bytes_equal_the_existing_calls(par, T, w, h, b):
         for k in out["old"]:
             assert out["old"][k].tobytes() == out["new"][k].tobytes(), f"rows {rows}: {k} differs from the existing call"
         assert out["new"]["applied"][cut_of(params, 4, rows)].tobytes() == cur[cut_of(params, 4, rows)].tobytes()
+        # the two families share their kernels, so each is also held to the model, which is not the library
+        cut = cut_of(params, 4, rows)
+        e_map, e_tiles, count = P.changed(params, 4, a[cut], cur[cut], rows)
+        listed = np.full(n_tiles, GUARD_WORD, dtype=np.uint32).view(np.int32)
+        listed[:count] = e_tiles
+        slots = np.full(n_tiles * slot, GUARD, dtype=np.uint8)
+        slots[:count * slot] = P.pack(params, 4, e_tiles, cur[cut], rows, GUARD)
+        model = dict(map=e_map, count=np.array([count], dtype=np.int32), tiles=listed, counted=slots, plain=slots,
+                     unpacked=P.unpack(params, 4, e_tiles, slots, a), assembled=P.assemble(params, 4, e_map, slots, fill, a, rows),
+                     fetched=np.array((count, count)), h_tiles=listed, h_packed=slots,
+                     applied=P.apply(params, 4, e_tiles, slots, rows, a))
+        assert set(model) == set(out["old"])
+        for which in ("old", "new"):
+            for k, exp in model.items():
+                assert out[which][k].tobytes() == exp.tobytes(), f"rows {rows}: {k} of the {which} calls differs from the model"
 
 
 # ---- 8. real planes ----------------------------------------------------------------------------------------------------

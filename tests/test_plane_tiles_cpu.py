@@ -444,6 +444,12 @@ def test_gpu_inputs_reach_what_they_are_named_for(T):
     assert unit_of(64, 8, 1, 4) == 4 and unit_of(64, 8, 1, 1) == 1 and unit_of(64, 8, 4, 0) == 16
     assert unit_of(64, 8, 28, 0) == 16 and unit_of(120, 40, 28, 8) == 8 and unit_of(140, 10, 28, 0) == 8
     assert unit_of(45, 9, 28, 0) == 4 and unit_of(45, 9, 1, 0) == 1
+    # at 4 bytes -- all the par_tiles_* calls have -- three frames take one unit each from buffers on 16-byte boundaries,
+    # whole and as a row block (whose planes start a whole number of rows further on)
+    for frame, unit in (((120, 45, 40), 16), ((140, 20, 10), 8), ((45, 20, 9), 4)):
+        assert frame in P.FRAMES
+        w, h, b = frame
+        assert [unit_of(w, b, 4, r0 * w * 4) for r0, _ in P.both_blocks(h)] == [unit, unit], frame
     for w, h, b in P.FRAMES:
         for e in P.SIZES:
             for rows in P.both_blocks(h):
