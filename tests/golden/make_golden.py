@@ -12,7 +12,9 @@ buffer, small planes verbatim) — never reference source.
   appendix_b.json                    whole-program known answers recorded by the survey.
   ref_checks.json / ref_checks.npz   what test_oracle_vs_reference.py holds the oracle to: constants, hashes of the
                                      tile sprite and palette, of every stage of its random scenes, of the golden
-                                     frames' debug lines, and the answers of its 3000 shadow walks.
+                                     frames' debug lines, and the answers of its 3000 shadow walks; and, for
+                                     test_sprite_normals_cpu.py, hashes of the reference's shading loop on G-buffers
+                                     with generated sprite normals ("sprite_normals": kind, light, plane).
 
 `python tests/golden/make_golden.py checks` writes ref_checks.* alone.
 """
@@ -205,6 +207,31 @@ def appendix_b():
         json.dump(data, f, indent=1, sort_keys=True)
 
 
+def sprite_normals(ref):
+    """The reference's own shading loop on G-buffers with generated sprite normals (tests/sprites.py: the sprites are
+    regenerated from their seeds). The reference's primary pass knows its tile sprite alone, so the G-buffer and the grid
+    are the oracle's; its hash is recorded beside the hashes of what the reference's loop made of it."""
+    import sprites as SP
+    from oracle.oracle import Oracle
+    oracle = Oracle()
+    params, aabbs, _ = SP.scene("main")
+    assert (params.width, params.height, params.length, params.bin_size) == tuple(
+        ref.consts[k] for k in ("width", "height", "length", "bin"))
+    grid = oracle.bin(params, aabbs, GridArrays(params))
+    out = {}
+    for kind in SP.KINDS:
+        sprite = SP.sprite(oracle.tile_floor(), kind, SP.SPRITE_SEED, params.palette_size)
+        gbuf, _ = oracle.primary(params, grid, sprite)
+        out[kind] = {}
+        for at in SP.REFERENCE_LIGHTS:
+            light = T.make_light(*at)
+            fb, br, lit = ref.shade(grid, gbuf, light)
+            own = ref.shade_own(grid, gbuf, light)
+            assert own.tobytes() == fb.tobytes(), (kind, at)
+            out[kind]["%d,%d,%d" % at] = {"gbuf": sha(gbuf), "fb": sha(own), "brightness": sha(br), "lit": sha(lit)}
+    return out
+
+
 def checks(ref):
     """The reference's answers behind test_oracle_vs_reference.py (same inputs: tests/helpers.py)."""
     params = ref.params()
@@ -239,6 +266,7 @@ def checks(ref):
             ref.debug_line_own(gbuf[my * 480 + mx:my * 480 + mx + 1], mx, my, light, fb)
             line.append(sha(fb))
         meta["debug_lines"][name] = line
+    meta["sprite_normals"] = sprite_normals(ref)
     aabbs, walks = shadow_walk_cases()
     h = ref.scene(aabbs)
     grid = GridArrays(params)

@@ -107,7 +107,7 @@ def compose_ranged(params, outs, lights):
     bgx = (bg % W).astype(np.int64)
     zero = np.zeros(len(bg), dtype=np.int64)
     per_light, rays = [], 0
-    with np.errstate(divide="ignore", invalid="ignore"):
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):  # (normals may be anything: inf, NaN, 3e38)
         for l, L in enumerate(lights):
             r = int(L["radius"])
             dx = (int(L["x"]) - x).astype(f32)
@@ -163,7 +163,7 @@ def scalar_pixel(params, outs, lights, p):
     y, z = int(g["y"]), int(g["z"])
     nx, ny, nz = (f32(g["normal"][k]) for k in ("x", "y", "z"))
     s, bits = f32(0), 0
-    with np.errstate(divide="ignore", invalid="ignore"):
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         for l, L in enumerate(lights):
             r = int(L["radius"])
             dx, dy, dz = f32(int(L["x"]) - x), f32(int(L["y"]) - y), f32(int(L["z"]) - z)

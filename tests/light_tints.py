@@ -42,7 +42,7 @@ def light_terms(params, outs, lights, ranged):
     n = gbuf["normal"][idx]
     f32 = np.float32
     terms = []
-    with np.errstate(divide="ignore", invalid="ignore"):
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):  # (normals may be anything: inf, NaN, 3e38)
         for L in lights:
             dx = (int(L["x"]) - x).astype(f32)
             dy = (int(L["y"]) - y).astype(f32)

@@ -50,7 +50,7 @@ def compose(params, outs, lights):
     s = np.zeros(len(idx), dtype=f32)
     lit = np.zeros(len(gbuf), dtype=np.uint8)
     per_light = []
-    with np.errstate(divide="ignore", invalid="ignore"):
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):  # (normals may be anything: inf, NaN, 3e38)
         for l, L in enumerate(lights):
             dx = (int(L["x"]) - x).astype(f32)
             dy = (int(L["y"]) - y).astype(f32)
