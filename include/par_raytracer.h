@@ -739,6 +739,78 @@ int par_finish_host(const par_params* params, int device,
                     const par_color* fb, int row_begin, int row_end,
                     void* out, uint8_t* index_out);
 
+/* --- upscale: a frame or an index plane through a pixel-art scaler (nothing in the reference) ----------------------
+ * At an integer scale of 2 to 4 a pixel-art frame is normally shown through an EPX-family scaler: Scale2x (AdvMAME2x),
+ * Scale3x, Scale4x. For every output pixel such a scaler SELECTS the source pixel under it or one of that pixel's four
+ * neighbours: hard edges and the palette stay, the staircase on the diagonals goes. It never makes a colour, so it
+ * works on an index plane too, and the scaled index plane can be palette-cycled with par_present_device. These calls
+ * are a pass over finished planes and take no context: retained frames, graphs and statistics are not involved and do
+ * not change. Everything is in integers and byte for byte; k = desc->scaler is the factor, W = params->width.
+ * Sources. Exactly one of `fb` and `index` is non-null. It addresses (src_row_begin, column 0) and holds rows [s0, s1) =
+ * [src_row_begin, src_row_end), dense and row-major as every plane is, and is only read. The output rows are [r0, r1) =
+ * [row_begin, row_end) with 0 <= s0 <= r0 < r1 <= s1 <= height, the halo rule of par_outline_device. Two elements are
+ * EQUAL iff their 32-bit words are equal with an fb source (the alpha byte counts, as in the changed-tiles calls), or
+ * their raw bytes with an index source: the comparison comes before any palette clamp, so the indices 200 and 255 over
+ * a 4-entry palette are different elements that show the same colour.
+ * Neighbourhood. For the source element E at column x and absolute row y, the element at offset (dx, dy) is read at
+ * column clamp(x + dx, 0, W - 1) and row clamp(y + dy, s0, s1 - 1). The nine, row by row, are A B C / D E F / G H I:
+ * B above E, D left, F right, H below.
+ * Scale2x (k = 2). With g = (B != H && D != F), the 2 x 2 block of E, row by row:
+ *     E0 = g && D == B ? D : E        E1 = g && B == F ? F : E
+ *     E2 = g && D == H ? D : E        E3 = g && H == F ? F : E
+ * Scale3x (k = 3). With the same g, the 3 x 3 block of E, row by row:
+ *     E0 = g && D == B ? D : E
+ *     E1 = g && ((D == B && E != C) || (B == F && E != A)) ? B : E
+ *     E2 = g && B == F ? F : E
+ *     E3 = g && ((D == B && E != G) || (D == H && E != A)) ? D : E
+ *     E4 = E
+ *     E5 = g && ((B == F && E != I) || (H == F && E != C)) ? F : E
+ *     E6 = g && D == H ? D : E
+ *     E7 = g && ((D == H && E != I) || (H == F && E != G)) ? H : E
+ *     E8 = g && H == F ? F : E
+ * Scale4x (k = 4). T is the Scale2x result of the source rows [s0, s1): a plane of 2 * W columns and rows
+ * [2 * s0, 2 * s1). The output is the Scale2x result of T, with T's own column clamp to [0, 2 * W - 1] and row clamp to
+ * [2 * s0, 2 * s1 - 1]. T is never written to memory.
+ * Output. The output element (X, Y), 0 <= X < k * W and k * r0 <= Y < k * r1, is sub-element (X % k, Y % k) of the block
+ * of the source element (X / k, Y / k): call it e; it is always one of the source's elements.
+ *     index_out (an index source only; nullable; dense, k * W bytes a row; addresses output row k * r0) gets the raw byte e
+ *     out (nullable; a surface exactly as par_present_device's: it addresses output row k * r0, byte 0, rows desc->pitch
+ *         bytes apart, pixel X at byte 4 * X; the bytes from 4 * k * W up to the pitch are NOT written) gets the 4 bytes of
+ *         c, red and blue exchanged under PAR_PRESENT_BGRA: c = e with an fb source, c = palette[min(e, n_colors - 1)]
+ *         with an index source, all four bytes, as present does
+ * At least one of `out` and `index_out` is non-null. The palette is required (1 <= n_colors <= PAR_MAX_PALETTE) exactly
+ * when the source is `index` and `out` is non-null; otherwise it must be NULL with n_colors 0.
+ * Row blocks. A block's output equals those output rows of the whole frame's, byte for byte, when the source block
+ * carries a halo wherever those rows exist in the frame: 1 row on each side for k = 2 and 3, 2 rows for k = 4
+ * (s0 = max(0, r0 - halo), s1 = min(height, r1 + halo)). A shorter halo is defined behaviour, the clamp, not an error.
+ * PAR_ERR_INVALID_ARG, before any device work and with nothing written (no GPU is needed to get it), for a null
+ * `params` or `desc`; both sources or neither; both outputs null; index_out with an fb source; the palette pairing above
+ * broken; a scaler that is none of the three; params->width <= 0; rows that are not 0 <= s0 <= r0 < r1 <= s1 <= height;
+ * and, when `out` is non-null (otherwise the pitch and the order are not read), an order that is neither of the two or a
+ * pitch that is not a multiple of 4 or is below 4 * W * k (formed in 64 bits: a product that does not fit an int32 is
+ * thereby refused).
+ * No overlap of an output with a source is defined. `fb`, the palette and `out` must be 4-byte aligned; `index` and
+ * `index_out` may sit on any byte. `out` on a 16-byte boundary with a pitch that is a multiple of 16, and `index_out` on
+ * a 4-byte boundary with k * W a multiple of 4, take the kernel's wider stores; every placement gives the same bytes. The
+ * kernel stays inside its arrays whatever the planes hold.
+ * Left out on purpose: no other scalers (hqx, xBR, Eagle: they blend colours, which an index plane cannot hold), no
+ * factor above 4, no nearest-neighbour magnification on top in the same call (the caller presents index_out, or a
+ * surface, with a par_params of the scaled width), no fusing into par_finish_device, no graph-capture helper (the device
+ * call is capturable as any stream-ordered launch is), and no change to what present or finish do. */
+/* device pointers (`d_palette` too), asynchronous on `stream` (a hipStream_t), no sync: on the frame's own stream, after
+ * the last call that writes the source */
+int par_upscale_device(const par_params* params, void* stream, const par_upscale_desc* desc,
+                       const par_color* fb, const uint8_t* index, const par_color* d_palette, int n_colors,
+                       int src_row_begin, int src_row_end, int row_begin, int row_end,
+                       void* out, uint8_t* index_out);
+/* host pointers, synchronous, everything on HIP device `device` (-1: the current device, as par_create): allocates,
+ * copies, launches, synchronises, copies back (`out` with a pitched copy: the caller's gap bytes stay) and frees;
+ * PAR_ERR_NO_DEVICE / PAR_ERR_OOM / PAR_ERR_HIP as par_present_host */
+int par_upscale_host(const par_params* params, int device, const par_upscale_desc* desc,
+                     const par_color* fb, const uint8_t* index, const par_color* palette, int n_colors,
+                     int src_row_begin, int src_row_end, int row_begin, int row_end,
+                     void* out, uint8_t* index_out);
+
 /* Debug overlay of alt:763-772 (Bresenham line from the picked pixel to the light) drawn into a host frame. */
 void par_debug_line(const par_params* params, const par_pixel* pick, int mouse_x, const par_light* light,
                     par_color* fb);

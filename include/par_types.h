@@ -89,6 +89,15 @@ typedef struct par_present_desc {
                                  PAR_PRESENT_BGRA: red and blue exchanged (an SDL RGB888 / ARGB8888 surface) */
 } par_present_desc;           /* 16 bytes */
 
+/* How par_upscale_device (par_raytracer.h; nothing in the reference) magnifies a frame or an index plane: by one of the
+ * EPX-family pixel-art scalers, onto a surface as par_present_desc describes one. */
+enum { PAR_UPSCALE_SCALE2X = 2, PAR_UPSCALE_SCALE3X = 3, PAR_UPSCALE_SCALE4X = 4 };   /* the value is the factor k */
+typedef struct par_upscale_desc {
+    int32_t scaler;  /* one of the three */
+    int32_t pitch;   /* bytes between output rows of `out`: a multiple of 4, >= 4 * width * k (formed in 64 bits) */
+    int32_t order;   /* PAR_PRESENT_RGBA or PAR_PRESENT_BGRA, as par_present_desc */
+} par_upscale_desc;  /* 12 bytes */
+
 /* `Ray`, alt:30-33 (20 bytes: fp32 inverse direction + short origin, 2 bytes tail padding). */
 typedef struct par_ray {
     float inv_x, inv_y, inv_z;

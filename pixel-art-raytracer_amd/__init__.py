@@ -17,8 +17,9 @@ import numpy as np
 
 from . import types as T
 from .types import (AABB, COLOR, LIGHT, LIGHT_TINT, MAX_SCALE, OUTLINE_STYLE, PIXEL, PRESENT_BGRA, PRESENT_DESC,
-                    PRESENT_RGBA, SPRITE, FrameStats, Outputs, Params, default_params, make_aabbs, make_light,
-                    make_outline_style, make_present_desc, make_tints, ptr)
+                    PRESENT_RGBA, SPRITE, UPSCALE_DESC, UPSCALE_SCALE2X, UPSCALE_SCALE3X, UPSCALE_SCALE4X, FrameStats,
+                    Outputs, Params, default_params, make_aabbs, make_light, make_outline_style, make_present_desc,
+                    make_tints, make_upscale_desc, ptr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libpar_raytracer.so")
@@ -46,7 +47,7 @@ ABI_SYMBOLS = (
     "par_present_device", "par_present_host", "par_finish_device", "par_finish_host", "par_tiles_changed_device",
     "par_tiles_pack_counted", "par_tiles_fetch", "par_tiles_apply_host", "par_plane_tiles_changed_device",
     "par_plane_tiles_pack", "par_plane_tiles_pack_counted", "par_plane_tiles_unpack", "par_plane_tiles_assemble",
-    "par_plane_tiles_fetch", "par_plane_tiles_apply_host",
+    "par_plane_tiles_fetch", "par_plane_tiles_apply_host", "par_upscale_device", "par_upscale_host",
 )
 MAX_LIGHTS = 8  # PAR_MAX_LIGHTS
 LIGHTS_UNBOUNDED, LIGHTS_RANGED = 0, 1  # par_set_light_model
@@ -158,6 +159,8 @@ def lib():
         L.par_present_host.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, vp]
         L.par_finish_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, i32, vp, vp]
         L.par_finish_host.argtypes = [vp, i32, vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, i32, vp, vp]
+        L.par_upscale_device.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
+        L.par_upscale_host.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
         L.par_debug_read_stamps.argtypes = [vp, vp, C.c_size_t]
         L.par_debug_set_hooks.argtypes = [vp, C.c_uint, i32]
         L.par_debug_read_light_walks.argtypes = [vp, vp]
@@ -805,3 +808,57 @@ def finish_host(params, desc, fb, rows=None, style=None, gbuf=None, gbuf_rows=No
     if rc != PAR_OK:
         raise ParError(rc, "par_finish_host")
     return (out, index) if want_index else out
+
+
+# ---- upscale -----------------------------------------------------------------------------------------------------
+
+def upscale(params, desc, out, rows, fb=None, index=None, d_palette=None, n_colors=0, src_rows=None, index_out=None,
+            stream=0):
+    """Device pointers (ints): rows [rows[0], rows[1]) of the frame block at `fb`, or of the index plane at `index`,
+    through the pixel-art scaler of `desc` (par_upscale_device: Scale2x, Scale3x or Scale4x; an UPSCALE_DESC array from
+    types.make_upscale_desc) onto the surface at `out` (None: no surface; an index source then needs no palette), the
+    raw scaled index plane to index_out when given. The source holds rows `src_rows` (default: `rows`): the halo of a row
+    block. `out` and `index_out` address output row rows[0] * scaler. Asynchronous on `stream`."""
+    desc = np.ascontiguousarray(desc, dtype=UPSCALE_DESC).reshape(-1)
+    s0, s1 = src_rows or rows
+    rc = lib().par_upscale_device(C.byref(params), C.c_void_p(stream), ptr(desc), C.c_void_p(fb), C.c_void_p(index),
+                                  C.c_void_p(d_palette), n_colors, s0, s1, rows[0], rows[1], C.c_void_p(out),
+                                  C.c_void_p(index_out))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_upscale_device")
+
+
+def upscale_host(params, desc, rows=None, fb=None, index=None, palette=None, src_rows=None, want_index=False,
+                 device=-1):
+    """The same on host arrays (par_upscale_host): `fb` a COLOR array or `index` a uint8 array holding rows `src_rows`
+    (default: `rows`, which defaults to the whole frame), `palette` a COLOR array with `index` (None with `index`: no
+    surface, which needs want_index). Returns the surface's rows as a (rows * scaler, pitch) uint8 array as present_host
+    does (zeros in the gap bytes), or (surface or None, the (rows * scaler, width * scaler) index plane) with
+    want_index."""
+    r0, r1 = rows or (0, params.height)
+    s0, s1 = src_rows or (r0, r1)
+    desc = np.ascontiguousarray(desc, dtype=UPSCALE_DESC).reshape(-1)
+    n = (s1 - s0) * params.width
+    if fb is not None:
+        fb = np.ascontiguousarray(fb, dtype=COLOR).reshape(-1)
+    if index is not None:
+        index = np.ascontiguousarray(index, dtype=np.uint8).reshape(-1)
+    for name, plane in (("fb", fb), ("index", index)):
+        if plane is not None and len(plane) != n:
+            raise ValueError(f"upscale_host: {name} holds {len(plane)} elements, rows {s0}..{s1} of width {params.width} "
+                             f"hold {n}")
+    n_colors = 0
+    if palette is not None:
+        palette = np.ascontiguousarray(palette, dtype=COLOR).reshape(-1)
+        n_colors = len(palette)
+    k = max(0, int(desc["scaler"][0]))
+    out_rows = max(0, r1 - r0) * k
+    out = None
+    if fb is not None or palette is not None or not want_index:
+        out = np.zeros((out_rows, max(0, int(desc["pitch"][0]))), dtype=np.uint8)
+    scaled = np.zeros((out_rows, max(0, params.width) * k), dtype=np.uint8) if want_index else None
+    rc = lib().par_upscale_host(C.byref(params), device, ptr(desc), ptr(fb), ptr(index), ptr(palette), n_colors, s0, s1,
+                                r0, r1, ptr(out), ptr(scaled))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_upscale_host")
+    return (out, scaled) if want_index else out

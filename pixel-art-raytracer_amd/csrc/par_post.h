@@ -1,6 +1,7 @@
 // par_post.h — the per-pixel arithmetic of the passes over finished planes, one implementation per contract: the
 // outline pass's (par_outline.hip), the palette pass's (par_quantize.hip) and the present pass's (par_present.hip), shared
-// with the kernel that runs the three in one launch (par_finish.hip). Everything here is __forceinline__ device code in
+// with the kernel that runs the three in one launch (par_finish.hip), and the scalers' rules (par_upscale.hip, which takes
+// the present pass's exchange from here too). Everything here is __forceinline__ device code in
 // an unnamed namespace: each unit gets its own copy, inlined where it is called.
 #ifndef PAR_POST_H
 #define PAR_POST_H
@@ -81,6 +82,36 @@ __device__ __forceinline__ uint32_t min3u(uint32_t a, uint32_t b, uint32_t c) { 
 // red and blue of a par_color read as one little-endian word exchanged
 __device__ __forceinline__ uint32_t exchanged(uint32_t c) {
     return (c & 0xFF00FF00u) | ((c & 0xFFu) << 16) | ((c >> 16) & 0xFFu);
+}
+
+// ---- upscale -------------------------------------------------------------------------------------------------------
+
+// The neighbourhood of E is A B C / D E F / G H I, every element one word; two elements are equal iff their words are.
+// (bitwise operators on purpose, as above: a rule is a handful of compares and one select)
+
+// Scale2x: the 2 x 2 block of E, row by row
+__device__ __forceinline__ void scale2x_block(uint32_t B, uint32_t D, uint32_t E, uint32_t F, uint32_t H, uint32_t o[4]) {
+    const bool g = (B != H) & (D != F);
+    o[0] = (g & (D == B)) ? D : E;
+    o[1] = (g & (B == F)) ? F : E;
+    o[2] = (g & (D == H)) ? D : E;
+    o[3] = (g & (H == F)) ? F : E;
+}
+
+// Scale3x: the 3 x 3 block of E, row by row
+__device__ __forceinline__ void scale3x_block(uint32_t A, uint32_t B, uint32_t C, uint32_t D, uint32_t E, uint32_t F,
+                                              uint32_t G, uint32_t H, uint32_t I, uint32_t o[9]) {
+    const bool g = (B != H) & (D != F);
+    const bool db = g & (D == B), bf = g & (B == F), dh = g & (D == H), hf = g & (H == F);
+    o[0] = db ? D : E;
+    o[1] = ((db & (E != C)) | (bf & (E != A))) ? B : E;
+    o[2] = bf ? F : E;
+    o[3] = ((db & (E != G)) | (dh & (E != A))) ? D : E;
+    o[4] = E;
+    o[5] = ((bf & (E != I)) | (hf & (E != C))) ? F : E;
+    o[6] = dh ? D : E;
+    o[7] = ((dh & (E != I)) | (hf & (E != G))) ? H : E;
+    o[8] = hf ? F : E;
 }
 
 }  // namespace

@@ -7,7 +7,7 @@
 // alt:815-817.
 //
 //   par_demo [--keys RRRRUUUUhhhhjjPP] [--frames N] [--out DIR] [--gif FILE] [--debug-line] [--as-sdl] [--size W H L]
-//            [--palette-levels K] [--dither S] [--outline S,C,D] [--scale SX[,SY]] [--finish]
+//            [--palette-levels K] [--dither S] [--outline S,C,D] [--scale SX[,SY]] [--finish] [--upscale K]
 //
 // --gif writes the frames as one animated GIF89a (100 ms per frame like the reference's gif.gif); a frame's colours
 // are palette entries times a brightness, at most a few hundred distinct values, so each frame gets an exact local
@@ -34,6 +34,11 @@
 // --dither, the scale of --scale (default 1), tight pitch, RGBA order. With a ramp the PPM shows the ramp's colours, and
 // the frame of --gif is that call's index plane; without a ramp the frame of --gif is the outlined frame at scale 1.
 // --debug-line and --as-sdl act between the stages and are refused together with it.
+//
+// --upscale K (with --out; K = 2, 3 or 4) writes the PPM frames at W * K x H * K through a pixel-art scaler, Scale2x,
+// Scale3x or Scale4x: the frame as it stands when it is written, exactly where --scale acts, through one
+// par_upscale_host call at tight pitch in RGBA order. It is refused together with --scale or --finish. GIFs stay at view
+// size.
 //
 // Letters: R L U D P N = right, left, up, down, page-up, page-down; a k j u h o as in the reference. Frame 0 gets no
 // key; frame k applies key k-1 (cycling when --frames exceeds the script).
@@ -212,6 +217,7 @@ int main(int argc, char** argv) {
     int frames = -1, W = 480, H = 320, L = 320, palette_levels = 0, dither = 0;
     bool debug_line = false, as_sdl = false, outline = false, finish = false;
     int scale_x = 0, scale_y = 0;  // 0: no --scale
+    int upscale = 0;               // 0: no --upscale
     par_outline_style outline_style{4, 256, 256};
     for (int i = 1; i < argc; i++) {
         if (!std::strcmp(argv[i], "--keys") && i + 1 < argc) keys = argv[++i];
@@ -239,10 +245,21 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
+        else if (!std::strcmp(argv[i], "--upscale") && i + 1 < argc) {
+            char tail = 0;
+            if (std::sscanf(argv[++i], "%d%c", &upscale, &tail) != 1 || upscale < PAR_UPSCALE_SCALE2X || upscale > PAR_UPSCALE_SCALE4X) {
+                std::fprintf(stderr, "--upscale wants 2, 3 or 4, got %s\n", argv[i]);
+                return 2;
+            }
+        }
         else if (!std::strcmp(argv[i], "--size") && i + 3 < argc) { W = std::atoi(argv[++i]); H = std::atoi(argv[++i]); L = std::atoi(argv[++i]); }
         else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
     if (frames < 0) frames = (int)keys.size() + 1;
+    if (upscale != 0) {
+        if (out_dir.empty()) { std::fprintf(stderr, "--upscale wants --out\n"); return 2; }
+        if (scale_x != 0 || finish) { std::fprintf(stderr, "--upscale cannot go with --scale or --finish\n"); return 2; }
+    }
     if (finish) {
         if (out_dir.empty()) { std::fprintf(stderr, "--finish wants --out\n"); return 2; }
         if (!outline && palette_levels == 0) { std::fprintf(stderr, "--finish wants --outline or --palette-levels: without both it is --scale\n"); return 2; }
@@ -274,9 +291,10 @@ int main(int argc, char** argv) {
     std::vector<par_color> fb((size_t)W * H);
     std::vector<par_pixel> gbuf((size_t)W * H);
     std::vector<unsigned char> rgb((size_t)W * H * 3);
-    std::vector<par_color> surface;  // --scale: the frame as the PPM shows it
+    std::vector<par_color> surface;  // --scale, --upscale: the frame as the PPM shows it
     std::vector<par_color> view;     // --finish with --gif, no ramp, a scale other than 1: the outlined frame at view size
     if (scale_x > 0 && !out_dir.empty()) surface.resize((size_t)W * scale_x * H * scale_y);
+    if (upscale != 0) surface.resize((size_t)W * upscale * H * upscale);
     // --palette-levels: the GIF's frames are index planes over the scene's ramp
     std::vector<par_color> ramp;
     std::vector<unsigned char> index;
@@ -349,7 +367,14 @@ int main(int argc, char** argv) {
             char name[64];
             std::snprintf(name, sizeof(name), "/frame_%03d.ppm", f);
             const par_color* shown = fb.data();
-            if (!surface.empty()) {
+            if (upscale != 0) {
+                const par_upscale_desc desc{upscale, 4 * W * upscale, PAR_PRESENT_RGBA};
+                if ((rc = par_upscale_host(&params, 0, &desc, fb.data(), nullptr, nullptr, 0, 0, H, 0, H, surface.data(), nullptr)) != PAR_OK) {
+                    std::fprintf(stderr, "par_upscale_host: %s\n", par_status_string(rc));
+                    return rc == PAR_ERR_INVALID_ARG ? 2 : 1;
+                }
+                shown = surface.data();
+            } else if (!surface.empty()) {
                 const par_present_desc desc{scale_x, scale_y, 4 * W * scale_x, PAR_PRESENT_RGBA};
                 if ((rc = par_present_host(&params, 0, &desc, fb.data(), nullptr, nullptr, 0, 0, H, surface.data())) != PAR_OK) {
                     std::fprintf(stderr, "par_present_host: %s\n", par_status_string(rc));
@@ -357,7 +382,8 @@ int main(int argc, char** argv) {
                 }
                 shown = surface.data();
             }
-            const int sw = surface.empty() ? W : W * scale_x, sh = surface.empty() ? H : H * scale_y;
+            const int kx = upscale != 0 ? upscale : scale_x, ky = upscale != 0 ? upscale : scale_y;
+            const int sw = surface.empty() ? W : W * kx, sh = surface.empty() ? H : H * ky;
             if (!write_ppm(out_dir + name, shown, sw, sh)) { std::fprintf(stderr, "cannot write %s%s\n", out_dir.c_str(), name); return 1; }
         }
         if (!ramp.empty()) {

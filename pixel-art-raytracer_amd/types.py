@@ -16,6 +16,7 @@ MAX_PALETTE = 256
 PALIDX_BACKGROUND = 0xFF
 MAX_SCALE = 16
 PRESENT_RGBA, PRESENT_BGRA = 0, 1
+UPSCALE_SCALE2X, UPSCALE_SCALE3X, UPSCALE_SCALE4X = 2, 3, 4  # the value is the factor
 
 COLOR = np.dtype([("red", "u1"), ("green", "u1"), ("blue", "u1"), ("alpha", "u1")])
 VEC3 = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")])
@@ -28,12 +29,14 @@ LIGHT = np.dtype([("x", "<i2"), ("y", "<i2"), ("z", "<i2"), ("radius", "<i2")])
 LIGHT_TINT = np.dtype([("r", "<f4"), ("g", "<f4"), ("b", "<f4")])  # par_light_tint
 OUTLINE_STYLE = np.dtype([("depth_step", "<i4"), ("silhouette_scale", "<i4"), ("crease_scale", "<i4")])  # par_outline_style
 PRESENT_DESC = np.dtype([("scale_x", "<i4"), ("scale_y", "<i4"), ("pitch", "<i4"), ("order", "<i4")])  # par_present_desc
+UPSCALE_DESC = np.dtype([("scaler", "<i4"), ("pitch", "<i4"), ("order", "<i4")])  # par_upscale_desc
 RAY = np.dtype([("inv_x", "<f4"), ("inv_y", "<f4"), ("inv_z", "<f4"), ("ox", "<i2"), ("oy", "<i2"), ("oz", "<i2"),
                 ("pad", "<i2")])
 
 assert COLOR.itemsize == 4 and VEC3.itemsize == 12 and PIXEL.itemsize == 28
 assert SPRITE.itemsize == 16000 and AABB.itemsize == 16 and LIGHT.itemsize == 8 and RAY.itemsize == 20
 assert LIGHT_TINT.itemsize == 12 and OUTLINE_STYLE.itemsize == 12 and PRESENT_DESC.itemsize == 16
+assert UPSCALE_DESC.itemsize == 12
 
 
 class Color(C.Structure):
@@ -112,6 +115,18 @@ def make_present_desc(scale_x=1, scale_y=None, pitch=None, order=PRESENT_RGBA, w
         pitch = 4 * width * scale_x
     d = np.zeros(1, dtype=PRESENT_DESC)
     d["scale_x"], d["scale_y"], d["pitch"], d["order"] = scale_x, scale_y, pitch, order
+    return d
+
+
+def make_upscale_desc(scaler, pitch=None, order=PRESENT_RGBA, width=None):
+    """1-element UPSCALE_DESC array (par_upscale_device): the scaler (its value is the factor), the bytes from one row
+    of the surface to the next (default: tight, 4 * width * scaler, which needs `width`) and the byte order."""
+    if pitch is None:
+        if width is None:
+            raise ValueError("make_upscale_desc: give pitch, or width for a tight pitch")
+        pitch = 4 * width * scaler
+    d = np.zeros(1, dtype=UPSCALE_DESC)
+    d["scaler"], d["pitch"], d["order"] = scaler, pitch, order
     return d
 
 
