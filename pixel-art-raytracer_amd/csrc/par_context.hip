@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "par_book.h"
+#include "par_hostcall.h"
 #include "par_internal.h"
 
 struct par_context {
@@ -649,6 +650,20 @@ std::array<par_dev_buffer, 19> dev_buffers(par_context* c, bool stamps) {
 
 }  // namespace
 
+// (declared in par_hostcall.h: the *_host forms of the passes over finished planes open with it too)
+int par_select_device(int* device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PAR_ERR_NO_DEVICE;
+    if (*device < 0) {
+        if (hipGetDevice(device) != hipSuccess) return PAR_ERR_NO_DEVICE;
+    }
+    if (*device >= ndev) return PAR_ERR_INVALID_ARG;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, *device) != hipSuccess) return PAR_ERR_NO_DEVICE;
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return PAR_ERR_NO_DEVICE;  // kernels are built for gfx950 only
+    return PAR_OK;
+}
+
 extern "C" {
 
 const char* par_last_error(const par_context* ctx) { return ctx ? ctx->err.c_str() : ""; }
@@ -674,15 +689,8 @@ static int par_create_impl(const par_params* params, int device, par_context** o
         gz > PAR_MAX_GRID_DIM || (int64_t)gx * gy * gz > 0x3FFFFFFF) {
         return PAR_ERR_UNSUPPORTED;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PAR_ERR_NO_DEVICE;
-    if (device < 0) {
-        if (hipGetDevice(&device) != hipSuccess) return PAR_ERR_NO_DEVICE;
-    }
-    if (device >= ndev) return PAR_ERR_INVALID_ARG;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return PAR_ERR_NO_DEVICE;
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return PAR_ERR_NO_DEVICE;  // kernels are built for gfx950 only
+    const int rc = par_select_device(&device);
+    if (rc != PAR_OK) return rc;
 
     par_context* ctx = new (std::nothrow) par_context;
     if (!ctx) return PAR_ERR_OOM;

@@ -1,9 +1,11 @@
 // par_finish.hip — finish: outline, quantise and present a frame in one launch (par_finish_device, par_finish_host). The
 // contract is beside the declarations in par_raytracer.h and is the composition of the three passes' contracts, byte for
 // byte; nothing here knows a par_context, and the three passes (par_outline.hip, par_quantize.hip, par_present.hip) know
-// nothing of this. The per-pixel arithmetic (texel_at .. exchanged) is the three passes' own, shared through par_post.h.
+// nothing of this. The per-pixel arithmetic, the tile's geometry and the group expand are the three passes' own, shared
+// through par_post.h; the stage and the search are restated here (as functions of that header they compiled to other,
+// slower code in both kernels: DESIGN, "Post passes").
 //
-// The kernel. A workgroup of 256 threads takes a tile of 64 x 16 source pixels, as outline_kernel does.
+// The kernel. A workgroup of 256 threads takes the outline pass's tile of 64 x 16 source pixels (par_post.h).
 // OUTLINE: the tile's texels plus the one-texel halo are staged into LDS exactly as outline_kernel stages them (16-byte
 // units aligned in memory, the LDS phase equal to the memory phase, one barrier), and a wavefront classifies four tile
 // rows, lane = column. The lane's four fb pixels are scaled by class.
@@ -15,40 +17,23 @@
 // The final words go into a 64 x 16 colour tile in LDS (4 KiB, beside the staged texels). Second barrier.
 // Expand: the tile's surface region is 64 * sx x 16 * sy pixels. A wavefront expands the four tile rows it classified:
 // 64 * sx groups of four output pixels in sx rounds, a lane's group lying in one source row. It reads the group's at
-// most four colour words from LDS and stores the 16-byte value to the sy output rows of that source row, `pitch` apart.
-// A tile starts at byte 256 * sx * (tile column) of a row, so every full group is 16-byte aligned when `out` and the
-// pitch are (VEC); the group that hangs over W', and every group otherwise, goes pixel by pixel.
+// most four colour words from LDS and stores them as present_kernel does (group_columns, store_group). A tile starts
+// at byte 256 * sx * (tile column) of a row, so every full group is 16-byte aligned when `out` and the pitch are (VEC);
+// the group that hangs over W', and every group otherwise, goes pixel by pixel.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
-#include <cstring>
 
 #include "par_fastdiv.h"
+#include "par_hostcall.h"
 #include "par_post.h"
 #include "par_raytracer.h"
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int TILE_W = 64;   // one wavefront's lanes
-constexpr int TILE_H = 16;   // four wavefronts x four rows
-constexpr int THREADS = 256;
-constexpr int WAVES = THREADS / 64;
-constexpr int ROWS_PER_WAVE = TILE_H / WAVES;
-constexpr int TEXEL_DWORDS = 7;
-constexpr int STAGED_W = TILE_W + 2, STAGED_H = TILE_H + 2;
-// dwords between staged rows: a row's 462 dwords, its phase shift of at most 3, rounded up to whole 16-byte units
-constexpr int STAGED_PITCH = (STAGED_W * TEXEL_DWORDS + 3 + 3) / 4 * 4;
-constexpr int UNITS_PER_ROW = (STAGED_W * TEXEL_DWORDS + 3 + 3) / 4;  // 16-byte units a row's run can touch
-constexpr int UNIT_ROUNDS = (UNITS_PER_ROW + 63) / 64;
-constexpr int STAGE_ROUNDS = (STAGED_H + WAVES - 1) / WAVES;
-// rows of one launch, cut where launch_outline cuts: the grid's y extent, and the launch's pixels below 2^31
-constexpr uint32_t MAX_TILE_ROWS = 65535u;
-constexpr uint32_t MAX_PX = 0x7FFFFFF0u;
-static_assert(TILE_W == 64 && ROWS_PER_WAVE == 4, "a wavefront classifies and expands 4 rows x 64 columns");
-static_assert(STAGED_PITCH % 4 == 0 && UNITS_PER_ROW * 4 <= STAGED_PITCH, "a staged row stays inside its pitch");
+constexpr int TILE_W = OUTLINE_TILE_W, TILE_H = OUTLINE_TILE_H, THREADS = OUTLINE_THREADS;
+constexpr int ROWS_PER_WAVE = OUTLINE_ROWS_PER_WAVE, WAVES = OUTLINE_WAVES;
 static_assert(THREADS == PAR_MAX_PALETTE, "one palette entry per thread");
 
 struct FinishArgs {
@@ -69,12 +54,6 @@ struct FinishArgs {
     bool index_wide;  // index_out on a 4-byte boundary and the width a multiple of 4
 };
 
-// The shift (0..3 dwords) of staged row `j` of the tile at column tx0, absolute row r: with it the LDS index of a
-// texel's dword is congruent, modulo 4, to its dword address in memory (7 = -1 modulo 4).
-__device__ __forceinline__ uint32_t row_shift(const FinishArgs& a, uint32_t galign, int r, uint32_t tx0) {
-    return (galign - (uint32_t)(r - a.g0) * a.width - tx0 + 1u) & 3u;
-}
-
 // OUTLINE: stage 1 runs (else no G-buffer is staged). QUANT: stage 2 runs (else no search). VEC: `out` and `pitch` are
 // multiples of 16. (spread == 0 needs no variant: dithered() then leaves the three channels as they are.)
 template <bool OUTLINE, bool QUANT, bool VEC>
@@ -94,15 +73,14 @@ __global__ __launch_bounds__(THREADS) void finish_kernel(FinishArgs a, const uin
     const bool in_cols = px < W;
 
     if (QUANT) {
-        // entry i is palette[min(i, n_colors - 1)] in the surface's byte order (an index never exceeds n_colors - 1:
-        // the clamp only keeps the load inside the palette)
-        const uint32_t e = palette[std::min<uint32_t>(threadIdx.x, (uint32_t)a.n_colors - 1u)];
+        const uint32_t e = palette_entry_load(palette, a.n_colors);
         pal[threadIdx.x] = a.swap ? exchanged(e) : e;
     }
 
     uint32_t cls[ROWS_PER_WAVE] = {0u, 0u, 0u, 0u};
     uint32_t src[ROWS_PER_WAVE] = {0u, 0u, 0u, 0u};
     if (OUTLINE) {
+        u32x4 v[STAGE_ROUNDS][UNIT_ROUNDS];
         const uint32_t galign = (uint32_t)(reinterpret_cast<uintptr_t>(a.gbuf) >> 2) & 3u;
         // ---- stage: staged row j holds absolute row ty0 - 1 + j, staged column c holds column tx0 - 1 + c ---------
         const uint32_t cx0 = tx0 == 0 ? 0u : tx0 - 1u;                    // the columns that exist
@@ -113,7 +91,6 @@ __global__ __launch_bounds__(THREADS) void finish_kernel(FinishArgs a, const uin
         // plane: what it brings along lands in LDS dwords of the row's own pitch that hold no texel of the tile. Only
         // the first and the last unit of the whole plane can go dword by dword.)
         const int64_t plane = (int64_t)(a.g1 - a.g0) * W * TEXEL_DWORDS;
-        u32x4 v[STAGE_ROUNDS][UNIT_ROUNDS];
         #pragma unroll
         for (int jj = 0; jj < STAGE_ROUNDS; jj++) {
             const int j = wave + WAVES * jj;
@@ -160,7 +137,6 @@ __global__ __launch_bounds__(THREADS) void finish_kernel(FinishArgs a, const uin
             }
         }
         __syncthreads();
-
         // ---- classify: this wavefront's rows ly0 .. ly0 + 3 of the tile, lane = column ---------------------------
         // Every read below stays inside `staged` and none is skipped: a texel of a row or column that was not staged
         // holds whatever LDS held, and its neighbour's `has_` flag keeps it out of the class.
@@ -263,30 +239,13 @@ __global__ __launch_bounds__(THREADS) void finish_kernel(FinishArgs a, const uin
         const uint32_t base = tile_x0 + local;                 // and within the surface's
         const int y = ty0 + ly0 + (int)k;
         if (y >= a.rb || base >= out_width) continue;
-        // tile column of pixel 0 by division, of the others by stepping; every column stays below 64
-        uint32_t at[4];
-        at[0] = par_udiv31_quotient(local, a.by_sx);
-        uint32_t rem = local - at[0] * sx;
-        for (int i = 1; i < 4; i++) {
-            const bool step = ++rem == sx;
-            rem = step ? 0u : rem;
-            at[i] = std::min(at[i - 1] + (step ? 1u : 0u), (uint32_t)TILE_W - 1u);
-        }
+        uint32_t at[4];  // tile columns: every one stays below 64
+        group_columns(local, sx, a.by_sx, (uint32_t)TILE_W - 1u, at);
         const uint32_t* row = colour + (ly0 + (int)k) * TILE_W;
         uint32_t c[4];
         for (int i = 0; i < 4; i++) c[i] = row[at[i]];
         char* const dst = a.out + (size_t)(y - a.ra) * sy * a.pitch + 4u * (size_t)base;
-        if (VEC && base + 4u <= out_width) {
-            const u32x4 v = {c[0], c[1], c[2], c[3]};
-            for (uint32_t yy = 0; yy < sy; yy++) *reinterpret_cast<u32x4*>(dst + yy * a.pitch) = v;
-        } else {
-            for (uint32_t yy = 0; yy < sy; yy++) {
-                uint32_t* const o = reinterpret_cast<uint32_t*>(dst + yy * a.pitch);
-                for (int i = 0; i < 4; i++) {
-                    if (base + i < out_width) o[i] = c[i];
-                }
-            }
-        }
+        store_group<VEC>(dst, c, base + 4u <= out_width, base, out_width, sy, a.pitch);
     }
 }
 
@@ -296,22 +255,15 @@ void launch_one(hipStream_t stream, const dim3& grid, bool vec, const FinishArgs
     else hipLaunchKernelGGL((finish_kernel<OUTLINE, QUANT, false>), grid, dim3(THREADS), 0, stream, a, palette);
 }
 
-// Rows [row_begin, row_end) in launches of whole tile rows, cut where launch_outline cuts: at most MAX_TILE_ROWS tile
-// rows (the grid's y extent) and at most MAX_PX source pixels each (a single tile row is never cut). One launch for
-// any frame below 2^31 pixels and 65535 tile rows. Every launch reads the one G-buffer plane: the rows beside a cut
-// are its halo.
+// Rows [row_begin, row_end) in launches of whole tile rows, cut by par_tile_row_cuts as launch_outline's are. Every
+// launch reads the one G-buffer plane: the rows beside a cut are its halo.
 hipError_t launch_finish(hipStream_t stream, const par_params* p, const par_outline_style* style, const par_pixel* gbuf,
                          int g0, int g1, const par_color* d_palette, int n_colors, int spread, const par_present_desc& d,
                          const par_color* fb, int row_begin, int row_end, void* out, uint8_t* index_out) {
     const uint32_t W = (uint32_t)p->width;
-    const uint32_t by_px = std::max<uint32_t>(1u, MAX_PX / W / TILE_H);
-    const uint32_t tile_rows_per_launch = std::min(MAX_TILE_ROWS, by_px);
     const uint32_t gray = p->background;
     const bool vec = (reinterpret_cast<uintptr_t>(out) & 15u) == 0 && (d.pitch & 15) == 0;
-    for (int ra = row_begin; ra < row_end;) {
-        const uint32_t tile_rows = std::min<uint32_t>(tile_rows_per_launch,
-                                                      ((uint32_t)(row_end - ra) + TILE_H - 1) / TILE_H);
-        const int rb = (int)std::min<int64_t>((int64_t)row_end, (int64_t)ra + (int64_t)tile_rows * TILE_H);
+    return (hipError_t)par_tile_row_cuts(row_begin, row_end, W, TILE_H, [&](int ra, int rb, uint32_t tile_rows) {
         const size_t at = (size_t)(ra - row_begin) * W;
         FinishArgs a;
         a.gbuf = reinterpret_cast<const uint32_t*>(gbuf);
@@ -338,11 +290,8 @@ hipError_t launch_finish(hipStream_t stream, const par_params* p, const par_outl
         if (style && d_palette) launch_one<true, true>(stream, grid, vec, a, palette);
         else if (style) launch_one<true, false>(stream, grid, vec, a, palette);
         else launch_one<false, true>(stream, grid, vec, a, palette);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        ra = rb;
-    }
-    return hipSuccess;
+        return (int)hipGetLastError();
+    });
 }
 
 bool finish_args_ok(const par_params* p, const par_outline_style* s, const par_pixel* gbuf, int g0, int g1,
@@ -364,10 +313,7 @@ bool finish_args_ok(const par_params* p, const par_outline_style* s, const par_p
     } else if (n_colors != 0 || spread != 0 || index_out) {
         return false;
     }
-    if (d->scale_x < 1 || d->scale_x > PAR_MAX_SCALE || d->scale_y < 1 || d->scale_y > PAR_MAX_SCALE) return false;
-    if (d->order != PAR_PRESENT_RGBA && d->order != PAR_PRESENT_BGRA) return false;
-    // (a pitch is an int32: a row of more bytes than that has no valid pitch)
-    return (d->pitch & 3) == 0 && (int64_t)d->pitch >= 4 * (int64_t)p->width * (int64_t)d->scale_x;
+    return present_desc_ok(d, p->width);
 }
 
 }  // namespace
@@ -395,46 +341,27 @@ int par_finish_host(const par_params* params, int device, const par_outline_styl
                         row_end, out, index_out)) {
         return PAR_ERR_INVALID_ARG;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PAR_ERR_NO_DEVICE;
-    if (device < 0) {
-        if (hipGetDevice(&device) != hipSuccess) return PAR_ERR_NO_DEVICE;
-    }
-    if (device >= ndev) return PAR_ERR_INVALID_ARG;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return PAR_ERR_NO_DEVICE;
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return PAR_ERR_NO_DEVICE;  // the kernel is built for gfx950 only
+    const int rc = par_select_device(&device);
+    if (rc != PAR_OK) return rc;
     hipError_t e = hipSetDevice(device);
     const size_t n = (size_t)(row_end - row_begin) * (size_t)params->width;
     const size_t n_g = style ? (size_t)(gbuf_row_end - gbuf_row_begin) * (size_t)params->width : 0;
     const size_t out_rows = (size_t)(row_end - row_begin) * (size_t)desc->scale_y;
     const size_t row_bytes = 4 * (size_t)params->width * (size_t)desc->scale_x;
-    par_pixel* d_gbuf = nullptr;
-    par_color *d_palette = nullptr, *d_fb = nullptr;
-    uint8_t* d_index = nullptr;
-    void* d_out = nullptr;
-    if (e == hipSuccess && style) e = hipMalloc(&d_gbuf, n_g * sizeof(par_pixel));
-    if (e == hipSuccess && palette) e = hipMalloc(&d_palette, (size_t)n_colors * sizeof(par_color));
-    if (e == hipSuccess) e = hipMalloc(&d_fb, n * sizeof(par_color));
-    if (e == hipSuccess && index_out) e = hipMalloc(&d_index, n);
-    if (e == hipSuccess) e = hipMalloc(&d_out, out_rows * (size_t)desc->pitch);
-    if (e == hipSuccess && style) e = hipMemcpy(d_gbuf, gbuf, n_g * sizeof(par_pixel), hipMemcpyHostToDevice);
-    if (e == hipSuccess && palette) e = hipMemcpy(d_palette, palette, (size_t)n_colors * sizeof(par_color), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_fb, fb, n * sizeof(par_color), hipMemcpyHostToDevice);
+    par_device_buffer d_gbuf(e, gbuf, n_g * sizeof(par_pixel), true);
+    par_device_buffer d_palette(e, palette, (size_t)n_colors * sizeof(par_color), true);
+    par_device_buffer d_fb(e, fb, n * sizeof(par_color), true), d_index(e, index_out, n, false);
+    par_device_buffer d_out(e, out, out_rows * (size_t)desc->pitch, false);
     if (e == hipSuccess) {
-        e = launch_finish(nullptr, params, style, d_gbuf, gbuf_row_begin, gbuf_row_end, d_palette, n_colors, spread, *desc,
-                          d_fb, row_begin, row_end, d_out, d_index);
+        e = launch_finish(nullptr, params, style, d_gbuf.as<par_pixel>(), gbuf_row_begin, gbuf_row_end,
+                          d_palette.as<par_color>(), n_colors, spread, *desc, d_fb.as<par_color>(), row_begin, row_end,
+                          d_out.as<void>(), d_index.as<uint8_t>());
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     // a pitched copy: the caller's gap bytes stay as they are
-    if (e == hipSuccess) e = hipMemcpy2D(out, (size_t)desc->pitch, d_out, (size_t)desc->pitch, row_bytes, out_rows, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && index_out) e = hipMemcpy(index_out, d_index, n, hipMemcpyDeviceToHost);
-    if (d_gbuf) (void)hipFree(d_gbuf);
-    if (d_palette) (void)hipFree(d_palette);
-    if (d_fb) (void)hipFree(d_fb);
-    if (d_index) (void)hipFree(d_index);
-    if (d_out) (void)hipFree(d_out);
-    return e == hipSuccess ? PAR_OK : (e == hipErrorOutOfMemory ? PAR_ERR_OOM : PAR_ERR_HIP);
+    if (e == hipSuccess) e = hipMemcpy2D(out, (size_t)desc->pitch, d_out.as<void>(), (size_t)desc->pitch, row_bytes, out_rows, hipMemcpyDeviceToHost);
+    d_index.download(index_out);
+    return par_status_of(e);
 }
 
 }  // extern "C"

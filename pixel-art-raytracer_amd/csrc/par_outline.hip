@@ -23,33 +23,15 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <cstring>
 
+#include "par_hostcall.h"
 #include "par_post.h"
 #include "par_raytracer.h"
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int OUTLINE_TILE_W = 64;   // one wavefront's lanes
-constexpr int OUTLINE_TILE_H = 16;   // four wavefronts x four rows
-constexpr int OUTLINE_THREADS = 256;
-constexpr int OUTLINE_WAVES = OUTLINE_THREADS / 64;
-constexpr int OUTLINE_ROWS_PER_WAVE = OUTLINE_TILE_H / OUTLINE_WAVES;
-constexpr int TEXEL_DWORDS = 7;
-constexpr int STAGED_W = OUTLINE_TILE_W + 2, STAGED_H = OUTLINE_TILE_H + 2;
-// dwords between staged rows: a row's 462 dwords, its phase shift of at most 3, rounded up to whole 16-byte units
-constexpr int STAGED_PITCH = (STAGED_W * TEXEL_DWORDS + 3 + 3) / 4 * 4;
-constexpr int UNITS_PER_ROW = (STAGED_W * TEXEL_DWORDS + 3 + 3) / 4;  // 16-byte units a row's run can touch
-constexpr int UNIT_ROUNDS = (UNITS_PER_ROW + 63) / 64;
-constexpr int STAGE_ROUNDS = (STAGED_H + OUTLINE_WAVES - 1) / OUTLINE_WAVES;
-// rows of one launch: the grid's y extent, and the launch's pixels below 2^31
-constexpr uint32_t OUTLINE_MAX_TILE_ROWS = 65535u;
-constexpr uint32_t OUTLINE_MAX_PX = 0x7FFFFFF0u;
-static_assert(OUTLINE_TILE_W == 64 && OUTLINE_ROWS_PER_WAVE == 4, "the vector outputs deal 4 rows x 16 lanes");
-static_assert(STAGED_PITCH % 4 == 0 && UNITS_PER_ROW * 4 <= STAGED_PITCH, "a staged row stays inside its pitch");
-
+// (OUTLINE_TILE_W .. STAGE_ROUNDS, the tile's geometry, and row_shift are par_post.h's: finish_kernel stages the same
+// tile, in its own copy of the stage below)
 struct OutlineArgs {
     const uint32_t* gbuf;  // dwords of the G-buffer plane, row g0 at index 0
     const uint32_t* fb;    // the three planes address (ra, 0)
@@ -62,12 +44,6 @@ struct OutlineArgs {
     int depth_step, silhouette_scale, crease_scale;
 };
 
-// The shift (0..3 dwords) of staged row `j` of the tile at column tx0, absolute row r: with it the LDS index of a
-// texel's dword is congruent, modulo 4, to its dword address in memory (7 = -1 modulo 4).
-__device__ __forceinline__ uint32_t row_shift(const OutlineArgs& a, uint32_t galign, int r, uint32_t tx0) {
-    return (galign - (uint32_t)(r - a.g0) * a.width - tx0 + 1u) & 3u;
-}
-
 template <bool VEC>
 __global__ __launch_bounds__(OUTLINE_THREADS) void outline_kernel(OutlineArgs a) {
     __shared__ u32x4 staged4[STAGED_H * STAGED_PITCH / 4];
@@ -78,6 +54,7 @@ __global__ __launch_bounds__(OUTLINE_THREADS) void outline_kernel(OutlineArgs a)
     const uint32_t W = a.width;
     const uint32_t tx0 = blockIdx.x * (uint32_t)OUTLINE_TILE_W;
     const int ty0 = a.ra + (int)blockIdx.y * OUTLINE_TILE_H;
+    u32x4 v[STAGE_ROUNDS][UNIT_ROUNDS];
     const uint32_t galign = (uint32_t)(reinterpret_cast<uintptr_t>(a.gbuf) >> 2) & 3u;
 
     // ---- stage: staged row j holds absolute row ty0 - 1 + j, staged column c holds column tx0 - 1 + c -------------
@@ -89,7 +66,6 @@ __global__ __launch_bounds__(OUTLINE_THREADS) void outline_kernel(OutlineArgs a)
     // what it brings along lands in LDS dwords of the row's own pitch that hold no texel of the tile. Only the first
     // and the last unit of the whole plane can go dword by dword.)
     const int64_t plane = (int64_t)(a.g1 - a.g0) * W * TEXEL_DWORDS;
-    u32x4 v[STAGE_ROUNDS][UNIT_ROUNDS];
     #pragma unroll
     for (int jj = 0; jj < STAGE_ROUNDS; jj++) {
         const int j = wave + OUTLINE_WAVES * jj;
@@ -152,6 +128,7 @@ __global__ __launch_bounds__(OUTLINE_THREADS) void outline_kernel(OutlineArgs a)
     }
     __syncthreads();
 
+    uint32_t cls[OUTLINE_ROWS_PER_WAVE];
     // ---- classify: this wavefront's rows ly0 .. ly0 + 3 of the tile, lane = column -------------------------------
     // Every read below stays inside `staged` and none is skipped: a texel of a row or column that was not staged holds
     // whatever LDS held, and its neighbour's `has_` flag keeps it out of the class.
@@ -162,7 +139,6 @@ __global__ __launch_bounds__(OUTLINE_THREADS) void outline_kernel(OutlineArgs a)
         const uint32_t* row = staged + (ly0 + k) * STAGED_PITCH + row_shift(a, galign, ty0 - 1 + ly0 + k, tx0);
         centre[k] = texel_at(row + (lane + 1) * TEXEL_DWORDS, a.background);
     }
-    uint32_t cls[OUTLINE_ROWS_PER_WAVE];
     #pragma unroll
     for (int k = 0; k < OUTLINE_ROWS_PER_WAVE; k++) {
         const int y = ty0 + ly0 + k;
@@ -220,24 +196,18 @@ __global__ __launch_bounds__(OUTLINE_THREADS) void outline_kernel(OutlineArgs a)
     }
 }
 
-// Rows [row_begin, row_end) in launches of whole tile rows: at most OUTLINE_MAX_TILE_ROWS tile rows (the grid's y
-// extent) and at most OUTLINE_MAX_PX pixels each (a single tile row is never cut). Every launch reads the one
+// Rows [row_begin, row_end) in launches of whole tile rows, cut by par_tile_row_cuts. Every launch reads the one
 // G-buffer plane: the rows beside a cut are its halo.
 hipError_t launch_outline(hipStream_t stream, const par_params* p, const par_outline_style* style, const par_pixel* gbuf,
                           int g0, int g1, const par_color* fb, int row_begin, int row_end, par_color* fb_out,
                           uint8_t* edge_out) {
     const uint32_t W = (uint32_t)p->width;
-    const uint32_t by_px = std::max<uint32_t>(1u, OUTLINE_MAX_PX / W / OUTLINE_TILE_H);
-    const uint32_t tile_rows_per_launch = std::min(OUTLINE_MAX_TILE_ROWS, by_px);
     const uint32_t gray = p->background;
     const uintptr_t in = reinterpret_cast<uintptr_t>(fb), out = reinterpret_cast<uintptr_t>(fb_out),
                     edge = reinterpret_cast<uintptr_t>(edge_out);
     // (a multiple of 4 pixels a row keeps every row of every launch at the phase of the plane's first byte)
     const bool vec = W % 4u == 0 && (!fb_out || ((in | out) & 15u) == 0) && (edge & 3u) == 0;
-    for (int ra = row_begin; ra < row_end;) {
-        const uint32_t tile_rows = std::min<uint32_t>(tile_rows_per_launch,
-                                                      ((uint32_t)(row_end - ra) + OUTLINE_TILE_H - 1) / OUTLINE_TILE_H);
-        const int rb = (int)std::min<int64_t>((int64_t)row_end, (int64_t)ra + (int64_t)tile_rows * OUTLINE_TILE_H);
+    return (hipError_t)par_tile_row_cuts(row_begin, row_end, W, OUTLINE_TILE_H, [&](int ra, int rb, uint32_t tile_rows) {
         const size_t at = (size_t)(ra - row_begin) * W;
         OutlineArgs a;
         a.gbuf = reinterpret_cast<const uint32_t*>(gbuf);
@@ -253,11 +223,8 @@ hipError_t launch_outline(hipStream_t stream, const par_params* p, const par_out
         const dim3 grid((W + OUTLINE_TILE_W - 1) / OUTLINE_TILE_W, tile_rows);
         if (vec) hipLaunchKernelGGL(outline_kernel<true>, grid, dim3(OUTLINE_THREADS), 0, stream, a);
         else hipLaunchKernelGGL(outline_kernel<false>, grid, dim3(OUTLINE_THREADS), 0, stream, a);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        ra = rb;
-    }
-    return hipSuccess;
+        return (int)hipGetLastError();
+    });
 }
 
 bool outline_args_ok(const par_params* p, const par_outline_style* s, const par_pixel* gbuf, int g0, int g1,
@@ -288,38 +255,22 @@ int par_outline_host(const par_params* params, int device, const par_outline_sty
     if (!outline_args_ok(params, style, gbuf, gbuf_row_begin, gbuf_row_end, fb, row_begin, row_end, fb_out, edge_out)) {
         return PAR_ERR_INVALID_ARG;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PAR_ERR_NO_DEVICE;
-    if (device < 0) {
-        if (hipGetDevice(&device) != hipSuccess) return PAR_ERR_NO_DEVICE;
-    }
-    if (device >= ndev) return PAR_ERR_INVALID_ARG;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return PAR_ERR_NO_DEVICE;
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return PAR_ERR_NO_DEVICE;  // the kernel is built for gfx950 only
+    const int rc = par_select_device(&device);
+    if (rc != PAR_OK) return rc;
     hipError_t e = hipSetDevice(device);
     const size_t n = (size_t)(row_end - row_begin) * (size_t)params->width;
     const size_t n_g = (size_t)(gbuf_row_end - gbuf_row_begin) * (size_t)params->width;
     // the device copy of fb is outlined in place when fb_out is asked for
-    par_pixel* d_gbuf = nullptr;
-    par_color* d_fb = nullptr;
-    uint8_t* d_edge = nullptr;
-    if (e == hipSuccess) e = hipMalloc(&d_gbuf, n_g * sizeof(par_pixel));
-    if (e == hipSuccess && fb_out) e = hipMalloc(&d_fb, n * sizeof(par_color));
-    if (e == hipSuccess && edge_out) e = hipMalloc(&d_edge, n);
-    if (e == hipSuccess) e = hipMemcpy(d_gbuf, gbuf, n_g * sizeof(par_pixel), hipMemcpyHostToDevice);
-    if (e == hipSuccess && fb_out) e = hipMemcpy(d_fb, fb, n * sizeof(par_color), hipMemcpyHostToDevice);
+    par_device_buffer d_gbuf(e, gbuf, n_g * sizeof(par_pixel), true);
+    par_device_buffer d_fb(e, fb_out ? fb : nullptr, n * sizeof(par_color), true), d_edge(e, edge_out, n, false);
     if (e == hipSuccess) {
-        e = launch_outline(nullptr, params, style, d_gbuf, gbuf_row_begin, gbuf_row_end, d_fb, row_begin, row_end, d_fb,
-                           d_edge);
+        e = launch_outline(nullptr, params, style, d_gbuf.as<par_pixel>(), gbuf_row_begin, gbuf_row_end,
+                           d_fb.as<par_color>(), row_begin, row_end, d_fb.as<par_color>(), d_edge.as<uint8_t>());
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess && fb_out) e = hipMemcpy(fb_out, d_fb, n * sizeof(par_color), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && edge_out) e = hipMemcpy(edge_out, d_edge, n, hipMemcpyDeviceToHost);
-    if (d_gbuf) (void)hipFree(d_gbuf);
-    if (d_fb) (void)hipFree(d_fb);
-    if (d_edge) (void)hipFree(d_edge);
-    return e == hipSuccess ? PAR_OK : (e == hipErrorOutOfMemory ? PAR_ERR_OOM : PAR_ERR_HIP);
+    d_fb.download(fb_out);
+    d_edge.download(edge_out);
+    return par_status_of(e);
 }
 
 }  // extern "C"

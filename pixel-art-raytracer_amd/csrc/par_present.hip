@@ -15,15 +15,13 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <cstring>
 
 #include "par_fastdiv.h"
+#include "par_hostcall.h"
 #include "par_post.h"
 #include "par_raytracer.h"
 
 namespace {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int PRESENT_THREADS = 256;
 // Output pixels of one row of one launch, summed over its source rows (the groups' padding included): flat group
@@ -44,8 +42,7 @@ __global__ __launch_bounds__(PRESENT_THREADS) void present_kernel(const void* __
     __shared__ uint32_t pal[PAR_MAX_PALETTE];
     if (INDEXED) {
         static_assert(PRESENT_THREADS == PAR_MAX_PALETTE, "one palette entry per thread");
-        const uint32_t e = palette[std::min<uint32_t>(threadIdx.x, (uint32_t)n_colors - 1u)];
-        pal[threadIdx.x] = swap ? exchanged(e) : e;
+        pal[threadIdx.x] = palette_entry(palette, n_colors, swap);
         __syncthreads();
     }
     const uint32_t t = blockIdx.x * (uint32_t)PRESENT_THREADS + threadIdx.x;
@@ -61,17 +58,10 @@ __global__ __launch_bounds__(PRESENT_THREADS) void present_kernel(const void* __
         const u32x4 v = *reinterpret_cast<const u32x4*>(static_cast<const uint32_t*>(src) + src_row + base);
         for (int i = 0; i < 4; i++) c[i] = v[i];
     } else {
-        // source column of pixel 0 by division, of the others by stepping; a pixel past the row's end takes the last
-        // column, so that every load stays inside the row, and is not stored. No load waits for a decision: the four
-        // are issued together, and those of one source element are one address
+        // the source columns (group_columns): a pixel past the row's end takes the last column and is not stored. No
+        // load waits for a decision: the four are issued together, and those of one source element are one address
         uint32_t at[4];
-        at[0] = par_udiv31_quotient(base, by_sx);
-        uint32_t rem = base - at[0] * sx;
-        for (int i = 1; i < 4; i++) {
-            const bool step = ++rem == sx;
-            rem = step ? 0u : rem;
-            at[i] = std::min(at[i - 1] + (step ? 1u : 0u), width - 1u);
-        }
+        group_columns(base, sx, by_sx, width - 1u, at);
         if (INDEXED) {
             uint32_t k[4];
             for (int i = 0; i < 4; i++) k[i] = static_cast<const uint8_t*>(src)[src_row + at[i]];
@@ -84,17 +74,7 @@ __global__ __launch_bounds__(PRESENT_THREADS) void present_kernel(const void* __
         for (int i = 0; i < 4; i++) c[i] = exchanged(c[i]);
     }
 
-    if (VEC && full) {
-        const u32x4 v = {c[0], c[1], c[2], c[3]};
-        for (uint32_t y = 0; y < sy; y++) *reinterpret_cast<u32x4*>(dst + y * pitch) = v;
-    } else {
-        for (uint32_t y = 0; y < sy; y++) {
-            uint32_t* const o = reinterpret_cast<uint32_t*>(dst + y * pitch);
-            for (int i = 0; i < 4; i++) {
-                if (base + i < out_width) o[i] = c[i];
-            }
-        }
-    }
+    store_group<VEC>(dst, c, full, base, out_width, sy, pitch);
 }
 
 template <bool INDEXED, bool VEC>
@@ -143,10 +123,7 @@ bool present_args_ok(const par_params* p, const par_present_desc* d, const par_c
     if (index && (!palette || n_colors < 1 || n_colors > PAR_MAX_PALETTE)) return false;
     if (fb && (palette || n_colors != 0)) return false;
     if (p->width <= 0 || row_begin < 0 || row_begin >= row_end || row_end > p->height) return false;
-    if (d->scale_x < 1 || d->scale_x > PAR_MAX_SCALE || d->scale_y < 1 || d->scale_y > PAR_MAX_SCALE) return false;
-    if (d->order != PAR_PRESENT_RGBA && d->order != PAR_PRESENT_BGRA) return false;
-    // (a pitch is an int32: a row of more bytes than that has no valid pitch)
-    return (d->pitch & 3) == 0 && (int64_t)d->pitch >= 4 * (int64_t)p->width * (int64_t)d->scale_x;
+    return present_desc_ok(d, p->width);
 }
 
 }  // namespace
@@ -165,38 +142,22 @@ int par_present_device(const par_params* params, void* stream, const par_present
 int par_present_host(const par_params* params, int device, const par_present_desc* desc, const par_color* fb,
                      const uint8_t* index, const par_color* palette, int n_colors, int row_begin, int row_end, void* out) {
     if (!present_args_ok(params, desc, fb, index, palette, n_colors, row_begin, row_end, out)) return PAR_ERR_INVALID_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PAR_ERR_NO_DEVICE;
-    if (device < 0) {
-        if (hipGetDevice(&device) != hipSuccess) return PAR_ERR_NO_DEVICE;
-    }
-    if (device >= ndev) return PAR_ERR_INVALID_ARG;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return PAR_ERR_NO_DEVICE;
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return PAR_ERR_NO_DEVICE;  // the kernel is built for gfx950 only
+    const int rc = par_select_device(&device);
+    if (rc != PAR_OK) return rc;
     hipError_t e = hipSetDevice(device);
     const size_t n = (size_t)(row_end - row_begin) * (size_t)params->width;
     const size_t out_rows = (size_t)(row_end - row_begin) * (size_t)desc->scale_y;
     const size_t row_bytes = 4 * (size_t)params->width * (size_t)desc->scale_x;
-    par_color *d_palette = nullptr, *d_fb = nullptr;
-    uint8_t* d_index = nullptr;
-    void* d_out = nullptr;
-    if (e == hipSuccess && index) e = hipMalloc(&d_palette, (size_t)n_colors * sizeof(par_color));
-    if (e == hipSuccess && index) e = hipMalloc(&d_index, n);
-    if (e == hipSuccess && fb) e = hipMalloc(&d_fb, n * sizeof(par_color));
-    if (e == hipSuccess) e = hipMalloc(&d_out, out_rows * (size_t)desc->pitch);
-    if (e == hipSuccess && index) e = hipMemcpy(d_palette, palette, (size_t)n_colors * sizeof(par_color), hipMemcpyHostToDevice);
-    if (e == hipSuccess && index) e = hipMemcpy(d_index, index, n, hipMemcpyHostToDevice);
-    if (e == hipSuccess && fb) e = hipMemcpy(d_fb, fb, n * sizeof(par_color), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_present(nullptr, *desc, params->width, d_fb, d_index, d_palette, n_colors, row_begin, row_end, d_out);
+    par_device_buffer d_palette(e, palette, (size_t)n_colors * sizeof(par_color), true), d_index(e, index, n, true);
+    par_device_buffer d_fb(e, fb, n * sizeof(par_color), true), d_out(e, out, out_rows * (size_t)desc->pitch, false);
+    if (e == hipSuccess) {
+        e = launch_present(nullptr, *desc, params->width, d_fb.as<par_color>(), d_index.as<uint8_t>(),
+                           d_palette.as<par_color>(), n_colors, row_begin, row_end, d_out.as<void>());
+    }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     // a pitched copy: the caller's gap bytes stay as they are
-    if (e == hipSuccess) e = hipMemcpy2D(out, (size_t)desc->pitch, d_out, (size_t)desc->pitch, row_bytes, out_rows, hipMemcpyDeviceToHost);
-    if (d_palette) (void)hipFree(d_palette);
-    if (d_index) (void)hipFree(d_index);
-    if (d_fb) (void)hipFree(d_fb);
-    if (d_out) (void)hipFree(d_out);
-    return e == hipSuccess ? PAR_OK : (e == hipErrorOutOfMemory ? PAR_ERR_OOM : PAR_ERR_HIP);
+    if (e == hipSuccess) e = hipMemcpy2D(out, (size_t)desc->pitch, d_out.as<void>(), (size_t)desc->pitch, row_bytes, out_rows, hipMemcpyDeviceToHost);
+    return par_status_of(e);
 }
 
 }  // extern "C"

@@ -14,15 +14,13 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <cstring>
 
 #include "par_fastdiv.h"
+#include "par_hostcall.h"
 #include "par_post.h"
 #include "par_raytracer.h"
 
 namespace {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int QUANT_THREADS = 256;
 // Pixels of one launch: flat indices and the division by the width stay below 2^31 (par_udiv31).
@@ -177,36 +175,21 @@ int par_quantize_host(const par_params* params, int device, const par_color* pal
     if (!quantize_args_ok(params, palette, n_colors, spread, fb, row_begin, row_end, fb_out, index_out)) {
         return PAR_ERR_INVALID_ARG;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PAR_ERR_NO_DEVICE;
-    if (device < 0) {
-        if (hipGetDevice(&device) != hipSuccess) return PAR_ERR_NO_DEVICE;
-    }
-    if (device >= ndev) return PAR_ERR_INVALID_ARG;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return PAR_ERR_NO_DEVICE;
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return PAR_ERR_NO_DEVICE;  // the kernel is built for gfx950 only
+    const int rc = par_select_device(&device);
+    if (rc != PAR_OK) return rc;
     hipError_t e = hipSetDevice(device);
     const size_t n = (size_t)(row_end - row_begin) * (size_t)params->width;
     // the device copy of fb is quantised in place when fb_out is asked for
-    par_color *d_palette = nullptr, *d_fb = nullptr;
-    uint8_t* d_index = nullptr;
-    if (e == hipSuccess) e = hipMalloc(&d_palette, (size_t)n_colors * sizeof(par_color));
-    if (e == hipSuccess) e = hipMalloc(&d_fb, n * sizeof(par_color));
-    if (e == hipSuccess && index_out) e = hipMalloc(&d_index, n);
-    if (e == hipSuccess) e = hipMemcpy(d_palette, palette, (size_t)n_colors * sizeof(par_color), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_fb, fb, n * sizeof(par_color), hipMemcpyHostToDevice);
+    par_device_buffer d_palette(e, palette, (size_t)n_colors * sizeof(par_color), true);
+    par_device_buffer d_fb(e, fb, n * sizeof(par_color), true), d_index(e, index_out, n, false);
     if (e == hipSuccess) {
-        e = launch_quantize(nullptr, d_palette, n_colors, spread, params->width, d_fb, row_begin, row_end,
-                            fb_out ? d_fb : nullptr, d_index);
+        e = launch_quantize(nullptr, d_palette.as<par_color>(), n_colors, spread, params->width, d_fb.as<par_color>(),
+                            row_begin, row_end, fb_out ? d_fb.as<par_color>() : nullptr, d_index.as<uint8_t>());
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess && fb_out) e = hipMemcpy(fb_out, d_fb, n * sizeof(par_color), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && index_out) e = hipMemcpy(index_out, d_index, n, hipMemcpyDeviceToHost);
-    if (d_palette) (void)hipFree(d_palette);
-    if (d_fb) (void)hipFree(d_fb);
-    if (d_index) (void)hipFree(d_index);
-    return e == hipSuccess ? PAR_OK : (e == hipErrorOutOfMemory ? PAR_ERR_OOM : PAR_ERR_HIP);
+    if (fb_out) d_fb.download(fb_out);
+    d_index.download(index_out);
+    return par_status_of(e);
 }
 
 int par_palette_ramp(const par_params* params, int levels, par_color* out, int capacity) {

@@ -21,14 +21,12 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <cstring>
 
+#include "par_hostcall.h"
 #include "par_post.h"
 #include "par_raytracer.h"
 
 namespace {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int UP_THREADS = 256;
 constexpr int UP_TW = 128;  // source columns of a workgroup's tile
@@ -108,7 +106,7 @@ __global__ __launch_bounds__(UP_THREADS) void upscale_kernel(const UpscaleArgs a
         // (the palette's entry is loaded behind the tile's loads and before their waits: one trip to memory, not two)
         static_assert(UP_THREADS == PAR_MAX_PALETTE, "one palette entry per thread");
         uint32_t entry = 0;
-        if (INDEXED && a.out) entry = a.palette[std::min<uint32_t>(threadIdx.x, (uint32_t)a.n_colors - 1u)];
+        if (INDEXED && a.out) entry = palette_entry_load(a.palette, a.n_colors);
 #pragma unroll
         for (int pass = 0; pass < SH / 2; pass++) {
             const int j = 2 * pass + half;
@@ -306,45 +304,26 @@ int par_upscale_host(const par_params* params, int device, const par_upscale_des
     if (!upscale_args_ok(params, desc, fb, index, palette, n_colors, src_row_begin, src_row_end, row_begin, row_end, out, index_out)) {
         return PAR_ERR_INVALID_ARG;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PAR_ERR_NO_DEVICE;
-    if (device < 0) {
-        if (hipGetDevice(&device) != hipSuccess) return PAR_ERR_NO_DEVICE;
-    }
-    if (device >= ndev) return PAR_ERR_INVALID_ARG;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return PAR_ERR_NO_DEVICE;
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return PAR_ERR_NO_DEVICE;  // the kernel is built for gfx950 only
+    const int rc = par_select_device(&device);
+    if (rc != PAR_OK) return rc;
     hipError_t e = hipSetDevice(device);
     const size_t k = (size_t)desc->scaler;
     const size_t n = (size_t)(src_row_end - src_row_begin) * (size_t)params->width;
     const size_t out_rows = (size_t)(row_end - row_begin) * k;
     const size_t row_px = (size_t)params->width * k;
-    par_color *d_palette = nullptr, *d_fb = nullptr;
-    uint8_t *d_index = nullptr, *d_index_out = nullptr;
-    void* d_out = nullptr;
-    if (e == hipSuccess && palette) e = hipMalloc(&d_palette, (size_t)n_colors * sizeof(par_color));
-    if (e == hipSuccess && index) e = hipMalloc(&d_index, n);
-    if (e == hipSuccess && fb) e = hipMalloc(&d_fb, n * sizeof(par_color));
-    if (e == hipSuccess && out) e = hipMalloc(&d_out, out_rows * (size_t)desc->pitch);
-    if (e == hipSuccess && index_out) e = hipMalloc(&d_index_out, out_rows * row_px);
-    if (e == hipSuccess && palette) e = hipMemcpy(d_palette, palette, (size_t)n_colors * sizeof(par_color), hipMemcpyHostToDevice);
-    if (e == hipSuccess && index) e = hipMemcpy(d_index, index, n, hipMemcpyHostToDevice);
-    if (e == hipSuccess && fb) e = hipMemcpy(d_fb, fb, n * sizeof(par_color), hipMemcpyHostToDevice);
+    par_device_buffer d_palette(e, palette, (size_t)n_colors * sizeof(par_color), true), d_index(e, index, n, true);
+    par_device_buffer d_fb(e, fb, n * sizeof(par_color), true), d_out(e, out, out_rows * (size_t)desc->pitch, false);
+    par_device_buffer d_index_out(e, index_out, out_rows * row_px, false);
     if (e == hipSuccess) {
-        e = launch_upscale(nullptr, *desc, params->width, d_fb, d_index, d_palette, n_colors, src_row_begin, src_row_end,
-                           row_begin, row_end, d_out, d_index_out);
+        e = launch_upscale(nullptr, *desc, params->width, d_fb.as<par_color>(), d_index.as<uint8_t>(),
+                           d_palette.as<par_color>(), n_colors, src_row_begin, src_row_end, row_begin, row_end,
+                           d_out.as<void>(), d_index_out.as<uint8_t>());
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     // a pitched copy: the caller's gap bytes stay as they are
-    if (e == hipSuccess && out) e = hipMemcpy2D(out, (size_t)desc->pitch, d_out, (size_t)desc->pitch, 4 * row_px, out_rows, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && index_out) e = hipMemcpy(index_out, d_index_out, out_rows * row_px, hipMemcpyDeviceToHost);
-    if (d_palette) (void)hipFree(d_palette);
-    if (d_index) (void)hipFree(d_index);
-    if (d_fb) (void)hipFree(d_fb);
-    if (d_out) (void)hipFree(d_out);
-    if (d_index_out) (void)hipFree(d_index_out);
-    return e == hipSuccess ? PAR_OK : (e == hipErrorOutOfMemory ? PAR_ERR_OOM : PAR_ERR_HIP);
+    if (e == hipSuccess && out) e = hipMemcpy2D(out, (size_t)desc->pitch, d_out.as<void>(), (size_t)desc->pitch, 4 * row_px, out_rows, hipMemcpyDeviceToHost);
+    d_index_out.download(index_out);
+    return par_status_of(e);
 }
 
 }  // extern "C"
