@@ -621,9 +621,10 @@ int par_outline_host(const par_params* params, int device, const par_outline_sty
  * the arrays is undefined. PAR_ERR_INVALID_ARG, before any device work and with nothing written (no GPU is needed
  * to get it), for a null `params`, palette or `fb`, both outputs null, n_colors outside [1, PAR_MAX_PALETTE], spread
  * outside [0, 255], params->width <= 0, or rows that are not 0 <= row_begin < row_end <= params->height.
- * Left out on purpose: no palette made from the image's content (median cut, k-means: the caller's art direction), no
- * error-diffusion dithering (sequential by nature), no metric other than L1, no fusing into the render kernels, and no
- * graph-capture helper (the device call is capturable as any stream-ordered launch is). */
+ * A palette made from the image's content comes from the fitted-palette calls below (par_palette_*_device), which go
+ * directly before this call on the same stream.
+ * Left out on purpose: no error-diffusion dithering (sequential by nature), no metric other than L1, no fusing into the
+ * render kernels, and no graph-capture helper (the device call is capturable as any stream-ordered launch is). */
 /* device pointers (`d_palette` too), asynchronous on `stream` (a hipStream_t), no sync: in a frame loop it goes on the
  * frame's own stream, after the render or relight call */
 int par_quantize_device(const par_params* params, void* stream, const par_color* d_palette, int n_colors, int spread,
@@ -641,6 +642,68 @@ int par_quantize_host(const par_params* params, int device, const par_color* pal
  * or `out`, capacity < 0, levels outside [2, 255], a count above PAR_MAX_PALETTE, an ambient outside [0, 1] or a
  * palette_size outside [1, PAR_MAX_PALETTE]. */
 int par_palette_ramp(const par_params* params, int levels, par_color* out, int capacity);
+
+/* --- fitted palettes: a frame's palette made on the device by median cut (nothing in the reference) ---------------
+ * par_palette_ramp holds every sprite-palette entry under ONE white factor. Tinted lights, ranged lights and outlines
+ * scale the three channels independently, and a ramp cannot hold those colours: under a tinted light the ramp of a gray
+ * sprite palette is all gray. These calls fit a palette to the colours a frame (or several) actually holds, without a
+ * copy to the host. They run over finished planes as quantise, outline and present do: no context, nothing allocated,
+ * asynchronous on the caller's stream, no synchronisation; retained frames, graphs and statistics are not involved. In
+ * a frame loop they go after render, relight or outline and directly before par_quantize_device, on the same stream:
+ * reset, count, cut, sum, emit. Everything is integer arithmetic and does not depend on the order in which the device
+ * runs anything.
+ * The state is a par_palette_work block (par_types.h) in device memory, 8-byte aligned. cell(p) = (p.red >> 3) |
+ * (p.green >> 3) << 5 | (p.blue >> 3) << 10; alpha takes no part anywhere. `fb` addresses (row_begin, column 0) and
+ * holds (row_end - row_begin) * width pixels, dense and row-major, 4-byte aligned.
+ *   reset  zeroes the whole block.
+ *   count  hist[cell(p)] += 1 (modulo 2^32) for every pixel of the rows. It ADDS: several frames or row blocks counted
+ *          one after another give the histogram of all of them (a GIF's global palette). Reads only `fb`, writes only
+ *          `hist`.
+ *   cut    reads `hist`; writes all of `lut` and `n_entries` and zeroes `sums` (`hist` and `reserved` stay). With
+ *          uint64 sums, a coordinate being a cell's 5-bit value on an axis, the axes in the order red, green, blue:
+ *          a REGION is a box of cells given by inclusive ranges; the regions always partition the 32 x 32 x 32 cube. Its
+ *          population n is the sum of `hist` over it, its tight bounds are the smallest and largest coordinate on each
+ *          axis over its cells with hist > 0, its extent e is the largest hi - lo of its tight bounds.
+ *          If every count is 0: n_entries = 0 and `lut` is all 0. Else region 0 is the whole cube, K = 1, and while
+ *          K < n_colors:
+ *            the region: among those with e >= 1 the largest e, among equals the larger n, then the lower index; none
+ *              ends the cut.
+ *            the axis: the first of red, green, blue whose tight hi - lo equals e.
+ *            the split point: with m[v] the region's population at coordinate v on that axis, s is the smallest v in
+ *              [lo, hi - 1] with 2 * (m[lo] + ... + m[v]) >= n, and hi - 1 if there is none (lo, hi: the tight bounds).
+ *            the split: the region keeps its index with its range on that axis cut to [its lo, s]; region K gets
+ *              [s + 1, its hi]; K += 1. Both halves hold an occupied cell.
+ *          n_entries = K, and lut[c] is the index of the region that holds cell c, the empty cells too, so that a later
+ *          frame's new colours map somewhere. A histogram with C occupied cells gives n_entries = min(n_colors, C).
+ *   sum    sums[lut[cell(p)]] += {red, green, blue, 1} for every pixel of the rows; it adds, as count does. `lut` is
+ *          read as it is found: every byte value names one of the 256 rows of `sums`.
+ *   emit   writes exactly n_colors entries to d_palette. With m = min(n_entries, n_colors): entry k < m with count
+ *          n_k > 0 is {R, G, B, 255}, a channel being the low 8 bits of (2 * sum + n_k) / (2 * n_k) in uint64 (truncating:
+ *          the rounded mean); entry k < m with n_k == 0 is {0, 0, 0, 0}; an entry k >= m is a copy of entry 0 when
+ *          m > 0, else {0, 0, 0, 0}. par_quantize_device takes the lowest index among equals, so a padded entry never
+ *          shows in an index plane and the caller passes n_colors on to it without learning n_entries: no host wait.
+ * A frame whose colours lie one per cell, at most n_colors of them, gets exactly those colours, and quantised with them
+ * at spread 0 it comes back as it is.
+ * PAR_ERR_INVALID_ARG, before any device work and with nothing written (no GPU is needed to get it), for a null
+ * pointer, n_colors outside [1, PAR_MAX_PALETTE], params->width <= 0, rows that are not
+ * 0 <= row_begin < row_end <= params->height, or a `work` that is not 8-byte aligned.
+ * Left out on purpose: no finer cells than 5 bits a channel (a frame gets at most one entry per occupied cell), no
+ * k-means iterations beyond the one mean per region, no weighting by perception, no dither awareness, no fusing into
+ * the quantise or finish kernels, and no graph-capture helper (the calls are capturable as any stream-ordered launch
+ * is). */
+/* device pointers, asynchronous on `stream` (a hipStream_t), no sync */
+int par_palette_reset_device(void* stream, par_palette_work* work);
+int par_palette_count_device(const par_params* params, void* stream, const par_color* fb, int row_begin, int row_end,
+                             par_palette_work* work);
+int par_palette_cut_device(void* stream, par_palette_work* work, int n_colors);
+int par_palette_sum_device(const par_params* params, void* stream, const par_color* fb, int row_begin, int row_end,
+                           par_palette_work* work);
+int par_palette_emit_device(void* stream, const par_palette_work* work, int n_colors, par_color* d_palette);
+/* One frame on host pointers, synchronous, everything on HIP device `device` (-1: the current device, as par_create):
+ * allocates, copies, runs reset, count, cut, sum and emit, synchronises, copies back the n_colors entries and
+ * n_entries, and frees; PAR_ERR_NO_DEVICE / PAR_ERR_OOM / PAR_ERR_HIP as par_quantize_host */
+int par_palette_fit_host(const par_params* params, int device, const par_color* fb, int row_begin, int row_end,
+                         int n_colors, par_color* palette_out, int* n_entries_out);
 
 /* --- present: a frame or an index plane scaled onto a surface (the reference's present, alt:774-788) ---------------
  * The last step of a frame loop: render or relight, then outline, then quantise, then present. The reference copies its

@@ -98,6 +98,18 @@ typedef struct par_upscale_desc {
     int32_t order;   /* PAR_PRESENT_RGBA or PAR_PRESENT_BGRA, as par_present_desc */
 } par_upscale_desc;  /* 12 bytes */
 
+/* The work block of the fitted-palette calls (par_palette_*_device, par_raytracer.h; nothing in the reference): a 15-bit
+ * colour histogram, the table the cut makes of it and the sums the palette's entries are the means of. The cell of a
+ * pixel p is (p.red >> 3) | (p.green >> 3) << 5 | (p.blue >> 3) << 10. */
+#define PAR_PALETTE_CELLS 32768
+typedef struct par_palette_work {
+    uint32_t hist[PAR_PALETTE_CELLS];  /* pixels counted per cell, modulo 2^32 */
+    uint64_t sums[PAR_MAX_PALETTE][4]; /* per entry: sum of red, green, blue, and the pixel count */
+    uint8_t lut[PAR_PALETTE_CELLS];    /* cell -> entry */
+    int32_t n_entries;                 /* entries the cut made, 0..256 */
+    int32_t reserved[3];
+} par_palette_work;                    /* 172 048 bytes; device memory, 8-byte aligned */
+
 /* `Ray`, alt:30-33 (20 bytes: fp32 inverse direction + short origin, 2 bytes tail padding). */
 typedef struct par_ray {
     float inv_x, inv_y, inv_z;

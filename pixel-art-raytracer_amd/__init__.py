@@ -48,6 +48,8 @@ ABI_SYMBOLS = (
     "par_tiles_pack_counted", "par_tiles_fetch", "par_tiles_apply_host", "par_plane_tiles_changed_device",
     "par_plane_tiles_pack", "par_plane_tiles_pack_counted", "par_plane_tiles_unpack", "par_plane_tiles_assemble",
     "par_plane_tiles_fetch", "par_plane_tiles_apply_host", "par_upscale_device", "par_upscale_host",
+    "par_palette_reset_device", "par_palette_count_device", "par_palette_cut_device", "par_palette_sum_device",
+    "par_palette_emit_device", "par_palette_fit_host",
 )
 MAX_LIGHTS = 8  # PAR_MAX_LIGHTS
 LIGHTS_UNBOUNDED, LIGHTS_RANGED = 0, 1  # par_set_light_model
@@ -153,6 +155,12 @@ def lib():
         L.par_quantize_device.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, vp, vp]
         L.par_quantize_host.argtypes = [vp, i32, vp, i32, i32, vp, i32, i32, vp, vp]
         L.par_palette_ramp.argtypes = [vp, i32, vp, i32]
+        L.par_palette_reset_device.argtypes = [vp, vp]
+        L.par_palette_count_device.argtypes = [vp, vp, vp, i32, i32, vp]
+        L.par_palette_cut_device.argtypes = [vp, vp, i32]
+        L.par_palette_sum_device.argtypes = [vp, vp, vp, i32, i32, vp]
+        L.par_palette_emit_device.argtypes = [vp, vp, i32, vp]
+        L.par_palette_fit_host.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp]
         L.par_outline_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, i32, vp, vp]
         L.par_outline_host.argtypes = [vp, i32, vp, vp, i32, i32, vp, i32, i32, vp, vp]
         L.par_present_device.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
@@ -714,6 +722,67 @@ def palette_ramp(params, levels):
     if n < 0:
         raise ParError(-n, "par_palette_ramp")
     return out[:n].copy()
+
+
+# ---- fitted palettes ---------------------------------------------------------------------------------------------
+
+def palette_reset(work, stream=0):
+    """Device pointer (int) of a par_palette_work block (types.PALETTE_WORK, 8-byte aligned): zeroes it
+    (par_palette_reset_device). Asynchronous on `stream`, as all five calls are: reset, count, cut, sum, emit, then
+    quantize with the same n_colors, with no host wait between."""
+    rc = lib().par_palette_reset_device(C.c_void_p(stream), C.c_void_p(work))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_palette_reset_device")
+
+
+def palette_count(params, fb, rows, work, stream=0):
+    """Device pointers (ints): adds rows [rows[0], rows[1]) of the frame block at `fb` to the block's 15-bit colour
+    histogram (par_palette_count_device). Several frames or row blocks counted in turn give the histogram of all."""
+    rc = lib().par_palette_count_device(C.byref(params), C.c_void_p(stream), C.c_void_p(fb), rows[0], rows[1],
+                                        C.c_void_p(work))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_palette_count_device")
+
+
+def palette_cut(work, n_colors, stream=0):
+    """Device pointer (int): the median cut of the block's histogram into at most n_colors regions
+    (par_palette_cut_device): writes the cell -> entry table and n_entries and zeroes the sums."""
+    rc = lib().par_palette_cut_device(C.c_void_p(stream), C.c_void_p(work), n_colors)
+    if rc != PAR_OK:
+        raise ParError(rc, "par_palette_cut_device")
+
+
+def palette_sum(params, fb, rows, work, stream=0):
+    """Device pointers (ints): adds the channels and the count of every pixel of the rows to the sums of the entry its
+    cell maps to (par_palette_sum_device)."""
+    rc = lib().par_palette_sum_device(C.byref(params), C.c_void_p(stream), C.c_void_p(fb), rows[0], rows[1],
+                                      C.c_void_p(work))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_palette_sum_device")
+
+
+def palette_emit(work, n_colors, d_palette, stream=0):
+    """Device pointers (ints): the n_colors palette entries at d_palette from the block's sums, each region's rounded
+    mean, padded with copies of entry 0 beyond the entries the cut made (par_palette_emit_device)."""
+    rc = lib().par_palette_emit_device(C.c_void_p(stream), C.c_void_p(work), n_colors, C.c_void_p(d_palette))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_palette_emit_device")
+
+
+def palette_fit_host(params, fb, n_colors, rows=None, device=-1):
+    """One frame on host arrays (par_palette_fit_host): `fb` is a COLOR array holding rows `rows` (default: the whole
+    frame). Returns (palette, n_entries): a COLOR array of n_colors entries and the number the cut made."""
+    r0, r1 = rows or (0, params.height)
+    fb = np.ascontiguousarray(fb, dtype=COLOR).reshape(-1)
+    n = (r1 - r0) * params.width
+    if len(fb) != n:
+        raise ValueError(f"palette_fit_host: fb holds {len(fb)} pixels, rows {r0}..{r1} of width {params.width} hold {n}")
+    out = np.zeros(max(0, n_colors), dtype=COLOR)
+    n_entries = C.c_int(0)
+    rc = lib().par_palette_fit_host(C.byref(params), device, ptr(fb), r0, r1, n_colors, ptr(out), C.byref(n_entries))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_palette_fit_host")
+    return out, n_entries.value
 
 
 # ---- present -----------------------------------------------------------------------------------------------------

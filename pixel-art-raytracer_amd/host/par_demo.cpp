@@ -8,6 +8,7 @@
 //
 //   par_demo [--keys RRRRUUUUhhhhjjPP] [--frames N] [--out DIR] [--gif FILE] [--debug-line] [--as-sdl] [--size W H L]
 //            [--palette-levels K] [--dither S] [--outline S,C,D] [--scale SX[,SY]] [--finish] [--upscale K]
+//            [--palette-fit N]
 //
 // --gif writes the frames as one animated GIF89a (100 ms per frame like the reference's gif.gif); a frame's colours
 // are palette entries times a brightness, at most a few hundred distinct values, so each frame gets an exact local
@@ -19,6 +20,11 @@
 // palette, par_palette_ramp(params, K): each sprite-palette entry at K brightness bands, then the background. That
 // palette is every frame's local colour table and the index plane is written as it comes back; --dither S (0..255) adds
 // the ordered dither. The PPM frames of --out stay unquantised.
+//
+// --palette-fit N (with --gif; N = 1..256) gives every frame of the GIF a palette of N entries fitted to that frame on
+// the GPU by median cut (par_palette_fit_host) and quantises the frame to it (par_quantize_host): the fitted palette is
+// the frame's local colour table, the index plane is written as it comes back, --dither S applies as with
+// --palette-levels. It is refused together with --palette-levels or --finish. The PPM frames stay unquantised.
 //
 // --outline S,C,D draws every frame's outlines on the GPU (par_outline_host) from the frame's own G-buffer: silhouettes
 // scaled by S / 256, creases by C / 256, a silhouette between two entities from a depth difference of D (128,320,4 is a
@@ -214,7 +220,7 @@ class GifWriter {
 
 int main(int argc, char** argv) {
     std::string keys = "RRRRUUUUhhhhjjPP", out_dir, gif_path;
-    int frames = -1, W = 480, H = 320, L = 320, palette_levels = 0, dither = 0;
+    int frames = -1, W = 480, H = 320, L = 320, palette_levels = 0, dither = 0, palette_fit = 0;
     bool debug_line = false, as_sdl = false, outline = false, finish = false;
     int scale_x = 0, scale_y = 0;  // 0: no --scale
     int upscale = 0;               // 0: no --upscale
@@ -229,6 +235,13 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--finish")) finish = true;
         else if (!std::strcmp(argv[i], "--palette-levels") && i + 1 < argc) palette_levels = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--dither") && i + 1 < argc) dither = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--palette-fit") && i + 1 < argc) {
+            char tail;
+            if (std::sscanf(argv[++i], "%d%c", &palette_fit, &tail) != 1 || palette_fit < 1 || palette_fit > PAR_MAX_PALETTE) {
+                std::fprintf(stderr, "--palette-fit wants 1..%d, got %s\n", PAR_MAX_PALETTE, argv[i]);
+                return 2;
+            }
+        }
         else if (!std::strcmp(argv[i], "--outline") && i + 1 < argc) {
             int s = 0, c = 0, d = 0;
             if (std::sscanf(argv[++i], "%d,%d,%d", &s, &c, &d) != 3) { std::fprintf(stderr, "--outline wants S,C,D, got %s\n", argv[i]); return 2; }
@@ -259,6 +272,10 @@ int main(int argc, char** argv) {
     if (upscale != 0) {
         if (out_dir.empty()) { std::fprintf(stderr, "--upscale wants --out\n"); return 2; }
         if (scale_x != 0 || finish) { std::fprintf(stderr, "--upscale cannot go with --scale or --finish\n"); return 2; }
+    }
+    if (palette_fit != 0 && (palette_levels != 0 || finish)) {
+        std::fprintf(stderr, "--palette-fit cannot go with --palette-levels or --finish: a frame has one palette\n");
+        return 2;
     }
     if (finish) {
         if (out_dir.empty()) { std::fprintf(stderr, "--finish wants --out\n"); return 2; }
@@ -303,6 +320,12 @@ int main(int argc, char** argv) {
         const int n_ramp = par_palette_ramp(&params, palette_levels, ramp.data(), (int)ramp.size());
         if (n_ramp < 0) { std::fprintf(stderr, "--palette-levels %d: %s\n", palette_levels, par_status_string(-n_ramp)); return 2; }
         ramp.resize((size_t)n_ramp);
+        index.resize((size_t)W * H);
+    }
+    // --palette-fit: the GIF's frames are index planes over a palette fitted to each frame
+    std::vector<par_color> fitted;
+    if (palette_fit != 0 && !gif_path.empty()) {
+        fitted.resize((size_t)palette_fit);
         index.resize((size_t)W * H);
     }
     GifWriter gif;
@@ -386,7 +409,18 @@ int main(int argc, char** argv) {
             const int sw = surface.empty() ? W : W * kx, sh = surface.empty() ? H : H * ky;
             if (!write_ppm(out_dir + name, shown, sw, sh)) { std::fprintf(stderr, "cannot write %s%s\n", out_dir.c_str(), name); return 1; }
         }
-        if (!ramp.empty()) {
+        if (!fitted.empty()) {
+            int made = 0;
+            if ((rc = par_palette_fit_host(&params, 0, fb.data(), 0, H, palette_fit, fitted.data(), &made)) != PAR_OK) {
+                std::fprintf(stderr, "par_palette_fit_host: %s\n", par_status_string(rc));
+                return 1;
+            }
+            if ((rc = par_quantize_host(&params, 0, fitted.data(), palette_fit, dither, fb.data(), 0, H, nullptr, index.data())) != PAR_OK) {
+                std::fprintf(stderr, "par_quantize_host: %s\n", par_status_string(rc));
+                return 1;
+            }
+            gif.frame(index, fitted, 10);
+        } else if (!ramp.empty()) {
             if ((rc = par_quantize_host(&params, 0, ramp.data(), (int)ramp.size(), dither, fb.data(), 0, H, nullptr, index.data())) != PAR_OK) {
                 std::fprintf(stderr, "par_quantize_host: %s\n", par_status_string(rc));
                 return 1;

@@ -30,13 +30,17 @@ LIGHT_TINT = np.dtype([("r", "<f4"), ("g", "<f4"), ("b", "<f4")])  # par_light_t
 OUTLINE_STYLE = np.dtype([("depth_step", "<i4"), ("silhouette_scale", "<i4"), ("crease_scale", "<i4")])  # par_outline_style
 PRESENT_DESC = np.dtype([("scale_x", "<i4"), ("scale_y", "<i4"), ("pitch", "<i4"), ("order", "<i4")])  # par_present_desc
 UPSCALE_DESC = np.dtype([("scaler", "<i4"), ("pitch", "<i4"), ("order", "<i4")])  # par_upscale_desc
+PALETTE_CELLS = 32768  # PAR_PALETTE_CELLS
+# par_palette_work: one element is the whole block (np.zeros(1, dtype=PALETTE_WORK))
+PALETTE_WORK = np.dtype([("hist", "<u4", (PALETTE_CELLS,)), ("sums", "<u8", (MAX_PALETTE, 4)),
+                         ("lut", "u1", (PALETTE_CELLS,)), ("n_entries", "<i4"), ("reserved", "<i4", (3,))])
 RAY = np.dtype([("inv_x", "<f4"), ("inv_y", "<f4"), ("inv_z", "<f4"), ("ox", "<i2"), ("oy", "<i2"), ("oz", "<i2"),
                 ("pad", "<i2")])
 
 assert COLOR.itemsize == 4 and VEC3.itemsize == 12 and PIXEL.itemsize == 28
 assert SPRITE.itemsize == 16000 and AABB.itemsize == 16 and LIGHT.itemsize == 8 and RAY.itemsize == 20
 assert LIGHT_TINT.itemsize == 12 and OUTLINE_STYLE.itemsize == 12 and PRESENT_DESC.itemsize == 16
-assert UPSCALE_DESC.itemsize == 12
+assert UPSCALE_DESC.itemsize == 12 and PALETTE_WORK.itemsize == 172048
 
 
 class Color(C.Structure):
@@ -65,6 +69,21 @@ class FrameStats(C.Structure):
                 ("occupied_columns", C.c_int64), ("overflow_columns", C.c_int64),
                 ("ms_bin", C.c_float), ("ms_fill", C.c_float), ("ms_render", C.c_float),
                 ("ms_overflow", C.c_float), ("ms_launch", C.c_float * 5), ("render_merged", C.c_int32)]
+
+
+class PaletteWork(C.Structure):
+    """par_palette_work as a ctypes structure (PALETTE_WORK is the same layout as a numpy dtype)."""
+    _fields_ = [("hist", C.c_uint32 * PALETTE_CELLS), ("sums", (C.c_uint64 * 4) * MAX_PALETTE),
+                ("lut", C.c_uint8 * PALETTE_CELLS), ("n_entries", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+assert C.sizeof(PaletteWork) == PALETTE_WORK.itemsize
+
+
+def palette_cell(colors):
+    """The histogram cell of each entry of a COLOR array: red >> 3 | green >> 3 << 5 | blue >> 3 << 10."""
+    return ((colors["red"].astype(np.int32) >> 3) | ((colors["green"].astype(np.int32) >> 3) << 5) |
+            ((colors["blue"].astype(np.int32) >> 3) << 10))
 
 
 def default_params(width=480, height=320, length=None, bin_size=40):
