@@ -705,6 +705,51 @@ int par_palette_emit_device(void* stream, const par_palette_work* work, int n_co
 int par_palette_fit_host(const par_params* params, int device, const par_color* fb, int row_begin, int row_end,
                          int n_colors, par_color* palette_out, int* n_entries_out);
 
+/* --- refined palettes: k-medians rounds over a palette on the device (nothing in the reference) --------------------
+ * The fit above stops at one mean per box of cells. par_quantize_device assigns by L1 distance, and the refinement
+ * that matches it is k-medians: assign every pixel to its L1-nearest entry, then move each entry to the per-channel
+ * median of its pixels. Either step lowers the summed L1 error or leaves it as it is, which per-channel means do not.
+ * The call runs over finished planes as the fit does: no context, nothing allocated, asynchronous on the caller's
+ * stream, no synchronisation and no host copy. In a frame loop it goes after par_palette_emit_device and before
+ * par_quantize_device, on the same stream; any palette will do, a ramp or a hand-made one too.
+ * `fb` addresses (row_begin, column 0) and holds (row_end - row_begin) * width pixels, dense and row-major, 4-byte
+ * aligned; `d_palette` holds n_colors entries and is read and written. For each of `iterations` rounds, in integers:
+ *   assign  k(p) is the index par_quantize_device gives pixel p against the palette as it stands now, at spread 0:
+ *           the L1-nearest entry over red, green and blue, the lowest index among equals; alpha takes no part.
+ *   update  for every entry k with n_k > 0 assigned pixels, and for each of red, green and blue, the new channel value
+ *           is the LOWER MEDIAN of that channel over its pixels: element (n_k - 1) / 2 (truncating) of the values
+ *           sorted in ascending order. The entry's alpha becomes 255. An entry with n_k == 0 keeps all four bytes.
+ *           All entries are updated from the same assignment.
+ * `d_index` holds (row_end - row_begin) * width bytes, may sit on any byte and is scratch the caller supplies. On return
+ * it holds the assignment of the LAST round: the index plane against the palette as it was BEFORE the last update (not
+ * against the palette the call leaves, unless that round changed nothing). `d_changed` is nullable; when given,
+ * d_changed[0] is the number of entries of which a red, green, blue or alpha byte changed in the last round. 0 means a
+ * fixed point, which further rounds leave alone; a caller may read it whenever it next waits anyway.
+ * `work` is a par_palette_refine_work block (par_types.h) in device memory, 8-byte aligned. The call initialises
+ * whatever it needs in it; between calls its content is the library's. Nothing but it, d_palette, d_index and
+ * d_changed[0] is written.
+ * Consequences: the summed L1 error of the frame quantised at spread 0 never rises from round to round (the largest
+ * error of a single pixel may). Padded copies of entry 0 (par_palette_emit_device's) receive no pixel in the first
+ * round, keep the old entry 0, and may pick up pixels in later rounds. A frame whose colours are all palette entries is
+ * a fixed point. The result does not depend on the order in which the device runs anything.
+ * PAR_ERR_INVALID_ARG, before any device work and with nothing written (no GPU is needed to get it), for a null
+ * `params`, `fb`, `d_palette`, `d_index` or `work`, n_colors outside [1, PAR_MAX_PALETTE], iterations outside [1, 16],
+ * params->width <= 0, rows that are not 0 <= row_begin < row_end <= params->height, or a `work` that is not 8-byte
+ * aligned. PAR_ERR_UNSUPPORTED, as early, when (row_end - row_begin) * width >= 2^32: the tallies are 32-bit.
+ * Left out on purpose: several frames in one refinement (a GIF's global palette), dither awareness (the assignment is
+ * at spread 0), any metric or centre other than L1 and the median, early exit on the device, and fusing into the
+ * quantise or finish kernels. */
+/* device pointers, asynchronous on `stream` (a hipStream_t), no sync */
+int par_palette_refine_device(const par_params* params, void* stream, const par_color* fb, int row_begin, int row_end,
+                              par_color* d_palette, int n_colors, int iterations,
+                              uint8_t* d_index, par_palette_refine_work* work, int32_t* d_changed);
+/* One frame on host pointers, synchronous, everything on HIP device `device` (-1: the current device, as par_create):
+ * allocates, copies `palette` in, runs the rounds, synchronises, copies back the n_colors entries and, where
+ * `changed_out` is not NULL, the changed count, and frees; the same argument checks (`palette` for d_palette; there is
+ * no d_index or work), and PAR_ERR_NO_DEVICE / PAR_ERR_OOM / PAR_ERR_HIP as par_palette_fit_host */
+int par_palette_refine_host(const par_params* params, int device, const par_color* fb, int row_begin, int row_end,
+                            par_color* palette, int n_colors, int iterations, int* changed_out);
+
 /* --- present: a frame or an index plane scaled onto a surface (the reference's present, alt:774-788) ---------------
  * The last step of a frame loop: render or relight, then outline, then quantise, then present. The reference copies its
  * frame row by row into a locked SDL texture, honouring the texture's pitch (alt:776-780); the texture is

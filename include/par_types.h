@@ -110,6 +110,16 @@ typedef struct par_palette_work {
     int32_t reserved[3];
 } par_palette_work;                    /* 172 048 bytes; device memory, 8-byte aligned */
 
+/* The work block of par_palette_refine_device (par_raytracer.h; nothing in the reference): the tallies from which a
+ * round selects every entry's per-channel median by radix, the high four bits of a channel value first and the low four
+ * among the pixels that share the chosen high four. The call initialises what it needs; between calls the content is
+ * the library's. */
+typedef struct par_palette_refine_work {
+    uint32_t bins[PAR_MAX_PALETTE][3][16]; /* per entry and channel: pixels counted per nibble value of the stage */
+    uint32_t rank[PAR_MAX_PALETTE][4];     /* per channel: the median's rank within its high nibble; [3]: the pixels n_k */
+    uint32_t high[PAR_MAX_PALETTE];        /* the chosen high nibbles where a par_color's word has them: 0x00B0G0R0 */
+} par_palette_refine_work;                 /* 54 272 bytes; device memory, 8-byte aligned */
+
 /* `Ray`, alt:30-33 (20 bytes: fp32 inverse direction + short origin, 2 bytes tail padding). */
 typedef struct par_ray {
     float inv_x, inv_y, inv_z;

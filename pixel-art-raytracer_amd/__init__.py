@@ -49,7 +49,7 @@ ABI_SYMBOLS = (
     "par_plane_tiles_pack", "par_plane_tiles_pack_counted", "par_plane_tiles_unpack", "par_plane_tiles_assemble",
     "par_plane_tiles_fetch", "par_plane_tiles_apply_host", "par_upscale_device", "par_upscale_host",
     "par_palette_reset_device", "par_palette_count_device", "par_palette_cut_device", "par_palette_sum_device",
-    "par_palette_emit_device", "par_palette_fit_host",
+    "par_palette_emit_device", "par_palette_fit_host", "par_palette_refine_device", "par_palette_refine_host",
 )
 MAX_LIGHTS = 8  # PAR_MAX_LIGHTS
 LIGHTS_UNBOUNDED, LIGHTS_RANGED = 0, 1  # par_set_light_model
@@ -161,6 +161,8 @@ def lib():
         L.par_palette_sum_device.argtypes = [vp, vp, vp, i32, i32, vp]
         L.par_palette_emit_device.argtypes = [vp, vp, i32, vp]
         L.par_palette_fit_host.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp]
+        L.par_palette_refine_device.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp]
+        L.par_palette_refine_host.argtypes = [vp, i32, vp, i32, i32, vp, i32, i32, vp]
         L.par_outline_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, i32, vp, vp]
         L.par_outline_host.argtypes = [vp, i32, vp, vp, i32, i32, vp, i32, i32, vp, vp]
         L.par_present_device.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
@@ -783,6 +785,38 @@ def palette_fit_host(params, fb, n_colors, rows=None, device=-1):
     if rc != PAR_OK:
         raise ParError(rc, "par_palette_fit_host")
     return out, n_entries.value
+
+
+def palette_refine_device(params, fb, rows, d_palette, n_colors, iterations, d_index, work, d_changed=None, stream=0):
+    """Device pointers (ints): `iterations` k-medians rounds over the n_colors entries at d_palette against rows
+    [rows[0], rows[1]) of the frame block at `fb` (par_palette_refine_device): assign as quantize does at spread 0, move
+    every entry to the per-channel lower median of its pixels. `d_index` is a byte per pixel of scratch and holds the last
+    round's assignment afterwards, `work` a par_palette_refine_work block (types.PALETTE_REFINE_WORK, 8-byte aligned),
+    `d_changed` (None or an int32) gets the number of entries the last round changed. After palette_emit, before
+    quantize, on the same stream."""
+    rc = lib().par_palette_refine_device(C.byref(params), C.c_void_p(stream), C.c_void_p(fb), rows[0], rows[1],
+                                         C.c_void_p(d_palette), n_colors, iterations, C.c_void_p(d_index),
+                                         C.c_void_p(work), C.c_void_p(d_changed))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_palette_refine_device")
+
+
+def palette_refine_host(params, fb, palette, iterations, rows=None, device=-1):
+    """The same on host arrays (par_palette_refine_host): `fb` is a COLOR array holding rows `rows` (default: the whole
+    frame), `palette` a COLOR array, which is not changed. Returns (palette, changed): the refined entries and the number
+    of entries the last round changed (0: a fixed point)."""
+    r0, r1 = rows or (0, params.height)
+    fb = np.ascontiguousarray(fb, dtype=COLOR).reshape(-1)
+    n = (r1 - r0) * params.width
+    if len(fb) != n:
+        raise ValueError(f"palette_refine_host: fb holds {len(fb)} pixels, rows {r0}..{r1} of width {params.width} hold {n}")
+    out = np.array(palette, dtype=COLOR).reshape(-1)
+    changed = C.c_int(0)
+    rc = lib().par_palette_refine_host(C.byref(params), device, ptr(fb), r0, r1, ptr(out), len(out), iterations,
+                                       C.byref(changed))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_palette_refine_host")
+    return out, changed.value
 
 
 # ---- present -----------------------------------------------------------------------------------------------------

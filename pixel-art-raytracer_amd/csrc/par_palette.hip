@@ -1,6 +1,7 @@
 // par_palette.hip — fitted palettes: a frame's palette made on the device by median cut over a 15-bit colour histogram
-// (par_palette_reset_device, _count_device, _cut_device, _sum_device, _emit_device, par_palette_fit_host). The contract
-// is beside the declarations in par_raytracer.h; nothing here knows a par_context, and everything is integer arithmetic
+// (par_palette_reset_device, _count_device, _cut_device, _sum_device, _emit_device, par_palette_fit_host), and a palette
+// refined by k-medians rounds (par_palette_refine_device, par_palette_refine_host). The contracts
+// are beside the declarations in par_raytracer.h; nothing here knows a par_context, and everything is integer arithmetic
 // whose result does not depend on the order in which the device runs it.
 //
 // Count and sum. The rows of a call are one dense array of n pixels, cut into slices, one per workgroup of 1024 lanes. A
@@ -20,6 +21,16 @@
 // bit mask per bin; from those 32 bins the first wavefront finds the split, both halves' populations and tight bounds
 // (prefix sum, ballots, OR reductions) and chooses the next region among the at most 256 (four a lane, then a butterfly).
 // Two barriers a step. The table is written at the end, a region's box per wavefront.
+//
+// Refine (par_palette_refine_device, par_palette_refine_host). A round is par_quantize_device's index plane and then
+// every entry's per-channel lower median over its pixels. An exact median wants 256 bins per entry and channel, 768 KiB,
+// which no workgroup can hold; it is selected by radix instead, four bits a stage. tally_kernel<., false> counts the
+// high nibble of every channel value per (entry, channel), select_kernel<false> finds per (entry, channel) the nibble
+// the rank (n - 1) / 2 falls into and the rank within it, tally_kernel<., true> counts the low nibble of the values that
+// have that high nibble, and select_kernel<true> finds the low nibble and writes the entry. The tally is laid as count
+// and sum are (load_group, launch_over_rows) with 256 x 3 x 16 private dwords in LDS, 48 KiB, and keeps their two
+// remedies: a wavefront of one index and one colour adds once, a lane merges equal neighbours. The stages are ordered by
+// kernel boundaries alone, and a select leaves the bins zero for the next tally.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,6 +45,10 @@ static_assert(sizeof(par_palette_work) == 172048 && offsetof(par_palette_work, h
                   offsetof(par_palette_work, sums) == 131072 && offsetof(par_palette_work, lut) == 139264 &&
                   offsetof(par_palette_work, n_entries) == 172032 && offsetof(par_palette_work, reserved) == 172036,
               "par_palette_work is a public layout");
+static_assert(sizeof(par_palette_refine_work) == 54272 && offsetof(par_palette_refine_work, bins) == 0 &&
+                  offsetof(par_palette_refine_work, rank) == 49152 && offsetof(par_palette_refine_work, high) == 53248 &&
+                  alignof(par_palette_refine_work) <= 8,
+              "par_palette_refine_work is a public layout");
 
 namespace {
 
@@ -442,6 +457,172 @@ __global__ __launch_bounds__(PAR_MAX_PALETTE) void emit_kernel(const par_palette
     palette[k] = out;
 }
 
+// ---- refine ------------------------------------------------------------------------------------------------------
+
+constexpr int REFINE_BINS = PAR_MAX_PALETTE * 3 * 16;  // dwords of par_palette_refine_work::bins
+constexpr uint32_t HIGH_NIBBLES = 0x00F0F0F0u;         // of red, green and blue in a par_color's word
+constexpr int REFINE_MAX_ITERATIONS = 16;
+static_assert(REFINE_BINS % (4 * PALETTE_THREADS) == 0, "a workgroup zeroes and flushes its tallies in whole rounds");
+
+// `n` pixels of entry k and colour rgb into the tallies t of a stage: every channel's high nibble, or (LO) the low
+// nibble of the channels whose high nibble is the one chosen for (k, channel), high[k].
+template <bool LO>
+__device__ __forceinline__ void tally_add(uint32_t* t, const uint32_t* high, uint32_t k, uint32_t rgb, uint32_t n) {
+    uint32_t* const row = t + k * 48u;
+    if (LO) {
+        const uint32_t other = (rgb ^ high[k]) & HIGH_NIBBLES;
+        for (int c = 0; c < 3; c++) {
+            if (((other >> (8 * c)) & 0xFFu) == 0u) atomicAdd(&row[16 * c + ((rgb >> (8 * c)) & 15u)], n);
+        }
+    } else {
+        for (int c = 0; c < 3; c++) atomicAdd(&row[16 * c + ((rgb >> (8 * c + 4)) & 15u)], n);
+    }
+}
+
+// `index` holds the launch's index bytes; index_words: index + (a whole group's first pixel) is on a 4-byte boundary.
+template <bool VEC, bool LO>
+__global__ __launch_bounds__(PALETTE_THREADS) void tally_kernel(const uint32_t* fb, const uint8_t* index, bool index_words,
+                                                                par_palette_refine_work* work, uint32_t n_px,
+                                                                uint32_t lead, uint32_t rounds) {
+    __shared__ __attribute__((aligned(16))) uint32_t t[REFINE_BINS];
+    __shared__ uint32_t high[PAR_MAX_PALETTE];
+    const u32x4 zero = {0u, 0u, 0u, 0u};
+    for (int i = threadIdx.x; i < REFINE_BINS / 4; i += PALETTE_THREADS) reinterpret_cast<u32x4*>(t)[i] = zero;
+    if (LO && threadIdx.x < PAR_MAX_PALETTE) high[threadIdx.x] = work->high[threadIdx.x];
+    __syncthreads();
+
+    const uint32_t g0 = blockIdx.x * rounds * PALETTE_THREADS + threadIdx.x;
+    for (uint32_t it = 0; it < rounds; it++) {
+        uint32_t src[4], n[4], k[4];
+        const uint32_t g = g0 + it * PALETTE_THREADS;
+        const bool full = load_group<VEC>(fb, g, n_px, lead, src, n);
+        const uint32_t base = 4u * g - lead;  // (as load_group forms it; used only where a pixel exists)
+        if (full && index_words) {
+            const uint32_t w = *reinterpret_cast<const uint32_t*>(index + base);
+            for (int i = 0; i < 4; i++) k[i] = (w >> (8 * i)) & 0xFFu;
+        } else {
+            for (int i = 0; i < 4; i++) k[i] = n[i] ? index[base + i] : 0u;
+        }
+        for (int i = 0; i < 4; i++) src[i] &= QUANT_RGB;
+        // a wavefront of one index and one colour adds once
+        const uint32_t k0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)k[0]);
+        const uint32_t c0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)src[0]);
+        const bool one = full && k[0] == k0 && k[1] == k0 && k[2] == k0 && k[3] == k0 && src[0] == c0 && src[1] == c0 &&
+                         src[2] == c0 && src[3] == c0;
+        if (__ballot(one) == ~0ull) {
+            if ((threadIdx.x & 63) == 0) tally_add<LO>(t, high, k0, c0, 256u);
+            continue;
+        }
+        // equal neighbours merge to the right (a pixel that does not exist counts 0 wherever it lands)
+        for (int i = 1; i < 4; i++) {
+            if (k[i] == k[i - 1] && src[i] == src[i - 1]) { n[i] += n[i - 1]; n[i - 1] = 0u; }
+        }
+        for (int i = 0; i < 4; i++) {
+            if (n[i]) tally_add<LO>(t, high, k[i], src[i], n[i]);
+        }
+    }
+    __syncthreads();
+
+    uint32_t* const bins = &work->bins[0][0][0];
+    for (int i = threadIdx.x; i < REFINE_BINS / 4; i += PALETTE_THREADS) {
+        const u32x4 v = reinterpret_cast<const u32x4*>(t)[i];
+        for (int j = 0; j < 4; j++) {
+            if (v[j]) atomicAdd(&bins[4 * i + j], v[j]);
+        }
+    }
+}
+
+// One lane per entry. Stage hi (LO false): per channel n is the sum of the 16 bins and the rank (n - 1) / 2; the high
+// nibble is the first at which the running count passes the rank; it goes to `high`, the rank within it to `rank`, n to
+// rank[k][3]. Stage lo: the low nibble likewise from the rank within; an entry with pixels gets its three medians and
+// alpha 255; the entries that changed are counted into changed[0] where `changed` is given. Both leave the bins zero.
+template <bool LO>
+__global__ __launch_bounds__(PAR_MAX_PALETTE) void select_kernel(par_palette_refine_work* work, uint32_t* palette,
+                                                                 int n_colors, int32_t* changed) {
+    const int k = threadIdx.x;
+    const uint32_t high = LO ? work->high[k] : 0u;
+    uint32_t n_k = LO ? work->rank[k][3] : 0u, picked = 0u;
+    for (int c = 0; c < 3; c++) {
+        uint32_t* const row = work->bins[k][c];
+        uint32_t b[16], n = 0u;
+        // (the block is 8-byte aligned, and so is a row of 16 dwords in it)
+        for (int v = 0; v < 16; v += 2) {
+            const uint2 two = *reinterpret_cast<const uint2*>(row + v);
+            b[v] = two.x; b[v + 1] = two.y;
+            n += two.x + two.y;
+            *reinterpret_cast<uint2*>(row + v) = make_uint2(0u, 0u);
+        }
+        const uint32_t rank = LO ? work->rank[k][c] : (n ? (n - 1u) / 2u : 0u);
+        uint32_t nibble = 0u, below = 0u, cum = 0u;
+        bool found = false;
+        for (int v = 0; v < 16; v++) {
+            if (!found && cum + b[v] > rank) { nibble = (uint32_t)v; below = cum; found = true; }
+            cum += b[v];
+        }
+        if (LO) {
+            picked |= (((high >> (8 * c)) & 0xF0u) | nibble) << (8 * c);
+        } else {
+            picked |= nibble << (8 * c + 4);
+            work->rank[k][c] = rank - below;
+            n_k = n;
+        }
+    }
+    if (LO) {
+        bool moved = false;
+        if (k < n_colors && n_k > 0u) {
+            const uint32_t entry = picked | 0xFF000000u;
+            moved = palette[k] != entry;
+            palette[k] = entry;
+        }
+        const int total = __syncthreads_count(moved);
+        if (changed && k == 0) changed[0] = total;
+    } else {
+        work->rank[k][3] = n_k;
+        work->high[k] = picked;
+    }
+}
+
+template <bool LO>
+hipError_t launch_tally(hipStream_t stream, int width, const par_color* fb, int row_begin, int row_end,
+                        const uint8_t* d_index, par_palette_refine_work* work) {
+    return launch_over_rows(
+        fb, width, row_begin, row_end,
+        [&](const uint32_t* src, uint32_t n_px, uint32_t lead, bool vec, uint32_t rounds, uint32_t blocks) {
+            const dim3 grid(blocks), block(PALETTE_THREADS);
+            const uint8_t* index = d_index + (src - reinterpret_cast<const uint32_t*>(fb));
+            // a whole group's first pixel is 4 * g - lead
+            const bool index_words = ((reinterpret_cast<uintptr_t>(index) - lead) & 3u) == 0;
+            if (vec) hipLaunchKernelGGL((tally_kernel<true, LO>), grid, block, 0, stream, src, index, index_words, work, n_px, lead, rounds);
+            else hipLaunchKernelGGL((tally_kernel<false, LO>), grid, block, 0, stream, src, index, index_words, work, n_px, lead, rounds);
+        });
+}
+
+template <bool LO>
+hipError_t launch_select(hipStream_t stream, par_palette_refine_work* work, par_color* d_palette, int n_colors,
+                         int32_t* d_changed) {
+    hipLaunchKernelGGL(select_kernel<LO>, dim3(1), dim3(PAR_MAX_PALETTE), 0, stream, work, reinterpret_cast<uint32_t*>(d_palette),
+                       n_colors, d_changed);
+    return hipGetLastError();
+}
+
+// The rounds of a refinement on `stream`, the arguments checked: a par_status.
+int run_refine(const par_params* params, hipStream_t stream, const par_color* fb, int row_begin, int row_end,
+               par_color* d_palette, int n_colors, int iterations, uint8_t* d_index, par_palette_refine_work* work,
+               int32_t* d_changed) {
+    const int W = params->width;
+    if (hipMemsetAsync(work->bins, 0, sizeof(work->bins), stream) != hipSuccess) return PAR_ERR_HIP;
+    for (int it = 0; it < iterations; it++) {
+        const int rc = par_quantize_device(params, stream, d_palette, n_colors, 0, fb, row_begin, row_end, nullptr, d_index);
+        if (rc != PAR_OK) return rc;
+        hipError_t e = launch_tally<false>(stream, W, fb, row_begin, row_end, d_index, work);
+        if (e == hipSuccess) e = launch_select<false>(stream, work, d_palette, n_colors, nullptr);
+        if (e == hipSuccess) e = launch_tally<true>(stream, W, fb, row_begin, row_end, d_index, work);
+        if (e == hipSuccess) e = launch_select<true>(stream, work, d_palette, n_colors, it == iterations - 1 ? d_changed : nullptr);
+        if (e != hipSuccess) return PAR_ERR_HIP;
+    }
+    return PAR_OK;
+}
+
 bool work_ok(const par_palette_work* work) { return work && (reinterpret_cast<uintptr_t>(work) & 7u) == 0; }
 bool colors_ok(int n_colors) { return n_colors >= 1 && n_colors <= PAR_MAX_PALETTE; }
 bool plane_args_ok(const par_params* p, const par_color* fb, int row_begin, int row_end) {
@@ -449,6 +630,17 @@ bool plane_args_ok(const par_params* p, const par_color* fb, int row_begin, int 
 }
 
 int status_of_launch() { return hipGetLastError() == hipSuccess ? PAR_OK : PAR_ERR_HIP; }
+
+// PAR_OK, or the status the contract gives these arguments of a refinement (`palette`: the host's or the device's)
+int refine_args_status(const par_params* params, const par_color* fb, int row_begin, int row_end, const par_color* palette,
+                       int n_colors, int iterations) {
+    if (!plane_args_ok(params, fb, row_begin, row_end) || !palette || !colors_ok(n_colors) || iterations < 1 ||
+        iterations > REFINE_MAX_ITERATIONS) {
+        return PAR_ERR_INVALID_ARG;
+    }
+    // the tallies are 32-bit
+    return (int64_t)(row_end - row_begin) * (int64_t)params->width >= (1ll << 32) ? PAR_ERR_UNSUPPORTED : PAR_OK;
+}
 
 }  // namespace
 
@@ -514,6 +706,42 @@ int par_palette_fit_host(const par_params* params, int device, const par_color* 
     if (e == hipSuccess) e = hipMemcpy(&n_entries, &work->n_entries, sizeof(int), hipMemcpyDeviceToHost);
     d_palette.download(palette_out);
     if (e == hipSuccess) *n_entries_out = n_entries;
+    return par_status_of(e);
+}
+
+int par_palette_refine_device(const par_params* params, void* stream, const par_color* fb, int row_begin, int row_end,
+                              par_color* d_palette, int n_colors, int iterations, uint8_t* d_index,
+                              par_palette_refine_work* work, int32_t* d_changed) {
+    if (!d_index || !work || (reinterpret_cast<uintptr_t>(work) & 7u) != 0) return PAR_ERR_INVALID_ARG;
+    const int rc = refine_args_status(params, fb, row_begin, row_end, d_palette, n_colors, iterations);
+    if (rc != PAR_OK) return rc;
+    return run_refine(params, (hipStream_t)stream, fb, row_begin, row_end, d_palette, n_colors, iterations, d_index, work,
+                      d_changed);
+}
+
+int par_palette_refine_host(const par_params* params, int device, const par_color* fb, int row_begin, int row_end,
+                            par_color* palette, int n_colors, int iterations, int* changed_out) {
+    int rc = refine_args_status(params, fb, row_begin, row_end, palette, n_colors, iterations);
+    if (rc != PAR_OK) return rc;
+    rc = par_select_device(&device);
+    if (rc != PAR_OK) return rc;
+    hipError_t e = hipSetDevice(device);
+    const size_t n = (size_t)(row_end - row_begin) * (size_t)params->width;
+    par_device_buffer d_fb(e, fb, n * sizeof(par_color), true);
+    par_device_buffer d_palette(e, palette, (size_t)n_colors * sizeof(par_color), true);
+    // (none of the three is uploaded: `palette` only says that they are in use)
+    par_device_buffer d_index(e, palette, n, false);
+    par_device_buffer d_work(e, palette, sizeof(par_palette_refine_work), false);
+    par_device_buffer d_changed(e, palette, sizeof(int32_t), false);
+    if (e != hipSuccess) return par_status_of(e);
+    rc = run_refine(params, nullptr, d_fb.as<par_color>(), row_begin, row_end, d_palette.as<par_color>(), n_colors,
+                    iterations, d_index.as<uint8_t>(), d_work.as<par_palette_refine_work>(), d_changed.as<int32_t>());
+    if (rc != PAR_OK) return rc;
+    e = hipDeviceSynchronize();
+    int32_t changed = 0;
+    d_changed.download(&changed);
+    d_palette.download(palette);
+    if (e == hipSuccess && changed_out) *changed_out = changed;
     return par_status_of(e);
 }
 

@@ -8,7 +8,7 @@
 //
 //   par_demo [--keys RRRRUUUUhhhhjjPP] [--frames N] [--out DIR] [--gif FILE] [--debug-line] [--as-sdl] [--size W H L]
 //            [--palette-levels K] [--dither S] [--outline S,C,D] [--scale SX[,SY]] [--finish] [--upscale K]
-//            [--palette-fit N]
+//            [--palette-fit N] [--palette-refine I]
 //
 // --gif writes the frames as one animated GIF89a (100 ms per frame like the reference's gif.gif); a frame's colours
 // are palette entries times a brightness, at most a few hundred distinct values, so each frame gets an exact local
@@ -25,6 +25,8 @@
 // the GPU by median cut (par_palette_fit_host) and quantises the frame to it (par_quantize_host): the fitted palette is
 // the frame's local colour table, the index plane is written as it comes back, --dither S applies as with
 // --palette-levels. It is refused together with --palette-levels or --finish. The PPM frames stay unquantised.
+// --palette-refine I (with --palette-fit; I = 1..16) refines each frame's fitted palette by I k-medians rounds on the GPU
+// (par_palette_refine_host) before the frame is quantised to it.
 //
 // --outline S,C,D draws every frame's outlines on the GPU (par_outline_host) from the frame's own G-buffer: silhouettes
 // scaled by S / 256, creases by C / 256, a silhouette between two entities from a depth difference of D (128,320,4 is a
@@ -220,7 +222,7 @@ class GifWriter {
 
 int main(int argc, char** argv) {
     std::string keys = "RRRRUUUUhhhhjjPP", out_dir, gif_path;
-    int frames = -1, W = 480, H = 320, L = 320, palette_levels = 0, dither = 0, palette_fit = 0;
+    int frames = -1, W = 480, H = 320, L = 320, palette_levels = 0, dither = 0, palette_fit = 0, palette_refine = 0;
     bool debug_line = false, as_sdl = false, outline = false, finish = false;
     int scale_x = 0, scale_y = 0;  // 0: no --scale
     int upscale = 0;               // 0: no --upscale
@@ -239,6 +241,13 @@ int main(int argc, char** argv) {
             char tail;
             if (std::sscanf(argv[++i], "%d%c", &palette_fit, &tail) != 1 || palette_fit < 1 || palette_fit > PAR_MAX_PALETTE) {
                 std::fprintf(stderr, "--palette-fit wants 1..%d, got %s\n", PAR_MAX_PALETTE, argv[i]);
+                return 2;
+            }
+        }
+        else if (!std::strcmp(argv[i], "--palette-refine") && i + 1 < argc) {
+            char tail;
+            if (std::sscanf(argv[++i], "%d%c", &palette_refine, &tail) != 1 || palette_refine < 1 || palette_refine > 16) {
+                std::fprintf(stderr, "--palette-refine wants 1..16, got %s\n", argv[i]);
                 return 2;
             }
         }
@@ -275,6 +284,10 @@ int main(int argc, char** argv) {
     }
     if (palette_fit != 0 && (palette_levels != 0 || finish)) {
         std::fprintf(stderr, "--palette-fit cannot go with --palette-levels or --finish: a frame has one palette\n");
+        return 2;
+    }
+    if (palette_refine != 0 && palette_fit == 0) {
+        std::fprintf(stderr, "--palette-refine wants --palette-fit: it refines the fitted palette\n");
         return 2;
     }
     if (finish) {
@@ -413,6 +426,11 @@ int main(int argc, char** argv) {
             int made = 0;
             if ((rc = par_palette_fit_host(&params, 0, fb.data(), 0, H, palette_fit, fitted.data(), &made)) != PAR_OK) {
                 std::fprintf(stderr, "par_palette_fit_host: %s\n", par_status_string(rc));
+                return 1;
+            }
+            if (palette_refine != 0 &&
+                (rc = par_palette_refine_host(&params, 0, fb.data(), 0, H, fitted.data(), palette_fit, palette_refine, nullptr)) != PAR_OK) {
+                std::fprintf(stderr, "par_palette_refine_host: %s\n", par_status_string(rc));
                 return 1;
             }
             if ((rc = par_quantize_host(&params, 0, fitted.data(), palette_fit, dither, fb.data(), 0, H, nullptr, index.data())) != PAR_OK) {

@@ -34,13 +34,16 @@ PALETTE_CELLS = 32768  # PAR_PALETTE_CELLS
 # par_palette_work: one element is the whole block (np.zeros(1, dtype=PALETTE_WORK))
 PALETTE_WORK = np.dtype([("hist", "<u4", (PALETTE_CELLS,)), ("sums", "<u8", (MAX_PALETTE, 4)),
                          ("lut", "u1", (PALETTE_CELLS,)), ("n_entries", "<i4"), ("reserved", "<i4", (3,))])
+# par_palette_refine_work: one element is the whole block
+PALETTE_REFINE_WORK = np.dtype([("bins", "<u4", (MAX_PALETTE, 3, 16)), ("rank", "<u4", (MAX_PALETTE, 4)),
+                                ("high", "<u4", (MAX_PALETTE,))])
 RAY = np.dtype([("inv_x", "<f4"), ("inv_y", "<f4"), ("inv_z", "<f4"), ("ox", "<i2"), ("oy", "<i2"), ("oz", "<i2"),
                 ("pad", "<i2")])
 
 assert COLOR.itemsize == 4 and VEC3.itemsize == 12 and PIXEL.itemsize == 28
 assert SPRITE.itemsize == 16000 and AABB.itemsize == 16 and LIGHT.itemsize == 8 and RAY.itemsize == 20
 assert LIGHT_TINT.itemsize == 12 and OUTLINE_STYLE.itemsize == 12 and PRESENT_DESC.itemsize == 16
-assert UPSCALE_DESC.itemsize == 12 and PALETTE_WORK.itemsize == 172048
+assert UPSCALE_DESC.itemsize == 12 and PALETTE_WORK.itemsize == 172048 and PALETTE_REFINE_WORK.itemsize == 54272
 
 
 class Color(C.Structure):
@@ -78,6 +81,15 @@ class PaletteWork(C.Structure):
 
 
 assert C.sizeof(PaletteWork) == PALETTE_WORK.itemsize
+
+
+class PaletteRefineWork(C.Structure):
+    """par_palette_refine_work as a ctypes structure (PALETTE_REFINE_WORK is the same layout as a numpy dtype)."""
+    _fields_ = [("bins", ((C.c_uint32 * 16) * 3) * MAX_PALETTE), ("rank", (C.c_uint32 * 4) * MAX_PALETTE),
+                ("high", C.c_uint32 * MAX_PALETTE)]
+
+
+assert C.sizeof(PaletteRefineWork) == PALETTE_REFINE_WORK.itemsize
 
 
 def palette_cell(colors):
