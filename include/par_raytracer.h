@@ -623,8 +623,9 @@ int par_outline_host(const par_params* params, int device, const par_outline_sty
  * outside [0, 255], params->width <= 0, or rows that are not 0 <= row_begin < row_end <= params->height.
  * A palette made from the image's content comes from the fitted-palette calls below (par_palette_*_device), which go
  * directly before this call on the same stream.
- * Left out on purpose: no error-diffusion dithering (sequential by nature), no metric other than L1, no fusing into the
- * render kernels, and no graph-capture helper (the device call is capturable as any stream-ordered launch is). */
+ * Left out on purpose: no error-diffusion dithering (sequential by nature; its parallel substitute, pattern dithering,
+ * is par_quantize_pattern_device below), no metric other than L1, no fusing into the render kernels, and no
+ * graph-capture helper (the device call is capturable as any stream-ordered launch is). */
 /* device pointers (`d_palette` too), asynchronous on `stream` (a hipStream_t), no sync: in a frame loop it goes on the
  * frame's own stream, after the render or relight call */
 int par_quantize_device(const par_params* params, void* stream, const par_color* d_palette, int n_colors, int spread,
@@ -642,6 +643,52 @@ int par_quantize_host(const par_params* params, int device, const par_color* pal
  * or `out`, capacity < 0, levels outside [2, 255], a count above PAR_MAX_PALETTE, an ambient outside [0, 1] or a
  * palette_size outside [1, PAR_MAX_PALETTE]. */
 int par_palette_ramp(const par_params* params, int levels, par_color* out, int capacity);
+
+/* --- pattern dither: palette-aware ordered dithering (nothing in the reference) -----------------------------------
+ * par_quantize_device's dither adds one offset of one strength to all three channels, which suits a regular palette
+ * whose neighbouring entries lie about `spread` apart on every channel. A fitted or refined palette (below) is
+ * irregular: dense where the frame has colours, sparse elsewhere, and off the gray axis under tinted lights. This call
+ * is Thomas Knoll's pattern dithering, the order-free substitute for error diffusion: each pixel builds its own list of
+ * `depth` palette entries whose mean approximates the pixel, and the Bayer matrix picks one of them. It reads only the
+ * pixel and its absolute position.
+ * The planes, the row addressing, the outputs and the in-place rule are exactly par_quantize_device's: `fb`, `fb_out`
+ * and `index_out` address the element of (row_begin, column 0) and hold (row_end - row_begin) * width elements, dense
+ * and row-major; fb_out == fb is allowed, any other overlap is undefined; the pixel's own alpha passes through, and
+ * alpha takes no part otherwise. Every pixel of the rows is processed. For the pixel {r, g, b, a} at column x and
+ * ABSOLUTE frame row y, in integers, with B4 the matrix of the quantise contract:
+ *     e = (0, 0, 0)
+ *     for j in 0 .. depth-1:
+ *         t_c  = min(255, max(0, c + floor(e_c * strength / 256)))   for c = r, g, b  (floor towards minus infinity)
+ *         k_j  = the entry par_quantize_device gives the colour t at spread 0 (L1-nearest, lowest index among equals)
+ *         e_c += c - P[k_j].c                                        (the pixel's own c, not t_c; |e_c| <= 255 * depth)
+ *     key_j = ((77 * P[k_j].red + 150 * P[k_j].green + 29 * P[k_j].blue) << 8) | k_j      (luma <= 65 280: 24 bits)
+ *     sort the depth keys ascending   (equal keys are the same entry, so the order is total: darker first, then the
+ *                                      lower index)
+ *     rank = (B4[y & 3][x & 3] * depth) >> 4
+ *     k    = key_sorted[rank] & 255
+ *     index_out = (uint8_t)k                        when index_out is not NULL
+ *     fb_out    = {P[k].red, P[k].green, P[k].blue, a}   when fb_out is not NULL (the pixel's own alpha)
+ * Consequences: depth == 1 or strength == 0 gives what par_quantize_device gives at spread 0. A pixel whose colour is a
+ * palette entry comes back as that entry at any depth and strength, because e stays 0. A padded copy of entry 0
+ * (par_palette_emit_device's) never shows, since every k_j is the lowest index among equals. The result depends on
+ * nothing but the pixel, x & 3 and y & 3, so a row block equals the whole frame's rows.
+ * PAR_ERR_INVALID_ARG, before any device work and with nothing written (no GPU is needed to get it), for a null
+ * `params`, palette or `fb`, both outputs null, n_colors outside [1, PAR_MAX_PALETTE], depth outside [1, 16], strength
+ * outside [0, 256], params->width <= 0, or rows that are not 0 <= row_begin < row_end <= params->height.
+ * In a frame loop it takes par_quantize_device's place: after the palette calls below, on the same stream.
+ * Left out on purpose: no matrix other than B4, no sort key other than that luma, no fusing into par_finish_device, no
+ * dither awareness in par_palette_refine_device (its assignment stays at spread 0), and no graph-capture helper (the
+ * device call is capturable as any stream-ordered launch is). */
+/* device pointers (`d_palette` too), asynchronous on `stream` (a hipStream_t), no sync */
+int par_quantize_pattern_device(const par_params* params, void* stream, const par_color* d_palette, int n_colors,
+                                int depth, int strength, const par_color* fb, int row_begin, int row_end,
+                                par_color* fb_out, uint8_t* index_out);
+/* host pointers, synchronous, everything on HIP device `device` (-1: the current device, as par_create): allocates,
+ * copies, launches, synchronises, copies back and frees; PAR_ERR_NO_DEVICE / PAR_ERR_OOM / PAR_ERR_HIP as
+ * par_quantize_host */
+int par_quantize_pattern_host(const par_params* params, int device, const par_color* palette, int n_colors,
+                              int depth, int strength, const par_color* fb, int row_begin, int row_end,
+                              par_color* fb_out, uint8_t* index_out);
 
 /* --- fitted palettes: a frame's palette made on the device by median cut (nothing in the reference) ---------------
  * par_palette_ramp holds every sprite-palette entry under ONE white factor. Tinted lights, ranged lights and outlines

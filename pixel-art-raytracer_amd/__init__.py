@@ -50,6 +50,7 @@ ABI_SYMBOLS = (
     "par_plane_tiles_fetch", "par_plane_tiles_apply_host", "par_upscale_device", "par_upscale_host",
     "par_palette_reset_device", "par_palette_count_device", "par_palette_cut_device", "par_palette_sum_device",
     "par_palette_emit_device", "par_palette_fit_host", "par_palette_refine_device", "par_palette_refine_host",
+    "par_quantize_pattern_device", "par_quantize_pattern_host",
 )
 MAX_LIGHTS = 8  # PAR_MAX_LIGHTS
 LIGHTS_UNBOUNDED, LIGHTS_RANGED = 0, 1  # par_set_light_model
@@ -154,6 +155,8 @@ def lib():
         L.par_plane_tiles_apply_host.argtypes = [vp, i32, vp, i32, vp, i32, i32, vp]
         L.par_quantize_device.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, vp, vp]
         L.par_quantize_host.argtypes = [vp, i32, vp, i32, i32, vp, i32, i32, vp, vp]
+        L.par_quantize_pattern_device.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, vp, vp]
+        L.par_quantize_pattern_host.argtypes = [vp, i32, vp, i32, i32, i32, vp, i32, i32, vp, vp]
         L.par_palette_ramp.argtypes = [vp, i32, vp, i32]
         L.par_palette_reset_device.argtypes = [vp, vp]
         L.par_palette_count_device.argtypes = [vp, vp, vp, i32, i32, vp]
@@ -713,6 +716,42 @@ def quantize_host(params, palette, fb, rows=None, spread=0, planes=("index",), d
                                  ptr(out.get("fb")), ptr(out.get("index")))
     if rc != PAR_OK:
         raise ParError(rc, "par_quantize_host")
+    return out
+
+
+def quantize_pattern(params, d_palette, n_colors, fb, rows, depth, strength=256, fb_out=None, index_out=None, stream=0):
+    """Device pointers (ints): rows [rows[0], rows[1]) of the frame block at `fb` quantised to the n_colors entries at
+    d_palette by pattern dithering (par_quantize_pattern_device: `depth` candidates a pixel, 1..16, their error fed back
+    at strength / 256, 0..256, the 4x4 Bayer matrix picking one by luma rank) into the index plane at index_out and / or
+    the RGBA plane at fb_out (fb_out == fb: in place). Asynchronous on `stream`."""
+    rc = lib().par_quantize_pattern_device(C.byref(params), C.c_void_p(stream), C.c_void_p(d_palette), n_colors, depth,
+                                           strength, C.c_void_p(fb), rows[0], rows[1], C.c_void_p(fb_out),
+                                           C.c_void_p(index_out))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_quantize_pattern_device")
+
+
+def quantize_pattern_host(params, palette, fb, depth, strength=256, rows=None, planes=("index",), device=-1):
+    """The same on host arrays (par_quantize_pattern_host): `palette` and `fb` are COLOR arrays, fb the rows `rows`
+    (default: the whole frame). Returns {"index": uint8 array, "fb": COLOR array} for the planes asked for."""
+    r0, r1 = rows or (0, params.height)
+    palette = np.ascontiguousarray(palette, dtype=COLOR).reshape(-1)
+    fb = np.ascontiguousarray(fb, dtype=COLOR).reshape(-1)
+    n = (r1 - r0) * params.width
+    if len(fb) != n:
+        raise ValueError(f"quantize_pattern_host: fb holds {len(fb)} pixels, rows {r0}..{r1} of width {params.width} hold {n}")
+    unknown = set(planes) - {"index", "fb"}
+    if unknown:
+        raise ValueError(f"quantize_pattern_host: unknown planes {sorted(unknown)}")
+    out = {}
+    if "index" in planes:
+        out["index"] = np.zeros(n, dtype=np.uint8)
+    if "fb" in planes:
+        out["fb"] = np.zeros(n, dtype=COLOR)
+    rc = lib().par_quantize_pattern_host(C.byref(params), device, ptr(palette), len(palette), depth, strength, ptr(fb), r0,
+                                         r1, ptr(out.get("fb")), ptr(out.get("index")))
+    if rc != PAR_OK:
+        raise ParError(rc, "par_quantize_pattern_host")
     return out
 
 

@@ -8,7 +8,7 @@
 //
 //   par_demo [--keys RRRRUUUUhhhhjjPP] [--frames N] [--out DIR] [--gif FILE] [--debug-line] [--as-sdl] [--size W H L]
 //            [--palette-levels K] [--dither S] [--outline S,C,D] [--scale SX[,SY]] [--finish] [--upscale K]
-//            [--palette-fit N] [--palette-refine I]
+//            [--palette-fit N] [--palette-refine I] [--dither-pattern N[,S]]
 //
 // --gif writes the frames as one animated GIF89a (100 ms per frame like the reference's gif.gif); a frame's colours
 // are palette entries times a brightness, at most a few hundred distinct values, so each frame gets an exact local
@@ -27,6 +27,9 @@
 // --palette-levels. It is refused together with --palette-levels or --finish. The PPM frames stay unquantised.
 // --palette-refine I (with --palette-fit; I = 1..16) refines each frame's fitted palette by I k-medians rounds on the GPU
 // (par_palette_refine_host) before the frame is quantised to it.
+// --dither-pattern N[,S] (with --palette-levels or --palette-fit; N = 1..16 candidates a pixel, S = 0..256 the strength
+// of the error fed back, 256 when left out) takes the GIF's index planes from par_quantize_pattern_host, pattern
+// dithering, in place of par_quantize_host. It is refused together with --dither or --finish.
 //
 // --outline S,C,D draws every frame's outlines on the GPU (par_outline_host) from the frame's own G-buffer: silhouettes
 // scaled by S / 256, creases by C / 256, a silhouette between two entities from a depth difference of D (128,320,4 is a
@@ -223,7 +226,8 @@ class GifWriter {
 int main(int argc, char** argv) {
     std::string keys = "RRRRUUUUhhhhjjPP", out_dir, gif_path;
     int frames = -1, W = 480, H = 320, L = 320, palette_levels = 0, dither = 0, palette_fit = 0, palette_refine = 0;
-    bool debug_line = false, as_sdl = false, outline = false, finish = false;
+    bool debug_line = false, as_sdl = false, outline = false, finish = false, dither_given = false;
+    int pattern_depth = 0, pattern_strength = 256;  // depth 0: no --dither-pattern
     int scale_x = 0, scale_y = 0;  // 0: no --scale
     int upscale = 0;               // 0: no --upscale
     par_outline_style outline_style{4, 256, 256};
@@ -236,7 +240,16 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--as-sdl")) as_sdl = true;
         else if (!std::strcmp(argv[i], "--finish")) finish = true;
         else if (!std::strcmp(argv[i], "--palette-levels") && i + 1 < argc) palette_levels = std::atoi(argv[++i]);
-        else if (!std::strcmp(argv[i], "--dither") && i + 1 < argc) dither = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--dither") && i + 1 < argc) { dither = std::atoi(argv[++i]); dither_given = true; }
+        else if (!std::strcmp(argv[i], "--dither-pattern") && i + 1 < argc) {
+            char tail = 0;
+            const bool alone = std::sscanf(argv[++i], "%d%c", &pattern_depth, &tail) == 1;
+            if ((!alone && std::sscanf(argv[i], "%d,%d%c", &pattern_depth, &pattern_strength, &tail) != 2) || pattern_depth < 1 ||
+                pattern_depth > 16 || pattern_strength < 0 || pattern_strength > 256) {
+                std::fprintf(stderr, "--dither-pattern wants N[,S], N 1..16 and S 0..256, got %s\n", argv[i]);
+                return 2;
+            }
+        }
         else if (!std::strcmp(argv[i], "--palette-fit") && i + 1 < argc) {
             char tail;
             if (std::sscanf(argv[++i], "%d%c", &palette_fit, &tail) != 1 || palette_fit < 1 || palette_fit > PAR_MAX_PALETTE) {
@@ -290,6 +303,16 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--palette-refine wants --palette-fit: it refines the fitted palette\n");
         return 2;
     }
+    if (pattern_depth != 0) {
+        if (palette_levels == 0 && palette_fit == 0) {
+            std::fprintf(stderr, "--dither-pattern wants --palette-levels or --palette-fit: it dithers towards a palette\n");
+            return 2;
+        }
+        if (dither_given || finish) {
+            std::fprintf(stderr, "--dither-pattern cannot go with --dither or --finish: a frame has one dither\n");
+            return 2;
+        }
+    }
     if (finish) {
         if (out_dir.empty()) { std::fprintf(stderr, "--finish wants --out\n"); return 2; }
         if (!outline && palette_levels == 0) { std::fprintf(stderr, "--finish wants --outline or --palette-levels: without both it is --scale\n"); return 2; }
@@ -341,6 +364,18 @@ int main(int argc, char** argv) {
         fitted.resize((size_t)palette_fit);
         index.resize((size_t)W * H);
     }
+    // the index plane of the frame as it stands over `pal`: the ordered dither of --dither, or --dither-pattern's
+    const auto quantise = [&](const std::vector<par_color>& pal) {
+        if (pattern_depth != 0) {
+            const int status = par_quantize_pattern_host(&params, 0, pal.data(), (int)pal.size(), pattern_depth, pattern_strength,
+                                                         fb.data(), 0, H, nullptr, index.data());
+            if (status != PAR_OK) std::fprintf(stderr, "par_quantize_pattern_host: %s\n", par_status_string(status));
+            return status;
+        }
+        const int status = par_quantize_host(&params, 0, pal.data(), (int)pal.size(), dither, fb.data(), 0, H, nullptr, index.data());
+        if (status != PAR_OK) std::fprintf(stderr, "par_quantize_host: %s\n", par_status_string(status));
+        return status;
+    };
     GifWriter gif;
     if (!gif_path.empty() && !gif.open(gif_path, W, H)) { std::fprintf(stderr, "cannot write %s\n", gif_path.c_str()); return 1; }
     const int mouse_x = 0, mouse_y = 0;  // the reference's mouse position before any motion event (alt:133-134)
@@ -433,16 +468,10 @@ int main(int argc, char** argv) {
                 std::fprintf(stderr, "par_palette_refine_host: %s\n", par_status_string(rc));
                 return 1;
             }
-            if ((rc = par_quantize_host(&params, 0, fitted.data(), palette_fit, dither, fb.data(), 0, H, nullptr, index.data())) != PAR_OK) {
-                std::fprintf(stderr, "par_quantize_host: %s\n", par_status_string(rc));
-                return 1;
-            }
+            if (quantise(fitted) != PAR_OK) return 1;
             gif.frame(index, fitted, 10);
         } else if (!ramp.empty()) {
-            if ((rc = par_quantize_host(&params, 0, ramp.data(), (int)ramp.size(), dither, fb.data(), 0, H, nullptr, index.data())) != PAR_OK) {
-                std::fprintf(stderr, "par_quantize_host: %s\n", par_status_string(rc));
-                return 1;
-            }
+            if (quantise(ramp) != PAR_OK) return 1;
             gif.frame(index, ramp, 10);
         } else if (!gif_path.empty()) {
             for (size_t i = 0; i < fb.size(); i++) { rgb[i * 3] = fb[i].red; rgb[i * 3 + 1] = fb[i].green; rgb[i * 3 + 2] = fb[i].blue; }
