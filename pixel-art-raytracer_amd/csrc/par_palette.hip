@@ -88,6 +88,28 @@ __device__ __forceinline__ bool load_group(const uint32_t* fb, uint32_t g, uint3
     return full;
 }
 
+// ---- zeroing a work block ----------------------------------------------------------------------------------------
+
+// Zeroes the n 8-byte words from dst on. A kernel and not hipMemsetAsync: the calls here are promised to be capturable as
+// any stream-ordered launch is, and a memset node does not keep that promise everywhere. In a graph that torch.cuda.graph
+// captured on the HIP 7.0 runtime that PyTorch-ROCm bundles, the memset of par_palette_reset_device zeroed the block in
+// the graph's first launch and filled it with other bytes in every later one (tests/test_gpu_post_graph.py). A kernel
+// node carries its arguments by value.
+__global__ __launch_bounds__(256) void zero_kernel(unsigned long long* dst, uint32_t n) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) dst[i] = 0ull;
+}
+
+// `bytes` bytes from the 8-byte aligned `dst` on, a multiple of 8
+hipError_t launch_zero(hipStream_t stream, void* dst, size_t bytes) {
+    const uint32_t n = (uint32_t)(bytes / 8);
+    hipLaunchKernelGGL(zero_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, static_cast<unsigned long long*>(dst), n);
+    return hipGetLastError();
+}
+static_assert(sizeof(par_palette_work) % 8 == 0 && sizeof(par_palette_refine_work::bins) % 8 == 0 &&
+                  offsetof(par_palette_refine_work, bins) % 8 == 0,
+              "launch_zero stores 8-byte words; the work blocks are 8-byte aligned");
+
 // ---- count -------------------------------------------------------------------------------------------------------
 
 template <bool VEC>
@@ -610,7 +632,7 @@ int run_refine(const par_params* params, hipStream_t stream, const par_color* fb
                par_color* d_palette, int n_colors, int iterations, uint8_t* d_index, par_palette_refine_work* work,
                int32_t* d_changed) {
     const int W = params->width;
-    if (hipMemsetAsync(work->bins, 0, sizeof(work->bins), stream) != hipSuccess) return PAR_ERR_HIP;
+    if (launch_zero(stream, work->bins, sizeof(work->bins)) != hipSuccess) return PAR_ERR_HIP;
     for (int it = 0; it < iterations; it++) {
         const int rc = par_quantize_device(params, stream, d_palette, n_colors, 0, fb, row_begin, row_end, nullptr, d_index);
         if (rc != PAR_OK) return rc;
@@ -648,7 +670,7 @@ extern "C" {
 
 int par_palette_reset_device(void* stream, par_palette_work* work) {
     if (!work_ok(work)) return PAR_ERR_INVALID_ARG;
-    return hipMemsetAsync(work, 0, sizeof(par_palette_work), (hipStream_t)stream) == hipSuccess ? PAR_OK : PAR_ERR_HIP;
+    return launch_zero((hipStream_t)stream, work, sizeof(par_palette_work)) == hipSuccess ? PAR_OK : PAR_ERR_HIP;
 }
 
 int par_palette_count_device(const par_params* params, void* stream, const par_color* fb, int row_begin, int row_end,
@@ -690,7 +712,7 @@ int par_palette_fit_host(const par_params* params, int device, const par_color* 
     par_device_buffer d_work(e, palette_out, sizeof(par_palette_work), false);
     par_device_buffer d_palette(e, palette_out, (size_t)n_colors * sizeof(par_color), false);
     par_palette_work* work = d_work.as<par_palette_work>();
-    if (e == hipSuccess) e = hipMemsetAsync(work, 0, sizeof(par_palette_work), nullptr);
+    if (e == hipSuccess) e = launch_zero(nullptr, work, sizeof(par_palette_work));
     if (e == hipSuccess) e = launch_count(nullptr, params->width, d_fb.as<par_color>(), row_begin, row_end, work);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(cut_kernel, dim3(1), dim3(PALETTE_THREADS), 0, nullptr, work, n_colors);

@@ -5,7 +5,7 @@ par_palette_sum_device: a round is one quantise and two passes shaped like sum p
 expectation it is held against is 1.25 * (quantize + 2 * sum). After a warm-up of every call, batches of back-to-back
 launches between two events on one stream; the median batch over its launch count, and the fastest. A batch is sized to
 last a few milliseconds at least. The frame stays resident (one buffer), as it is directly after the render that made
-it. `refine_N_1` is a call of one round (it includes the call's one memset of the tallies), `refine_N_4` a call of four
+it. `refine_N_1` is a call of one round (it includes the call's one zeroing of the tallies), `refine_N_4` a call of four
 rounds over four. The palette is the frame's fitted palette before the first launch and moves towards its fixed point
 under the timed launches; the work per round does not depend on it beyond which tallies the adds meet. Prints one JSON
 line and writes it to --out (default profiles/palette_refine.json).
