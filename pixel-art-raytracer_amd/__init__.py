@@ -32,26 +32,94 @@ RENDER_COUNT_RAYS = 1 << 1
 RENDER_PIPELINED = 1 << 2
 RENDER_TIMED_AS_LAUNCHED = 1 << 3
 
-# every symbol include/par_raytracer.h declares
-ABI_SYMBOLS = (
-    "par_status_string", "par_last_error", "par_default_params", "par_grid_dims", "par_device_count", "par_create",
-    "par_destroy", "par_set_sprites", "par_set_entities", "par_set_entities_ref_layout", "par_update_aabbs",
-    "par_update_aabbs_async",
-    "par_set_light", "par_render", "par_render_rows", "par_render_device", "par_render_device_timed",
-    "par_graph_capture", "par_graph_stage", "par_graph_launch", "par_pick", "par_get_stats", "par_read_grid",
-    "par_sprite_tile_floor", "par_scene_graybox", "par_scene_synthetic", "par_debug_line", "par_debug_units",
-    "par_render_device_slots", "par_row_block", "par_scene_tiles", "par_tiles_pack", "par_tiles_unpack",
-    "par_background_fill", "par_tiles_assemble", "par_scene_tile_map", "par_set_lights", "par_graph_capture_lights",
-    "par_graph_stage_lights", "par_set_light_model", "par_set_light_tints", "par_relight_device", "par_relight_rows",
-    "par_quantize_device", "par_quantize_host", "par_palette_ramp", "par_outline_device", "par_outline_host",
-    "par_present_device", "par_present_host", "par_finish_device", "par_finish_host", "par_tiles_changed_device",
-    "par_tiles_pack_counted", "par_tiles_fetch", "par_tiles_apply_host", "par_plane_tiles_changed_device",
-    "par_plane_tiles_pack", "par_plane_tiles_pack_counted", "par_plane_tiles_unpack", "par_plane_tiles_assemble",
-    "par_plane_tiles_fetch", "par_plane_tiles_apply_host", "par_upscale_device", "par_upscale_host",
-    "par_palette_reset_device", "par_palette_count_device", "par_palette_cut_device", "par_palette_sum_device",
-    "par_palette_emit_device", "par_palette_fit_host", "par_palette_refine_device", "par_palette_refine_host",
-    "par_quantize_pattern_device", "par_quantize_pattern_host",
-)
+_p, _i, _u = C.c_void_p, C.c_int, C.c_uint
+# The C ABI, in the header's order: symbol -> argument types, or (return type, argument types) where the function does
+# not return an int. Every pointer is a c_void_p. lib() sets these on the library's functions and
+# tests/test_abi_cpu.py holds them to the prototypes of include/par_raytracer.h.
+ABI = {
+    "par_status_string": (C.c_char_p, [_i]),
+    "par_last_error": (C.c_char_p, [_p]),
+    "par_default_params": (None, [_p]),
+    "par_grid_dims": [_p, _p, _p, _p],
+    "par_device_count": [],
+    "par_create": [_p, _i, _p],
+    "par_destroy": (None, [_p]),
+    "par_set_sprites": [_p, _p, _i],
+    "par_set_entities": [_p, _p, _p, _i],
+    "par_set_entities_ref_layout": [_p, _p, _p, _i],
+    "par_update_aabbs": [_p, _p, _i, _i],
+    "par_update_aabbs_async": [_p, _p, _i, _i, _p],
+    "par_set_light": [_p, _p],
+    "par_set_lights": [_p, _p, _i],
+    "par_set_light_model": [_p, _i],
+    "par_set_light_tints": [_p, _p, _i],
+    "par_render": [_p, _p, _u],
+    "par_render_rows": [_p, _i, _i, _p, _u],
+    "par_render_device": [_p, _p, _i, _i, _p, _u],
+    "par_render_device_slots": [_p, _p, _p, _i, _i, _i, _i, _i, _u],
+    "par_render_device_timed": [_p, _p, _i, _i, _p, _u, _p],
+    "par_relight_device": [_p, _p, _i, _i, _p, _p, _u],
+    "par_relight_rows": [_p, _i, _i, _p, _u],
+    "par_graph_capture": [_p, _p, _i, _i, _p, _u],
+    "par_graph_stage": [_p, _p, _i, _i, _p],
+    "par_graph_launch": [_p, _p],
+    "par_graph_capture_lights": [_p, _p, _i, _i, _p, _u],
+    "par_graph_stage_lights": [_p, _p, _i, _i, _p, _i],
+    "par_pick": [_p, _i, _i, _p],
+    "par_get_stats": [_p, _p],
+    "par_read_grid": [_p, _p, _p, _p],
+    "par_debug_units": [_i, _i, _p, _p, _i, _p],
+    "par_sprite_tile_floor": (None, [_p]),
+    "par_scene_graybox": [_i, _i, _p, _i],
+    "par_scene_synthetic": [_i, _i, _i, _i, C.c_uint64, _p, _p],
+    "par_row_block": (None, [_i, _i, _i, _i, _p, _p]),
+    "par_scene_tiles": [_p, _p, _i, _p, _i],
+    "par_tiles_pack": [_p, _p, _p, _i, _p, _i, _i, _p],
+    "par_tiles_unpack": [_p, _p, _p, _i, _p, _p],
+    "par_background_fill": [_p, _p, _p, _i],
+    "par_tiles_assemble": [_p, _p, _p, _p, _p, _i, _i],
+    "par_scene_tile_map": [_p, _p, _i, _p, _i],
+    "par_tiles_changed_device": [_p, _p, _p, _p, _i, _i, _p, _p, _i, _p],
+    "par_tiles_pack_counted": [_p, _p, _p, _p, _i, _p, _i, _i, _p],
+    "par_tiles_fetch": [_p, _p, _p, _p, _p, _i, _p, _p, _p, _p],
+    "par_tiles_apply_host": [_p, _p, _i, _p, _i, _i, _p],
+    "par_plane_tiles_changed_device": [_p, _p, _i, _p, _p, _i, _i, _p, _p, _i, _p],
+    "par_plane_tiles_pack": [_p, _p, _i, _p, _i, _p, _i, _i, _p],
+    "par_plane_tiles_pack_counted": [_p, _p, _i, _p, _p, _i, _p, _i, _i, _p],
+    "par_plane_tiles_unpack": [_p, _p, _i, _p, _i, _p, _p],
+    "par_plane_tiles_assemble": [_p, _p, _i, _p, _p, _p, _p, _i, _i],
+    "par_plane_tiles_fetch": [_p, _p, _i, _p, _p, _p, _i, _p, _p, _p, _p],
+    "par_plane_tiles_apply_host": [_p, _i, _p, _i, _p, _i, _i, _p],
+    "par_outline_device": [_p, _p, _p, _p, _i, _i, _p, _i, _i, _p, _p],
+    "par_outline_host": [_p, _i, _p, _p, _i, _i, _p, _i, _i, _p, _p],
+    "par_quantize_device": [_p, _p, _p, _i, _i, _p, _i, _i, _p, _p],
+    "par_quantize_host": [_p, _i, _p, _i, _i, _p, _i, _i, _p, _p],
+    "par_palette_ramp": [_p, _i, _p, _i],
+    "par_quantize_pattern_device": [_p, _p, _p, _i, _i, _i, _p, _i, _i, _p, _p],
+    "par_quantize_pattern_host": [_p, _i, _p, _i, _i, _i, _p, _i, _i, _p, _p],
+    "par_palette_reset_device": [_p, _p],
+    "par_palette_count_device": [_p, _p, _p, _i, _i, _p],
+    "par_palette_cut_device": [_p, _p, _i],
+    "par_palette_sum_device": [_p, _p, _p, _i, _i, _p],
+    "par_palette_emit_device": [_p, _p, _i, _p],
+    "par_palette_fit_host": [_p, _i, _p, _i, _i, _i, _p, _p],
+    "par_palette_refine_device": [_p, _p, _p, _i, _i, _p, _i, _i, _p, _p, _p],
+    "par_palette_refine_host": [_p, _i, _p, _i, _i, _p, _i, _i, _p],
+    "par_present_device": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
+    "par_present_host": [_p, _i, _p, _p, _p, _p, _i, _i, _i, _p],
+    "par_finish_device": [_p, _p, _p, _p, _i, _i, _p, _i, _i, _p, _p, _i, _i, _p, _p],
+    "par_finish_host": [_p, _i, _p, _p, _i, _i, _p, _i, _i, _p, _p, _i, _i, _p, _p],
+    "par_upscale_device": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p],
+    "par_upscale_host": [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p],
+    "par_debug_line": (None, [_p, _p, _i, _p, _p]),
+}
+# exported for the tests and tools, not declared in the public header (csrc/par_context.hip)
+ABI_DEBUG_HOOKS = {
+    "par_debug_read_stamps": [_p, _p, C.c_size_t],
+    "par_debug_set_hooks": [_p, _u, _i],
+    "par_debug_read_light_walks": [_p, _p],
+}
+ABI_SYMBOLS = tuple(ABI)  # every symbol include/par_raytracer.h declares
 MAX_LIGHTS = 8  # PAR_MAX_LIGHTS
 LIGHTS_UNBOUNDED, LIGHTS_RANGED = 0, 1  # par_set_light_model
 
@@ -93,94 +161,37 @@ def lib():
                               "(or __graft_entry__.build()). There is no CPU fallback.")
         _share_hip_runtime_with_torch()
         L = C.CDLL(LIB_PATH)
-        vp, i32 = C.c_void_p, C.c_int
-        L.par_status_string.restype = C.c_char_p
-        L.par_status_string.argtypes = [i32]
-        L.par_last_error.restype = C.c_char_p
-        L.par_last_error.argtypes = [vp]
-        L.par_default_params.restype = None
-        L.par_default_params.argtypes = [vp]
-        L.par_grid_dims.argtypes = [vp, vp, vp, vp]
-        L.par_device_count.argtypes = []
-        L.par_create.argtypes = [vp, i32, vp]
-        L.par_destroy.restype = None
-        L.par_destroy.argtypes = [vp]
-        L.par_set_sprites.argtypes = [vp, vp, i32]
-        L.par_set_entities.argtypes = [vp, vp, vp, i32]
-        L.par_set_entities_ref_layout.argtypes = [vp, vp, vp, i32]
-        L.par_update_aabbs.argtypes = [vp, vp, i32, i32]
-        L.par_update_aabbs_async.argtypes = [vp, vp, i32, i32, vp]
-        L.par_set_light.argtypes = [vp, vp]
-        L.par_set_lights.argtypes = [vp, vp, i32]
-        L.par_set_light_model.argtypes = [vp, i32]
-        L.par_set_light_tints.argtypes = [vp, vp, i32]
-        L.par_render.argtypes = [vp, vp, C.c_uint]
-        L.par_render_rows.argtypes = [vp, i32, i32, vp, C.c_uint]
-        L.par_render_device.argtypes = [vp, vp, i32, i32, vp, C.c_uint]
-        L.par_render_device_timed.argtypes = [vp, vp, i32, i32, vp, C.c_uint, vp]
-        L.par_relight_device.argtypes = [vp, vp, i32, i32, vp, vp, C.c_uint]
-        L.par_relight_rows.argtypes = [vp, i32, i32, vp, C.c_uint]
-        L.par_graph_capture.argtypes = [vp, vp, i32, i32, vp, C.c_uint]
-        L.par_graph_stage.argtypes = [vp, vp, i32, i32, vp]
-        L.par_graph_launch.argtypes = [vp, vp]
-        L.par_graph_capture_lights.argtypes = [vp, vp, i32, i32, vp, C.c_uint]
-        L.par_graph_stage_lights.argtypes = [vp, vp, i32, i32, vp, i32]
-        L.par_pick.argtypes = [vp, i32, i32, vp]
-        L.par_get_stats.argtypes = [vp, vp]
-        L.par_read_grid.argtypes = [vp, vp, vp, vp]
-        L.par_sprite_tile_floor.restype = None
-        L.par_sprite_tile_floor.argtypes = [vp]
-        L.par_scene_graybox.argtypes = [i32, i32, vp, i32]
-        L.par_scene_synthetic.argtypes = [i32, i32, i32, i32, C.c_uint64, vp, vp]
-        L.par_debug_units.argtypes = [i32, i32, vp, vp, i32, vp]
-        L.par_render_device_slots.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, C.c_uint]
-        L.par_row_block.restype = None
-        L.par_row_block.argtypes = [i32, i32, i32, i32, vp, vp]
-        L.par_scene_tiles.argtypes = [vp, vp, i32, vp, i32]
-        L.par_tiles_pack.argtypes = [vp, vp, vp, i32, vp, i32, i32, vp]
-        L.par_tiles_unpack.argtypes = [vp, vp, vp, i32, vp, vp]
-        L.par_background_fill.argtypes = [vp, vp, vp, i32]
-        L.par_tiles_assemble.argtypes = [vp, vp, vp, vp, vp, i32, i32]
-        L.par_scene_tile_map.argtypes = [vp, vp, i32, vp, i32]
-        L.par_tiles_changed_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, i32, vp]
-        L.par_tiles_pack_counted.argtypes = [vp, vp, vp, vp, i32, vp, i32, i32, vp]
-        L.par_tiles_fetch.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
-        L.par_tiles_apply_host.argtypes = [vp, vp, i32, vp, i32, i32, vp]
-        L.par_plane_tiles_changed_device.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp, i32, vp]
-        L.par_plane_tiles_pack.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, vp]
-        L.par_plane_tiles_pack_counted.argtypes = [vp, vp, i32, vp, vp, i32, vp, i32, i32, vp]
-        L.par_plane_tiles_unpack.argtypes = [vp, vp, i32, vp, i32, vp, vp]
-        L.par_plane_tiles_assemble.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, i32]
-        L.par_plane_tiles_fetch.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]
-        L.par_plane_tiles_apply_host.argtypes = [vp, i32, vp, i32, vp, i32, i32, vp]
-        L.par_quantize_device.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, vp, vp]
-        L.par_quantize_host.argtypes = [vp, i32, vp, i32, i32, vp, i32, i32, vp, vp]
-        L.par_quantize_pattern_device.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, vp, vp]
-        L.par_quantize_pattern_host.argtypes = [vp, i32, vp, i32, i32, i32, vp, i32, i32, vp, vp]
-        L.par_palette_ramp.argtypes = [vp, i32, vp, i32]
-        L.par_palette_reset_device.argtypes = [vp, vp]
-        L.par_palette_count_device.argtypes = [vp, vp, vp, i32, i32, vp]
-        L.par_palette_cut_device.argtypes = [vp, vp, i32]
-        L.par_palette_sum_device.argtypes = [vp, vp, vp, i32, i32, vp]
-        L.par_palette_emit_device.argtypes = [vp, vp, i32, vp]
-        L.par_palette_fit_host.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp]
-        L.par_palette_refine_device.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp]
-        L.par_palette_refine_host.argtypes = [vp, i32, vp, i32, i32, vp, i32, i32, vp]
-        L.par_outline_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, i32, vp, vp]
-        L.par_outline_host.argtypes = [vp, i32, vp, vp, i32, i32, vp, i32, i32, vp, vp]
-        L.par_present_device.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
-        L.par_present_host.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, vp]
-        L.par_finish_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, i32, vp, vp]
-        L.par_finish_host.argtypes = [vp, i32, vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, i32, vp, vp]
-        L.par_upscale_device.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
-        L.par_upscale_host.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
-        L.par_debug_read_stamps.argtypes = [vp, vp, C.c_size_t]
-        L.par_debug_set_hooks.argtypes = [vp, C.c_uint, i32]
-        L.par_debug_read_light_walks.argtypes = [vp, vp]
-        L.par_debug_line.restype = None
-        L.par_debug_line.argtypes = [vp, vp, i32, vp, vp]
+        for name, sig in (*ABI.items(), *ABI_DEBUG_HOOKS.items()):
+            fn = getattr(L, name)
+            if type(sig) is tuple:
+                fn.restype, sig = sig
+            fn.argtypes = sig
         _lib = L
     return _lib
+
+
+# The call path of the free functions: _ok(lib().par_x, ...), the symbol looked up on lib() at the call and named once.
+# (A context's calls go through Renderer._check, whose detail is par_last_error.)
+
+def _ok(fn, *args):
+    """Call a library function that returns a status; any but PAR_OK raises ParError with the symbol's name."""
+    rc = fn(*args)
+    if rc:
+        raise ParError(rc, fn.__name__)
+
+
+def _count(fn, *args):
+    """Call a library function that returns a count, or minus the status."""
+    n = fn(*args)
+    if n < 0:
+        raise ParError(-n, fn.__name__)
+    return n
+
+
+# A device pointer or a stream handle, an int or None, for a void* parameter. The wrappers convert it themselves: the
+# conversion ctypes applies to a c_void_p argument takes a str or bytes too (and passes its buffer), this constructor
+# raises TypeError for anything but an int or None.
+_dp = C.c_void_p
 
 
 def debug_units(kind, in_a, in_b=None, device=0):
@@ -193,9 +204,7 @@ def debug_units(kind, in_a, in_b=None, device=0):
     n = len(a)
     out = np.zeros(n, dtype=np.uint8) if kind in (0, 3, 4) else (np.zeros((n, 4), dtype=np.uint8) if kind == 1
                                                          else np.zeros((n, 3), dtype=np.float32))
-    rc = lib().par_debug_units(device, kind, ptr(a), ptr(b), n, ptr(out))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_debug_units")
+    _ok(lib().par_debug_units, device, kind, ptr(a), ptr(b), n, ptr(out))
     return out
 
 
@@ -231,9 +240,7 @@ def scene_synthetic(n, width, height, length, seed):
     """SURVEY §8d synthetic scene: (aabbs, light)."""
     a = np.zeros(n, dtype=AABB)
     l = np.zeros(1, dtype=LIGHT)
-    rc = lib().par_scene_synthetic(n, width, height, length, C.c_uint64(seed), ptr(a), ptr(l))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_scene_synthetic")
+    _ok(lib().par_scene_synthetic, n, width, height, length, C.c_uint64(seed), ptr(a), ptr(l))
     return a, l
 
 
@@ -340,14 +347,18 @@ class Renderer:
         self.set_light(light)
 
     # render ------------------------------------------------------------------------------------------------
-    def render(self, planes=("fb",), rows=None, flags=0):
-        """One frame (or rows [r0, r1)) into fresh host arrays; returns {plane: flat row-major array}."""
+    def _host_frame(self, symbol, planes, rows, flags):
+        """render and relight: rows [r0, r1) from `symbol` into fresh host arrays."""
         r0, r1 = rows or (0, self.height)
         n = (r1 - r0) * self.width
         out = {k: np.zeros(n, dtype=_PLANE_DTYPE[k]) for k in planes}
         o = Outputs(*[out[k].ctypes.data if k in out else None for k in _PLANES])
-        self._check(lib().par_render_rows(self._ctx, r0, r1, C.byref(o), flags))
+        self._check(getattr(lib(), symbol)(self._ctx, r0, r1, C.byref(o), flags))
         return out
+
+    def render(self, planes=("fb",), rows=None, flags=0):
+        """One frame (or rows [r0, r1)) into fresh host arrays; returns {plane: flat row-major array}."""
+        return self._host_frame("par_render_rows", planes, rows, flags)
 
     def render_device(self, device_ptrs, rows=None, flags=0, stream=0, timed=False):
         """Asynchronous render into device memory. `device_ptrs` maps plane name -> raw device pointer (int) that
@@ -373,12 +384,7 @@ class Renderer:
         """The last render() again under the lights, light model and tints of now (par_relight_rows): no hash build, no
         primary pass. That render must have had a "gbuf" plane (the renderer keeps its device copy) and cover `rows`;
         planes out of "fb", "brightness", "lit". Returns {plane: flat row-major array}."""
-        r0, r1 = rows or (0, self.height)
-        n = (r1 - r0) * self.width
-        out = {k: np.zeros(n, dtype=_PLANE_DTYPE[k]) for k in planes}
-        o = Outputs(*[out[k].ctypes.data if k in out else None for k in _PLANES])
-        self._check(lib().par_relight_rows(self._ctx, r0, r1, C.byref(o), flags))
-        return out
+        return self._host_frame("par_relight_rows", planes, rows, flags)
 
     def relight_device(self, gbuf_ptr, device_ptrs, rows=None, flags=0, stream=0):
         """Asynchronous relit frame (par_relight_device): `gbuf_ptr` is the device pointer of the retained frame's gbuf
@@ -386,19 +392,20 @@ class Renderer:
         takes them (no "gbuf" or "palidx": they do not depend on lights). Enqueue it on the retained frame's stream."""
         r0, r1 = rows or (0, self.height)
         o = Outputs(*[device_ptrs.get(k) for k in _PLANES])
-        self._check(lib().par_relight_device(self._ctx, C.c_void_p(stream), r0, r1, C.c_void_p(gbuf_ptr), C.byref(o), flags))
+        self._check(lib().par_relight_device(self._ctx, _dp(stream), r0, r1, _dp(gbuf_ptr), C.byref(o), flags))
 
-    def graph_capture(self, device_ptrs, rows=None, flags=0, stream=0):
+    def _capture(self, symbol, device_ptrs, rows, flags, stream):
         r0, r1 = rows or (0, self.height)
         o = Outputs(*[device_ptrs.get(k) for k in _PLANES])
-        self._check(lib().par_graph_capture(self._ctx, C.c_void_p(stream), r0, r1, C.byref(o), flags))
+        self._check(getattr(lib(), symbol)(self._ctx, _dp(stream), r0, r1, C.byref(o), flags))
+
+    def graph_capture(self, device_ptrs, rows=None, flags=0, stream=0):
+        self._capture("par_graph_capture", device_ptrs, rows, flags, stream)
 
     def graph_capture_lights(self, device_ptrs, rows=None, flags=0, stream=0):
         """A graph of the light path (par_graph_capture_lights): its launches render whatever lights the context holds
         then, 1 .. MAX_LIGHTS of them."""
-        r0, r1 = rows or (0, self.height)
-        o = Outputs(*[device_ptrs.get(k) for k in _PLANES])
-        self._check(lib().par_graph_capture_lights(self._ctx, C.c_void_p(stream), r0, r1, C.byref(o), flags))
+        self._capture("par_graph_capture_lights", device_ptrs, rows, flags, stream)
 
     def graph_stage(self, aabbs=None, first=0, light=None, lights=None):
         """The next graph frame's AABBs [first, first + len(aabbs)), and either lights[0] (`light`, par_graph_stage) or
@@ -468,9 +475,7 @@ def scene_tiles(params, aabbs):
     a = np.ascontiguousarray(aabbs, dtype=AABB)
     gx, gy, _ = params.grid_dims()
     tiles = np.zeros(gx * gy, dtype=np.int32)
-    n = lib().par_scene_tiles(C.byref(params), ptr(a), len(a), ptr(tiles), len(tiles))
-    if n < 0:
-        raise ParError(-n, "par_scene_tiles")
+    n = _count(lib().par_scene_tiles, C.byref(params), ptr(a), len(a), ptr(tiles), len(tiles))
     return tiles[:n].copy()
 
 
@@ -479,40 +484,28 @@ def scene_tile_map(params, tiles):
     t = np.ascontiguousarray(tiles, dtype=np.int32)
     gx, gy, _ = params.grid_dims()
     m = np.empty(gx * gy, dtype=np.int32)
-    rc = lib().par_scene_tile_map(C.byref(params), ptr(t), len(t), ptr(m), len(m))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_scene_tile_map")
+    _ok(lib().par_scene_tile_map, C.byref(params), ptr(t), len(t), ptr(m), len(m))
     return m
 
 
 def tiles_assemble(params, d_map, packed, frame, rows, stream=0):
     """Device pointers (ints): rows [rows[0], rows[1]) of the frame at `frame` (row 0) from the packed tiles the map
     names and the background elsewhere, in one pass (asynchronous)."""
-    rc = lib().par_tiles_assemble(C.byref(params), C.c_void_p(stream), C.c_void_p(d_map), C.c_void_p(packed),
-                                  C.c_void_p(frame), rows[0], rows[1])
-    if rc != PAR_OK:
-        raise ParError(rc, "par_tiles_assemble")
+    _ok(lib().par_tiles_assemble, C.byref(params), _dp(stream), _dp(d_map), _dp(packed), _dp(frame), rows[0], rows[1])
 
 
 def tiles_pack(params, d_tiles, n, fb_block, rows, packed, stream=0):
     """Device pointers (ints): tiles d_tiles[0, n) of the frame block `rows` at fb_block -> packed slots (asynchronous)."""
-    rc = lib().par_tiles_pack(C.byref(params), C.c_void_p(stream), C.c_void_p(d_tiles), n, C.c_void_p(fb_block), rows[0],
-                              rows[1], C.c_void_p(packed))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_tiles_pack")
+    _ok(lib().par_tiles_pack, C.byref(params), _dp(stream), _dp(d_tiles), n, _dp(fb_block), rows[0], rows[1],
+        _dp(packed))
 
 
 def tiles_unpack(params, d_tiles, n, packed, frame, stream=0):
-    rc = lib().par_tiles_unpack(C.byref(params), C.c_void_p(stream), C.c_void_p(d_tiles), n, C.c_void_p(packed),
-                                C.c_void_p(frame))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_tiles_unpack")
+    _ok(lib().par_tiles_unpack, C.byref(params), _dp(stream), _dp(d_tiles), n, _dp(packed), _dp(frame))
 
 
 def background_fill(params, rows_ptr, n_rows, stream=0):
-    rc = lib().par_background_fill(C.byref(params), C.c_void_p(stream), C.c_void_p(rows_ptr), n_rows)
-    if rc != PAR_OK:
-        raise ParError(rc, "par_background_fill")
+    _ok(lib().par_background_fill, C.byref(params), _dp(stream), _dp(rows_ptr), n_rows)
 
 
 # ---- changed tiles -----------------------------------------------------------------------------------------------
@@ -521,18 +514,14 @@ def tiles_changed(params, a, b, rows, d_map, d_tiles, capacity, d_count, stream=
     """Device pointers (ints): the tiles of the frame block `rows` that differ between the planes at `a` and `b`
     (par_tiles_changed_device, asynchronous): ranks or -1 into d_map (grid-x * grid-y entries), the first `capacity`
     tile words into d_tiles, the total into d_count[0]."""
-    rc = lib().par_tiles_changed_device(C.byref(params), C.c_void_p(stream), C.c_void_p(a), C.c_void_p(b), rows[0],
-                                        rows[1], C.c_void_p(d_map), C.c_void_p(d_tiles), capacity, C.c_void_p(d_count))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_tiles_changed_device")
+    _ok(lib().par_tiles_changed_device, C.byref(params), _dp(stream), _dp(a), _dp(b), rows[0], rows[1], _dp(d_map),
+        _dp(d_tiles), capacity, _dp(d_count))
 
 
 def tiles_pack_counted(params, d_tiles, d_count, capacity, fb_block, rows, packed, stream=0):
     """Device pointers (ints): tiles_pack with n = min(max(d_count[0], 0), capacity) read on the device (asynchronous)."""
-    rc = lib().par_tiles_pack_counted(C.byref(params), C.c_void_p(stream), C.c_void_p(d_tiles), C.c_void_p(d_count),
-                                      capacity, C.c_void_p(fb_block), rows[0], rows[1], C.c_void_p(packed))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_tiles_pack_counted")
+    _ok(lib().par_tiles_pack_counted, C.byref(params), _dp(stream), _dp(d_tiles), _dp(d_count), capacity, _dp(fb_block),
+        rows[0], rows[1], _dp(packed))
 
 
 def tiles_fetch(params, d_count, d_tiles, d_packed, capacity, tiles, packed, stream=0):
@@ -540,21 +529,16 @@ def tiles_fetch(params, d_count, d_tiles, d_packed, capacity, tiles, packed, str
     the device pointers (ints) into the host arrays `tiles` (int32) and `packed` (COLOR), pageable or pinned
     (par_tiles_fetch). Returns (n, count): n == count when the list is complete, else n == 0 and nothing was copied."""
     n, count = C.c_int(0), C.c_int(0)
-    rc = lib().par_tiles_fetch(C.byref(params), C.c_void_p(stream), C.c_void_p(d_count), C.c_void_p(d_tiles),
-                               C.c_void_p(d_packed), capacity, _host_ptr(tiles), _host_ptr(packed), C.byref(n),
-                               C.byref(count))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_tiles_fetch")
+    _ok(lib().par_tiles_fetch, C.byref(params), _dp(stream), _dp(d_count), _dp(d_tiles), _dp(d_packed), capacity,
+        _host_ptr(tiles), _host_ptr(packed), C.byref(n), C.byref(count))
     return n.value, count.value
 
 
 def tiles_apply_host(params, tiles, n, packed, rows, frame):
     """Host arrays (or host addresses as ints): slots packed[0, n) of the tiles tiles[0, n) to their place in the whole
     host frame `frame`, on the rows `rows` only (par_tiles_apply_host: host arithmetic, no GPU needed)."""
-    rc = lib().par_tiles_apply_host(C.byref(params), _host_ptr(tiles), n, _host_ptr(packed), rows[0], rows[1],
-                                    _host_ptr(frame))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_tiles_apply_host")
+    _ok(lib().par_tiles_apply_host, C.byref(params), _host_ptr(tiles), n, _host_ptr(packed), rows[0], rows[1],
+        _host_ptr(frame))
 
 
 def _host_ptr(a):
@@ -567,38 +551,28 @@ def _host_ptr(a):
 def plane_tiles_changed(params, elem_bytes, a, b, rows, d_map, d_tiles, capacity, d_count, stream=0):
     """Device pointers (ints): tiles_changed on planes of `elem_bytes`-byte elements (par_plane_tiles_changed_device,
     asynchronous)."""
-    rc = lib().par_plane_tiles_changed_device(C.byref(params), C.c_void_p(stream), elem_bytes, C.c_void_p(a), C.c_void_p(b),
-                                              rows[0], rows[1], C.c_void_p(d_map), C.c_void_p(d_tiles), capacity,
-                                              C.c_void_p(d_count))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_plane_tiles_changed_device")
+    _ok(lib().par_plane_tiles_changed_device, C.byref(params), _dp(stream), elem_bytes, _dp(a), _dp(b), rows[0],
+        rows[1], _dp(d_map), _dp(d_tiles), capacity, _dp(d_count))
 
 
 def plane_tiles_pack(params, elem_bytes, d_tiles, n, block, rows, packed, stream=0):
     """Device pointers (ints): tiles d_tiles[0, n) of the plane block `rows` at `block` -> packed slots of
     bin_size * bin_size * elem_bytes bytes (par_plane_tiles_pack, asynchronous)."""
-    rc = lib().par_plane_tiles_pack(C.byref(params), C.c_void_p(stream), elem_bytes, C.c_void_p(d_tiles), n,
-                                    C.c_void_p(block), rows[0], rows[1], C.c_void_p(packed))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_plane_tiles_pack")
+    _ok(lib().par_plane_tiles_pack, C.byref(params), _dp(stream), elem_bytes, _dp(d_tiles), n, _dp(block), rows[0],
+        rows[1], _dp(packed))
 
 
 def plane_tiles_pack_counted(params, elem_bytes, d_tiles, d_count, capacity, block, rows, packed, stream=0):
     """Device pointers (ints): plane_tiles_pack with n = min(max(d_count[0], 0), capacity) read on the device
     (par_plane_tiles_pack_counted, asynchronous)."""
-    rc = lib().par_plane_tiles_pack_counted(C.byref(params), C.c_void_p(stream), elem_bytes, C.c_void_p(d_tiles),
-                                            C.c_void_p(d_count), capacity, C.c_void_p(block), rows[0], rows[1],
-                                            C.c_void_p(packed))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_plane_tiles_pack_counted")
+    _ok(lib().par_plane_tiles_pack_counted, C.byref(params), _dp(stream), elem_bytes, _dp(d_tiles), _dp(d_count),
+        capacity, _dp(block), rows[0], rows[1], _dp(packed))
 
 
 def plane_tiles_unpack(params, elem_bytes, d_tiles, n, packed, frame, stream=0):
     """Device pointers (ints): slots -> their place in the whole plane at `frame` (par_plane_tiles_unpack, asynchronous)."""
-    rc = lib().par_plane_tiles_unpack(C.byref(params), C.c_void_p(stream), elem_bytes, C.c_void_p(d_tiles), n,
-                                      C.c_void_p(packed), C.c_void_p(frame))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_plane_tiles_unpack")
+    _ok(lib().par_plane_tiles_unpack, C.byref(params), _dp(stream), elem_bytes, _dp(d_tiles), n, _dp(packed),
+        _dp(frame))
 
 
 def plane_tiles_assemble(params, elem_bytes, d_map, packed, fill, frame, rows, stream=0):
@@ -607,31 +581,70 @@ def plane_tiles_assemble(params, elem_bytes, d_map, packed, fill, frame, rows, s
     fill = bytes(fill)
     if len(fill) != elem_bytes:
         raise ParError(1, f"par_plane_tiles_assemble: a fill of {len(fill)} bytes for elements of {elem_bytes}")
-    rc = lib().par_plane_tiles_assemble(C.byref(params), C.c_void_p(stream), elem_bytes, C.c_void_p(d_map),
-                                        C.c_void_p(packed), C.c_char_p(fill), C.c_void_p(frame), rows[0], rows[1])
-    if rc != PAR_OK:
-        raise ParError(rc, "par_plane_tiles_assemble")
+    _ok(lib().par_plane_tiles_assemble, C.byref(params), _dp(stream), elem_bytes, _dp(d_map), _dp(packed),
+        C.c_char_p(fill), _dp(frame), rows[0], rows[1])
 
 
 def plane_tiles_fetch(params, elem_bytes, d_count, d_tiles, d_packed, capacity, tiles, packed, stream=0):
     """tiles_fetch with slots of bin_size * bin_size * elem_bytes bytes (par_plane_tiles_fetch): waits for `stream`.
     Returns (n, count): n == count when the list is complete, else n == 0 and nothing was copied."""
     n, count = C.c_int(0), C.c_int(0)
-    rc = lib().par_plane_tiles_fetch(C.byref(params), C.c_void_p(stream), elem_bytes, C.c_void_p(d_count),
-                                     C.c_void_p(d_tiles), C.c_void_p(d_packed), capacity, _host_ptr(tiles),
-                                     _host_ptr(packed), C.byref(n), C.byref(count))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_plane_tiles_fetch")
+    _ok(lib().par_plane_tiles_fetch, C.byref(params), _dp(stream), elem_bytes, _dp(d_count), _dp(d_tiles),
+        _dp(d_packed), capacity, _host_ptr(tiles), _host_ptr(packed), C.byref(n), C.byref(count))
     return n.value, count.value
 
 
 def plane_tiles_apply_host(params, elem_bytes, tiles, n, packed, rows, frame):
     """Host arrays (or host addresses as ints): tiles_apply_host on a plane of `elem_bytes`-byte elements
     (par_plane_tiles_apply_host: host arithmetic, no GPU needed)."""
-    rc = lib().par_plane_tiles_apply_host(C.byref(params), elem_bytes, _host_ptr(tiles), n, _host_ptr(packed), rows[0],
-                                          rows[1], _host_ptr(frame))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_plane_tiles_apply_host")
+    _ok(lib().par_plane_tiles_apply_host, C.byref(params), elem_bytes, _host_ptr(tiles), n, _host_ptr(packed), rows[0],
+        rows[1], _host_ptr(frame))
+
+
+# ---- what the *_host forms of the post passes share: preparing their arrays ---------------------------------------
+
+def _rows(params, rows):
+    return rows or (0, params.height)
+
+
+def _flat(a, dtype):
+    return np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+
+
+def _plane(who, name, a, dtype, params, rows):
+    """`a` as a flat contiguous `dtype` plane that holds the rows [rows[0], rows[1]) of the frame."""
+    a = _flat(a, dtype)
+    n = (rows[1] - rows[0]) * params.width
+    if len(a) != n:
+        raise ValueError(f"{who}: {name} holds {len(a)} elements, rows {rows[0]}..{rows[1]} of width {params.width} "
+                         f"hold {n}")
+    return a
+
+
+def _out_planes(who, planes, first, n):
+    """The output dict of a pass that writes a uint8 plane called `first` and / or a COLOR plane "fb", n elements each."""
+    unknown = set(planes) - {first, "fb"}
+    if unknown:
+        raise ValueError(f"{who}: unknown planes {sorted(unknown)}")
+    out = {}
+    if first in planes:
+        out[first] = np.zeros(n, dtype=np.uint8)
+    if "fb" in planes:
+        out["fb"] = np.zeros(n, dtype=COLOR)
+    return out
+
+
+def _palette(palette):
+    """(flat COLOR array, its length), or (None, 0)."""
+    if palette is None:
+        return None, 0
+    palette = _flat(palette, COLOR)
+    return palette, len(palette)
+
+
+def _surface(n_rows, scale, pitch):
+    """A zeroed surface of n_rows * scale rows, `pitch` bytes each (the library leaves a row's gap bytes alone)."""
+    return np.zeros((max(0, n_rows) * max(0, int(scale)), max(0, int(pitch))), dtype=np.uint8)
 
 
 # ---- outlines ----------------------------------------------------------------------------------------------------
@@ -644,41 +657,23 @@ def outline(params, style, gbuf, gbuf_rows, fb, rows, fb_out=None, edge_out=None
     to fb_out (fb_out == fb: in place; fb may be None without fb_out). Asynchronous on `stream`: in a frame loop after
     the render or relight call and before quantize."""
     style = np.ascontiguousarray(style, dtype=OUTLINE_STYLE).reshape(-1)
-    rc = lib().par_outline_device(C.byref(params), C.c_void_p(stream), ptr(style), C.c_void_p(gbuf), gbuf_rows[0],
-                                  gbuf_rows[1], C.c_void_p(fb), rows[0], rows[1], C.c_void_p(fb_out),
-                                  C.c_void_p(edge_out))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_outline_device")
+    _ok(lib().par_outline_device, C.byref(params), _dp(stream), ptr(style), _dp(gbuf), gbuf_rows[0], gbuf_rows[1],
+        _dp(fb), rows[0], rows[1], _dp(fb_out), _dp(edge_out))
 
 
 def outline_host(params, style, gbuf, fb=None, rows=None, gbuf_rows=None, planes=("edge",), device=-1):
     """The same on host arrays (par_outline_host): `gbuf` is a PIXEL array holding rows `gbuf_rows` (default: `rows`),
     `fb` a COLOR array holding rows `rows` (default: the whole frame; needed for the "fb" plane only). Returns
     {"edge": uint8 array, "fb": COLOR array} for the planes asked for."""
-    r0, r1 = rows or (0, params.height)
+    r0, r1 = _rows(params, rows)
     g0, g1 = gbuf_rows or (r0, r1)
-    style = np.ascontiguousarray(style, dtype=OUTLINE_STYLE).reshape(-1)
-    gbuf = np.ascontiguousarray(gbuf, dtype=PIXEL).reshape(-1)
-    n = (r1 - r0) * params.width
-    if len(gbuf) != (g1 - g0) * params.width:
-        raise ValueError(f"outline_host: gbuf holds {len(gbuf)} texels, rows {g0}..{g1} of width {params.width} hold "
-                         f"{(g1 - g0) * params.width}")
-    unknown = set(planes) - {"edge", "fb"}
-    if unknown:
-        raise ValueError(f"outline_host: unknown planes {sorted(unknown)}")
+    style = _flat(style, OUTLINE_STYLE)
+    gbuf = _plane("outline_host", "gbuf", gbuf, PIXEL, params, (g0, g1))
     if fb is not None:
-        fb = np.ascontiguousarray(fb, dtype=COLOR).reshape(-1)
-        if len(fb) != n:
-            raise ValueError(f"outline_host: fb holds {len(fb)} pixels, rows {r0}..{r1} of width {params.width} hold {n}")
-    out = {}
-    if "edge" in planes:
-        out["edge"] = np.zeros(n, dtype=np.uint8)
-    if "fb" in planes:
-        out["fb"] = np.zeros(n, dtype=COLOR)
-    rc = lib().par_outline_host(C.byref(params), device, ptr(style), ptr(gbuf), g0, g1, ptr(fb), r0, r1,
-                                ptr(out.get("fb")), ptr(out.get("edge")))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_outline_host")
+        fb = _plane("outline_host", "fb", fb, COLOR, params, (r0, r1))
+    out = _out_planes("outline_host", planes, "edge", (r1 - r0) * params.width)
+    _ok(lib().par_outline_host, C.byref(params), device, ptr(style), ptr(gbuf), g0, g1, ptr(fb), r0, r1,
+        ptr(out.get("fb")), ptr(out.get("edge")))
     return out
 
 
@@ -689,34 +684,25 @@ def quantize(params, d_palette, n_colors, fb, rows, fb_out=None, index_out=None,
     d_palette (par_quantize_device: L1-nearest entry, lowest index among equals, 4x4 ordered dither of strength
     `spread`) into the index plane at index_out and / or the RGBA plane at fb_out (fb_out == fb: in place).
     Asynchronous on `stream`."""
-    rc = lib().par_quantize_device(C.byref(params), C.c_void_p(stream), C.c_void_p(d_palette), n_colors, spread,
-                                   C.c_void_p(fb), rows[0], rows[1], C.c_void_p(fb_out), C.c_void_p(index_out))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_quantize_device")
+    _ok(lib().par_quantize_device, C.byref(params), _dp(stream), _dp(d_palette), n_colors, spread, _dp(fb), rows[0],
+        rows[1], _dp(fb_out), _dp(index_out))
+
+
+def _quantize_host(who, params, palette, dither, fb, rows, planes, device):
+    """quantize_host and quantize_pattern_host: par_<who>, whose prototypes differ in the `dither` arguments alone."""
+    r0, r1 = _rows(params, rows)
+    palette = _flat(palette, COLOR)
+    fb = _plane(who, "fb", fb, COLOR, params, (r0, r1))
+    out = _out_planes(who, planes, "index", len(fb))
+    _ok(getattr(lib(), "par_" + who), C.byref(params), device, ptr(palette), len(palette), *dither, ptr(fb), r0, r1,
+        ptr(out.get("fb")), ptr(out.get("index")))
+    return out
 
 
 def quantize_host(params, palette, fb, rows=None, spread=0, planes=("index",), device=-1):
     """The same on host arrays (par_quantize_host): `palette` and `fb` are COLOR arrays, fb the rows `rows` (default:
     the whole frame). Returns {"index": uint8 array, "fb": COLOR array} for the planes asked for."""
-    r0, r1 = rows or (0, params.height)
-    palette = np.ascontiguousarray(palette, dtype=COLOR).reshape(-1)
-    fb = np.ascontiguousarray(fb, dtype=COLOR).reshape(-1)
-    n = (r1 - r0) * params.width
-    if len(fb) != n:
-        raise ValueError(f"quantize_host: fb holds {len(fb)} pixels, rows {r0}..{r1} of width {params.width} hold {n}")
-    unknown = set(planes) - {"index", "fb"}
-    if unknown:
-        raise ValueError(f"quantize_host: unknown planes {sorted(unknown)}")
-    out = {}
-    if "index" in planes:
-        out["index"] = np.zeros(n, dtype=np.uint8)
-    if "fb" in planes:
-        out["fb"] = np.zeros(n, dtype=COLOR)
-    rc = lib().par_quantize_host(C.byref(params), device, ptr(palette), len(palette), spread, ptr(fb), r0, r1,
-                                 ptr(out.get("fb")), ptr(out.get("index")))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_quantize_host")
-    return out
+    return _quantize_host("quantize_host", params, palette, (spread,), fb, rows, planes, device)
 
 
 def quantize_pattern(params, d_palette, n_colors, fb, rows, depth, strength=256, fb_out=None, index_out=None, stream=0):
@@ -724,44 +710,21 @@ def quantize_pattern(params, d_palette, n_colors, fb, rows, depth, strength=256,
     d_palette by pattern dithering (par_quantize_pattern_device: `depth` candidates a pixel, 1..16, their error fed back
     at strength / 256, 0..256, the 4x4 Bayer matrix picking one by luma rank) into the index plane at index_out and / or
     the RGBA plane at fb_out (fb_out == fb: in place). Asynchronous on `stream`."""
-    rc = lib().par_quantize_pattern_device(C.byref(params), C.c_void_p(stream), C.c_void_p(d_palette), n_colors, depth,
-                                           strength, C.c_void_p(fb), rows[0], rows[1], C.c_void_p(fb_out),
-                                           C.c_void_p(index_out))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_quantize_pattern_device")
+    _ok(lib().par_quantize_pattern_device, C.byref(params), _dp(stream), _dp(d_palette), n_colors, depth, strength,
+        _dp(fb), rows[0], rows[1], _dp(fb_out), _dp(index_out))
 
 
 def quantize_pattern_host(params, palette, fb, depth, strength=256, rows=None, planes=("index",), device=-1):
     """The same on host arrays (par_quantize_pattern_host): `palette` and `fb` are COLOR arrays, fb the rows `rows`
     (default: the whole frame). Returns {"index": uint8 array, "fb": COLOR array} for the planes asked for."""
-    r0, r1 = rows or (0, params.height)
-    palette = np.ascontiguousarray(palette, dtype=COLOR).reshape(-1)
-    fb = np.ascontiguousarray(fb, dtype=COLOR).reshape(-1)
-    n = (r1 - r0) * params.width
-    if len(fb) != n:
-        raise ValueError(f"quantize_pattern_host: fb holds {len(fb)} pixels, rows {r0}..{r1} of width {params.width} hold {n}")
-    unknown = set(planes) - {"index", "fb"}
-    if unknown:
-        raise ValueError(f"quantize_pattern_host: unknown planes {sorted(unknown)}")
-    out = {}
-    if "index" in planes:
-        out["index"] = np.zeros(n, dtype=np.uint8)
-    if "fb" in planes:
-        out["fb"] = np.zeros(n, dtype=COLOR)
-    rc = lib().par_quantize_pattern_host(C.byref(params), device, ptr(palette), len(palette), depth, strength, ptr(fb), r0,
-                                         r1, ptr(out.get("fb")), ptr(out.get("index")))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_quantize_pattern_host")
-    return out
+    return _quantize_host("quantize_pattern_host", params, palette, (depth, strength), fb, rows, planes, device)
 
 
 def palette_ramp(params, levels):
     """The natural output palette of a scene (par_palette_ramp): every sprite-palette entry at `levels` brightness bands
     from ambient to full, then the background; a COLOR array of palette_size * levels + 1 entries."""
     out = np.zeros(T.MAX_PALETTE, dtype=COLOR)
-    n = lib().par_palette_ramp(C.byref(params), levels, ptr(out), len(out))
-    if n < 0:
-        raise ParError(-n, "par_palette_ramp")
+    n = _count(lib().par_palette_ramp, C.byref(params), levels, ptr(out), len(out))
     return out[:n].copy()
 
 
@@ -771,58 +734,41 @@ def palette_reset(work, stream=0):
     """Device pointer (int) of a par_palette_work block (types.PALETTE_WORK, 8-byte aligned): zeroes it
     (par_palette_reset_device). Asynchronous on `stream`, as all five calls are: reset, count, cut, sum, emit, then
     quantize with the same n_colors, with no host wait between."""
-    rc = lib().par_palette_reset_device(C.c_void_p(stream), C.c_void_p(work))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_palette_reset_device")
+    _ok(lib().par_palette_reset_device, _dp(stream), _dp(work))
 
 
 def palette_count(params, fb, rows, work, stream=0):
     """Device pointers (ints): adds rows [rows[0], rows[1]) of the frame block at `fb` to the block's 15-bit colour
     histogram (par_palette_count_device). Several frames or row blocks counted in turn give the histogram of all."""
-    rc = lib().par_palette_count_device(C.byref(params), C.c_void_p(stream), C.c_void_p(fb), rows[0], rows[1],
-                                        C.c_void_p(work))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_palette_count_device")
+    _ok(lib().par_palette_count_device, C.byref(params), _dp(stream), _dp(fb), rows[0], rows[1], _dp(work))
 
 
 def palette_cut(work, n_colors, stream=0):
     """Device pointer (int): the median cut of the block's histogram into at most n_colors regions
     (par_palette_cut_device): writes the cell -> entry table and n_entries and zeroes the sums."""
-    rc = lib().par_palette_cut_device(C.c_void_p(stream), C.c_void_p(work), n_colors)
-    if rc != PAR_OK:
-        raise ParError(rc, "par_palette_cut_device")
+    _ok(lib().par_palette_cut_device, _dp(stream), _dp(work), n_colors)
 
 
 def palette_sum(params, fb, rows, work, stream=0):
     """Device pointers (ints): adds the channels and the count of every pixel of the rows to the sums of the entry its
     cell maps to (par_palette_sum_device)."""
-    rc = lib().par_palette_sum_device(C.byref(params), C.c_void_p(stream), C.c_void_p(fb), rows[0], rows[1],
-                                      C.c_void_p(work))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_palette_sum_device")
+    _ok(lib().par_palette_sum_device, C.byref(params), _dp(stream), _dp(fb), rows[0], rows[1], _dp(work))
 
 
 def palette_emit(work, n_colors, d_palette, stream=0):
     """Device pointers (ints): the n_colors palette entries at d_palette from the block's sums, each region's rounded
     mean, padded with copies of entry 0 beyond the entries the cut made (par_palette_emit_device)."""
-    rc = lib().par_palette_emit_device(C.c_void_p(stream), C.c_void_p(work), n_colors, C.c_void_p(d_palette))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_palette_emit_device")
+    _ok(lib().par_palette_emit_device, _dp(stream), _dp(work), n_colors, _dp(d_palette))
 
 
 def palette_fit_host(params, fb, n_colors, rows=None, device=-1):
     """One frame on host arrays (par_palette_fit_host): `fb` is a COLOR array holding rows `rows` (default: the whole
     frame). Returns (palette, n_entries): a COLOR array of n_colors entries and the number the cut made."""
-    r0, r1 = rows or (0, params.height)
-    fb = np.ascontiguousarray(fb, dtype=COLOR).reshape(-1)
-    n = (r1 - r0) * params.width
-    if len(fb) != n:
-        raise ValueError(f"palette_fit_host: fb holds {len(fb)} pixels, rows {r0}..{r1} of width {params.width} hold {n}")
+    r0, r1 = _rows(params, rows)
+    fb = _plane("palette_fit_host", "fb", fb, COLOR, params, (r0, r1))
     out = np.zeros(max(0, n_colors), dtype=COLOR)
     n_entries = C.c_int(0)
-    rc = lib().par_palette_fit_host(C.byref(params), device, ptr(fb), r0, r1, n_colors, ptr(out), C.byref(n_entries))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_palette_fit_host")
+    _ok(lib().par_palette_fit_host, C.byref(params), device, ptr(fb), r0, r1, n_colors, ptr(out), C.byref(n_entries))
     return out, n_entries.value
 
 
@@ -833,28 +779,20 @@ def palette_refine_device(params, fb, rows, d_palette, n_colors, iterations, d_i
     round's assignment afterwards, `work` a par_palette_refine_work block (types.PALETTE_REFINE_WORK, 8-byte aligned),
     `d_changed` (None or an int32) gets the number of entries the last round changed. After palette_emit, before
     quantize, on the same stream."""
-    rc = lib().par_palette_refine_device(C.byref(params), C.c_void_p(stream), C.c_void_p(fb), rows[0], rows[1],
-                                         C.c_void_p(d_palette), n_colors, iterations, C.c_void_p(d_index),
-                                         C.c_void_p(work), C.c_void_p(d_changed))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_palette_refine_device")
+    _ok(lib().par_palette_refine_device, C.byref(params), _dp(stream), _dp(fb), rows[0], rows[1], _dp(d_palette),
+        n_colors, iterations, _dp(d_index), _dp(work), _dp(d_changed))
 
 
 def palette_refine_host(params, fb, palette, iterations, rows=None, device=-1):
     """The same on host arrays (par_palette_refine_host): `fb` is a COLOR array holding rows `rows` (default: the whole
     frame), `palette` a COLOR array, which is not changed. Returns (palette, changed): the refined entries and the number
     of entries the last round changed (0: a fixed point)."""
-    r0, r1 = rows or (0, params.height)
-    fb = np.ascontiguousarray(fb, dtype=COLOR).reshape(-1)
-    n = (r1 - r0) * params.width
-    if len(fb) != n:
-        raise ValueError(f"palette_refine_host: fb holds {len(fb)} pixels, rows {r0}..{r1} of width {params.width} hold {n}")
+    r0, r1 = _rows(params, rows)
+    fb = _plane("palette_refine_host", "fb", fb, COLOR, params, (r0, r1))
     out = np.array(palette, dtype=COLOR).reshape(-1)
     changed = C.c_int(0)
-    rc = lib().par_palette_refine_host(C.byref(params), device, ptr(fb), r0, r1, ptr(out), len(out), iterations,
-                                       C.byref(changed))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_palette_refine_host")
+    _ok(lib().par_palette_refine_host, C.byref(params), device, ptr(fb), r0, r1, ptr(out), len(out), iterations,
+        C.byref(changed))
     return out, changed.value
 
 
@@ -866,36 +804,24 @@ def present(params, desc, out, rows, fb=None, index=None, d_palette=None, n_colo
     the integer scales, byte order and pitch of `desc`, a PRESENT_DESC array from types.make_present_desc; `out`
     addresses output row rows[0] * scale_y). Asynchronous on `stream`: the last call of a frame loop."""
     desc = np.ascontiguousarray(desc, dtype=PRESENT_DESC).reshape(-1)
-    rc = lib().par_present_device(C.byref(params), C.c_void_p(stream), ptr(desc), C.c_void_p(fb), C.c_void_p(index),
-                                  C.c_void_p(d_palette), n_colors, rows[0], rows[1], C.c_void_p(out))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_present_device")
+    _ok(lib().par_present_device, C.byref(params), _dp(stream), ptr(desc), _dp(fb), _dp(index), _dp(d_palette),
+        n_colors, rows[0], rows[1], _dp(out))
 
 
 def present_host(params, desc, rows=None, fb=None, index=None, palette=None, device=-1):
     """The same on host arrays (par_present_host): `fb` a COLOR array or `index` a uint8 array holding rows `rows`
     (default: the whole frame), `palette` a COLOR array with `index`. Returns the surface's rows as a
     (rows * scale_y, pitch) uint8 array; the bytes of a row beyond 4 * width * scale_x are not written (zeros here)."""
-    r0, r1 = rows or (0, params.height)
-    desc = np.ascontiguousarray(desc, dtype=PRESENT_DESC).reshape(-1)
-    n = (r1 - r0) * params.width
+    r0, r1 = _rows(params, rows)
+    desc = _flat(desc, PRESENT_DESC)
     if fb is not None:
-        fb = np.ascontiguousarray(fb, dtype=COLOR).reshape(-1)
+        fb = _plane("present_host", "fb", fb, COLOR, params, (r0, r1))
     if index is not None:
-        index = np.ascontiguousarray(index, dtype=np.uint8).reshape(-1)
-    for name, plane in (("fb", fb), ("index", index)):
-        if plane is not None and len(plane) != n:
-            raise ValueError(f"present_host: {name} holds {len(plane)} elements, rows {r0}..{r1} of width {params.width} "
-                             f"hold {n}")
-    n_colors = 0
-    if palette is not None:
-        palette = np.ascontiguousarray(palette, dtype=COLOR).reshape(-1)
-        n_colors = len(palette)
-    out = np.zeros((max(0, r1 - r0) * max(0, int(desc["scale_y"][0])), max(0, int(desc["pitch"][0]))), dtype=np.uint8)
-    rc = lib().par_present_host(C.byref(params), device, ptr(desc), ptr(fb), ptr(index), ptr(palette), n_colors, r0, r1,
-                                out.ctypes.data_as(C.c_void_p))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_present_host")
+        index = _plane("present_host", "index", index, np.uint8, params, (r0, r1))
+    palette, n_colors = _palette(palette)
+    out = _surface(r1 - r0, desc["scale_y"][0], desc["pitch"][0])
+    _ok(lib().par_present_host, C.byref(params), device, ptr(desc), ptr(fb), ptr(index), ptr(palette), n_colors, r0, r1,
+        ptr(out))
     return out
 
 
@@ -912,11 +838,8 @@ def finish(params, desc, out, rows, fb, style=None, gbuf=None, gbuf_rows=None, d
     if style is not None:
         style = np.ascontiguousarray(style, dtype=OUTLINE_STYLE).reshape(-1)
     g0, g1 = gbuf_rows or rows
-    rc = lib().par_finish_device(C.byref(params), C.c_void_p(stream), ptr(style), C.c_void_p(gbuf), g0, g1,
-                                 C.c_void_p(d_palette), n_colors, spread, ptr(desc), C.c_void_p(fb), rows[0], rows[1],
-                                 C.c_void_p(out), C.c_void_p(index_out))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_finish_device")
+    _ok(lib().par_finish_device, C.byref(params), _dp(stream), ptr(style), _dp(gbuf), g0, g1, _dp(d_palette), n_colors,
+        spread, ptr(desc), _dp(fb), rows[0], rows[1], _dp(out), _dp(index_out))
 
 
 def finish_host(params, desc, fb, rows=None, style=None, gbuf=None, gbuf_rows=None, palette=None, spread=0,
@@ -925,30 +848,19 @@ def finish_host(params, desc, fb, rows=None, style=None, gbuf=None, gbuf_rows=No
     a PIXEL array holding rows `gbuf_rows` (default: `rows`) with `style`, `palette` a COLOR array. Returns the surface's
     rows as a (rows * scale_y, pitch) uint8 array as present_host does (zeros in the gap bytes), or (surface, index plane)
     with want_index."""
-    r0, r1 = rows or (0, params.height)
+    r0, r1 = _rows(params, rows)
     g0, g1 = gbuf_rows or (r0, r1)
-    desc = np.ascontiguousarray(desc, dtype=PRESENT_DESC).reshape(-1)
-    n = (r1 - r0) * params.width
-    fb = np.ascontiguousarray(fb, dtype=COLOR).reshape(-1)
-    if len(fb) != n:
-        raise ValueError(f"finish_host: fb holds {len(fb)} pixels, rows {r0}..{r1} of width {params.width} hold {n}")
+    desc = _flat(desc, PRESENT_DESC)
+    fb = _plane("finish_host", "fb", fb, COLOR, params, (r0, r1))
     if style is not None:
-        style = np.ascontiguousarray(style, dtype=OUTLINE_STYLE).reshape(-1)
+        style = _flat(style, OUTLINE_STYLE)
     if gbuf is not None:
-        gbuf = np.ascontiguousarray(gbuf, dtype=PIXEL).reshape(-1)
-        if len(gbuf) != (g1 - g0) * params.width:
-            raise ValueError(f"finish_host: gbuf holds {len(gbuf)} texels, rows {g0}..{g1} of width {params.width} hold "
-                             f"{(g1 - g0) * params.width}")
-    n_colors = 0
-    if palette is not None:
-        palette = np.ascontiguousarray(palette, dtype=COLOR).reshape(-1)
-        n_colors = len(palette)
-    out = np.zeros((max(0, r1 - r0) * max(0, int(desc["scale_y"][0])), max(0, int(desc["pitch"][0]))), dtype=np.uint8)
-    index = np.zeros(n, dtype=np.uint8) if want_index else None
-    rc = lib().par_finish_host(C.byref(params), device, ptr(style), ptr(gbuf), g0, g1, ptr(palette), n_colors, spread,
-                               ptr(desc), ptr(fb), r0, r1, out.ctypes.data_as(C.c_void_p), ptr(index))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_finish_host")
+        gbuf = _plane("finish_host", "gbuf", gbuf, PIXEL, params, (g0, g1))
+    palette, n_colors = _palette(palette)
+    out = _surface(r1 - r0, desc["scale_y"][0], desc["pitch"][0])
+    index = np.zeros(len(fb), dtype=np.uint8) if want_index else None
+    _ok(lib().par_finish_host, C.byref(params), device, ptr(style), ptr(gbuf), g0, g1, ptr(palette), n_colors, spread,
+        ptr(desc), ptr(fb), r0, r1, ptr(out), ptr(index))
     return (out, index) if want_index else out
 
 
@@ -963,11 +875,8 @@ def upscale(params, desc, out, rows, fb=None, index=None, d_palette=None, n_colo
     block. `out` and `index_out` address output row rows[0] * scaler. Asynchronous on `stream`."""
     desc = np.ascontiguousarray(desc, dtype=UPSCALE_DESC).reshape(-1)
     s0, s1 = src_rows or rows
-    rc = lib().par_upscale_device(C.byref(params), C.c_void_p(stream), ptr(desc), C.c_void_p(fb), C.c_void_p(index),
-                                  C.c_void_p(d_palette), n_colors, s0, s1, rows[0], rows[1], C.c_void_p(out),
-                                  C.c_void_p(index_out))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_upscale_device")
+    _ok(lib().par_upscale_device, C.byref(params), _dp(stream), ptr(desc), _dp(fb), _dp(index), _dp(d_palette),
+        n_colors, s0, s1, rows[0], rows[1], _dp(out), _dp(index_out))
 
 
 def upscale_host(params, desc, rows=None, fb=None, index=None, palette=None, src_rows=None, want_index=False,
@@ -977,30 +886,19 @@ def upscale_host(params, desc, rows=None, fb=None, index=None, palette=None, src
     surface, which needs want_index). Returns the surface's rows as a (rows * scaler, pitch) uint8 array as present_host
     does (zeros in the gap bytes), or (surface or None, the (rows * scaler, width * scaler) index plane) with
     want_index."""
-    r0, r1 = rows or (0, params.height)
+    r0, r1 = _rows(params, rows)
     s0, s1 = src_rows or (r0, r1)
-    desc = np.ascontiguousarray(desc, dtype=UPSCALE_DESC).reshape(-1)
-    n = (s1 - s0) * params.width
+    desc = _flat(desc, UPSCALE_DESC)
     if fb is not None:
-        fb = np.ascontiguousarray(fb, dtype=COLOR).reshape(-1)
+        fb = _plane("upscale_host", "fb", fb, COLOR, params, (s0, s1))
     if index is not None:
-        index = np.ascontiguousarray(index, dtype=np.uint8).reshape(-1)
-    for name, plane in (("fb", fb), ("index", index)):
-        if plane is not None and len(plane) != n:
-            raise ValueError(f"upscale_host: {name} holds {len(plane)} elements, rows {s0}..{s1} of width {params.width} "
-                             f"hold {n}")
-    n_colors = 0
-    if palette is not None:
-        palette = np.ascontiguousarray(palette, dtype=COLOR).reshape(-1)
-        n_colors = len(palette)
+        index = _plane("upscale_host", "index", index, np.uint8, params, (s0, s1))
+    palette, n_colors = _palette(palette)
     k = max(0, int(desc["scaler"][0]))
-    out_rows = max(0, r1 - r0) * k
     out = None
     if fb is not None or palette is not None or not want_index:
-        out = np.zeros((out_rows, max(0, int(desc["pitch"][0]))), dtype=np.uint8)
-    scaled = np.zeros((out_rows, max(0, params.width) * k), dtype=np.uint8) if want_index else None
-    rc = lib().par_upscale_host(C.byref(params), device, ptr(desc), ptr(fb), ptr(index), ptr(palette), n_colors, s0, s1,
-                                r0, r1, ptr(out), ptr(scaled))
-    if rc != PAR_OK:
-        raise ParError(rc, "par_upscale_host")
+        out = _surface(r1 - r0, k, desc["pitch"][0])
+    scaled = _surface(r1 - r0, k, max(0, params.width) * k) if want_index else None
+    _ok(lib().par_upscale_host, C.byref(params), device, ptr(desc), ptr(fb), ptr(index), ptr(palette), n_colors, s0, s1,
+        r0, r1, ptr(out), ptr(scaled))
     return (out, scaled) if want_index else out

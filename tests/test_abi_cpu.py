@@ -20,6 +20,74 @@ def test_exports_every_declared_symbol(par):
         assert getattr(L, name) is not None
 
 
+def header_without_comments():
+    header = open(os.path.join(ROOT, "include", "par_raytracer.h")).read()
+    return re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+
+
+def signature(entry):
+    """(return type, argument types) of an entry of the binding's table: an int return is not written out there."""
+    return entry if isinstance(entry, tuple) else (ctypes.c_int, entry)
+
+
+RETURNS = {"int": ctypes.c_int, "void": None, "const char*": ctypes.c_char_p}
+SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "uint64_t": ctypes.c_uint64}
+
+
+def test_the_bindings_table_is_the_headers_prototypes(par):
+    """Every prototype of the header, its parameters in count, order and kind: the table lib() walks agrees, and so do
+    the argtypes and restypes that the loaded library's functions carry. A parameter type the mapping does not know fails
+    here: a new scalar type is to be decided, not defaulted."""
+    protos = re.findall(r"^(const char\*|void|int)\s+(par_[a-z_0-9]+)\(([^;]*?)\);", header_without_comments(),
+                        flags=re.M | re.S)
+    assert len(protos) == 75 == len(par.ABI)
+    assert [name for _, name, _ in protos] == list(par.ABI) == list(par.ABI_SYMBOLS)  # the header's order
+    L = par.lib()
+    for ret, name, params in protos:
+        want = []
+        for p in (" ".join(p.split()) for p in params.split(",")):
+            if p == "void":
+                assert params.strip() == "void"
+            elif "*" in p:
+                want.append(ctypes.c_void_p)
+            else:
+                kind, _ = p.rsplit(" ", 1)  # "<type> <name>"
+                assert kind in SCALARS, f"{name}: no ctypes type decided for a parameter `{p}`"
+                want.append(SCALARS[kind])
+        restype, argtypes = signature(par.ABI[name])
+        assert list(argtypes) == want, name
+        assert restype is RETURNS[ret], name
+        fn = getattr(L, name)
+        assert list(fn.argtypes) == want and fn.restype is RETURNS[ret], name
+        if ret == "int":
+            assert not isinstance(par.ABI[name], tuple), f"{name}: the default restype is not written out"
+
+
+def test_the_debug_hooks_are_apart_and_bound(par):
+    assert set(par.ABI_DEBUG_HOOKS) == {"par_debug_read_stamps", "par_debug_set_hooks", "par_debug_read_light_walks"}
+    assert not set(par.ABI_DEBUG_HOOKS) & set(par.ABI)
+    header = header_without_comments()
+    for name, entry in par.ABI_DEBUG_HOOKS.items():
+        assert name not in header
+        restype, argtypes = signature(entry)
+        fn = getattr(par.lib(), name)
+        assert list(fn.argtypes) == list(argtypes) and fn.restype is restype is ctypes.c_int
+
+
+def test_constants_are_the_headers(par):
+    header = header_without_comments()
+    status = re.search(r"typedef enum par_status \{(.*?)\} par_status;", header, flags=re.S).group(1)
+    assert {int(v): k for k, v in re.findall(r"(PAR_\w+) = (\d+)", status)} == par.STATUS_NAMES
+    assert par.PAR_OK == 0 and par.STATUS_NAMES[0] == "PAR_OK"
+    flags = dict(re.findall(r"PAR_(RENDER_\w+) = 1u << (\d+)", header))
+    assert len(flags) == 4
+    for name, shift in flags.items():
+        assert getattr(par, name) == 1 << int(shift), name
+    assert par.MAX_LIGHTS == int(re.search(r"#define PAR_MAX_LIGHTS (\d+)", header).group(1))
+    models = re.search(r"enum \{ PAR_LIGHTS_UNBOUNDED = (\d+), PAR_LIGHTS_RANGED = (\d+) \};", header)
+    assert (par.LIGHTS_UNBOUNDED, par.LIGHTS_RANGED) == (int(models.group(1)), int(models.group(2)))
+
+
 def test_library_carries_no_tuning_or_test_switches(par):
     """Launch shapes are constants of the library and test switches are per-context hooks (par_debug_set_hooks):
     nothing in the shipped library reads an environment variable that changes how it renders."""
