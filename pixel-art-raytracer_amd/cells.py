@@ -1,0 +1,84 @@
+"""Colour cells: a frame quantised under per-cell sub-palettes (include/par_cells.h). The three calls are declared in a
+header of their own and bound here, apart from the package module's table: ABI_CELLS has the format of the package's ABI
+(symbol -> argument types, every pointer a c_void_p, an int return not written out) and is installed on the library
+the package loaded, at first use. The calls go through the package's own path: _ok / _count raise ParError with the
+symbol's name, a device pointer or a stream is an int or None (_dp).
+
+    cells = importlib.import_module("pixel-art-raytracer_amd.cells")
+"""
+import ctypes as C
+import sys
+
+import numpy as np
+
+from .types import COLOR, MAX_PALETTE, ptr
+
+_par = sys.modules[__package__]  # the package module: its lib() is looked up at every call, as its own wrappers do
+
+_p, _i = C.c_void_p, C.c_int
+# include/par_cells.h, in the header's order; tests/test_cells_cpu.py holds the table to the header's prototypes
+ABI_CELLS = {
+    "par_quantize_cells_device": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p],
+    "par_quantize_cells_host": [_p, _i, _p, _i, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p],
+    "par_cells_pairs": [_p, _i, _p, _i],
+}
+ABI_CELLS_SYMBOLS = tuple(ABI_CELLS)
+
+_installed_on = None
+
+
+def lib():
+    """The package's library with ABI_CELLS set on its functions."""
+    global _installed_on
+    L = _par.lib()
+    if L is not _installed_on:
+        for name, sig in ABI_CELLS.items():
+            fn = getattr(L, name)
+            if type(sig) is tuple:
+                fn.restype, sig = sig
+            fn.argtypes = sig
+        _installed_on = L
+    return L
+
+
+def quantize_cells(params, d_palette, n_sub, sub_size, cell, fb, rows, fb_out=None, index_out=None, cell_out=None,
+                   spread=0, stream=None):
+    """Device pointers (ints): rows [rows[0], rows[1]) of the frame block at `fb` quantised under the n_sub sub-palettes of
+    sub_size entries each at d_palette, one sub-palette a cell of cell[0] x cell[1] pixels (par_quantize_cells_device: the
+    sub-palette with the smallest summed L1 distance over the cell, the lowest among equals, the 4x4 ordered dither of
+    strength `spread`) into the index plane at index_out (indices into the flat table) and / or the RGBA plane at fb_out
+    (fb_out == fb: in place), the chosen sub-palette of every cell to cell_out when given. The rows are cut at cell rows.
+    Asynchronous on `stream`."""
+    _par._ok(lib().par_quantize_cells_device, C.byref(params), _par._dp(stream), _par._dp(d_palette), n_sub, sub_size,
+             cell[0], cell[1], spread, _par._dp(fb), rows[0], rows[1], _par._dp(fb_out), _par._dp(index_out),
+             _par._dp(cell_out))
+
+
+def quantize_cells_host(params, palette, n_sub, sub_size, cell, fb, rows=None, spread=0, planes=("index",), device=-1):
+    """The same on host arrays (par_quantize_cells_host): `palette` is a COLOR array of n_sub * sub_size entries, `fb` a
+    COLOR array holding rows `rows` (default: the whole frame). Returns {"index": uint8 array, "fb": COLOR array,
+    "cells": uint8 array, one byte a cell of the block's cell rows} for the planes asked for."""
+    who = "quantize_cells_host"
+    r0, r1 = _par._rows(params, rows)
+    palette = _par._flat(palette, COLOR)
+    if len(palette) != n_sub * sub_size:
+        raise ValueError(f"{who}: palette holds {len(palette)} entries, {n_sub} sub-palettes of {sub_size} hold "
+                         f"{n_sub * sub_size}")
+    fb = _par._plane(who, "fb", fb, COLOR, params, (r0, r1))
+    want_cells = "cells" in planes
+    out = _par._out_planes(who, [k for k in planes if k != "cells"], "index", len(fb))
+    if want_cells:
+        cw, ch = max(1, int(cell[0])), max(1, int(cell[1]))
+        out["cells"] = np.zeros(-(-params.width // cw) * -(-(r1 - r0) // ch), dtype=np.uint8)
+    _par._ok(lib().par_quantize_cells_host, C.byref(params), device, ptr(palette), n_sub, sub_size, cell[0], cell[1],
+             spread, ptr(fb), r0, r1, ptr(out.get("fb")), ptr(out.get("index")), ptr(out.get("cells")))
+    return out
+
+
+def cells_pairs(palette):
+    """The sub-palettes of the any-two-colours mode (par_cells_pairs): every unordered pair (i, j), i < j, of the 2 .. 16
+    entries of `palette`, a flat COLOR array of n * (n - 1) / 2 pairs of 2 entries."""
+    palette = _par._flat(palette, COLOR)
+    out = np.zeros(MAX_PALETTE, dtype=COLOR)
+    n = _par._count(lib().par_cells_pairs, ptr(palette), len(palette), ptr(out), len(out))
+    return out[:2 * n].copy()

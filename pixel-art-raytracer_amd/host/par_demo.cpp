@@ -8,7 +8,7 @@
 //
 //   par_demo [--keys RRRRUUUUhhhhjjPP] [--frames N] [--out DIR] [--gif FILE] [--debug-line] [--as-sdl] [--size W H L]
 //            [--palette-levels K] [--dither S] [--outline S,C,D] [--scale SX[,SY]] [--finish] [--upscale K]
-//            [--palette-fit N] [--palette-refine I] [--dither-pattern N[,S]]
+//            [--palette-fit N] [--palette-refine I] [--dither-pattern N[,S]] [--cells CW,CH]
 //
 // --gif writes the frames as one animated GIF89a (100 ms per frame like the reference's gif.gif); a frame's colours
 // are palette entries times a brightness, at most a few hundred distinct values, so each frame gets an exact local
@@ -30,6 +30,11 @@
 // --dither-pattern N[,S] (with --palette-levels or --palette-fit; N = 1..16 candidates a pixel, S = 0..256 the strength
 // of the error fed back, 256 when left out) takes the GIF's index planes from par_quantize_pattern_host, pattern
 // dithering, in place of par_quantize_host. It is refused together with --dither or --finish.
+// --cells CW,CH (with --palette-fit N, N = 2..16; CW and CH each 8 or 16) quantises every frame of the GIF under colour
+// cells (par_quantize_cells_host): a cell of CW x CH pixels may use any two colours of the frame's fitted (and refined)
+// palette. The pairs of that palette (par_cells_pairs: N * (N - 1) / 2 sub-palettes of two entries) are the frame's local
+// colour table and the index plane is written as it comes back; --dither S keeps its meaning. It is refused together
+// with --dither-pattern or --finish.
 //
 // --outline S,C,D draws every frame's outlines on the GPU (par_outline_host) from the frame's own G-buffer: silhouettes
 // scaled by S / 256, creases by C / 256, a silhouette between two entities from a depth difference of D (128,320,4 is a
@@ -64,6 +69,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "par_cells.h"
 #include "par_raytracer.h"
 
 static void apply_key(char k, par_aabb& player, par_light& light) {
@@ -230,6 +236,7 @@ int main(int argc, char** argv) {
     int pattern_depth = 0, pattern_strength = 256;  // depth 0: no --dither-pattern
     int scale_x = 0, scale_y = 0;  // 0: no --scale
     int upscale = 0;               // 0: no --upscale
+    int cell_w = 0, cell_h = 0;    // 0: no --cells
     par_outline_style outline_style{4, 256, 256};
     for (int i = 1; i < argc; i++) {
         if (!std::strcmp(argv[i], "--keys") && i + 1 < argc) keys = argv[++i];
@@ -247,6 +254,14 @@ int main(int argc, char** argv) {
             if ((!alone && std::sscanf(argv[i], "%d,%d%c", &pattern_depth, &pattern_strength, &tail) != 2) || pattern_depth < 1 ||
                 pattern_depth > 16 || pattern_strength < 0 || pattern_strength > 256) {
                 std::fprintf(stderr, "--dither-pattern wants N[,S], N 1..16 and S 0..256, got %s\n", argv[i]);
+                return 2;
+            }
+        }
+        else if (!std::strcmp(argv[i], "--cells") && i + 1 < argc) {
+            char tail = 0;
+            if (std::sscanf(argv[++i], "%d,%d%c", &cell_w, &cell_h, &tail) != 2 || (cell_w != 8 && cell_w != 16) ||
+                (cell_h != 8 && cell_h != 16)) {
+                std::fprintf(stderr, "--cells wants CW,CH, each 8 or 16, got %s\n", argv[i]);
                 return 2;
             }
         }
@@ -313,6 +328,16 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    if (cell_w != 0) {
+        if (palette_fit < 2 || palette_fit > 16) {
+            std::fprintf(stderr, "--cells wants --palette-fit 2..16: a cell uses two colours of the fitted palette\n");
+            return 2;
+        }
+        if (pattern_depth != 0 || finish) {
+            std::fprintf(stderr, "--cells cannot go with --dither-pattern or --finish: they know one flat palette\n");
+            return 2;
+        }
+    }
     if (finish) {
         if (out_dir.empty()) { std::fprintf(stderr, "--finish wants --out\n"); return 2; }
         if (!outline && palette_levels == 0) { std::fprintf(stderr, "--finish wants --outline or --palette-levels: without both it is --scale\n"); return 2; }
@@ -359,7 +384,7 @@ int main(int argc, char** argv) {
         index.resize((size_t)W * H);
     }
     // --palette-fit: the GIF's frames are index planes over a palette fitted to each frame
-    std::vector<par_color> fitted;
+    std::vector<par_color> fitted, pairs;  // (pairs: --cells, the table of the fitted palette's pairs)
     if (palette_fit != 0 && !gif_path.empty()) {
         fitted.resize((size_t)palette_fit);
         index.resize((size_t)W * H);
@@ -468,8 +493,20 @@ int main(int argc, char** argv) {
                 std::fprintf(stderr, "par_palette_refine_host: %s\n", par_status_string(rc));
                 return 1;
             }
-            if (quantise(fitted) != PAR_OK) return 1;
-            gif.frame(index, fitted, 10);
+            if (cell_w != 0) {
+                pairs.resize((size_t)palette_fit * (palette_fit - 1));
+                const int n_sub = par_cells_pairs(fitted.data(), palette_fit, pairs.data(), (int)pairs.size());
+                if (n_sub < 0) { std::fprintf(stderr, "par_cells_pairs: %s\n", par_status_string(-n_sub)); return 1; }
+                if ((rc = par_quantize_cells_host(&params, 0, pairs.data(), n_sub, 2, cell_w, cell_h, dither, fb.data(), 0, H,
+                                                  nullptr, index.data(), nullptr)) != PAR_OK) {
+                    std::fprintf(stderr, "par_quantize_cells_host: %s\n", par_status_string(rc));
+                    return 1;
+                }
+                gif.frame(index, pairs, 10);
+            } else {
+                if (quantise(fitted) != PAR_OK) return 1;
+                gif.frame(index, fitted, 10);
+            }
         } else if (!ramp.empty()) {
             if (quantise(ramp) != PAR_OK) return 1;
             gif.frame(index, ramp, 10);
