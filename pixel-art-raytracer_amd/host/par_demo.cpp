@@ -8,7 +8,7 @@
 //
 //   par_demo [--keys RRRRUUUUhhhhjjPP] [--frames N] [--out DIR] [--gif FILE] [--debug-line] [--as-sdl] [--size W H L]
 //            [--palette-levels K] [--dither S] [--outline S,C,D] [--scale SX[,SY]] [--finish] [--upscale K]
-//            [--palette-fit N] [--palette-refine I] [--dither-pattern N[,S]] [--cells CW,CH]
+//            [--palette-fit N] [--palette-refine I] [--dither-pattern N[,S]] [--cells CW,CH] [--tileset TW,TH[,FLIPS]]
 //
 // --gif writes the frames as one animated GIF89a (100 ms per frame like the reference's gif.gif); a frame's colours
 // are palette entries times a brightness, at most a few hundred distinct values, so each frame gets an exact local
@@ -35,6 +35,11 @@
 // palette. The pairs of that palette (par_cells_pairs: N * (N - 1) / 2 sub-palettes of two entries) are the frame's local
 // colour table and the index plane is written as it comes back; --dither S keeps its meaning. It is refused together
 // with --dither-pattern or --finish.
+// --tileset TW,TH[,FLIPS] (with --gif and --palette-levels, --palette-fit or --cells, wherever a frame of the GIF is an
+// index plane; TW and TH each 8 or 16, FLIPS a mask 0..3 of the mirrors allowed, 0 when left out) counts the distinct
+// tiles of every frame's index plane on the GPU (par_tileset_build_host with capacity 0, behind the quantise) and prints
+// one line a frame, `tileset frame <i>: <T> tiles of <N> cells`: whether the frame fits a tile budget. It changes no
+// byte of the GIF.
 //
 // --outline S,C,D draws every frame's outlines on the GPU (par_outline_host) from the frame's own G-buffer: silhouettes
 // scaled by S / 256, creases by C / 256, a silhouette between two entities from a depth difference of D (128,320,4 is a
@@ -71,6 +76,7 @@
 
 #include "par_cells.h"
 #include "par_raytracer.h"
+#include "par_tileset.h"
 
 static void apply_key(char k, par_aabb& player, par_light& light) {
     switch (k) {
@@ -237,6 +243,7 @@ int main(int argc, char** argv) {
     int scale_x = 0, scale_y = 0;  // 0: no --scale
     int upscale = 0;               // 0: no --upscale
     int cell_w = 0, cell_h = 0;    // 0: no --cells
+    int tile_w = 0, tile_h = 0, tile_flips = 0;  // 0: no --tileset
     par_outline_style outline_style{4, 256, 256};
     for (int i = 1; i < argc; i++) {
         if (!std::strcmp(argv[i], "--keys") && i + 1 < argc) keys = argv[++i];
@@ -262,6 +269,15 @@ int main(int argc, char** argv) {
             if (std::sscanf(argv[++i], "%d,%d%c", &cell_w, &cell_h, &tail) != 2 || (cell_w != 8 && cell_w != 16) ||
                 (cell_h != 8 && cell_h != 16)) {
                 std::fprintf(stderr, "--cells wants CW,CH, each 8 or 16, got %s\n", argv[i]);
+                return 2;
+            }
+        }
+        else if (!std::strcmp(argv[i], "--tileset") && i + 1 < argc) {
+            char tail = 0;
+            const bool two = std::sscanf(argv[++i], "%d,%d%c", &tile_w, &tile_h, &tail) == 2;
+            if ((!two && std::sscanf(argv[i], "%d,%d,%d%c", &tile_w, &tile_h, &tile_flips, &tail) != 3) ||
+                (tile_w != 8 && tile_w != 16) || (tile_h != 8 && tile_h != 16) || tile_flips < 0 || tile_flips > 3) {
+                std::fprintf(stderr, "--tileset wants TW,TH[,FLIPS], TW and TH each 8 or 16 and FLIPS 0..3, got %s\n", argv[i]);
                 return 2;
             }
         }
@@ -338,6 +354,10 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    if (tile_w != 0 && (gif_path.empty() || (palette_levels == 0 && palette_fit == 0))) {
+        std::fprintf(stderr, "--tileset wants --gif and --palette-levels, --palette-fit or --cells: it counts the tiles of an index plane\n");
+        return 2;
+    }
     if (finish) {
         if (out_dir.empty()) { std::fprintf(stderr, "--finish wants --out\n"); return 2; }
         if (!outline && palette_levels == 0) { std::fprintf(stderr, "--finish wants --outline or --palette-levels: without both it is --scale\n"); return 2; }
@@ -401,6 +421,20 @@ int main(int argc, char** argv) {
         if (status != PAR_OK) std::fprintf(stderr, "par_quantize_host: %s\n", par_status_string(status));
         return status;
     };
+    // --tileset: the tiles of the index plane of frame f as it stands, counted and printed
+    const auto count_tiles = [&](int f) -> int {
+        if (tile_w == 0) return PAR_OK;
+        int tiles = 0;
+        const int status = par_tileset_build_host(&params, 0, index.data(), 0, H, tile_w, tile_h, 0, tile_flips, nullptr, 0,
+                                                  nullptr, &tiles);
+        if (status != PAR_OK) {
+            std::fprintf(stderr, "par_tileset_build_host: %s\n", par_status_string(status));
+            return status;
+        }
+        std::printf("tileset frame %d: %d tiles of %d cells\n", f, tiles,
+                    ((W + tile_w - 1) / tile_w) * ((H + tile_h - 1) / tile_h));
+        return (int)PAR_OK;
+    };
     GifWriter gif;
     if (!gif_path.empty() && !gif.open(gif_path, W, H)) { std::fprintf(stderr, "cannot write %s\n", gif_path.c_str()); return 1; }
     const int mouse_x = 0, mouse_y = 0;  // the reference's mouse position before any motion event (alt:133-134)
@@ -433,6 +467,7 @@ int main(int argc, char** argv) {
             std::snprintf(name, sizeof(name), "/frame_%03d.ppm", f);
             if (!write_ppm(out_dir + name, surface.data(), W * scale_x, H * scale_y)) { std::fprintf(stderr, "cannot write %s%s\n", out_dir.c_str(), name); return 1; }
             if (pal && !gif_path.empty()) {
+                if (count_tiles(f) != PAR_OK) return 1;
                 gif.frame(index, ramp, 10);
             } else if (!gif_path.empty()) {
                 // the outlined frame at view size: the surface itself at scale 1, else one more call at scale 1
@@ -502,13 +537,14 @@ int main(int argc, char** argv) {
                     std::fprintf(stderr, "par_quantize_cells_host: %s\n", par_status_string(rc));
                     return 1;
                 }
+                if (count_tiles(f) != PAR_OK) return 1;
                 gif.frame(index, pairs, 10);
             } else {
-                if (quantise(fitted) != PAR_OK) return 1;
+                if (quantise(fitted) != PAR_OK || count_tiles(f) != PAR_OK) return 1;
                 gif.frame(index, fitted, 10);
             }
         } else if (!ramp.empty()) {
-            if (quantise(ramp) != PAR_OK) return 1;
+            if (quantise(ramp) != PAR_OK || count_tiles(f) != PAR_OK) return 1;
             gif.frame(index, ramp, 10);
         } else if (!gif_path.empty()) {
             for (size_t i = 0; i < fb.size(); i++) { rgb[i * 3] = fb[i].red; rgb[i * 3 + 1] = fb[i].green; rgb[i * 3 + 2] = fb[i].blue; }

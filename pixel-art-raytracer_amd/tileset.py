@@ -1,0 +1,117 @@
+"""Tile sets: an index plane deduplicated into its distinct tiles and a tile map, and the map drawn back into a plane
+(include/par_tileset.h). The five calls are declared in a header of their own and bound here as cells.py binds its
+three: ABI_TILESET has the format of the package's ABI (symbol -> argument types, every pointer a c_void_p, an int return
+not written out, any other return as (restype, argument types)) and is installed on the library the package loaded, at
+first use. The calls go through the package's own path: _ok raises ParError with the symbol's name, a device pointer or
+a stream is an int or None (_dp).
+
+    tileset = importlib.import_module("pixel-art-raytracer_amd.tileset")
+"""
+import ctypes as C
+import sys
+
+import numpy as np
+
+from .types import ptr
+
+_par = sys.modules[__package__]  # the package module: its lib() is looked up at every call, as its own wrappers do
+
+_p, _i = C.c_void_p, C.c_int
+# include/par_tileset.h, in the header's order; tests/test_tileset_cpu.py holds the table to the header's prototypes
+ABI_TILESET = {
+    "par_tileset_work_bytes": (C.c_size_t, [_i]),
+    "par_tileset_build_device": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p],
+    "par_tileset_expand_device": [_p, _p, _p, _i, _i, _i, _p, _i, _i, _p],
+    "par_tileset_build_host": [_p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _p],
+    "par_tileset_expand_host": [_p, _i, _p, _i, _i, _i, _p, _i, _i, _p],
+}
+ABI_TILESET_SYMBOLS = tuple(ABI_TILESET)
+MAX_CELLS = 1 << 20  # PAR_TILESET_MAX_CELLS
+FLIP_X, FLIP_Y = 1, 2
+
+_installed_on = None
+
+
+def lib():
+    """The package's library with ABI_TILESET set on its functions."""
+    global _installed_on
+    L = _par.lib()
+    if L is not _installed_on:
+        for name, sig in ABI_TILESET.items():
+            fn = getattr(L, name)
+            if type(sig) is tuple:
+                fn.restype, sig = sig
+            fn.argtypes = sig
+        _installed_on = L
+    return L
+
+
+def n_cells(params, tile, rows=None):
+    """The cells of rows `rows` (default: the whole frame) under tiles of tile[0] x tile[1] pixels."""
+    r0, r1 = _par._rows(params, rows)
+    tw, th = max(1, int(tile[0])), max(1, int(tile[1]))
+    return -(-params.width // tw) * -(-(r1 - r0) // th)
+
+
+def tileset_work_bytes(cells):
+    """The bytes of the work block of a tileset_build over `cells` cells (par_tileset_work_bytes); 0 outside
+    [1, MAX_CELLS]."""
+    return lib().par_tileset_work_bytes(cells)
+
+
+def tileset_build(params, index, rows, tile, work, count_out, tiles_out=None, capacity=0, map_out=None, pad=0, flips=0,
+                  stream=None):
+    """Device pointers (ints): the index plane at `index`, which holds rows [rows[0], rows[1]), cut into tiles of
+    tile[0] x tile[1] pixels and deduplicated under the flips the mask `flips` allows (par_tileset_build_device): the tile
+    count as a uint32 to count_out, the tile map (a uint32 a cell: id | flip << 30) to map_out and the first `capacity`
+    tiles to tiles_out when given. `work` holds tileset_work_bytes(cells) bytes and needs no preparation. Asynchronous on
+    `stream`."""
+    _par._ok(lib().par_tileset_build_device, C.byref(params), _par._dp(stream), _par._dp(index), rows[0], rows[1], tile[0],
+             tile[1], pad, flips, _par._dp(work), _par._dp(tiles_out), capacity, _par._dp(map_out), _par._dp(count_out))
+
+
+def tileset_expand(params, tiles, n_tiles, tile, tile_map, rows, index_out, stream=None):
+    """Device pointers (ints): the tile map at `tile_map` drawn with the n_tiles tiles at `tiles` into the index plane at
+    index_out, rows [rows[0], rows[1]) (par_tileset_expand_device); a tile number past the last takes the last tile.
+    Asynchronous on `stream`."""
+    _par._ok(lib().par_tileset_expand_device, C.byref(params), _par._dp(stream), _par._dp(tiles), n_tiles, tile[0], tile[1],
+             _par._dp(tile_map), rows[0], rows[1], _par._dp(index_out))
+
+
+def tileset_build_host(params, index, tile, rows=None, pad=0, flips=0, capacity=None, device=-1):
+    """The same on host arrays (par_tileset_build_host): `index` is a uint8 array holding rows `rows` (default: the whole
+    frame). Returns {"tiles": uint8 array (min(count, capacity), tile[1], tile[0]), "map": uint32 array, one entry a cell,
+    "count": T}; `capacity` defaults to the cell count, which holds every tile."""
+    who = "tileset_build_host"
+    r0, r1 = _par._rows(params, rows)
+    index = _par._plane(who, "index", index, np.uint8, params, (r0, r1))
+    cells = n_cells(params, tile, (r0, r1))
+    capacity = cells if capacity is None else capacity
+    size = max(1, int(tile[0])) * max(1, int(tile[1]))
+    tiles = np.zeros(max(0, capacity) * size, dtype=np.uint8)
+    tile_map = np.zeros(cells, dtype=np.uint32)
+    count = C.c_int(0)
+    _par._ok(lib().par_tileset_build_host, C.byref(params), device, ptr(index), r0, r1, tile[0], tile[1], pad, flips,
+             ptr(tiles) if capacity > 0 else None, capacity, ptr(tile_map), C.byref(count))
+    kept = min(count.value, capacity)
+    return {"tiles": tiles[:kept * size].reshape(kept, tile[1], tile[0]), "map": tile_map, "count": count.value}
+
+
+def tileset_expand_host(params, tiles, tile, tile_map, rows=None, device=-1):
+    """The index plane of rows `rows` (default: the whole frame) drawn from host arrays (par_tileset_expand_host): `tiles`
+    is a uint8 array of whole tiles, `tile_map` a uint32 array of one entry a cell. Returns the uint8 plane."""
+    who = "tileset_expand_host"
+    r0, r1 = _par._rows(params, rows)
+    tiles = _par._flat(tiles, np.uint8)
+    tile_map = _par._flat(tile_map, np.uint32)
+    size = max(1, int(tile[0])) * max(1, int(tile[1]))
+    if len(tiles) % size:
+        raise ValueError(f"{who}: tiles holds {len(tiles)} bytes, no whole number of tiles of {size}")
+    cells = n_cells(params, tile, (r0, r1))
+    if len(tile_map) != cells:
+        raise ValueError(f"{who}: the map holds {len(tile_map)} entries, rows {r0}..{r1} of width {params.width} hold {cells} "
+                         f"cells")
+    out = np.zeros(max(0, r1 - r0) * max(0, params.width), dtype=np.uint8)
+    _par._ok(lib().par_tileset_expand_host, C.byref(params), device, ptr(tiles), len(tiles) // size, tile[0], tile[1],
+             ptr(tile_map), r0, r1, ptr(out))
+    return out

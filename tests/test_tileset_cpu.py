@@ -1,0 +1,519 @@
+"""Tile sets without a GPU: the five calls are declared in include/par_tileset.h (and in no other header), exported
+and bound by the tileset module, whose table is held to the header's prototypes by the method of tests/test_abi_cpu.py;
+the header compiles as pedantic C11 alone and beside the other two in any order; every PAR_ERR_INVALID_ARG of the four
+calls that take planes comes back before any device work and with nothing written, each rule on its own;
+par_tileset_work_bytes is the header's formula; the vectorised model the GPU tests lean on (tileset.model) equals a
+per-cell loop with a dict on random planes and on crafted planes whose tiles, maps and counts are worked out by hand;
+the consequences the contract states hold; and the tile counts of the graybox frame that DESIGN and README quote."""
+import ctypes as C
+import importlib
+import itertools
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import tileset as TS
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ERR_INVALID_ARG = 1
+SYMBOLS = ("par_tileset_work_bytes", "par_tileset_build_device", "par_tileset_expand_device", "par_tileset_build_host",
+           "par_tileset_expand_host")
+
+
+@pytest.fixture(scope="module")
+def tileset(par):
+    return importlib.import_module("pixel-art-raytracer_amd.tileset")
+
+
+def header_without_comments(name="par_tileset.h"):
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
+
+
+# ---- declared, exported, bound -------------------------------------------------------------------------------------
+
+def test_declared_exported_and_bound(par, tileset):
+    protos = re.findall(r"^(?:int|size_t)\s+(par_[a-z_0-9]+)\(", header_without_comments(), flags=re.M)
+    assert tuple(protos) == SYMBOLS == tuple(tileset.ABI_TILESET) == tileset.ABI_TILESET_SYMBOLS
+    for other in ("par_raytracer.h", "par_cells.h"):
+        assert "par_tileset" not in open(os.path.join(ROOT, "include", other)).read()
+    assert '#include "par_types.h"' in header_without_comments() and "par_raytracer.h" not in header_without_comments()
+    cells = importlib.import_module("pixel-art-raytracer_amd.cells")
+    for name in SYMBOLS:
+        assert name not in par.ABI and name not in par.ABI_DEBUG_HOOKS and name not in cells.ABI_CELLS
+        assert getattr(par.lib(), name) is not None
+    for fn in ("tileset_work_bytes", "tileset_build", "tileset_expand", "tileset_build_host", "tileset_expand_host"):
+        assert callable(getattr(tileset, fn)) and not hasattr(par, fn)
+    assert tileset.MAX_CELLS == TS.MAX_CELLS == 1 << 20
+    assert re.search(r"#define PAR_TILESET_MAX_CELLS \(1 << 20\)", header_without_comments())
+
+
+RETURNS = {"int": C.c_int, "size_t": C.c_size_t}
+SCALARS = {"int": C.c_int}
+
+
+def test_the_tileset_table_is_the_headers_prototypes(par, tileset):
+    protos = re.findall(r"^(size_t|int)\s+(par_[a-z_0-9]+)\(([^;]*?)\);", header_without_comments(), flags=re.M | re.S)
+    assert len(protos) == 5 == len(tileset.ABI_TILESET)
+    assert [name for _, name, _ in protos] == list(tileset.ABI_TILESET)  # the header's order
+    L = tileset.lib()
+    assert L is par.lib()
+    for ret, name, params in protos:
+        want = []
+        for p in (" ".join(p.split()) for p in params.split(",")):
+            if "*" in p:
+                want.append(C.c_void_p)
+            else:
+                kind, _ = p.rsplit(" ", 1)  # "<type> <name>"
+                assert kind in SCALARS, f"{name}: no ctypes type decided for a parameter `{p}`"
+                want.append(SCALARS[kind])
+        entry = tileset.ABI_TILESET[name]
+        if ret == "int":
+            assert not isinstance(entry, tuple), f"{name}: the default restype is not written out"
+        else:
+            assert isinstance(entry, tuple) and entry[0] is RETURNS[ret], f"{name}: (restype, argument types)"
+            entry = entry[1]
+        assert list(entry) == want, name
+        fn = getattr(L, name)
+        assert list(fn.argtypes) == want and fn.restype is RETURNS[ret], name
+
+
+def test_the_prototypes_are_the_contracts():
+    header = " ".join(header_without_comments().split())
+    for proto in (
+            "size_t par_tileset_work_bytes(int n_cells);",
+            "int par_tileset_build_device(const par_params* params, void* stream, const uint8_t* index, int row_begin, "
+            "int row_end, int tile_w, int tile_h, int pad, int flips, void* work, uint8_t* tiles_out, int capacity, "
+            "uint32_t* map_out, uint32_t* count_out);",
+            "int par_tileset_expand_device(const par_params* params, void* stream, const uint8_t* tiles, int n_tiles, "
+            "int tile_w, int tile_h, const uint32_t* map, int row_begin, int row_end, uint8_t* index_out);",
+            "int par_tileset_build_host(const par_params* params, int device, const uint8_t* index, int row_begin, "
+            "int row_end, int tile_w, int tile_h, int pad, int flips, uint8_t* tiles_out, int capacity, uint32_t* map_out, "
+            "int* count_out);",
+            "int par_tileset_expand_host(const par_params* params, int device, const uint8_t* tiles, int n_tiles, int tile_w, "
+            "int tile_h, const uint32_t* map, int row_begin, int row_end, uint8_t* index_out);"):
+        assert proto in header, proto
+
+
+def test_the_header_is_plain_c(tmp_path):
+    """par_tileset.h alone, and beside par_raytracer.h and par_cells.h in every order, as pedantic C11; a C program links
+    the host arithmetic and gets an argument error."""
+    lib_dir = os.path.join(ROOT, "pixel-art-raytracer_amd", "lib")
+    names = ("par_tileset.h", "par_raytracer.h", "par_cells.h")
+    bodies = {"alone": '#include "par_tileset.h"\n', "twice": '#include "par_tileset.h"\n#include "par_tileset.h"\n'}
+    for k, order in enumerate(itertools.permutations(names)):
+        bodies[f"order{k}"] = "".join(f'#include "{n}"\n' for n in order)
+    assert len(bodies) == 8
+    for tag, includes in bodies.items():
+        src = tmp_path / f"{tag}.c"
+        src.write_text(includes + r'''
+#include <stdio.h>
+int main(void) {
+    uint8_t plane[64] = {0};
+    uint32_t map[1];
+    int count = -5;
+    printf("%lu %lu %d\n", (unsigned long)par_tileset_work_bytes(3), (unsigned long)par_tileset_work_bytes(0),
+           PAR_TILESET_MAX_CELLS);
+    return par_tileset_build_host(0, -1, plane, 0, 8, 8, 8, 0, 3, 0, 0, map, &count) == 1 && count == -5 ? 0 : 1;
+}
+''')
+        exe = tmp_path / tag
+        p = subprocess.run(["gcc", "-std=c11", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"),
+                            str(src), "-o", str(exe), "-L", lib_dir, "-lpar_raytracer", f"-Wl,-rpath,{lib_dir}"],
+                           capture_output=True, text=True)
+        assert p.returncode == 0, (tag, p.stderr)
+        out = subprocess.run([str(exe)], capture_output=True, text=True)
+        assert out.returncode == 0 and out.stdout.split() == [str(4096 + 48 + 32), "0", str(1 << 20)], (tag, out.stdout)
+
+
+# ---- par_tileset_work_bytes --------------------------------------------------------------------------------------------
+
+def test_work_bytes_is_the_headers_formula(tileset):
+    def formula(n):
+        p = 1
+        while p < 2 * n:
+            p *= 2
+        return 4096 + 16 * n + 4 * p
+
+    for n in (1, 2, 3, 4, 5, 15, 16, 17, 1000, 1023, 1024, 1025, 2400, 33024, (1 << 19) + 1, (1 << 20) - 1, 1 << 20):
+        got = tileset.tileset_work_bytes(n)
+        assert got == formula(n), n
+        assert got <= 4096 + 32 * n and (got - 4096 - 16 * n) // 4 >= 2 * n, n
+        assert got % 8 == 0
+    assert tileset.tileset_work_bytes(1 << 20) == 4096 + 24 * (1 << 20)
+    for n in (0, -1, -(1 << 31), (1 << 20) + 1, (1 << 31) - 1):
+        assert tileset.tileset_work_bytes(n) == 0, n
+    assert tileset.lib().par_tileset_work_bytes.restype is C.c_size_t
+
+
+# ---- argument errors: no device needed, nothing written -----------------------------------------------------------
+
+W, H = 24, 40
+BAD_GEOMETRY = [
+    ("null params", dict(params=None)),
+    ("tile_w 4", dict(tile=(4, 8))),
+    ("tile_w 12", dict(tile=(12, 8))),
+    ("tile_w 32", dict(tile=(32, 8))),
+    ("tile_w 0", dict(tile=(0, 8))),
+    ("tile_h 4", dict(tile=(8, 4))),
+    ("tile_h 32", dict(tile=(8, 32))),
+    ("tile_h 0", dict(tile=(8, 0))),
+    ("tile_h negative", dict(tile=(8, -8))),
+    ("width 0", dict(width=0)),
+    ("width negative", dict(width=-8)),
+    ("row_begin negative", dict(rows=(-8, 8))),
+    ("row_begin == row_end", dict(rows=(8, 8))),
+    ("row_begin > row_end", dict(rows=(16, 8))),
+    ("row_end > height", dict(rows=(0, 48))),
+    ("tile_h 8: row_begin inside a cell", dict(rows=(4, 16))),
+    ("tile_h 8: row_end inside a cell", dict(rows=(8, 12))),
+    ("tile_h 16: row_begin inside a cell", dict(rows=(8, 32), tile=(8, 16))),
+    ("tile_h 16: row_end inside a cell", dict(rows=(16, 24), tile=(8, 16))),
+    ("tile_h 8: row_end inside the last cell", dict(rows=(32, 36), height=37)),
+    ("one cell more than 2^20", dict(width=8 * 1025, height=8 * 1024, rows=(0, 8 * 1024))),
+    ("far more cells than 2^20", dict(width=(1 << 31) - 1, height=(1 << 31) - 1, rows=(0, (1 << 31) - 1))),
+]
+BAD_BUILD = BAD_GEOMETRY + [
+    ("null index", dict(index=None)),
+    ("null count_out", dict(count=None)),
+    ("null tiles_out with capacity 1", dict(tiles=None, capacity=1)),
+    ("capacity -1", dict(capacity=-1)),
+    ("capacity -1 and null tiles_out", dict(tiles=None, capacity=-1)),
+    ("pad -1", dict(pad=-1)),
+    ("pad 256", dict(pad=256)),
+    ("flips -1", dict(flips=-1)),
+    ("flips 4", dict(flips=4)),
+]
+BAD_BUILD_DEVICE = BAD_BUILD + [("null work", dict(work=None)), ("work off its 8 bytes", dict(work_shift=4))]
+BAD_EXPAND = BAD_GEOMETRY + [
+    ("null tiles", dict(tiles=None)),
+    ("null map", dict(map=None)),
+    ("null index_out", dict(index=None)),
+    ("n_tiles 0", dict(n_tiles=0)),
+    ("n_tiles negative", dict(n_tiles=-3)),
+]
+
+
+def raw_call(tileset, T, which, over):
+    """One call of the raw symbol on host dummies: (status, whether any buffer changed)."""
+    L = tileset.lib()
+    params = T.default_params(W, over.get("height", H))
+    params.width = over.get("width", W)
+    n = W * H
+    bufs = {"index": np.full(n, 0xA5, np.uint8), "tiles": np.full(n, 0xC3, np.uint8), "map": np.full(n, 0x3C3C3C3C, np.uint32),
+            "count": np.full(2, 0x69696969, np.uint32), "work": np.full(4096 + 32 * n, 0x5A, np.uint8)}
+    before = {k: v.copy() for k, v in bufs.items()}
+    arg = dict(params=params, tile=(8, 8), rows=(0, params.height), pad=0, flips=3, capacity=4, n_tiles=4, **bufs)
+    arg.update({k: v for k, v in over.items() if k not in ("width", "height", "work_shift")})
+    p = None if arg["params"] is None else C.byref(arg["params"])
+    ptr = T.ptr
+    work = ptr(arg["work"])
+    if "work_shift" in over:
+        work = C.c_void_p(arg["work"].ctypes.data + over["work_shift"])
+    (tw, th), (r0, r1) = arg["tile"], arg["rows"]
+    if which == "build_device":
+        rc = L.par_tileset_build_device(p, None, ptr(arg["index"]), r0, r1, tw, th, arg["pad"], arg["flips"], work,
+                                        ptr(arg["tiles"]), arg["capacity"], ptr(arg["map"]), ptr(arg["count"]))
+    elif which == "build_host":
+        rc = L.par_tileset_build_host(p, -1, ptr(arg["index"]), r0, r1, tw, th, arg["pad"], arg["flips"], ptr(arg["tiles"]),
+                                      arg["capacity"], ptr(arg["map"]), ptr(arg["count"]))
+    elif which == "expand_device":
+        rc = L.par_tileset_expand_device(p, None, ptr(arg["tiles"]), arg["n_tiles"], tw, th, ptr(arg["map"]), r0, r1,
+                                         ptr(arg["index"]))
+    else:
+        rc = L.par_tileset_expand_host(p, -1, ptr(arg["tiles"]), arg["n_tiles"], tw, th, ptr(arg["map"]), r0, r1,
+                                       ptr(arg["index"]))
+    return rc, any(bufs[k].tobytes() != before[k].tobytes() for k in bufs)
+
+
+@pytest.mark.parametrize("which,bad", [("build_device", BAD_BUILD_DEVICE), ("build_host", BAD_BUILD),
+                                       ("expand_device", BAD_EXPAND), ("expand_host", BAD_EXPAND)])
+def test_invalid_arguments_need_no_device_and_write_nothing(tileset, T, which, bad):
+    assert len({tag for tag, _ in bad}) == len(bad)
+    for tag, over in bad:
+        rc, changed = raw_call(tileset, T, which, over)
+        assert rc == ERR_INVALID_ARG, f"{which}: {tag}: status {rc}"
+        assert not changed, f"{which}: {tag}: something was written"
+
+
+def test_what_the_rules_admit_is_not_refused(par, tileset, T):
+    """The host forms on the arguments next to the refused ones (the device forms would take host dummies for device
+    memory): any status but PAR_ERR_INVALID_ARG, which without a GPU is PAR_ERR_NO_DEVICE."""
+    want = 0 if par.device_count() > 0 else 2
+    for over in (dict(rows=(8, 16)), dict(rows=(16, 32), tile=(8, 16)), dict(rows=(32, 37), tile=(16, 16), height=37),
+                 dict(rows=(32, 37), height=37), dict(pad=255), dict(flips=0), dict(capacity=0), dict(capacity=0, tiles=None),
+                 dict(map=None), dict(tile=(16, 8))):
+        rc, _ = raw_call(tileset, T, "build_host", over)
+        assert rc == want, (over, rc)
+    for over in (dict(rows=(8, 16)), dict(rows=(32, 37), height=37), dict(n_tiles=1), dict(tile=(16, 16))):
+        rc, _ = raw_call(tileset, T, "expand_host", over)
+        assert rc == want, (over, rc)
+
+
+def test_binding_raises_and_checks_its_arrays(par, T, tileset):
+    params = T.default_params(16, 16)
+    with pytest.raises(par.ParError) as e:
+        tileset.tileset_build(params, 0, (0, 16), (8, 8), 0x1000, 0x2000)
+    assert e.value.status == ERR_INVALID_ARG and str(e.value) == "PAR_ERR_INVALID_ARG: par_tileset_build_device"
+    with pytest.raises(par.ParError) as e:
+        tileset.tileset_expand(params, 0x1000, 0, (8, 8), 0x2000, (0, 16), 0x3000)
+    assert e.value.status == ERR_INVALID_ARG and str(e.value) == "PAR_ERR_INVALID_ARG: par_tileset_expand_device"
+    plane = np.zeros(256, np.uint8)
+    with pytest.raises(par.ParError) as e:
+        tileset.tileset_build_host(params, plane, (8, 12))
+    assert e.value.status == ERR_INVALID_ARG
+    with pytest.raises(ValueError, match="tileset_build_host: "):
+        tileset.tileset_build_host(params, plane[:-1], (8, 8))
+    with pytest.raises(ValueError, match="tileset_expand_host: "):
+        tileset.tileset_expand_host(params, np.zeros(65, np.uint8), (8, 8), np.zeros(4, np.uint32))
+    with pytest.raises(ValueError, match="tileset_expand_host: "):
+        tileset.tileset_expand_host(params, np.zeros(64, np.uint8), (8, 8), np.zeros(3, np.uint32))
+    for bad in ("s", 1.5, np.int64(0x1000)):
+        with pytest.raises(TypeError):
+            tileset.tileset_build(params, bad, (0, 16), (8, 8), 0x1000, 0x2000)
+        with pytest.raises(TypeError):
+            tileset.tileset_expand(params, 0x1000, 1, (8, 8), 0x2000, (0, 16), 0x3000, stream=bad)
+
+
+def test_arguments_reach_the_library_in_the_headers_order(par, T, tileset, monkeypatch):
+    from test_binding_cpu import A, StandIn
+    stand_in = StandIn(returns={"par_tileset_work_bytes": 777}, writes={"par_tileset_build_host": {12: 2}})
+    monkeypatch.setattr(par, "lib", lambda: stand_in)
+    P = T.default_params(140, 40)
+    assert tileset.tileset_work_bytes(90) == 777
+    assert stand_in.calls.pop() == ("par_tileset_work_bytes", [90])
+    tileset.tileset_build(P, 0x1000, (16, 32), (8, 16), 0x2000, 0x3000, tiles_out=0x4000, capacity=9, map_out=0x5000, pad=7,
+                          flips=2, stream=0x6000)
+    assert stand_in.calls.pop() == ("par_tileset_build_device", [A(P), 0x6000, 0x1000, 16, 32, 8, 16, 7, 2, 0x2000, 0x4000, 9,
+                                                                 0x5000, 0x3000])
+    tileset.tileset_build(P, 0x1000, (0, 40), (16, 8), 0x2000, 0x3000)
+    assert stand_in.calls.pop() == ("par_tileset_build_device", [A(P), None, 0x1000, 0, 40, 16, 8, 0, 0, 0x2000, None, 0, None,
+                                                                 0x3000])
+    tileset.tileset_expand(P, 0x1000, 5, (8, 16), 0x2000, (16, 32), 0x3000, stream=0x6000)
+    assert stand_in.calls.pop() == ("par_tileset_expand_device", [A(P), 0x6000, 0x1000, 5, 8, 16, 0x2000, 16, 32, 0x3000])
+    plane = np.zeros(16 * 140, dtype=np.uint8)
+    out = tileset.tileset_build_host(P, plane, (8, 16), rows=(16, 32), pad=7, flips=2, device=2)
+    assert list(out) == ["tiles", "map", "count"] and out["count"] == 2
+    assert out["tiles"].shape == (2, 16, 8) and out["map"].shape == (18,) and out["map"].dtype == np.uint32
+    name, args = stand_in.calls.pop()
+    assert name == "par_tileset_build_host"
+    assert args[:9] == [A(P), 2, A(plane), 16, 32, 8, 16, 7, 2] and args[9] == A(out["tiles"].base) and args[10] == 18
+    assert args[11] == A(out["map"])
+    out = tileset.tileset_build_host(P, np.zeros(40 * 140, dtype=np.uint8), (16, 16), capacity=0)
+    name, args = stand_in.calls.pop()
+    assert args[9] is None and args[10] == 0 and args[1] == -1 and args[3:5] == [0, 40] and out["tiles"].shape == (0, 16, 16)
+    tiles, tile_map = np.zeros(3 * 128, dtype=np.uint8), np.zeros(18, dtype=np.uint32)
+    back = tileset.tileset_expand_host(P, tiles, (8, 16), tile_map, rows=(16, 32), device=1)
+    assert back.shape == (16 * 140,) and back.dtype == np.uint8
+    assert stand_in.calls.pop() == ("par_tileset_expand_host", [A(P), 1, A(tiles), 3, 8, 16, A(tile_map), 16, 32, A(back)])
+    stand_in.status = 6
+    with pytest.raises(par.ParError) as e:
+        tileset.tileset_expand(P, 0x1000, 5, (8, 16), 0x2000, (16, 32), 0x3000)
+    assert e.value.status == 6 and str(e.value) == "PAR_ERR_EXTENT: par_tileset_expand_device"
+
+
+# ---- the model the GPU tests compare with --------------------------------------------------------------------------
+
+def same(a, b, tag):
+    for name, x, y in zip(("tiles", "map"), a, b):
+        assert x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes(), f"{tag}: {name}"
+    assert a[2] == b[2], f"{tag}: T"
+
+
+@pytest.mark.parametrize("tile", TS.TILES)
+def test_model_equals_the_loop_on_random_planes(tile):
+    """21 x 19 (ragged in both directions), 64 x 40, 9 x 9 (edge cells one pixel wide and high), 1 x 1; 2, 4 and 256
+    colours; every flips; pad a colour present and not; whole and clipped capacities."""
+    mirrored = 0
+    for w, h in ((21, 19), (64, 40), (9, 9), (1, 1), (37, 23)):
+        for colours in (2, 4, 256):
+            rng = np.random.default_rng(1000 * w + colours + tile[0] + 2 * tile[1])
+            plane = rng.integers(0, colours, w * h).astype(np.uint8) if colours == 256 else TS.mixed_plane(rng, w, h, tile, 3, colours)
+            for flips in range(4):
+                for pad in (0, 255):
+                    got = TS.model(plane, w, h, tile, pad, flips)
+                    same(got, TS.model_loop(plane, w, h, tile, pad, flips), f"{w}x{h} {tile} {colours} flips {flips} pad {pad}")
+                    gcx, gcy = TS.grid(w, h, tile)
+                    assert len(got[1]) == gcx * gcy and got[0].shape == (got[2], tile[1], tile[0])
+                    assert ((got[1] >> 30) & ~np.uint32(flips) == 0).all(), "only allowed codes"
+                    mirrored += int((got[1] >> 30).any())
+                    for capacity in (0, 1, got[2] + 2):
+                        clipped = TS.model(plane, w, h, tile, pad, flips, capacity)
+                        same(clipped, TS.model_loop(plane, w, h, tile, pad, flips, capacity), f"capacity {capacity}")
+                        assert clipped[0].tobytes() == got[0][:capacity].tobytes() and clipped[1].tobytes() == got[1].tobytes()
+    assert mirrored > 30
+
+
+def cell_plane(cells, gcx, tile):
+    """Whole cells (n, th, tw) laid out gcx a cell row."""
+    n = len(cells)
+    return np.ascontiguousarray(np.asarray(cells, np.uint8).reshape(n // gcx, gcx, tile[1], tile[0]).transpose(0, 2, 1, 3)).reshape(-1)
+
+
+def entries(*pairs):
+    return np.array([i | (f << 30) for i, f in pairs], dtype=np.uint32)
+
+
+def crafted():
+    """name -> (plane, w, rows, tile, pad, flips, (tiles or None, map, T)) worked out by hand."""
+    out = {}
+    tile = (8, 8)
+    # an asymmetric cell t: 1 in its top left corner, 2 right of it, 3 below it. Its x mirror has the 1 at (0, 7), its y
+    # mirror at (7, 0), its xy mirror at (7, 7). As strings: the xy mirror is all 0 until its last row, whose last three
+    # bytes are 0 3 | ... 2 1; it is the smallest. Then y (last row 1 2 0 ..., row 6 begins 3), then x, then t.
+    t = np.zeros((8, 8), np.uint8)
+    t[0, 0], t[0, 1], t[1, 0] = 1, 2, 3
+    four = [t, t[:, ::-1], t[::-1], t[::-1, ::-1]]
+    plane = cell_plane(four, 4, tile)
+    xy = t[::-1, ::-1]
+    # no flips: four tiles in their order of appearance
+    out["four mirrors, flips 0"] = (plane, 32, 8, tile, 0, 0, (np.stack(four), entries((0, 0), (1, 0), (2, 0), (3, 0)), 4))
+    # x alone: {t, tx} and {ty, txy} pair up. Of t and tx the smaller is tx (row 0 of t begins 1, of tx 0): cell 0 is tx
+    # under code 1 and cell 1 under code 0; of ty and txy the smaller is txy.
+    out["four mirrors, flips 1"] = (plane, 32, 8, tile, 0, 1,
+                                    (np.stack([t[:, ::-1], xy]), entries((0, 1), (0, 0), (1, 1), (1, 0)), 2))
+    # y alone: {t, ty} and {tx, txy}; ty < t and txy < tx
+    out["four mirrors, flips 2"] = (plane, 32, 8, tile, 0, 2,
+                                    (np.stack([t[::-1], xy]), entries((0, 2), (1, 2), (0, 0), (1, 0)), 2))
+    # both: one tile, txy, which cell 0 is under code 3, cell 1 under 2, cell 2 under 1 and cell 3 under 0
+    out["four mirrors, flips 3"] = (plane, 32, 8, tile, 0, 3, (xy[None], entries((0, 3), (0, 2), (0, 1), (0, 0)), 1))
+    # a cell that equals its x mirror (columns 3 and 4 set) and not its y mirror (row 0 only): under flips 3 the images
+    # under 0 and 1 are equal and those under 2 and 3 are equal and smaller (row 0 is 0): the code is 2, not 3. A cell
+    # that equals all its mirrors (the centre 2 x 2 set) takes code 0 under every mask.
+    sx = np.zeros((8, 8), np.uint8)
+    sx[0, 3] = sx[0, 4] = 5
+    sall = np.zeros((8, 8), np.uint8)
+    sall[3:5, 3:5] = 6
+    plane = cell_plane([sx, sall, sx[::-1]], 3, tile)
+    out["symmetric cells take the lowest code"] = (plane, 24, 8, tile, 0, 3,
+                                                   (np.stack([sx[::-1], sall]), entries((0, 2), (1, 0), (0, 0)), 2))
+    out["symmetric cells, x alone"] = (plane, 24, 8, tile, 0, 1,
+                                       (np.stack([sx, sall, sx[::-1]]), entries((0, 0), (1, 0), (2, 0)), 3))
+    # two cells that differ only in their last byte, 16 x 16: two tiles, in their order
+    a = np.full((16, 16), 3, np.uint8)
+    b = a.copy()
+    b[15, 15] = 4
+    out["the last byte"] = (cell_plane([a, b, a], 3, (16, 16)), 48, 16, (16, 16), 0, 0,
+                            (np.stack([a, b]), entries((0, 0), (1, 0), (0, 0)), 2))
+    # a ragged edge, 12 x 8 of colour 9: the second cell has four columns of the plane and four of pad. pad == 9: one
+    # tile. pad == 0 without flips: two tiles. pad == 0 with the x flip: the second cell's canonical form is its mirror
+    # (0 first), still another tile than the first.
+    nine = np.full(12 * 8, 9, np.uint8)
+    full = np.full((8, 8), 9, np.uint8)
+    half = full.copy()
+    half[:, 4:] = 0
+    out["ragged, pad is the colour"] = (nine, 12, 8, tile, 9, 3, (full[None], entries((0, 0), (0, 0)), 1))
+    out["ragged, pad is not"] = (nine, 12, 8, tile, 0, 0, (np.stack([full, half]), entries((0, 0), (1, 0)), 2))
+    out["ragged, pad is not, flipped"] = (nine, 12, 8, tile, 0, 1, (np.stack([full, half[:, ::-1]]), entries((0, 0), (1, 1)), 2))
+    # and ragged below: 8 x 12, the second cell row has four rows of the plane; under the y flip pad comes first
+    tall = np.full(8 * 12, 9, np.uint8)
+    low = full.copy()
+    low[4:] = 0
+    out["ragged below, flipped"] = (tall, 8, 12, tile, 0, 2, (np.stack([full, low[::-1]]), entries((0, 0), (1, 2)), 2))
+    return out
+
+
+CRAFTED = ["four mirrors, flips 0", "four mirrors, flips 1", "four mirrors, flips 2", "four mirrors, flips 3",
+           "symmetric cells take the lowest code", "symmetric cells, x alone", "the last byte", "ragged, pad is the colour",
+           "ragged, pad is not", "ragged, pad is not, flipped", "ragged below, flipped"]
+
+
+@pytest.mark.parametrize("name", CRAFTED)
+def test_crafted_planes(name):
+    cases = crafted()
+    assert sorted(cases) == sorted(CRAFTED)
+    plane, w, rows, tile, pad, flips, (tiles, tile_map, count) = cases[name]
+    got = TS.model(plane, w, rows, tile, pad, flips)
+    same(got, TS.model_loop(plane, w, rows, tile, pad, flips), name)
+    assert got[2] == count and np.array_equal(got[1], tile_map), (name, got[1], tile_map)
+    assert got[0].tobytes() == np.ascontiguousarray(tiles).tobytes(), name
+    assert TS.expand_model(got[0], tile, got[1], w, rows).tobytes() == plane.tobytes()
+
+
+# ---- the consequences ----------------------------------------------------------------------------------------------
+
+def test_one_colour_is_one_tile_or_two():
+    for tile in TS.TILES:
+        for w, h in ((64, 32), (61, 32), (64, 23), (61, 23)):
+            plane = np.full(w * h, 7, np.uint8)
+            ragged = w % tile[0] != 0 or h % tile[1] != 0
+            for flips in range(4):
+                assert TS.model(plane, w, h, tile, 7, flips)[2] == 1
+                got = TS.model(plane, w, h, tile, 0, flips)[2]
+                assert got >= 2 if ragged else got == 1
+            if ragged and (w % tile[0] == 0 or h % tile[1] == 0):
+                assert TS.model(plane, w, h, tile, 0, 0)[2] == 2, "one ragged edge shows pad in one way"
+
+
+def test_more_flips_never_raise_the_count_and_the_order_is_first_appearance():
+    rng = np.random.default_rng(5)
+    for tile in TS.TILES:
+        plane = TS.mixed_plane(rng, 131, 67, tile, 11, colours=2)
+        counts = [TS.model(plane, 131, 67, tile, 0, flips)[2] for flips in range(4)]
+        assert counts[3] <= min(counts[1], counts[2]) and max(counts[1], counts[2]) <= counts[0]
+        assert counts[3] < counts[0]
+        for flips in range(4):
+            ids = TS.model(plane, 131, 67, tile, 0, flips)[1] & TS.ID_MASK
+            seen = np.maximum.accumulate(ids)
+            assert ids[0] == 0 and (np.diff(seen) <= 1).all(), "a new tile takes the next number"
+
+
+def test_a_row_block_is_a_frame_of_its_rows_and_numbers_are_per_call():
+    rng = np.random.default_rng(6)
+    w, h, tile = 37, 43, (8, 8)
+    plane = TS.mixed_plane(rng, w, h, tile, 9, colours=2)
+    whole = TS.model(plane, w, h, tile, 0, 3)
+    gcx = TS.grid(w, h, tile)[0]
+    for r0, r1 in ((0, 16), (16, 32), (32, 43)):
+        assert TS.admits(r0, r1, h, tile)
+        part = TS.model(plane[r0 * w:r1 * w], w, r1 - r0, tile, 0, 3)
+        rows_of_whole = whole[1][r0 // 8 * gcx:-(-r1 // 8) * gcx]
+        assert np.array_equal(part[1] >> 30, rows_of_whole >> 30), "the flips are the cell's own"
+        # the same classes, numbered from 0 within the call
+        a, b = part[1] & TS.ID_MASK, rows_of_whole & TS.ID_MASK
+        assert a[0] == 0 and len(set(zip(a.tolist(), b.tolist()))) == len(set(a.tolist())) == len(set(b.tolist()))
+        assert TS.expand_model(part[0], tile, part[1], w, r1 - r0).tobytes() == plane[r0 * w:r1 * w].tobytes()
+    assert not TS.admits(4, 16, h, tile) and not TS.admits(8, 12, h, tile) and TS.admits(40, 43, h, tile)
+
+
+def test_expand_inverts_build_and_clamps():
+    rng = np.random.default_rng(7)
+    for tile in TS.TILES:
+        plane = TS.mixed_plane(rng, 61, 23, tile, 6, colours=3)
+        for flips in range(4):
+            tiles, tile_map, count = TS.model(plane, 61, 23, tile, 4, flips)
+            assert TS.expand_model(tiles, tile, tile_map, 61, 23).tobytes() == plane.tobytes()
+            wild = tile_map | np.uint32(TS.ID_MASK)
+            last = TS.expand_model(tiles, tile, wild, 61, 23)
+            only = TS.expand_model(tiles[count - 1:], tile, tile_map & np.uint32(~TS.ID_MASK & 0xFFFFFFFF), 61, 23)
+            assert last.tobytes() == only.tobytes(), "an id past the last tile takes the last"
+
+
+# ---- the figures DESIGN and README quote -----------------------------------------------------------------------------
+
+def test_the_graybox_frames_tile_counts(par, oracle, T):
+    """The frame of test_gpu_quantize.py::test_in_a_frame_loop (480 x 320, the graybox scene under two tinted ranged
+    lights), composed by the oracle, through its fitted 33-entry palette (palette.fit, quantize.model at spread 0). A
+    scratch run of the models gave, of 2400 cells of 8 x 8, 519 tiles without flips and 402 with both, and of 600 cells of
+    16 x 16, 337 and 305: the frame fits no 256-tile budget, which is the answer the call exists to give."""
+    import palette as P
+    import quantize as Q
+    from test_gpu_light_range import scene
+    from test_gpu_light_tints import COLOUR, TINTS, expected
+    sc = scene("graybox", par, oracle, T)
+    _, exp, _ = expected(T, sc, [3, 6], [200, 300], TINTS[:2], COLOUR, "graybox, two tinted ranged lights")
+    fb = exp["fb"]
+    assert (sc.params.width, sc.params.height) == (480, 320)
+    fitted, n_entries, _ = P.fit(T, fb, 33)
+    assert n_entries == 33
+    index = Q.model(sc.params, fitted, fb, None, 0)[0]
+    got = {}
+    for tile in ((8, 8), (16, 16)):
+        for flips in (0, 3):
+            tiles, tile_map, count = TS.model(index, 480, 320, tile, 0, flips)
+            got[(tile[0], flips)] = (count, len(tile_map), int((tile_map >> 30 != 0).sum()))
+            assert TS.expand_model(tiles, tile, tile_map, 480, 320).tobytes() == index.tobytes()
+    print(got)
+    assert got == {(8, 0): (519, 2400, 0), (8, 3): (402, 2400, 1305), (16, 0): (337, 600, 0), (16, 3): (305, 600, 414)}
