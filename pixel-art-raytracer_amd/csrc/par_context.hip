@@ -102,7 +102,7 @@ struct par_context {
 enum : unsigned {
     PAR_HOOK_FORCE_GENERIC = 1u << 0,  // every column through render_overflow_kernel (par_render_args::dense)
     PAR_HOOK_TWO_LAUNCHES = 1u << 1,   // the hash build always takes two launches
-    PAR_HOOK_RECORD_ITEMS = 1u << 2,   // columns emit no self-contained work items (PAR_FLAG_RECORD_ITEMS)
+    PAR_HOOK_RECORD_ITEMS = 1u << 2,   // columns emit no self-contained and no alone work items (PAR_FLAG_RECORD_ITEMS)
     PAR_HOOK_LOSE_BUILD_WG = 1u << 3,  // build workgroup 0 never arrives at the one-launch build's barrier
     PAR_HOOK_BAD_ALLOC = 1u << 4,      // the guarded host-allocating bodies fail as an exhausted heap would
     PAR_HOOK_LIGHTS_PATH = 1u << 5,    // a one-light frame takes the path of several lights (render_lights_kernel)
@@ -1346,6 +1346,35 @@ int par_debug_read_light_walks(par_context* ctx, int64_t* out) {
     if (hipMemcpy(v, ctx->d_ray_counter + 1, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return PAR_ERR_HIP;
     out[0] = (int64_t)v[0];
     out[1] = (int64_t)v[1];
+    return PAR_OK;
+}
+
+// Internal test aid (not part of the public header either): the work items of the last frame's entry passes (list 0 of
+// par_grid_dev::items, what render_items_kernel and the entry share of render_both_kernel consume), shard after shard,
+// as the column launch left them: eight 32-bit words per item (par_item). *n_items gets their number; the first
+// `capacity` of them are copied to `out` (which may be null when capacity is 0).
+int par_debug_read_items(par_context* ctx, uint32_t* out, size_t capacity, int* n_items) {
+    if (!ctx || !n_items || (capacity && !out)) return PAR_ERR_INVALID_ARG;
+    *n_items = 0;
+    if (!ctx->grid.items || !ctx->grid.item_counters) return PAR_ERR_NOT_READY;
+    if (hipSetDevice(ctx->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return PAR_ERR_HIP;
+    std::vector<int32_t> counters((size_t)PAR_ITEM_SHARDS * PAR_ITEM_COUNTER_STRIDE);
+    if (hipMemcpy(counters.data(), ctx->grid.item_counters, counters.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) {
+        return PAR_ERR_HIP;
+    }
+    size_t done = 0;
+    for (int s = 0; s < PAR_ITEM_SHARDS; s++) {
+        const int32_t c = counters[(size_t)s * PAR_ITEM_COUNTER_STRIDE];
+        const size_t n = (size_t)std::min(std::max(c, 0), ctx->grid.item_capacity);
+        const size_t take = std::min(n, capacity - std::min(capacity, done));
+        if (take && hipMemcpy(out + done * (sizeof(par_item) / sizeof(uint32_t)),
+                              ctx->grid.items + (size_t)s * ctx->grid.item_capacity, take * sizeof(par_item),
+                              hipMemcpyDeviceToHost) != hipSuccess) {
+            return PAR_ERR_HIP;
+        }
+        done += n;
+    }
+    *n_items = (int)done;
     return PAR_OK;
 }
 

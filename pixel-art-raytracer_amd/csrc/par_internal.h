@@ -161,7 +161,7 @@ constexpr uint32_t PAR_DEBUG_FLAGS = PAR_RENDER_COUNT_RAYS | (1u << 29);
 // Every flag a caller may pass: the public ones and the time stamps. Anything else is rejected (PAR_ERR_INVALID_ARG).
 constexpr uint32_t PAR_ACCEPTED_FLAGS = 0xFu | (1u << 29);
 // Set by the library alone, never by a caller (the record-items-only test hook, par_debug_set_hooks): columns emit
-// no self-contained (simple) work items, every column is rendered from its record.
+// no self-contained (simple) and no alone work items, every column is rendered from its record by the general pass.
 constexpr uint32_t PAR_FLAG_RECORD_ITEMS = 1u << 22;
 constexpr int PAR_WAVE_NW = 4;          // wavefronts per render workgroup
 // Render work items: columns_kernel lists every 64-pixel chunk of every column with a record as one item (par_item);
@@ -176,16 +176,29 @@ constexpr int PAR_ITEM_SHARDS = 1 << PAR_ITEM_SHARD_BITS;
 constexpr int PAR_ITEM_COUNTER_STRIDE = 32;  // int32 words between two shard counters: one 128-byte line each
 constexpr uint32_t PAR_ITEM_TILE = 0xFFFFu;
 constexpr uint32_t PAR_ITEM_NONE = 0xFFFFFFFFu;  // a reserved item slot whose column went to the overflow list
+// An ALONE item (PAR_ITEM_ALONE): the pass's entry is no repeat, the frame has no sprite-id table, the column is not
+// visited as a tile, and no other entry of the column that is no repeat has a rectangle that meets the entry's (both
+// clipped to the bin's footprint, whatever rows the frame renders). Every pixel of the item is then the entry's, at
+// the depth of the entry's own texel: the render wavefront runs no primary pass (render_item_alone), and the item
+// carries what that pass would have derived. Its `visit` and `bins` words are laid out for that:
+//   visit = chunk | first occupied bin << 16 | occupied bins << 26   (the bin of a simple column, else not read)
+//   bins  = dx | dy << 8 | rw << 16 | rh << 24: the rectangle visited (the entry's, clipped to the tile and the rows
+//           rendered), its corner relative to the bin's footprint (bx * B, by * B); every field is at most PAR_MAX_BIN
+// The item stays one 32-byte scalar load, as every item.
 struct par_item {
     uint32_t ci;        // index of the column (list and record), or PAR_ITEM_NONE
-    uint32_t visit;     // (pass << 16) | chunk of the pass
-    uint32_t where;     // bx | by << 10 | PAR_ITEM_SIMPLE
-    uint32_t bins;      // simple columns: first | last << 16 of the (contiguous) occupied bins; tile items: the
-                        // number of consecutive 64-pixel chunks the item covers, from chunk `visit & 0xFFFF` on
+    uint32_t visit;     // (pass << 16) | chunk of the pass; an alone item: see above (no pass: bins instead)
+    uint32_t where;     // bx | by << 10 | PAR_ITEM_ALONE | PAR_ITEM_SIMPLE
+    uint32_t bins;      // an alone item: the rectangle visited, see above. Else, simple columns: first | last << 16 of
+                        // the (contiguous) occupied bins (in a frame without a sprite-id table every simple column's
+                        // items are alone, so this form is read only with a table); tile items: the number of
+                        // consecutive 64-pixel chunks the item covers, from chunk `visit & 0xFFFF` on
     par_slot entry;     // the pass's entry (entry passes)
 };
 static_assert(sizeof(par_item) == 32, "work item layout");
 constexpr uint32_t PAR_ITEM_SIMPLE = 1u << 31;
+constexpr uint32_t PAR_ITEM_ALONE = 1u << 30;
+static_assert(PAR_MAX_GRID_DIM <= 1024 && PAR_COL_NB < 64 && PAR_MAX_BIN < 256, "the fields of an alone item");
 struct par_grid_dev {
     int32_t gx, gy, gz, volume;
     int32_t* head[2];         // [volume] node index + 1 of the most recent insertion, 0 = none

@@ -804,6 +804,25 @@ __device__ __forceinline__ void columns_wave(const par_grid_dev& g, const par_re
     const int list_shard = tile_mode * PAR_ITEM_SHARDS + shard;
     int item_base = 0;
     if (lane == 0 && n_items > 0) item_base = atomicAdd(&g.item_counters[list_shard * PAR_ITEM_COUNTER_STRIDE], n_items);
+    // Which entries are ALONE (par_item): lane e holds entry e's rectangle clipped to the bin's footprint; the
+    // rectangles of the entries that show and are no repeats pass by, one after the other, through scalar registers.
+    // (Clipped to the footprint and not to the rows rendered: conservative, and the same for every row range.)
+    bool alone = false;
+    if (role == 0 && !overflow && !tile_mode && !a.sprite_ids && !(a.flags & PAR_FLAG_RECORD_ITEMS)) {
+        int x0 = 0, x1 = 0, y0 = 0, y1 = 0;
+        if (lane < n_entries && !dup) {
+            const par_slot r = sm.entries[lane];
+            const int fx = bx * a.B, fy = by * a.B;
+            x0 = max((int)r.px, fx); x1 = min(r.px + r.ex, fx + a.B);
+            y0 = max(a.H - (r.py + r.ey + r.pz + r.ez), fy); y1 = min(a.H - (r.py + r.pz), fy + a.B);
+        }
+        alone = x1 > x0 && y1 > y0;
+        for (uint64_t m = __ballot(alone); m; m &= m - 1) {
+            const int f = __builtin_ctzll(m);
+            const int fx0 = wave_bcast(x0, f), fx1 = wave_bcast(x1, f), fy0 = wave_bcast(y0, f), fy1 = wave_bcast(y1, f);
+            if (lane != f && fx0 < x1 && fx1 > x0 && fy0 < y1 && fy1 > y0) alone = false;
+        }
+    }
 
     // ---- B: the shadow walks of this wavefront's share of the occupied bins, one after the other ---------------
     // The walk area of the record is handed out walk by walk: a team reserves from a counter in LDS (its wavefronts'
@@ -889,8 +908,17 @@ __device__ __forceinline__ void columns_wave(const par_grid_dev& g, const par_re
             }
         } else {
             if (my_chunks > 0) it.entry = sm.entries[lane];
+            uint32_t visit_hi = (uint32_t)lane;
+            if (my_chunks > 0 && alone) {  // the rectangle visited, as render_item works it out
+                const par_slot r = it.entry;
+                const int rx0 = max((int)r.px, c0), rw = min(r.px + r.ex, c0 + tw) - rx0;
+                const int ry0 = max(a.H - (r.py + r.ey + r.pz + r.ez), rows_lo), rh = min(a.H - (r.py + r.pz), rows_hi) - ry0;
+                it.where |= PAR_ITEM_ALONE;
+                it.bins = (uint32_t)(rx0 - c0) | ((uint32_t)(ry0 - by * a.B) << 8) | ((uint32_t)rw << 16) | ((uint32_t)rh << 24);
+                visit_hi = (uint32_t)bz_first | ((uint32_t)n_nb << 10);
+            }
             for (int k = 0; k < my_chunks; k++) {
-                it.visit = ((uint32_t)lane << 16) | (uint32_t)k;
+                it.visit = (visit_hi << 16) | (uint32_t)k;
                 if (item_base + first_item + k < g.item_capacity) dst[first_item + k] = it;
             }
         }
@@ -1249,11 +1277,9 @@ __global__ __launch_bounds__(256) void fill_generic_kernel(par_render_args a, ui
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// render_chunk: one pixel per lane, for up to 64 pixels of one column (wavefront level: no workgroup cooperation;
-// must be called by whole wavefronts). `rec_` is the column's record; `own` >= 0: the lanes render the pixels entry
-// `own` is the first to cover, -1: all pixels. `generic`: the column has no usable record (it overflowed one):
-// the primary pass then reads the column's bins straight from the hash, as the reference does, and every shadow
-// walk is done here.
+// Rendering a chunk: one pixel per lane, for up to 64 pixels of one column (wavefront level: no workgroup
+// cooperation; must be called by whole wavefronts), in two halves: the primary pass (primary_chunk, or none for an
+// alone item) and the shading (shade_chunk). `rec_` is the column's record.
 // ------------------------------------------------------------------------------------------------------------
 struct WaveScratch {  // per wavefront: what wave_walk needs
     par_slot stage[PAR_BIN_WALK];
@@ -1284,26 +1310,179 @@ struct OwnTexel {
     par_texel ti;
 };
 
+// The shading, shadow test, quantise and store of a 64-pixel chunk, alt:704-758: what follows the primary pass,
+// whichever way the pixel's texel was found (primary_chunk's pass over the column's entries, render_item_alone's
+// none). One copy of the arithmetic, in one order, for both. `nb`: lane n holds the column's occupied bin n
+// (ColumnRegs::nb); `pre`: the texel fetched ahead (tex = -1: none), used when it is the pixel's, p_tex.
+// The template flags of this and of the render functions below:
 // DBG: the debug / instrumentation flags of the frame are looked at (time stamps bit 29, ray counting); the production
 // kernels are compiled without them.
 // IDS: the scene may have a sprite-id table (looked at at run time); without one (the render launch knows) every
 // entity uses sprite 0 and the table arithmetic (two 32-bit multiplies per candidate entry) is compiled out.
 // FULL: the parity planes (brightness, lit, G-buffer) may be asked for; a production frame (RGBA + palette index)
 // runs kernels compiled without them (their pointers cost scalar registers the hot loops need).
-template <bool GENERIC, bool DBG, bool IDS = true, bool FULL = true>
-__device__ __forceinline__ void render_chunk(const par_grid_dev& g, const par_render_args& a, const par_colrec& rec_,
-                                             const ColumnRegs& cr, uint64_t dup, const par_frame_dyn& dyn,
-                                             int n_entries, int n_nb, int bx, int by, int own, int col, int row,
-                                             int row_lo, int row_hi, int col_lo, int col_hi, bool valid, int lane,
-                                             WaveScratch* ws,
-                                             const OwnTexel& pre = OwnTexel{-1, 0, 0, par_texel{0.f, 0.f, 0.f, 0u}}) {
+// GENERIC: the column has no usable record: every shadow walk is done here (render_chunk_generic).
+template <bool GENERIC, bool DBG, bool IDS, bool FULL>
+__device__ __forceinline__ void shade_chunk(const par_grid_dev& g, const par_render_args& a, const par_colrec& rec_,
+                                            const uint2& nb, int n_nb, const par_frame_dyn& dyn, int bx, int by, int col,
+                                            int row, bool valid, bool hit, int p_entity, int p_tex, int p_y, int p_z,
+                                            const OwnTexel& pre, int lane, WaveScratch* ws) {
     const int W = a.W, H = a.H;
     const uint32_t fl = DBG ? a.flags : 0u;
     const float ambient = a.ambient;
     const uint32_t bg_rgba = a.background | (a.background << 8) | (a.background << 16);
-    const int32_t* depth0 = a.sprites[0].depth;
     const int pre_tex = pre.tex, pre_pal = pre.pal;
     const par_texel pre_ti = pre.ti;
+    // ---- shading, alt:704-758 ---------------------------------------------------------------------------------
+    float nx = 0.f, ny = 0.f, nz = 0.f;
+    uint32_t rgba = bg_rgba;
+    int pal_index = PAR_PALIDX_BACKGROUND;
+    float bright = ambient;
+    bool lit = true;
+    bool need_walk = false;  // the shadow ray still has to be resolved
+    float inv_x = 0.f, inv_y = 0.f, inv_z = 0.f, b_lit = 0.f;
+    int sy = 0, sz = 0, ox = 0, oy = 0, oz = 0;
+    if (hit) {
+        // normal (alt:349-350) + resolved palette colour (alt:352-354)
+        par_texel ti = pre_ti;
+        pal_index = pre_pal;
+        if (p_tex != pre_tex) {  // another entry won (or nothing was fetched ahead)
+            ti = a.texinfo[p_tex];
+            if (a.out.palidx) {
+                const int sid = IDS ? p_tex / PAR_SPRITE_TEXELS : 0;
+                pal_index = a.sprites[sid].color[p_tex - sid * PAR_SPRITE_TEXELS];
+            }
+        }
+        nx = ti.nx; ny = ti.ny; nz = ti.nz;
+        rgba = ti.rgba;
+        const int wx = col, wy = p_y, wz = p_z;  // alt:707-709
+        const LightDir ld = light_dir(dyn, wx, wy, wz);
+        inv_x = ld.ix; inv_y = ld.iy; inv_z = ld.iz;
+        b_lit = std_min(1.f, diffuse(ld, nx, ny, nz) + ambient);          // alt:758
+        // alt:725-726: the start bin's row is bin(H - wy - wz). wy + wz is world_j whatever the texel's depth (it is
+        // subtracted from y and added to z, alt:356-361), and H - world_j is the pixel's screen row (alt:280; no
+        // view is taller than a `short` holds, par_create): a row of this column's tile, whose bin row is `by`. The
+        // overflow path keeps the division.
+        sy = GENERIC ? div_bin(H - wy - wz, a.magic_b) : by;
+        sz = div_bin(wz, a.magic_b);                                       // alt:727
+        ox = (int)(int16_t)col; oy = (int)(int16_t)p_y; oz = (int)(int16_t)p_z;  // alt:720-722
+        // shadow ray, alt:738-742: columns_kernel has walked from every occupied bin of the column
+        int woff = 0, wcnt = -1;
+        if (!GENERIC) {
+            for (int n = 0; n < n_nb; n++) {
+                const uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane((int)nb.x, n);
+                const uint32_t d1 = (uint32_t)__builtin_amdgcn_readlane((int)nb.y, n);
+                if ((int)(int16_t)(d0 & 0xFFFF) == sz) {
+                    woff = (int)(d1 & 0xFFFF);
+                    wcnt = (int)(int16_t)(d1 >> 16);  // -1: the walk was too long to record
+                }
+            }
+        }
+        if (wcnt >= 0) {
+            // two records (four 16-byte loads) per step: their loads are in flight together
+            const char* walk_base = reinterpret_cast<const char*>(rec_.walk);  // (wave-uniform; 32-bit lane offsets)
+            const float fox = (float)ox, foy = (float)oy, foz = (float)oz;
+            auto test_list = [&](auto finite) {
+                for (int r0 = 0; r0 < wcnt && lit; r0 += 2) {
+                    uint4 wa[2], wb[2];
+#pragma unroll
+                    for (int u = 0; u < 2; u++) {
+                        const uint32_t off = (uint32_t)(woff + min(r0 + u, wcnt - 1)) * (uint32_t)sizeof(par_walkrec);
+                        const uint4* q = reinterpret_cast<const uint4*>(walk_base + off);
+                        wa[u] = q[0];
+                        wb[u] = q[1];
+                    }
+                    // (all four loads are issued before the first record is looked at: the compiler otherwise sinks
+                    // a record's planes below the comparison of its entity, a second round trip)
+                    asm volatile("" ::"v"(wa[0].x), "v"(wa[1].x), "v"(wb[0].x), "v"(wb[1].x));
+#pragma unroll
+                    for (int u = 0; u < 2; u++) {
+                        const v2f rx = {__uint_as_float(wa[u].x), __uint_as_float(wa[u].y)};
+                        const v2f ry = {__uint_as_float(wa[u].z), __uint_as_float(wa[u].w)};
+                        const v2f rz = {__uint_as_float(wb[u].x), __uint_as_float(wb[u].y)};
+                        if (r0 + u < wcnt && (int)wb[u].z != p_entity &&
+                            slab_hit_rec<decltype(finite)::value>(rx, ry, rz, fox, foy, foz, inv_x, inv_y, inv_z)) {  // alt:484-491
+                            lit = false;
+                        }
+                    }
+                }
+            };
+            // (wave-uniform choice: an axis-parallel light direction, 1 / 0, takes the reference's own sequence)
+            if (__all(__builtin_isfinite(inv_x) && __builtin_isfinite(inv_y) && __builtin_isfinite(inv_z))) {
+                test_list(std::true_type{});
+            } else {
+                test_list(std::false_type{});
+            }
+        } else if (GENERIC) {
+            need_walk = true;
+        } else {
+            // a start bin that holds no primitive (negative world z, sprite depths outside the box) has no
+            // precomputed walk: trace_hash_for_light as written, per lane
+            lit = lane_shadow_walk(g, a.count, a.slots, bx, sy, sz, dyn, p_entity, ox, oy, oz, inv_x, inv_y, inv_z);
+        }
+    }
+    if (GENERIC) {
+        // No precomputed walks: the wavefront walks once per distinct start bin among its lanes; every lane of that
+        // bin then tests the staged records.
+        for (unsigned long long pending = __ballot(need_walk); pending; pending = __ballot(need_walk)) {
+            const int leader = __ffsll((long long)pending) - 1;
+            const int gsy = __shfl(sy, leader), gsz = __shfl(sz, leader);
+            const int n_rec = wave_walk(g, a.count, a.slots, dyn, bx, gsy, gsz, ws->stage);
+            if (need_walk && sy == gsy && sz == gsz) {
+                if (n_rec >= 0) {
+                    for (int r = 0; r < n_rec; r++) {
+                        const par_slot rec = ws->stage[r];
+                        if (rec.entity != p_entity && slab_hit(rec, ox, oy, oz, inv_x, inv_y, inv_z)) {  // alt:484-491
+                            lit = false;
+                            break;
+                        }
+                    }
+                } else {  // more records on the way than the stage holds: per lane, as the reference writes it
+                    lit = lane_shadow_walk(g, a.count, a.slots, bx, sy, sz, dyn, p_entity, ox, oy, oz, inv_x, inv_y,
+                                           inv_z);
+                }
+                need_walk = false;
+            }
+            wave_lds_fence();  // (every lane has read the stage before the next walk overwrites it)
+        }
+    }
+    if (hit) bright = lit ? b_lit : ambient;
+    const bool lit_px = lit;
+    if (!GENERIC) stamp(g, fl, 3, 4);
+    if ((fl & PAR_RENDER_COUNT_RAYS) && a.ray_counter) {
+        const unsigned long long m = __ballot(valid && hit);
+        if (lane == 0 && m) atomicAdd(a.ray_counter, (unsigned long long)__popcll(m));
+    }
+
+    // ---- quantise + store, alt:735, 757-758 -------------------------------------------------------------------
+    if (valid && hit) {  // (uncovered pixels keep what the fill wrote)
+        const size_t o = (size_t)(row - a.row_begin) * W + col;
+        if (a.out.fb) __builtin_nontemporal_store(color_scale(rgba, bright), reinterpret_cast<uint32_t*>(a.out.fb) + o);
+        if (a.out.palidx) __builtin_nontemporal_store((uint8_t)pal_index, a.out.palidx + o);
+        if (FULL && a.out.brightness) a.out.brightness[o] = bright;
+        if (FULL && a.out.lit) a.out.lit[o] = lit_px ? 1 : 0;
+        if (FULL && a.out.gbuf) a.out.gbuf[o] = gbuf_pixel(nx, ny, nz, rgba, p_y, p_z, p_entity);
+    }
+}
+
+// What the primary pass says of a lane's pixel: whether the lane renders one (valid), whether an entry covers it
+// (hit), and then the entry's entity, the texel (its index into texinfo) and the hit's world y and z.
+struct ChunkHit {
+    bool valid, hit;
+    int entity, tex, y, z;
+};
+
+// primary_chunk: the primary ray of one pixel per lane, alt:271-397. `own` >= 0: the lanes keep the pixels entry `own`
+// of the record is the first to cover, -1: all pixels. GENERIC: the column's bins are read straight from the hash, as
+// the reference does, instead of from the record's tables in `cr`.
+template <bool GENERIC, bool IDS = true>
+__device__ __forceinline__ ChunkHit primary_chunk(const par_grid_dev& g, const par_render_args& a, const ColumnRegs& cr,
+                                                  uint64_t dup, int n_entries, int bx, int by, int own, int col,
+                                                  int row, int row_lo, int row_hi, int col_lo, int col_hi, bool valid,
+                                                  int lane, const OwnTexel& pre) {
+    const int H = a.H;
+    const int32_t* depth0 = a.sprites[0].depth;
+    const int pre_tex = pre.tex;
     // ---- primary ray, alt:271-397: the column's slot records front to back ------------------------------------
     bool hit = false;
     int p_entity = 0, p_y = 0, p_z = 0, p_tex = 0;
@@ -1409,144 +1588,25 @@ __device__ __forceinline__ void render_chunk(const par_grid_dev& g, const par_re
         }
     }
 
-    if (!GENERIC) stamp(g, fl, 3, 3);
-    // ---- shading, alt:704-758 ---------------------------------------------------------------------------------
-    float nx = 0.f, ny = 0.f, nz = 0.f;
-    uint32_t rgba = bg_rgba;
-    int pal_index = PAR_PALIDX_BACKGROUND;
-    float bright = ambient;
-    bool lit = true;
-    bool need_walk = false;  // the shadow ray still has to be resolved
-    float inv_x = 0.f, inv_y = 0.f, inv_z = 0.f, b_lit = 0.f;
-    int sy = 0, sz = 0, ox = 0, oy = 0, oz = 0;
-    if (hit) {
-        // normal (alt:349-350) + resolved palette colour (alt:352-354)
-        par_texel ti = pre_ti;
-        pal_index = pre_pal;
-        if (p_tex != pre_tex) {  // another entry won (or nothing was fetched ahead)
-            ti = a.texinfo[p_tex];
-            if (a.out.palidx) {
-                const int sid = IDS ? p_tex / PAR_SPRITE_TEXELS : 0;
-                pal_index = a.sprites[sid].color[p_tex - sid * PAR_SPRITE_TEXELS];
-            }
-        }
-        nx = ti.nx; ny = ti.ny; nz = ti.nz;
-        rgba = ti.rgba;
-        const int wx = col, wy = p_y, wz = p_z;  // alt:707-709
-        const LightDir ld = light_dir(dyn, wx, wy, wz);
-        inv_x = ld.ix; inv_y = ld.iy; inv_z = ld.iz;
-        b_lit = std_min(1.f, diffuse(ld, nx, ny, nz) + ambient);          // alt:758
-        // alt:725-726: the start bin's row is bin(H - wy - wz). wy + wz is world_j whatever the texel's depth (it is
-        // subtracted from y and added to z, alt:356-361), and H - world_j is the pixel's screen row (alt:280; no
-        // view is taller than a `short` holds, par_create): a row of this column's tile, whose bin row is `by`. The
-        // overflow path keeps the division.
-        sy = GENERIC ? div_bin(H - wy - wz, a.magic_b) : by;
-        sz = div_bin(wz, a.magic_b);                                       // alt:727
-        ox = (int)(int16_t)col; oy = (int)(int16_t)p_y; oz = (int)(int16_t)p_z;  // alt:720-722
-        // shadow ray, alt:738-742: columns_kernel has walked from every occupied bin of the column
-        int woff = 0, wcnt = -1;
-        if (!GENERIC) {
-            for (int n = 0; n < n_nb; n++) {
-                const uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane((int)cr.nb.x, n);
-                const uint32_t d1 = (uint32_t)__builtin_amdgcn_readlane((int)cr.nb.y, n);
-                if ((int)(int16_t)(d0 & 0xFFFF) == sz) {
-                    woff = (int)(d1 & 0xFFFF);
-                    wcnt = (int)(int16_t)(d1 >> 16);  // -1: the walk was too long to record
-                }
-            }
-        }
-        if (wcnt >= 0) {
-            // two records (four 16-byte loads) per step: their loads are in flight together
-            const char* walk_base = reinterpret_cast<const char*>(rec_.walk);  // (wave-uniform; 32-bit lane offsets)
-            const float fox = (float)ox, foy = (float)oy, foz = (float)oz;
-            auto test_list = [&](auto finite) {
-                for (int r0 = 0; r0 < wcnt && lit; r0 += 2) {
-                    uint4 wa[2], wb[2];
-#pragma unroll
-                    for (int u = 0; u < 2; u++) {
-                        const uint32_t off = (uint32_t)(woff + min(r0 + u, wcnt - 1)) * (uint32_t)sizeof(par_walkrec);
-                        const uint4* q = reinterpret_cast<const uint4*>(walk_base + off);
-                        wa[u] = q[0];
-                        wb[u] = q[1];
-                    }
-                    // (all four loads are issued before the first record is looked at: the compiler otherwise sinks
-                    // a record's planes below the comparison of its entity, a second round trip)
-                    asm volatile("" ::"v"(wa[0].x), "v"(wa[1].x), "v"(wb[0].x), "v"(wb[1].x));
-#pragma unroll
-                    for (int u = 0; u < 2; u++) {
-                        const v2f rx = {__uint_as_float(wa[u].x), __uint_as_float(wa[u].y)};
-                        const v2f ry = {__uint_as_float(wa[u].z), __uint_as_float(wa[u].w)};
-                        const v2f rz = {__uint_as_float(wb[u].x), __uint_as_float(wb[u].y)};
-                        if (r0 + u < wcnt && (int)wb[u].z != p_entity &&
-                            slab_hit_rec<decltype(finite)::value>(rx, ry, rz, fox, foy, foz, inv_x, inv_y, inv_z)) {  // alt:484-491
-                            lit = false;
-                        }
-                    }
-                }
-            };
-            // (wave-uniform choice: an axis-parallel light direction, 1 / 0, takes the reference's own sequence)
-            if (__all(__builtin_isfinite(inv_x) && __builtin_isfinite(inv_y) && __builtin_isfinite(inv_z))) {
-                test_list(std::true_type{});
-            } else {
-                test_list(std::false_type{});
-            }
-        } else if (GENERIC) {
-            need_walk = true;
-        } else {
-            // a start bin that holds no primitive (negative world z, sprite depths outside the box) has no
-            // precomputed walk: trace_hash_for_light as written, per lane
-            lit = lane_shadow_walk(g, a.count, a.slots, bx, sy, sz, dyn, p_entity, ox, oy, oz, inv_x, inv_y, inv_z);
-        }
-    }
-    if (GENERIC) {
-        // No precomputed walks: the wavefront walks once per distinct start bin among its lanes; every lane of that
-        // bin then tests the staged records.
-        for (unsigned long long pending = __ballot(need_walk); pending; pending = __ballot(need_walk)) {
-            const int leader = __ffsll((long long)pending) - 1;
-            const int gsy = __shfl(sy, leader), gsz = __shfl(sz, leader);
-            const int n_rec = wave_walk(g, a.count, a.slots, dyn, bx, gsy, gsz, ws->stage);
-            if (need_walk && sy == gsy && sz == gsz) {
-                if (n_rec >= 0) {
-                    for (int r = 0; r < n_rec; r++) {
-                        const par_slot rec = ws->stage[r];
-                        if (rec.entity != p_entity && slab_hit(rec, ox, oy, oz, inv_x, inv_y, inv_z)) {  // alt:484-491
-                            lit = false;
-                            break;
-                        }
-                    }
-                } else {  // more records on the way than the stage holds: per lane, as the reference writes it
-                    lit = lane_shadow_walk(g, a.count, a.slots, bx, sy, sz, dyn, p_entity, ox, oy, oz, inv_x, inv_y,
-                                           inv_z);
-                }
-                need_walk = false;
-            }
-            wave_lds_fence();  // (every lane has read the stage before the next walk overwrites it)
-        }
-    }
-    if (hit) bright = lit ? b_lit : ambient;
-    const bool lit_px = lit;
-    if (!GENERIC) stamp(g, fl, 3, 4);
-    if ((fl & PAR_RENDER_COUNT_RAYS) && a.ray_counter) {
-        const unsigned long long m = __ballot(valid && hit);
-        if (lane == 0 && m) atomicAdd(a.ray_counter, (unsigned long long)__popcll(m));
-    }
+    return ChunkHit{valid, hit, p_entity, p_tex, p_y, p_z};
+}
 
-    // ---- quantise + store, alt:735, 757-758 -------------------------------------------------------------------
-    if (valid && hit) {  // (uncovered pixels keep what the fill wrote)
-        const size_t o = (size_t)(row - a.row_begin) * W + col;
-        if (a.out.fb) __builtin_nontemporal_store(color_scale(rgba, bright), reinterpret_cast<uint32_t*>(a.out.fb) + o);
-        if (a.out.palidx) __builtin_nontemporal_store((uint8_t)pal_index, a.out.palidx + o);
-        if (FULL && a.out.brightness) a.out.brightness[o] = bright;
-        if (FULL && a.out.lit) a.out.lit[o] = lit_px ? 1 : 0;
-        if (FULL && a.out.gbuf) a.out.gbuf[o] = gbuf_pixel(nx, ny, nz, rgba, p_y, p_z, p_entity);
-    }
+// A chunk of a column without a usable record: the primary pass straight from the hash, then the shading.
+__device__ __forceinline__ void render_chunk_generic(const par_grid_dev& g, const par_render_args& a,
+                                                     const par_colrec& rec_, const par_frame_dyn& dyn, int bx, int by,
+                                                     int col, int row, bool valid, int lane, WaveScratch* ws) {
+    const ColumnRegs cr{make_uint4(0, 0, 0, 0), 0, make_uint2(0, 0)};
+    const OwnTexel pre{-1, 0, 0, par_texel{0.f, 0.f, 0.f, 0u}};
+    const ChunkHit h = primary_chunk<true>(g, a, cr, 0, 0, bx, by, -1, col, row, 0, 0, 0, 0, valid, lane, pre);
+    shade_chunk<true, true, true, true>(g, a, rec_, cr.nb, 0, dyn, bx, by, col, row, h.valid, h.hit, h.entity, h.tex, h.y,
+                                        h.z, pre, lane, ws);
 }
 
 // ------------------------------------------------------------------------------------------------------------
 // render_column_generic: a column WITHOUT a usable record (it overflowed one, or a test hook forces it): the whole
 // tile, 64 pixels per wavefront; chunk k belongs to wavefront k mod (max_parts * PAR_WAVE_NW) of the column's
 // workgroups. The primary pass reads the column's bins straight from the hash, as the reference does, and the shadow
-// walks are done in the kernel (render_chunk<true>). Only bx, by of the record are read.
+// walks are done in the kernel (render_chunk_generic). Only bx, by of the record are read.
 // ------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void render_column_generic(const par_grid_dev& g, const par_render_args& a, int ci,
                                                       int part, int max_parts, WaveScratch* ws) {
@@ -1554,10 +1614,6 @@ __device__ __forceinline__ void render_column_generic(const par_grid_dev& g, con
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const par_colrec& rec_ = g.colrec[ci];
     const int bx = rec_.bx, by = rec_.by;
-    ColumnRegs cr;
-    cr.ent = make_uint4(0, 0, 0, 0);
-    cr.ebz = 0;
-    cr.nb = make_uint2(0, 0);
     const int n_workers = max_parts * PAR_WAVE_NW, worker = part * PAR_WAVE_NW + wave;
     const par_frame_dyn dyn = frame_dyn(a);
     const TileRect t = tile_rect(a, bx, by);
@@ -1571,31 +1627,86 @@ __device__ __forceinline__ void render_column_generic(const par_grid_dev& g, con
         const int pidx = c * 64 + lane;
         const int pyy = rm.row(pidx);
         const int col = c0 + (pidx - pyy * rw), row = ry0 + pyy;
-        // the chunk's first and last row (wave-uniform)
-        const int p_first = c * 64, p_last = min(p_first + 63, area - 1);
-        const int row_lo = ry0 + rm.row(p_first), row_hi = ry0 + rm.row(p_last);
-        render_chunk<true, true>(g, a, rec_, cr, 0, dyn, 0, 0, bx, by, -1, col, row, row_lo, row_hi, c0, c0 + rw - 1, pidx < area, lane,
-                           ws + wave);
+        render_chunk_generic(g, a, rec_, dyn, bx, by, col, row, pidx < area, lane, ws + wave);
     }
 }
 
-// render_item: one work item = one 64-pixel chunk of one column with a record (columns_kernel listed it), one
-// wavefront. `pass`: the entry whose rectangle is visited (the lanes render the pixels it is the first to cover), or
-// PAR_ITEM_TILE: the whole tile. The record is read where columns_kernel left it: its fields are wave-uniform, so
-// they arrive through the scalar cache; the entry and bin tables sit one element per lane in registers
-// (v_readlane). No LDS, no barrier, no loop over chunks: every wavefront of the launch is a handful of dependent
-// loads long, whatever its column looks like.
-// The item as two 16-byte words (par_item: {ci, visit, where, bins}, {entry}).
-template <bool DBG, bool IDS, bool FULL>
-__device__ __forceinline__ void render_item(const par_grid_dev& g, const par_render_args& a, uint4 ia, uint4 ib,
-                                            int lane) {
-    const uint32_t fl = DBG ? a.flags : 0u;
-    const int ci = (int)ia.x;
+// What an item's wavefront hands to shade_chunk, whichever way it got there (render_item).
+struct ItemPixel {
+    uint2 nb;          // lane n: the column's occupied bin n (ColumnRegs::nb)
+    int n_nb, bx, by;
+    int col, row;      // this lane's pixel
+    ChunkHit h;
+    OwnTexel pre;
+    uint32_t touched;  // (the touch of the walk lists; nothing reads it)
+};
+
+// render_item_alone: a work item whose entry is ALONE (par_item: no other entry of the column can cover a pixel of
+// its rectangle, and the frame has no sprite-id table). What primary_chunk (alt:282-374) would find is
+// known before the wavefront starts: every valid lane lies inside the entry's rectangle (the rectangle visited is that
+// rectangle, clipped), the entry is the only candidate, so `closest < depth` holds once, the entry is the first to
+// cover, `adjacent` never reaches 2, and the hit is the entry at the depth of its own texel, which is fetched right
+// away. No entry table, no record header, no candidate ballot, no loop: the pixel from the item's rectangle and the
+// texel. Of the record only the bin table (the walks' places) and, in shade_chunk, the walk lists are read, and not
+// even those for a simple column.
+template <bool DBG>
+__device__ __forceinline__ void render_item_alone(const par_grid_dev& g, const par_render_args& a,
+                                                  const par_colrec& rec_, uint4 ia, uint4 ib, int lane, ItemPixel& px) {
+    const int chunk = (int)(ia.y & 0xFFFFu);
+    const int bz_first = (int)((ia.y >> 16) & 0x3FFu), n_nb = (int)(ia.y >> 26);
+    const int bx = (int)(ia.z & 0x3FFu), by = (int)((ia.z >> 10) & 0x3FFu);
+    const bool simple = (ia.z & PAR_ITEM_SIMPLE) != 0;
+    const int rx0 = bx * a.B + (int)(ia.w & 0xFFu), ry0 = by * a.B + (int)((ia.w >> 8) & 0xFFu);
+    const int rw = (int)((ia.w >> 16) & 0xFFu), rh = (int)(ia.w >> 24);
+    const int e_px = (int)(int16_t)(ib.x & 0xFFFFu), e_py = (int)(int16_t)(ib.x >> 16);
+    const int e_pz = (int)(int16_t)(ib.y & 0xFFFFu);
+    const int e_ey = (int)(int16_t)(ib.z & 0xFFFFu), e_ez = (int)(int16_t)(ib.z >> 16);
+    // this lane's pixel: the rectangle in vertical strips of a sprite's width (par_strips.h), as render_item visits it
+    const par_strips st = par_strips_of(rw);
+    const int pidx = chunk * 64 + lane;
+    const bool valid = pidx < rw * rh;
+    int col, row, strip;
+    par_strip_pixel(st, rh, pidx, strip, col, row);
+    col += rx0;
+    row += ry0;
+    // the entry's texel at that pixel: depth, normal, colour and palette index, fetched side by side
+    const int sprite_row = e_py + e_ey + e_pz + e_ez - (int)(int16_t)(a.H - row);  // alt:280, 324-326
+    OwnTexel pre;
+    pre.tex = -1; pre.pal = 0; pre.depth = 0;
+    pre.ti = par_texel{0.f, 0.f, 0.f, 0u};
+    if (valid) {
+        pre.tex = sprite_row * PAR_SPRITE_W + (col - e_px);  // alt:330-332
+        pre.depth = a.sprites[0].depth[pre.tex];
+        pre.ti = a.texinfo[pre.tex];
+        if (a.out.palidx) pre.pal = a.sprites[0].color[pre.tex];
+    }
+    // the column's occupied bins, lane n holding bin n: a simple column's are bz_first .. with empty walks
+    uint2 nb = make_uint2((uint32_t)(uint16_t)(bz_first + lane), 0u);
+    uint32_t touched = 0;
+    if (!simple) {
+        nb = reinterpret_cast<const uint2*>(rec_.nb)[lane & (PAR_COL_NB - 1)];
+        // (lane n touches the first line of bin n's walk list, as render_item does)
+        if (lane < n_nb && (int)(int16_t)(nb.y >> 16) > 0) {
+            touched = *reinterpret_cast<const uint32_t*>(rec_.walk + (nb.y & 0xFFFFu));
+        }
+    }
+    stamp(g, DBG ? a.flags : 0u, 3, 2);
+    // alt:356-361: the hit's world y and z from the texel's depth
+    const int p_y = e_py + e_ey + e_ez - sprite_row - pre.depth, p_z = e_pz + pre.depth;
+    px = ItemPixel{nb, n_nb, bx, by, col, row, ChunkHit{valid, valid, (int)ib.w, pre.tex, p_y, p_z}, pre, touched};
+}
+
+// render_item_record: the general entry pass of an item, from the column's record (or, for a SIMPLE column, from the
+// item alone; since every simple column of a frame without a sprite-id table is alone as well, that branch is
+// reached only with a sprite-id table). False: the item has nothing to render.
+template <bool DBG, bool IDS>
+__device__ __forceinline__ bool render_item_record(const par_grid_dev& g, const par_render_args& a,
+                                                   const par_colrec& rec_, uint4 ia, uint4 ib, int lane,
+                                                   ItemPixel& px) {
     const uint32_t pass = ia.y >> 16;
     const int chunk = (int)(ia.y & 0xFFFFu);
     const bool simple = (ia.z & PAR_ITEM_SIMPLE) != 0;
     constexpr bool tile_mode = false;  // (whole-tile visits are render_tile_item's)
-    const par_colrec& rec_ = g.colrec[ci];
     // ---- everything the ITEM says: the column, the rectangle visited, this lane's pixel, and (entry passes) the
     // texel of the pass's own entry, the likeliest winner of the pixel. Its depth, normal, colour and palette index
     // are fetched right away, beside the column's record, instead of one and two round trips after it.
@@ -1618,10 +1729,10 @@ __device__ __forceinline__ void render_item(const par_grid_dev& g, const par_ren
         ry0 = max(H - (own_rec.py + own_rec.ey + own_rec.pz + own_rec.ez), rows_lo);
         rh = min(H - (own_rec.py + own_rec.pz), rows_hi) - ry0;
     }
-    if (rw <= 0 || rh <= 0) return;
+    if (rw <= 0 || rh <= 0) return false;
     const int area = rw * rh;
     const int p_first = chunk * 64, p_last = min(p_first + 63, area - 1);
-    if (p_first >= area) return;
+    if (p_first >= area) return false;
     // the rectangle is visited in vertical strips of a sprite's width, row by row within a strip (par_strips.h)
     static_assert(PAR_SPRITE_W == PAR_STRIP_W && PAR_MAX_BIN <= PAR_STRIP_MAX_SIDE, "par_strips.h is written for these");
     const par_strips st = par_strips_of(rw);
@@ -1677,9 +1788,9 @@ __device__ __forceinline__ void render_item(const par_grid_dev& g, const par_ren
         n_nb = (int)(int16_t)(h0.x & 0xFFFFu);
         n_entries = (int)(int16_t)(h0.x >> 16);
         dup = ((uint64_t)h1.z << 32) | h1.y;
-        if ((h0.y >> 16) != 0) return;  // overflow: render_overflow_kernel's
+        if ((h0.y >> 16) != 0) return false;  // overflow: render_overflow_kernel's
     }
-    stamp(g, fl, 3, 2);
+    stamp(g, DBG ? a.flags : 0u, 3, 2);
     // The shadow test will read the walk list of the pixel's start bin, which is known only after the primary pass
     // and its depth lookups: lane n touches the first line of bin n's list now, so that those reads find it in the
     // cache instead of adding a round trip to memory at the end of the chain.
@@ -1687,12 +1798,38 @@ __device__ __forceinline__ void render_item(const par_grid_dev& g, const par_ren
     if (!simple && lane < n_nb && (int)(int16_t)(cr.nb.y >> 16) > 0) {
         touched = *reinterpret_cast<const uint32_t*>(rec_.walk + (cr.nb.y & 0xFFFFu));
     }
-    const par_frame_dyn dyn = a.dyn_ptr ? ld_uniform(a.dyn_ptr) : a.dyn;  // (graph replay: uploaded before the frame)
     // (a simple column's only entry sits in every lane: it is read as entry 0 whatever its index in the record was)
     const int own = tile_mode ? -1 : (simple ? 0 : (int)pass);
-    render_chunk<false, DBG, IDS, FULL>(g, a, rec_, cr, dup, dyn, n_entries, n_nb, bx, by, own, col, row, row_lo, row_hi, col_lo, col_hi, valid,
-                             lane, nullptr, pre);
-    asm volatile("" ::"v"(touched));  // (keeps the touch alive; nothing reads it)
+    const ChunkHit h = primary_chunk<false, IDS>(g, a, cr, dup, n_entries, bx, by, own, col, row, row_lo, row_hi, col_lo,
+                                                 col_hi, valid, lane, pre);
+    px = ItemPixel{cr.nb, n_nb, bx, by, col, row, h, pre, touched};
+    return true;
+}
+
+// render_item: one work item = one 64-pixel chunk of one column with a record (columns_kernel listed it), one
+// wavefront. `pass`: the entry whose rectangle is visited (the lanes render the pixels it is the first to cover), or
+// PAR_ITEM_TILE: the whole tile. The record is read where columns_kernel left it: its fields are wave-uniform, so
+// they arrive through the scalar cache; the entry and bin tables sit one element per lane in registers
+// (v_readlane). No LDS, no barrier, no loop over chunks: every wavefront of the launch is a handful of dependent
+// loads long, whatever its column looks like.
+// The item as two 16-byte words (par_item: {ci, visit, where, bins}, {entry}). An ALONE item goes through
+// render_item_alone instead of render_item_record, a wave-uniform branch at the top; both end in the one shade_chunk.
+template <bool DBG, bool IDS, bool FULL>
+__device__ __forceinline__ void render_item(const par_grid_dev& g, const par_render_args& a, uint4 ia, uint4 ib,
+                                            int lane) {
+    const uint32_t fl = DBG ? a.flags : 0u;
+    const par_colrec& rec_ = g.colrec[(int)ia.x];
+    ItemPixel px;
+    if (ia.z & PAR_ITEM_ALONE) {  // (wave-uniform: the item is)
+        render_item_alone<DBG>(g, a, rec_, ia, ib, lane, px);
+    } else if (!render_item_record<DBG, IDS>(g, a, rec_, ia, ib, lane, px)) {
+        return;
+    }
+    stamp(g, fl, 3, 3);
+    const par_frame_dyn dyn = a.dyn_ptr ? ld_uniform(a.dyn_ptr) : a.dyn;  // (graph replay: uploaded before the frame)
+    shade_chunk<false, DBG, IDS, FULL>(g, a, rec_, px.nb, px.n_nb, dyn, px.bx, px.by, px.col, px.row, px.h.valid, px.h.hit,
+                                       px.h.entity, px.h.tex, px.h.y, px.h.z, px.pre, lane, nullptr);
+    asm volatile("" ::"v"(px.touched));  // (keeps the touch alive; nothing reads it)
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1708,7 +1845,7 @@ __device__ __forceinline__ void render_item(const par_grid_dev& g, const par_ren
 //     scalar registers: the bin bookkeeping costs no vector instruction;
 //   - the shadow test groups the lanes by start bin (nearly always one group) and reads that bin's walk list with
 //     scalar loads: no per-lane record loads, no address arithmetic, no unpacking.
-// Same arithmetic, in the same order, as render_chunk (alt:310-365, 704-758).
+// Same arithmetic, in the same order, as primary_chunk and shade_chunk (alt:310-365, 704-758).
 // ------------------------------------------------------------------------------------------------------------
 typedef uint64_t lanemask;
 __device__ __forceinline__ bool lane_of(lanemask m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
@@ -2255,7 +2392,7 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_both_kernel(par_grid_
 //   A. the column's occupied bins (a scan of `count` along z), and from each of them the walk towards EVERY light's
 //      bin (wave_walk), the (bin, light) pairs dealt to the workgroup's wavefronts; the occluder records go into the
 //      workgroup's walk area, handed out walk by walk (a walk that does not fit is "not recorded");
-//   B. the column's tile, 64 pixels per wavefront: the primary pass straight from the hash (as render_chunk<GENERIC>),
+//   B. the column's tile, 64 pixels per wavefront: the primary pass straight from the hash (as primary_chunk<GENERIC>),
 //      then per light the slab tests of the recorded walk of the pixel's start bin, or lane_shadow_walk where there is
 //      none (the start bin holds no primitive, or its walk did not fit), and the shading of the contract in
 //      par_raytracer.h (par_set_lights). Each walk is done once per column and light.
@@ -2531,7 +2668,7 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
                 p_entity = texel.entity;
                 p_y = texel.y;
                 p_z = texel.z;
-            } else {  // the column's bins as they lie in the hash (render_chunk<GENERIC>); kept in place: DESIGN 8c
+            } else {  // the column's bins as they lie in the hash (primary_chunk<GENERIC>); kept in place: DESIGN 8c
                 const int world_j = (int)(int16_t)(H - row);  // alt:280
                 int adjacent = 0;                             // alt:282
                 int closest = INT_MIN;                        // alt:289
@@ -2596,7 +2733,7 @@ __global__ __launch_bounds__(PAR_WAVE_NW * 64) void render_lights_kernel(par_gri
                         pal_index = a.sprites[sid].color[p_tex - sid * PAR_SPRITE_TEXELS];
                     }
                 }
-                // the start bin (alt:724-727): its row is this column's (render_chunk), its depth bin(z)
+                // the start bin (alt:724-727): its row is this column's (shade_chunk), its depth bin(z)
                 const int sz = div_bin(p_z, a.magic_b);
                 const int ox = (int)(int16_t)px_col, oy = (int)(int16_t)p_y, oz = (int)(int16_t)p_z;  // alt:720-722
                 const int zs = (sz >= 0 && sz < g.gz) ? (int)sh.zslot[sz] : -1;
