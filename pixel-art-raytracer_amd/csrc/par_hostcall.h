@@ -1,7 +1,8 @@
 // par_hostcall.h — what the host sides of the passes over finished planes share (par_outline.hip, par_quantize.hip,
 // par_present.hip, par_finish.hip, par_upscale.hip): the surface descriptor's check and the cut of a call's rows into
-// launches, in plain C++, and for units compiled as HIP the opening and the bookkeeping of the *_host forms: the device
-// a call runs on, its device buffers and its status. Host code only; nothing here knows a par_context.
+// launches, and the spans of the tile storage that par_tileset_extend_host copies, in plain C++, and for units compiled
+// as HIP the opening and the bookkeeping of the *_host forms: the device a call runs on, its device buffers and its
+// status. Host code only; nothing here knows a par_context.
 #ifndef PAR_HOSTCALL_H
 #define PAR_HOSTCALL_H
 
@@ -40,6 +41,18 @@ int par_tile_row_cuts(int row_begin, int row_end, uint32_t W, uint32_t tile_h, L
         ra = rb;
     }
     return 0;
+}
+
+// The bytes of `tiles` that par_tileset_extend_host moves for a set of `capacity` tiles of tile_bytes bytes that held
+// count_in tiles before the call and count_out after it (count_in <= count_out; either may exceed the capacity): up, the
+// stored tiles [0, min(count_in, capacity)); down, the added ones [min(count_in, capacity), min(count_out, capacity)).
+// Nothing beyond capacity * tile_bytes is ever named, and the caller's bytes from min(count_out, capacity) tiles on stay.
+struct par_tile_spans {
+    size_t upload_bytes, download_offset, download_bytes;
+};
+inline par_tile_spans par_tileset_extend_spans(uint64_t count_in, uint64_t count_out, uint64_t capacity, size_t tile_bytes) {
+    const uint64_t stored = std::min(count_in, capacity), kept = std::max(stored, std::min(count_out, capacity));
+    return {(size_t)stored * tile_bytes, (size_t)stored * tile_bytes, (size_t)(kept - stored) * tile_bytes};
 }
 
 #ifdef __HIP__

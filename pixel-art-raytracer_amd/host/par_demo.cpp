@@ -9,6 +9,7 @@
 //   par_demo [--keys RRRRUUUUhhhhjjPP] [--frames N] [--out DIR] [--gif FILE] [--debug-line] [--as-sdl] [--size W H L]
 //            [--palette-levels K] [--dither S] [--outline S,C,D] [--scale SX[,SY]] [--finish] [--upscale K]
 //            [--palette-fit N] [--palette-refine I] [--dither-pattern N[,S]] [--cells CW,CH] [--tileset TW,TH[,FLIPS]]
+//            [--tileset-shared CAP]
 //
 // --gif writes the frames as one animated GIF89a (100 ms per frame like the reference's gif.gif); a frame's colours
 // are palette entries times a brightness, at most a few hundred distinct values, so each frame gets an exact local
@@ -40,6 +41,11 @@
 // tiles of every frame's index plane on the GPU (par_tileset_build_host with capacity 0, behind the quantise) and prints
 // one line a frame, `tileset frame <i>: <T> tiles of <N> cells`: whether the frame fits a tile budget. It changes no
 // byte of the GIF.
+// --tileset-shared CAP (with --tileset; CAP = 0..1048576 tiles) also keeps ONE tile set of capacity CAP across the GIF's
+// frames, the way a tile map's set or a sprite sheet is kept: every frame's index plane extends it
+// (par_tileset_extend_host, the same tiles and flips), and after the frame's `tileset frame` line it prints
+// `tileset shared frame <i>: <new> new, <T> tiles, capacity <CAP>`: the tiles the frame adds, its upload, and whether
+// the animation fits the budget (T <= CAP; beyond it T is an upper bound). It changes no byte of the GIF either.
 //
 // --outline S,C,D draws every frame's outlines on the GPU (par_outline_host) from the frame's own G-buffer: silhouettes
 // scaled by S / 256, creases by C / 256, a silhouette between two entities from a depth difference of D (128,320,4 is a
@@ -77,6 +83,7 @@
 #include "par_cells.h"
 #include "par_raytracer.h"
 #include "par_tileset.h"
+#include "par_tileset_extend.h"
 
 static void apply_key(char k, par_aabb& player, par_light& light) {
     switch (k) {
@@ -244,6 +251,7 @@ int main(int argc, char** argv) {
     int upscale = 0;               // 0: no --upscale
     int cell_w = 0, cell_h = 0;    // 0: no --cells
     int tile_w = 0, tile_h = 0, tile_flips = 0;  // 0: no --tileset
+    int shared_capacity = -1;                    // -1: no --tileset-shared
     par_outline_style outline_style{4, 256, 256};
     for (int i = 1; i < argc; i++) {
         if (!std::strcmp(argv[i], "--keys") && i + 1 < argc) keys = argv[++i];
@@ -278,6 +286,14 @@ int main(int argc, char** argv) {
             if ((!two && std::sscanf(argv[i], "%d,%d,%d%c", &tile_w, &tile_h, &tile_flips, &tail) != 3) ||
                 (tile_w != 8 && tile_w != 16) || (tile_h != 8 && tile_h != 16) || tile_flips < 0 || tile_flips > 3) {
                 std::fprintf(stderr, "--tileset wants TW,TH[,FLIPS], TW and TH each 8 or 16 and FLIPS 0..3, got %s\n", argv[i]);
+                return 2;
+            }
+        }
+        else if (!std::strcmp(argv[i], "--tileset-shared") && i + 1 < argc) {
+            char tail = 0;
+            if (std::sscanf(argv[++i], "%d%c", &shared_capacity, &tail) != 1 || shared_capacity < 0 ||
+                shared_capacity > PAR_TILESET_MAX_CELLS) {
+                std::fprintf(stderr, "--tileset-shared wants a capacity of 0..%d tiles, got %s\n", PAR_TILESET_MAX_CELLS, argv[i]);
                 return 2;
             }
         }
@@ -358,6 +374,10 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--tileset wants --gif and --palette-levels, --palette-fit or --cells: it counts the tiles of an index plane\n");
         return 2;
     }
+    if (shared_capacity >= 0 && tile_w == 0) {
+        std::fprintf(stderr, "--tileset-shared wants --tileset TW,TH[,FLIPS]: it keeps the set of those tiles across the frames\n");
+        return 2;
+    }
     if (finish) {
         if (out_dir.empty()) { std::fprintf(stderr, "--finish wants --out\n"); return 2; }
         if (!outline && palette_levels == 0) { std::fprintf(stderr, "--finish wants --outline or --palette-levels: without both it is --scale\n"); return 2; }
@@ -421,6 +441,10 @@ int main(int argc, char** argv) {
         if (status != PAR_OK) std::fprintf(stderr, "par_quantize_host: %s\n", par_status_string(status));
         return status;
     };
+    // --tileset-shared: the one set the frames extend, and its count
+    std::vector<unsigned char> shared_tiles;
+    int shared_count = 0;
+    if (shared_capacity > 0) shared_tiles.resize((size_t)shared_capacity * (size_t)(tile_w * tile_h));
     // --tileset: the tiles of the index plane of frame f as it stands, counted and printed
     const auto count_tiles = [&](int f) -> int {
         if (tile_w == 0) return PAR_OK;
@@ -433,6 +457,17 @@ int main(int argc, char** argv) {
         }
         std::printf("tileset frame %d: %d tiles of %d cells\n", f, tiles,
                     ((W + tile_w - 1) / tile_w) * ((H + tile_h - 1) / tile_h));
+        if (shared_capacity < 0) return (int)PAR_OK;
+        int first_new = 0;
+        const int shared_status = par_tileset_extend_host(&params, 0, index.data(), 0, H, tile_w, tile_h, 0, tile_flips,
+                                                          shared_capacity > 0 ? shared_tiles.data() : nullptr, shared_capacity,
+                                                          &shared_count, nullptr, &first_new);
+        if (shared_status != PAR_OK) {
+            std::fprintf(stderr, "par_tileset_extend_host: %s\n", par_status_string(shared_status));
+            return shared_status;
+        }
+        std::printf("tileset shared frame %d: %d new, %d tiles, capacity %d\n", f, shared_count - first_new, shared_count,
+                    shared_capacity);
         return (int)PAR_OK;
     };
     GifWriter gif;
