@@ -16,6 +16,7 @@ import sys
 import numpy as np
 
 from . import types as T
+from .abi import ABI, ABI_DEBUG_HOOKS, ABI_HEADERS, install
 from .types import (AABB, COLOR, LIGHT, LIGHT_TINT, MAX_SCALE, OUTLINE_STYLE, PIXEL, PRESENT_BGRA, PRESENT_DESC,
                     PRESENT_RGBA, SPRITE, UPSCALE_DESC, UPSCALE_SCALE2X, UPSCALE_SCALE3X, UPSCALE_SCALE4X, FrameStats,
                     Outputs, Params, default_params, make_aabbs, make_light, make_outline_style, make_present_desc,
@@ -32,93 +33,6 @@ RENDER_COUNT_RAYS = 1 << 1
 RENDER_PIPELINED = 1 << 2
 RENDER_TIMED_AS_LAUNCHED = 1 << 3
 
-_p, _i, _u = C.c_void_p, C.c_int, C.c_uint
-# The C ABI, in the header's order: symbol -> argument types, or (return type, argument types) where the function does
-# not return an int. Every pointer is a c_void_p. lib() sets these on the library's functions and
-# tests/test_abi_cpu.py holds them to the prototypes of include/par_raytracer.h.
-ABI = {
-    "par_status_string": (C.c_char_p, [_i]),
-    "par_last_error": (C.c_char_p, [_p]),
-    "par_default_params": (None, [_p]),
-    "par_grid_dims": [_p, _p, _p, _p],
-    "par_device_count": [],
-    "par_create": [_p, _i, _p],
-    "par_destroy": (None, [_p]),
-    "par_set_sprites": [_p, _p, _i],
-    "par_set_entities": [_p, _p, _p, _i],
-    "par_set_entities_ref_layout": [_p, _p, _p, _i],
-    "par_update_aabbs": [_p, _p, _i, _i],
-    "par_update_aabbs_async": [_p, _p, _i, _i, _p],
-    "par_set_light": [_p, _p],
-    "par_set_lights": [_p, _p, _i],
-    "par_set_light_model": [_p, _i],
-    "par_set_light_tints": [_p, _p, _i],
-    "par_render": [_p, _p, _u],
-    "par_render_rows": [_p, _i, _i, _p, _u],
-    "par_render_device": [_p, _p, _i, _i, _p, _u],
-    "par_render_device_slots": [_p, _p, _p, _i, _i, _i, _i, _i, _u],
-    "par_render_device_timed": [_p, _p, _i, _i, _p, _u, _p],
-    "par_relight_device": [_p, _p, _i, _i, _p, _p, _u],
-    "par_relight_rows": [_p, _i, _i, _p, _u],
-    "par_graph_capture": [_p, _p, _i, _i, _p, _u],
-    "par_graph_stage": [_p, _p, _i, _i, _p],
-    "par_graph_launch": [_p, _p],
-    "par_graph_capture_lights": [_p, _p, _i, _i, _p, _u],
-    "par_graph_stage_lights": [_p, _p, _i, _i, _p, _i],
-    "par_pick": [_p, _i, _i, _p],
-    "par_get_stats": [_p, _p],
-    "par_read_grid": [_p, _p, _p, _p],
-    "par_debug_units": [_i, _i, _p, _p, _i, _p],
-    "par_sprite_tile_floor": (None, [_p]),
-    "par_scene_graybox": [_i, _i, _p, _i],
-    "par_scene_synthetic": [_i, _i, _i, _i, C.c_uint64, _p, _p],
-    "par_row_block": (None, [_i, _i, _i, _i, _p, _p]),
-    "par_scene_tiles": [_p, _p, _i, _p, _i],
-    "par_tiles_pack": [_p, _p, _p, _i, _p, _i, _i, _p],
-    "par_tiles_unpack": [_p, _p, _p, _i, _p, _p],
-    "par_background_fill": [_p, _p, _p, _i],
-    "par_tiles_assemble": [_p, _p, _p, _p, _p, _i, _i],
-    "par_scene_tile_map": [_p, _p, _i, _p, _i],
-    "par_tiles_changed_device": [_p, _p, _p, _p, _i, _i, _p, _p, _i, _p],
-    "par_tiles_pack_counted": [_p, _p, _p, _p, _i, _p, _i, _i, _p],
-    "par_tiles_fetch": [_p, _p, _p, _p, _p, _i, _p, _p, _p, _p],
-    "par_tiles_apply_host": [_p, _p, _i, _p, _i, _i, _p],
-    "par_plane_tiles_changed_device": [_p, _p, _i, _p, _p, _i, _i, _p, _p, _i, _p],
-    "par_plane_tiles_pack": [_p, _p, _i, _p, _i, _p, _i, _i, _p],
-    "par_plane_tiles_pack_counted": [_p, _p, _i, _p, _p, _i, _p, _i, _i, _p],
-    "par_plane_tiles_unpack": [_p, _p, _i, _p, _i, _p, _p],
-    "par_plane_tiles_assemble": [_p, _p, _i, _p, _p, _p, _p, _i, _i],
-    "par_plane_tiles_fetch": [_p, _p, _i, _p, _p, _p, _i, _p, _p, _p, _p],
-    "par_plane_tiles_apply_host": [_p, _i, _p, _i, _p, _i, _i, _p],
-    "par_outline_device": [_p, _p, _p, _p, _i, _i, _p, _i, _i, _p, _p],
-    "par_outline_host": [_p, _i, _p, _p, _i, _i, _p, _i, _i, _p, _p],
-    "par_quantize_device": [_p, _p, _p, _i, _i, _p, _i, _i, _p, _p],
-    "par_quantize_host": [_p, _i, _p, _i, _i, _p, _i, _i, _p, _p],
-    "par_palette_ramp": [_p, _i, _p, _i],
-    "par_quantize_pattern_device": [_p, _p, _p, _i, _i, _i, _p, _i, _i, _p, _p],
-    "par_quantize_pattern_host": [_p, _i, _p, _i, _i, _i, _p, _i, _i, _p, _p],
-    "par_palette_reset_device": [_p, _p],
-    "par_palette_count_device": [_p, _p, _p, _i, _i, _p],
-    "par_palette_cut_device": [_p, _p, _i],
-    "par_palette_sum_device": [_p, _p, _p, _i, _i, _p],
-    "par_palette_emit_device": [_p, _p, _i, _p],
-    "par_palette_fit_host": [_p, _i, _p, _i, _i, _i, _p, _p],
-    "par_palette_refine_device": [_p, _p, _p, _i, _i, _p, _i, _i, _p, _p, _p],
-    "par_palette_refine_host": [_p, _i, _p, _i, _i, _p, _i, _i, _p],
-    "par_present_device": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
-    "par_present_host": [_p, _i, _p, _p, _p, _p, _i, _i, _i, _p],
-    "par_finish_device": [_p, _p, _p, _p, _i, _i, _p, _i, _i, _p, _p, _i, _i, _p, _p],
-    "par_finish_host": [_p, _i, _p, _p, _i, _i, _p, _i, _i, _p, _p, _i, _i, _p, _p],
-    "par_upscale_device": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p],
-    "par_upscale_host": [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p],
-    "par_debug_line": (None, [_p, _p, _i, _p, _p]),
-}
-# exported for the tests and tools, not declared in the public header (csrc/par_context.hip)
-ABI_DEBUG_HOOKS = {
-    "par_debug_read_stamps": [_p, _p, C.c_size_t],
-    "par_debug_set_hooks": [_p, _u, _i],
-    "par_debug_read_light_walks": [_p, _p],
-}
 ABI_SYMBOLS = tuple(ABI)  # every symbol include/par_raytracer.h declares
 MAX_LIGHTS = 8  # PAR_MAX_LIGHTS
 LIGHTS_UNBOUNDED, LIGHTS_RANGED = 0, 1  # par_set_light_model
@@ -131,6 +45,19 @@ class ParError(RuntimeError):
 
 
 _lib = None
+_hip = None
+
+
+def _torch_hip_path():
+    """The libamdhip64.so that an installed torch bundles, or None. Does not import torch."""
+    try:
+        spec = importlib.util.find_spec("torch")
+    except (ImportError, ValueError):
+        spec = None
+    if spec is None or not spec.origin:
+        return None
+    cand = os.path.join(os.path.dirname(spec.origin), "lib", "libamdhip64.so")
+    return cand if os.path.exists(cand) else None
 
 
 def _share_hip_runtime_with_torch():
@@ -141,19 +68,26 @@ def _share_hip_runtime_with_torch():
     imported, or absent, there is nothing to do."""
     if "torch" in sys.modules:
         return
-    try:
-        spec = importlib.util.find_spec("torch")
-    except (ImportError, ValueError):
-        spec = None
-    if spec is None or not spec.origin:
-        return
-    cand = os.path.join(os.path.dirname(spec.origin), "lib", "libamdhip64.so")
-    if os.path.exists(cand):
+    cand = _torch_hip_path()
+    if cand:
         C.CDLL(cand, mode=C.RTLD_GLOBAL)
 
 
+def hip_runtime():
+    """The HIP runtime this process holds, for the few runtime calls the plumbing and the tools make themselves: torch's
+    own copy where it ships one, else the system's. One handle a process."""
+    global _hip
+    if _hip is None:
+        _hip = C.CDLL(_torch_hip_path() or "libamdhip64.so")
+        _hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        _hip.hipStreamSynchronize.argtypes = [C.c_void_p]
+        _hip.hipGetDevice.argtypes = [C.c_void_p]
+    return _hip
+
+
 def lib():
-    """Load libpar_raytracer.so (built in-tree by __graft_entry__.build() / csrc/Makefile). No fallback."""
+    """Load libpar_raytracer.so (built in-tree by __graft_entry__.build() / csrc/Makefile) and set every table of abi.py
+    on its functions. No fallback."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -161,11 +95,7 @@ def lib():
                               "(or __graft_entry__.build()). There is no CPU fallback.")
         _share_hip_runtime_with_torch()
         L = C.CDLL(LIB_PATH)
-        for name, sig in (*ABI.items(), *ABI_DEBUG_HOOKS.items()):
-            fn = getattr(L, name)
-            if type(sig) is tuple:
-                fn.restype, sig = sig
-            fn.argtypes = sig
+        install(L)
         _lib = L
     return _lib
 

@@ -1,8 +1,7 @@
 """Colour cells: a frame quantised under per-cell sub-palettes (include/par_cells.h). The three calls are declared in a
-header of their own and bound here, apart from the package module's table: ABI_CELLS has the format of the package's ABI
-(symbol -> argument types, every pointer a c_void_p, an int return not written out) and is installed on the library
-the package loaded, at first use. The calls go through the package's own path: _ok / _count raise ParError with the
-symbol's name, a device pointer or a stream is an int or None (_dp).
+header of their own and wrapped here, apart from the package module's wrappers: their signatures are abi.py's ABI_CELLS,
+which the package's lib() sets with every other table when it loads the library. The calls go through the package's own
+path: _ok / _count raise ParError with the symbol's name, a device pointer or a stream is an int or None (_dp).
 
     cells = importlib.import_module("pixel-art-raytracer_amd.cells")
 """
@@ -11,34 +10,17 @@ import sys
 
 import numpy as np
 
+from .abi import ABI_CELLS
 from .types import COLOR, MAX_PALETTE, ptr
 
 _par = sys.modules[__package__]  # the package module: its lib() is looked up at every call, as its own wrappers do
 
-_p, _i = C.c_void_p, C.c_int
-# include/par_cells.h, in the header's order; tests/test_cells_cpu.py holds the table to the header's prototypes
-ABI_CELLS = {
-    "par_quantize_cells_device": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p],
-    "par_quantize_cells_host": [_p, _i, _p, _i, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p],
-    "par_cells_pairs": [_p, _i, _p, _i],
-}
 ABI_CELLS_SYMBOLS = tuple(ABI_CELLS)
-
-_installed_on = None
 
 
 def lib():
-    """The package's library with ABI_CELLS set on its functions."""
-    global _installed_on
-    L = _par.lib()
-    if L is not _installed_on:
-        for name, sig in ABI_CELLS.items():
-            fn = getattr(L, name)
-            if type(sig) is tuple:
-                fn.restype, sig = sig
-            fn.argtypes = sig
-        _installed_on = L
-    return L
+    """The package's library: kept as a name for callers that reach the raw symbols through this module."""
+    return _par.lib()
 
 
 def quantize_cells(params, d_palette, n_sub, sub_size, cell, fb, rows, fb_out=None, index_out=None, cell_out=None,
@@ -49,7 +31,7 @@ def quantize_cells(params, d_palette, n_sub, sub_size, cell, fb, rows, fb_out=No
     strength `spread`) into the index plane at index_out (indices into the flat table) and / or the RGBA plane at fb_out
     (fb_out == fb: in place), the chosen sub-palette of every cell to cell_out when given. The rows are cut at cell rows.
     Asynchronous on `stream`."""
-    _par._ok(lib().par_quantize_cells_device, C.byref(params), _par._dp(stream), _par._dp(d_palette), n_sub, sub_size,
+    _par._ok(_par.lib().par_quantize_cells_device, C.byref(params), _par._dp(stream), _par._dp(d_palette), n_sub, sub_size,
              cell[0], cell[1], spread, _par._dp(fb), rows[0], rows[1], _par._dp(fb_out), _par._dp(index_out),
              _par._dp(cell_out))
 
@@ -70,7 +52,7 @@ def quantize_cells_host(params, palette, n_sub, sub_size, cell, fb, rows=None, s
     if want_cells:
         cw, ch = max(1, int(cell[0])), max(1, int(cell[1]))
         out["cells"] = np.zeros(-(-params.width // cw) * -(-(r1 - r0) // ch), dtype=np.uint8)
-    _par._ok(lib().par_quantize_cells_host, C.byref(params), device, ptr(palette), n_sub, sub_size, cell[0], cell[1],
+    _par._ok(_par.lib().par_quantize_cells_host, C.byref(params), device, ptr(palette), n_sub, sub_size, cell[0], cell[1],
              spread, ptr(fb), r0, r1, ptr(out.get("fb")), ptr(out.get("index")), ptr(out.get("cells")))
     return out
 
@@ -80,5 +62,5 @@ def cells_pairs(palette):
     entries of `palette`, a flat COLOR array of n * (n - 1) / 2 pairs of 2 entries."""
     palette = _par._flat(palette, COLOR)
     out = np.zeros(MAX_PALETTE, dtype=COLOR)
-    n = _par._count(lib().par_cells_pairs, ptr(palette), len(palette), ptr(out), len(out))
+    n = _par._count(_par.lib().par_cells_pairs, ptr(palette), len(palette), ptr(out), len(out))
     return out[:2 * n].copy()

@@ -10,13 +10,10 @@ block is copied instead.
 Host-side plumbing over the C ABI (par_tiles_changed_device and its neighbours in include/par_raytracer.h); a C++ host
 does the same with the four calls and a pinned buffer. With elem_bytes 1 or 28 the plane is an index plane (palidx, lit,
 the index plane of palette output, the edge plane of outlines) or the G-buffer, through the par_plane_tiles_* calls."""
-import ctypes as C
-import os
-
 import torch
 
-from . import (ParError, plane_tiles_apply_host, plane_tiles_changed, plane_tiles_fetch, plane_tiles_pack_counted,
-               tiles_apply_host, tiles_changed, tiles_fetch, tiles_pack_counted)
+from . import (ParError, hip_runtime, plane_tiles_apply_host, plane_tiles_changed, plane_tiles_fetch,
+               plane_tiles_pack_counted, tiles_apply_host, tiles_changed, tiles_fetch, tiles_pack_counted)
 from .types import COLOR, PIXEL
 
 # The changed share of the grid up to which this path beats one pinned copy of the whole plane: the largest fraction of
@@ -102,23 +99,9 @@ def _sized(call, elem_bytes):
     return sized
 
 
-_hip = None
-
-
-def _hip_runtime():
-    """The HIP runtime this process already holds (torch's own copy where it ships one)."""
-    global _hip
-    if _hip is None:
-        bundled = os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so")
-        _hip = C.CDLL(bundled if os.path.exists(bundled) else "libamdhip64.so")
-        _hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
-        _hip.hipStreamSynchronize.argtypes = [C.c_void_p]
-    return _hip
-
-
 def _copy_to_host(host, device, nbytes, stream):
     """One device-to-host copy on `stream` and a wait for it."""
-    hip = _hip_runtime()
+    hip = hip_runtime()
     rc = hip.hipMemcpyAsync(host, device, nbytes, 2, stream)  # hipMemcpyDeviceToHost
     if rc == 0:
         rc = hip.hipStreamSynchronize(stream)

@@ -1,9 +1,8 @@
 """Tile sets: an index plane deduplicated into its distinct tiles and a tile map, and the map drawn back into a plane
-(include/par_tileset.h). The five calls are declared in a header of their own and bound here as cells.py binds its
-three: ABI_TILESET has the format of the package's ABI (symbol -> argument types, every pointer a c_void_p, an int return
-not written out, any other return as (restype, argument types)) and is installed on the library the package loaded, at
-first use. The calls go through the package's own path: _ok raises ParError with the symbol's name, a device pointer or
-a stream is an int or None (_dp).
+(include/par_tileset.h). The five calls are declared in a header of their own and wrapped here as cells.py wraps its
+three: their signatures are abi.py's ABI_TILESET, which the package's lib() sets with every other table when it loads the
+library. The calls go through the package's own path: _ok raises ParError with the symbol's name, a device pointer or a
+stream is an int or None (_dp).
 
     tileset = importlib.import_module("pixel-art-raytracer_amd.tileset")
 """
@@ -12,38 +11,19 @@ import sys
 
 import numpy as np
 
+from .abi import ABI_TILESET
 from .types import ptr
 
 _par = sys.modules[__package__]  # the package module: its lib() is looked up at every call, as its own wrappers do
 
-_p, _i = C.c_void_p, C.c_int
-# include/par_tileset.h, in the header's order; tests/test_tileset_cpu.py holds the table to the header's prototypes
-ABI_TILESET = {
-    "par_tileset_work_bytes": (C.c_size_t, [_i]),
-    "par_tileset_build_device": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p],
-    "par_tileset_expand_device": [_p, _p, _p, _i, _i, _i, _p, _i, _i, _p],
-    "par_tileset_build_host": [_p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _p],
-    "par_tileset_expand_host": [_p, _i, _p, _i, _i, _i, _p, _i, _i, _p],
-}
 ABI_TILESET_SYMBOLS = tuple(ABI_TILESET)
 MAX_CELLS = 1 << 20  # PAR_TILESET_MAX_CELLS
 FLIP_X, FLIP_Y = 1, 2
 
-_installed_on = None
-
 
 def lib():
-    """The package's library with ABI_TILESET set on its functions."""
-    global _installed_on
-    L = _par.lib()
-    if L is not _installed_on:
-        for name, sig in ABI_TILESET.items():
-            fn = getattr(L, name)
-            if type(sig) is tuple:
-                fn.restype, sig = sig
-            fn.argtypes = sig
-        _installed_on = L
-    return L
+    """The package's library: kept as a name for callers that reach the raw symbols through this module."""
+    return _par.lib()
 
 
 def n_cells(params, tile, rows=None):
@@ -56,7 +36,7 @@ def n_cells(params, tile, rows=None):
 def tileset_work_bytes(cells):
     """The bytes of the work block of a tileset_build over `cells` cells (par_tileset_work_bytes); 0 outside
     [1, MAX_CELLS]."""
-    return lib().par_tileset_work_bytes(cells)
+    return _par.lib().par_tileset_work_bytes(cells)
 
 
 def tileset_build(params, index, rows, tile, work, count_out, tiles_out=None, capacity=0, map_out=None, pad=0, flips=0,
@@ -66,7 +46,7 @@ def tileset_build(params, index, rows, tile, work, count_out, tiles_out=None, ca
     count as a uint32 to count_out, the tile map (a uint32 a cell: id | flip << 30) to map_out and the first `capacity`
     tiles to tiles_out when given. `work` holds tileset_work_bytes(cells) bytes and needs no preparation. Asynchronous on
     `stream`."""
-    _par._ok(lib().par_tileset_build_device, C.byref(params), _par._dp(stream), _par._dp(index), rows[0], rows[1], tile[0],
+    _par._ok(_par.lib().par_tileset_build_device, C.byref(params), _par._dp(stream), _par._dp(index), rows[0], rows[1], tile[0],
              tile[1], pad, flips, _par._dp(work), _par._dp(tiles_out), capacity, _par._dp(map_out), _par._dp(count_out))
 
 
@@ -74,7 +54,7 @@ def tileset_expand(params, tiles, n_tiles, tile, tile_map, rows, index_out, stre
     """Device pointers (ints): the tile map at `tile_map` drawn with the n_tiles tiles at `tiles` into the index plane at
     index_out, rows [rows[0], rows[1]) (par_tileset_expand_device); a tile number past the last takes the last tile.
     Asynchronous on `stream`."""
-    _par._ok(lib().par_tileset_expand_device, C.byref(params), _par._dp(stream), _par._dp(tiles), n_tiles, tile[0], tile[1],
+    _par._ok(_par.lib().par_tileset_expand_device, C.byref(params), _par._dp(stream), _par._dp(tiles), n_tiles, tile[0], tile[1],
              _par._dp(tile_map), rows[0], rows[1], _par._dp(index_out))
 
 
@@ -91,7 +71,7 @@ def tileset_build_host(params, index, tile, rows=None, pad=0, flips=0, capacity=
     tiles = np.zeros(max(0, capacity) * size, dtype=np.uint8)
     tile_map = np.zeros(cells, dtype=np.uint32)
     count = C.c_int(0)
-    _par._ok(lib().par_tileset_build_host, C.byref(params), device, ptr(index), r0, r1, tile[0], tile[1], pad, flips,
+    _par._ok(_par.lib().par_tileset_build_host, C.byref(params), device, ptr(index), r0, r1, tile[0], tile[1], pad, flips,
              ptr(tiles) if capacity > 0 else None, capacity, ptr(tile_map), C.byref(count))
     kept = min(count.value, capacity)
     return {"tiles": tiles[:kept * size].reshape(kept, tile[1], tile[0]), "map": tile_map, "count": count.value}
@@ -112,6 +92,6 @@ def tileset_expand_host(params, tiles, tile, tile_map, rows=None, device=-1):
         raise ValueError(f"{who}: the map holds {len(tile_map)} entries, rows {r0}..{r1} of width {params.width} hold {cells} "
                          f"cells")
     out = np.zeros(max(0, r1 - r0) * max(0, params.width), dtype=np.uint8)
-    _par._ok(lib().par_tileset_expand_host, C.byref(params), device, ptr(tiles), len(tiles) // size, tile[0], tile[1],
+    _par._ok(_par.lib().par_tileset_expand_host, C.byref(params), device, ptr(tiles), len(tiles) // size, tile[0], tile[1],
              ptr(tile_map), r0, r1, ptr(out))
     return out

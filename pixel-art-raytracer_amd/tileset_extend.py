@@ -1,8 +1,8 @@
 """Shared tile sets: a tile-set build that starts from a set that already exists (include/par_tileset_extend.h). The
-three calls are declared in a header of their own and bound here as tileset.py binds its five: ABI_TILESET_EXTEND has
-the format of the package's ABI and is installed on the library the package loaded, at first use; the calls go through
-the package's own path (_ok raises ParError with the symbol's name, a device pointer or a stream is an int or None).
-SharedTileSet is plumbing over them in the spirit of FrameDelta: the device buffers of one kept set.
+three calls are declared in a header of their own and wrapped here as tileset.py wraps its five: their signatures are
+abi.py's ABI_TILESET_EXTEND, which the package's lib() sets with every other table when it loads the library; the calls
+go through the package's own path (_ok raises ParError with the symbol's name, a device pointer or a stream is an int or
+None). SharedTileSet is plumbing over them in the spirit of FrameDelta: the device buffers of one kept set.
 
     extend = importlib.import_module("pixel-art-raytracer_amd.tileset_extend")
 """
@@ -11,41 +11,24 @@ import sys
 
 import numpy as np
 
+from .abi import ABI_TILESET_EXTEND
 from .tileset import MAX_CELLS, n_cells
 from .types import ptr
 
 _par = sys.modules[__package__]  # the package module: its lib() is looked up at every call, as its own wrappers do
 
-_p, _i = C.c_void_p, C.c_int
-# include/par_tileset_extend.h, in the header's order; tests/test_tileset_extend_cpu.py holds the table to its prototypes
-ABI_TILESET_EXTEND = {
-    "par_tileset_extend_work_bytes": (C.c_size_t, [_i, _i]),
-    "par_tileset_extend_device": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p],
-    "par_tileset_extend_host": [_p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _p, _p],
-}
 ABI_TILESET_EXTEND_SYMBOLS = tuple(ABI_TILESET_EXTEND)
-
-_installed_on = None
 
 
 def lib():
-    """The package's library with ABI_TILESET_EXTEND set on its functions."""
-    global _installed_on
-    L = _par.lib()
-    if L is not _installed_on:
-        for name, sig in ABI_TILESET_EXTEND.items():
-            fn = getattr(L, name)
-            if type(sig) is tuple:
-                fn.restype, sig = sig
-            fn.argtypes = sig
-        _installed_on = L
-    return L
+    """The package's library: kept as a name for callers that reach the raw symbols through this module."""
+    return _par.lib()
 
 
 def tileset_extend_work_bytes(cells, capacity):
     """The bytes of the work block of a tileset_extend over `cells` cells into a set of `capacity` tiles
     (par_tileset_extend_work_bytes); 0 for cells outside [1, MAX_CELLS] or capacity outside [0, MAX_CELLS]."""
-    return lib().par_tileset_extend_work_bytes(cells, capacity)
+    return _par.lib().par_tileset_extend_work_bytes(cells, capacity)
 
 
 def tileset_extend(params, index, rows, tile, work, tiles, capacity, count, map_out=None, first_new_out=None, pad=0, flips=0,
@@ -56,7 +39,7 @@ def tileset_extend(params, index, rows, tile, work, tiles, capacity, count, map_
     tiles numbered from the count on; the count is updated, the new tiles below `capacity` are stored, the map (a uint32
     a cell) goes to map_out and the count as the call found it to first_new_out when given. `work` holds
     tileset_extend_work_bytes(cells, capacity) bytes and needs no preparation. Asynchronous on `stream`."""
-    _par._ok(lib().par_tileset_extend_device, C.byref(params), _par._dp(stream), _par._dp(index), rows[0], rows[1], tile[0],
+    _par._ok(_par.lib().par_tileset_extend_device, C.byref(params), _par._dp(stream), _par._dp(index), rows[0], rows[1], tile[0],
              tile[1], pad, flips, _par._dp(work), _par._dp(tiles), capacity, _par._dp(count), _par._dp(map_out),
              _par._dp(first_new_out))
 
@@ -80,7 +63,7 @@ def tileset_extend_host(params, index, tile, tiles, count, capacity, rows=None, 
     room[:len(stored)] = stored
     tile_map = np.zeros(cells, dtype=np.uint32)
     c_count, c_first = C.c_int(count), C.c_int(0)
-    _par._ok(lib().par_tileset_extend_host, C.byref(params), device, ptr(index), r0, r1, tile[0], tile[1], pad, flips,
+    _par._ok(_par.lib().par_tileset_extend_host, C.byref(params), device, ptr(index), r0, r1, tile[0], tile[1], pad, flips,
              ptr(room) if capacity > 0 else None, capacity, C.byref(c_count), ptr(tile_map), C.byref(c_first))
     kept = min(c_count.value, capacity)
     return {"tiles": room[:kept * size].reshape(kept, tile[1], tile[0]), "map": tile_map, "count": c_count.value,

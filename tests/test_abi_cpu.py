@@ -1,81 +1,127 @@
-"""CPU-side checks of the product library: it loads, exports every symbol include/par_raytracer.h declares, the
-host-side scene helpers match the reference's scene, and rendering without a GPU fails loudly (no fallback)."""
+"""CPU-side checks of the product library: it loads, exports every symbol the four headers of include/ declare and no
+other but the debug hooks, the binding's tables (pixel-art-raytracer_amd/abi.py) are the headers' prototypes and are all
+set when the library loads, the headers compile as pedantic C11 alone, twice and together in every order, the host-side
+scene helpers match the reference's scene, and rendering without a GPU fails loudly (no fallback)."""
 import ctypes
 import importlib
+import itertools
+import json
 import os
 import re
+import shutil
+import subprocess
+import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import headers
+
+ROOT = headers.ROOT
+MAIN = "par_raytracer.h"
+PROTOTYPES = {MAIN: 75, "par_cells.h": 3, "par_tileset.h": 5, "par_tileset_extend.h": 3}  # par.ABI_HEADERS, counted
 
 
 def test_exports_every_declared_symbol(par):
     L = par.lib()
-    header = open(os.path.join(ROOT, "include", "par_raytracer.h")).read()
-    declared = set(re.findall(r"^(?:const char\*|void|int)\s+(par_[a-z_0-9]+)\(", header, flags=re.M))
-    assert declared == set(par.ABI_SYMBOLS), declared ^ set(par.ABI_SYMBOLS)
-    for name in declared:
-        assert getattr(L, name) is not None
+    assert list(par.ABI_HEADERS) == list(PROTOTYPES) and par.ABI_HEADERS[MAIN] is par.ABI
+    for header, table in par.ABI_HEADERS.items():
+        declared = {name for _, name, _ in headers.prototypes(header)}
+        assert declared == set(table), (header, declared ^ set(table))
+        for name in declared:
+            assert getattr(L, name) is not None
+    assert par.ABI_SYMBOLS == tuple(par.ABI)
 
 
-def header_without_comments():
-    header = open(os.path.join(ROOT, "include", "par_raytracer.h")).read()
-    return re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-
-
-def signature(entry):
-    """(return type, argument types) of an entry of the binding's table: an int return is not written out there."""
-    return entry if isinstance(entry, tuple) else (ctypes.c_int, entry)
-
-
-RETURNS = {"int": ctypes.c_int, "void": None, "const char*": ctypes.c_char_p}
-SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "uint64_t": ctypes.c_uint64}
-
-
-def test_the_bindings_table_is_the_headers_prototypes(par):
-    """Every prototype of the header, its parameters in count, order and kind: the table lib() walks agrees, and so do
+@pytest.mark.parametrize("header", PROTOTYPES)
+def test_the_bindings_table_is_the_headers_prototypes(par, header):
+    """Every prototype of the header, its parameters in count, order and kind: the table install() walks agrees, and so do
     the argtypes and restypes that the loaded library's functions carry. A parameter type the mapping does not know fails
     here: a new scalar type is to be decided, not defaulted."""
-    protos = re.findall(r"^(const char\*|void|int)\s+(par_[a-z_0-9]+)\(([^;]*?)\);", header_without_comments(),
-                        flags=re.M | re.S)
-    assert len(protos) == 75 == len(par.ABI)
-    assert [name for _, name, _ in protos] == list(par.ABI) == list(par.ABI_SYMBOLS)  # the header's order
+    protos, table = headers.prototypes(header), par.ABI_HEADERS[header]
+    assert len(protos) == PROTOTYPES[header] == len(table)
+    assert [name for _, name, _ in protos] == list(table)  # the header's order
     L = par.lib()
-    for ret, name, params in protos:
-        want = []
-        for p in (" ".join(p.split()) for p in params.split(",")):
-            if p == "void":
-                assert params.strip() == "void"
-            elif "*" in p:
-                want.append(ctypes.c_void_p)
-            else:
-                kind, _ = p.rsplit(" ", 1)  # "<type> <name>"
-                assert kind in SCALARS, f"{name}: no ctypes type decided for a parameter `{p}`"
-                want.append(SCALARS[kind])
-        restype, argtypes = signature(par.ABI[name])
+    for proto in protos:
+        ret, name, _ = proto
+        want_restype, want = headers.want_signature(proto)
+        restype, argtypes = headers.signature(table[name])
         assert list(argtypes) == want, name
-        assert restype is RETURNS[ret], name
+        assert restype is want_restype, name
         fn = getattr(L, name)
-        assert list(fn.argtypes) == want and fn.restype is RETURNS[ret], name
+        assert list(fn.argtypes) == want and fn.restype is want_restype, name
         if ret == "int":
-            assert not isinstance(par.ABI[name], tuple), f"{name}: the default restype is not written out"
+            assert not isinstance(table[name], tuple), f"{name}: the default restype is not written out"
+        else:
+            assert isinstance(table[name], tuple), f"{name}: (restype, argument types)"
 
 
 def test_the_debug_hooks_are_apart_and_bound(par):
-    assert set(par.ABI_DEBUG_HOOKS) == {"par_debug_read_stamps", "par_debug_set_hooks", "par_debug_read_light_walks"}
-    assert not set(par.ABI_DEBUG_HOOKS) & set(par.ABI)
-    header = header_without_comments()
+    assert set(par.ABI_DEBUG_HOOKS) == {"par_debug_read_stamps", "par_debug_set_hooks", "par_debug_read_light_walks",
+                                        "par_debug_read_items"}
+    for header, table in par.ABI_HEADERS.items():
+        assert not set(par.ABI_DEBUG_HOOKS) & set(table)
+        plain = headers.without_comments(header)
+        for name in par.ABI_DEBUG_HOOKS:
+            assert name not in plain
     for name, entry in par.ABI_DEBUG_HOOKS.items():
-        assert name not in header
-        restype, argtypes = signature(entry)
+        restype, argtypes = headers.signature(entry)
         fn = getattr(par.lib(), name)
         assert list(fn.argtypes) == list(argtypes) and fn.restype is restype is ctypes.c_int
 
 
+def test_every_exported_symbol_is_in_exactly_one_table(par):
+    """The par_* functions the built library defines are the disjoint union of the four headers' tables and the hooks."""
+    nm = shutil.which("nm")
+    if nm is None:
+        pytest.skip("no nm to list the library's symbols")
+    out = subprocess.run([nm, "-D", "--defined-only", par.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = sorted(f[2] for f in (line.split() for line in out.splitlines())
+                      if len(f) == 3 and f[1] == "T" and f[2].startswith("par_"))
+    bound = [name for table in (*par.ABI_HEADERS.values(), par.ABI_DEBUG_HOOKS) for name in table]
+    assert len(bound) == len(set(bound)), "a symbol is in two tables"
+    assert exported == sorted(bound), set(exported) ^ set(bound)
+
+
+INSTALLED_AT_LOAD = r"""
+import ctypes, importlib, json, sys
+par = importlib.import_module("pixel-art-raytracer_amd")
+loaded = sorted(m for m in sys.modules if m.startswith("pixel-art-raytracer_amd."))
+L = par.lib()
+wrong, sized = [], []
+for table in (*par.ABI_HEADERS.values(), par.ABI_DEBUG_HOOKS):
+    for name, sig in table.items():
+        restype, argtypes = sig if type(sig) is tuple else (ctypes.c_int, sig)
+        fn = getattr(L, name)
+        if fn.argtypes is None or list(fn.argtypes) != list(argtypes) or fn.restype is not restype:
+            wrong.append(name)
+        if fn.restype is ctypes.c_size_t:
+            sized.append(name)
+print(json.dumps({"loaded": loaded, "wrong": wrong, "size_t": sized}))
+"""
+
+
+def test_every_table_is_installed_at_load(par):
+    """A fresh interpreter that imports the package alone and calls lib(): every function of every table carries its
+    table's types, the two size_t returns of the side headers among them, with no side module imported."""
+    p = subprocess.run([sys.executable, "-c", INSTALLED_AT_LOAD], cwd=ROOT, capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr
+    got = json.loads(p.stdout.strip().splitlines()[-1])
+    assert got["loaded"] == ["pixel-art-raytracer_amd.abi", "pixel-art-raytracer_amd.types"]
+    assert got["wrong"] == []
+    assert got["size_t"] == ["par_tileset_work_bytes", "par_tileset_extend_work_bytes"]
+
+
+def test_the_hip_runtime_is_one_handle(par):
+    pytest.importorskip("torch")
+    hip = par.hip_runtime()
+    assert par.hip_runtime() is hip
+    assert len(hip.hipMemcpyAsync.argtypes) == 5 and len(hip.hipStreamSynchronize.argtypes) == 1
+    assert len(hip.hipGetDevice.argtypes) == 1
+
+
 def test_constants_are_the_headers(par):
-    header = header_without_comments()
+    header = headers.without_comments(MAIN)
     status = re.search(r"typedef enum par_status \{(.*?)\} par_status;", header, flags=re.S).group(1)
     assert {int(v): k for k, v in re.findall(r"(PAR_\w+) = (\d+)", status)} == par.STATUS_NAMES
     assert par.PAR_OK == 0 and par.STATUS_NAMES[0] == "PAR_OK"
@@ -162,13 +208,10 @@ def test_no_gpu_means_loud_failure(par, T):
     assert e.value.status == 2  # PAR_ERR_NO_DEVICE: there is no CPU rendering path
 
 
-def test_headers_are_plain_c(tmp_path):
-    """include/*.h is a C ABI: it must compile as C11 (no C++), and a C program must link against the library."""
-    import subprocess
-    src = tmp_path / "abi.c"
-    src.write_text(r'''
+# header -> (a C program that calls into it, the first words of what it prints)
+PLAIN_C = {
+    MAIN: (r'''
 #include <stdio.h>
-#include "par_raytracer.h"
 int main(void) {
     par_params p;
     int gx, gy, gz;
@@ -181,18 +224,66 @@ int main(void) {
     printf("%zu %zu %zu\n", sizeof(par_params), sizeof(par_frame_stats), sizeof(par_outputs));
     return 0;
 }
-''')
-    exe = tmp_path / "abi"
-    lib_dir = os.path.join(ROOT, "pixel-art-raytracer_amd", "lib")
-    p = subprocess.run(["gcc", "-std=c11", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"),
-                        str(src), "-o", str(exe), "-L", lib_dir, "-lpar_raytracer", f"-Wl,-rpath,{lib_dir}"],
-                       capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr
-    out = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert out.returncode == 0
-    assert out.stdout.split()[:7] == ["12", "8", "8", "19", "28", "16", "16000"]
+''', ["12", "8", "8", "19", "28", "16", "16000"]),
+    "par_cells.h": (r'''
+#include <stdio.h>
+int main(void) {
+    par_color in[3] = {{1, 2, 3, 4}, {5, 6, 7, 8}, {9, 10, 11, 12}}, out[6];
+    int n = par_cells_pairs(in, 3, out, 6);
+    printf("%d %d %d %d\n", n, out[1].red, out[4].red, out[5].alpha);
+    return par_quantize_cells_host(0, -1, in, 1, 3, 8, 8, 0, in, 0, 1, out, 0, 0) == 1 ? 0 : 1;
+}
+''', ["3", "5", "5", "12"]),
+    "par_tileset.h": (r'''
+#include <stdio.h>
+int main(void) {
+    uint8_t plane[64] = {0};
+    uint32_t map[1];
+    int count = -5;
+    printf("%lu %lu %d\n", (unsigned long)par_tileset_work_bytes(3), (unsigned long)par_tileset_work_bytes(0),
+           PAR_TILESET_MAX_CELLS);
+    return par_tileset_build_host(0, -1, plane, 0, 8, 8, 8, 0, 3, 0, 0, map, &count) == 1 && count == -5 ? 0 : 1;
+}
+''', [str(4096 + 48 + 32), "0", str(1 << 20)]),
+    "par_tileset_extend.h": (r'''
+#include <stdio.h>
+int main(void) {
+    uint8_t plane[64] = {0};
+    uint32_t map[1];
+    int count = -5, first_new = -7;
+    printf("%lu %lu %lu\n", (unsigned long)par_tileset_extend_work_bytes(3, 2), (unsigned long)par_tileset_extend_work_bytes(0, 2),
+           (unsigned long)par_tileset_extend_work_bytes(3, -1));
+    return par_tileset_extend_host(0, -1, plane, 0, 8, 8, 8, 0, 3, 0, 0, &count, map, &first_new) == 1 && count == -5 &&
+                   first_new == -7
+               ? 0
+               : 1;
+}
+''', [str(4096 + 48 + 4 * 16 + 8), "0", "0"]),
+}
+
+
+def test_headers_are_plain_c(tmp_path):
+    """include/*.h is a C ABI: it must compile as C11 (no C++), and a C program must link against the library."""
+    body, first = PLAIN_C[MAIN]
+    out = headers.compile_and_run(tmp_path, [MAIN], body)
+    assert out.split()[:7] == first
     # the ctypes mirrors of the structures are laid out as the header's
     import ctypes as C
     T = importlib.import_module("pixel-art-raytracer_amd.types")
-    assert [int(v) for v in out.stdout.splitlines()[1].split()] == [C.sizeof(T.Params), C.sizeof(T.FrameStats),
-                                                                   C.sizeof(T.Outputs)]
+    assert [int(v) for v in out.splitlines()[1].split()] == [C.sizeof(T.Params), C.sizeof(T.FrameStats),
+                                                             C.sizeof(T.Outputs)]
+
+
+@pytest.mark.parametrize("header", PROTOTYPES)
+def test_every_header_is_plain_c_in_any_company(tmp_path, header):
+    """The header alone, twice, and the four together in each of their 24 orders, as pedantic C11; the header's program
+    links and prints the same every time."""
+    assert sorted(PLAIN_C) == sorted(PROTOTYPES) == sorted(h for h in os.listdir(headers.INCLUDE) if h != "par_types.h")
+    body, first = PLAIN_C[header]
+    orders = {"alone": [header], "twice": [header, header]}
+    orders.update((f"order{k}", list(order)) for k, order in enumerate(itertools.permutations(PROTOTYPES)))
+    assert len(orders) == 26
+    for tag, includes in orders.items():
+        words = headers.compile_and_run(tmp_path, includes, body, tag).split()
+        # (par_raytracer.h's program goes on with the text of a status and the sizes test_headers_are_plain_c reads)
+        assert words[:len(first)] == first and (header == MAIN or len(words) == len(first)), (tag, words)

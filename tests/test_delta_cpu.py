@@ -6,13 +6,13 @@ stand-alone program); the numpy models the GPU tests lean on (tests/delta.py) eq
 inputs reach what they are named for."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
 import delta as D
+import headers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "pixel-art-raytracer_amd", "csrc")
@@ -34,15 +34,7 @@ DECLARATIONS = {
 
 
 def test_declared_exported_and_bound(par):
-    header = open(os.path.join(ROOT, "include", "par_raytracer.h")).read()
-    for name, args in DECLARATIONS.items():
-        m = re.search(r"^int\s+%s\(([^;]*)\);" % name, header, flags=re.M)
-        assert m, f"{name} is not declared with an int return type"
-        assert " ".join(m.group(1).split()) == args, name
-        assert name in par.ABI_SYMBOLS
-        assert getattr(par.lib(), name) is not None
-    for fn in ("tiles_changed", "tiles_pack_counted", "tiles_fetch", "tiles_apply_host"):
-        assert callable(getattr(par, fn))
+    headers.assert_declared(par, "par_raytracer.h", DECLARATIONS, ("tiles_changed", "tiles_pack_counted", "tiles_fetch", "tiles_apply_host"))
     FD = __import__("importlib").import_module("pixel-art-raytracer_amd.delta")
     for fn in ("first", "update"):
         assert callable(getattr(FD.FrameDelta, fn))

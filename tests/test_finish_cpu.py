@@ -5,13 +5,13 @@ call's rows into launches, which this call shares with par_outline_device, holds
 (tests/tile_row_cuts_check.cpp, a stand-alone program)."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
 import finish as F
+import headers
 import outline as O
 import present as P
 import quantize as Q
@@ -32,15 +32,7 @@ DECLARATIONS = {
 
 
 def test_declared_exported_and_bound(par):
-    header = open(os.path.join(ROOT, "include", "par_raytracer.h")).read()
-    for name, args in DECLARATIONS.items():
-        m = re.search(r"^int\s+%s\(([^;]*)\);" % name, header, flags=re.M)
-        assert m, f"{name} is not declared with an int return type"
-        assert " ".join(m.group(1).split()) == args, name
-        assert name in par.ABI_SYMBOLS
-        assert getattr(par.lib(), name) is not None
-    for fn in ("finish", "finish_host"):
-        assert callable(getattr(par, fn))
+    headers.assert_declared(par, "par_raytracer.h", DECLARATIONS, ("finish", "finish_host"))
 
 
 # ---- argument errors: no device needed, nothing written -----------------------------------------------------------

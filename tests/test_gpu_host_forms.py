@@ -3,7 +3,6 @@ palette: a device index past the last device is PAR_ERR_INVALID_ARG and nothing 
 device, byte for byte; and the call makes its device the current one and leaves it so (it does not restore). That last
 half shows only where there are two GPUs: with one, the current device is the same before and after either way."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -17,10 +16,8 @@ FORMS = ("outline", "quantize", "present", "finish", "upscale")
 
 
 @pytest.fixture(scope="module")
-def hip():
-    import torch
-    bundled = os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so")
-    return C.CDLL(bundled if os.path.exists(bundled) else "libamdhip64.so")
+def hip(par):
+    return par.hip_runtime()
 
 
 def current_device(hip):

@@ -63,8 +63,7 @@ def frame(shape, with_ids):
 
 def read_items(par, r):
     """The entry items of the context's last frame, eight words each."""
-    fn = par.lib().par_debug_read_items
-    fn.argtypes, fn.restype = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p], C.c_int
+    fn = par.lib().par_debug_read_items  # typed by the binding's table (ABI_DEBUG_HOOKS)
     n = C.c_int(0)
     assert fn(r._ctx, None, 0, C.byref(n)) == 0
     items = np.zeros((n.value, 8), dtype=np.uint32)

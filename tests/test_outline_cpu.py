@@ -9,6 +9,7 @@ import re
 import numpy as np
 import pytest
 
+import headers
 import outline as O
 from helpers import random_stage_scene
 
@@ -26,15 +27,7 @@ DECLARATIONS = {
 
 
 def test_declared_exported_and_bound(par, T):
-    header = open(os.path.join(ROOT, "include", "par_raytracer.h")).read()
-    for name, args in DECLARATIONS.items():
-        m = re.search(r"^int\s+%s\(([^;]*)\);" % name, header, flags=re.M)
-        assert m, f"{name} is not declared with an int return type"
-        assert " ".join(m.group(1).split()) == args, name
-        assert name in par.ABI_SYMBOLS
-        assert getattr(par.lib(), name) is not None
-    for fn in ("outline", "outline_host"):
-        assert callable(getattr(par, fn))
+    headers.assert_declared(par, "par_raytracer.h", DECLARATIONS, ("outline", "outline_host"))
     types = open(os.path.join(ROOT, "include", "par_types.h")).read()
     m = re.search(r"typedef struct par_outline_style \{([^}]*)\} par_outline_style;", types)
     assert m and re.findall(r"int32_t\s+(\w+);", m.group(1)) == ["depth_step", "silhouette_scale", "crease_scale"]

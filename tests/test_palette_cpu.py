@@ -5,12 +5,12 @@ consequences the contract states hold; and on the tinted graybox frame a fitted 
 the frame than the ramp, in sum and at the worst pixel."""
 import ctypes as C
 import os
-import re
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
+import headers
 import palette as P
 import quantize as Q
 
@@ -31,15 +31,7 @@ DECLARATIONS = {
 
 
 def test_declared_exported_and_bound(par):
-    header = open(os.path.join(ROOT, "include", "par_raytracer.h")).read()
-    for name, args in DECLARATIONS.items():
-        m = re.search(r"^int\s+%s\(([^;]*)\);" % name, header, flags=re.M)
-        assert m, f"{name} is not declared with an int return type"
-        assert " ".join(m.group(1).split()) == args, name
-        assert name in par.ABI_SYMBOLS
-        assert getattr(par.lib(), name) is not None
-    for fn in ("palette_reset", "palette_count", "palette_cut", "palette_sum", "palette_emit", "palette_fit_host"):
-        assert callable(getattr(par, fn))
+    headers.assert_declared(par, "par_raytracer.h", DECLARATIONS, ("palette_reset", "palette_count", "palette_cut", "palette_sum", "palette_emit", "palette_fit_host"))
 
 
 def test_the_mirror_has_the_headers_layout(T, tmp_path):

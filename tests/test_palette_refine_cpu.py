@@ -6,12 +6,12 @@ states hold: the summed L1 error never rises from round to round, a fixed point 
 back exactly, and on the tinted graybox frame the error falls as the contract's authors measured it."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
+import headers
 import palette as P
 import palette_refine as R
 import quantize as Q
@@ -29,15 +29,7 @@ DECLARATIONS = {
 
 
 def test_declared_exported_and_bound(par):
-    header = open(os.path.join(ROOT, "include", "par_raytracer.h")).read()
-    for name, args in DECLARATIONS.items():
-        m = re.search(r"^int\s+%s\(([^;]*)\);" % name, header, flags=re.M)
-        assert m, f"{name} is not declared with an int return type"
-        assert " ".join(m.group(1).split()) == args, name
-        assert name in par.ABI_SYMBOLS
-        assert getattr(par.lib(), name) is not None
-    for fn in ("palette_refine_device", "palette_refine_host"):
-        assert callable(getattr(par, fn))
+    headers.assert_declared(par, "par_raytracer.h", DECLARATIONS, ("palette_refine_device", "palette_refine_host"))
 
 
 def test_the_mirror_has_the_headers_layout(T, tmp_path):

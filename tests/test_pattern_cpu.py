@@ -5,18 +5,16 @@ equals a per-pixel, per-entry, per-candidate loop over every depth, the strength
 hold; and on the tinted graybox frame the 4 x 4 block error of pattern dithering lies below that of every ordered spread
 tried, with the exact figures of the model."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
+import headers
 import palette as P
 import palette_refine as R
 import pattern as D
 import quantize as Q
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_INVALID_ARG = 1
 
 DECLARATIONS = {
@@ -30,15 +28,7 @@ DECLARATIONS = {
 
 
 def test_declared_exported_and_bound(par):
-    header = open(os.path.join(ROOT, "include", "par_raytracer.h")).read()
-    for name, args in DECLARATIONS.items():
-        m = re.search(r"^int\s+%s\(([^;]*)\);" % name, header, flags=re.M)
-        assert m, f"{name} is not declared with an int return type"
-        assert " ".join(m.group(1).split()) == args, name
-        assert name in par.ABI_SYMBOLS
-        assert getattr(par.lib(), name) is not None
-    for fn in ("quantize_pattern", "quantize_pattern_host"):
-        assert callable(getattr(par, fn))
+    headers.assert_declared(par, "par_raytracer.h", DECLARATIONS, ("quantize_pattern", "quantize_pattern_host"))
 
 
 # ---- argument errors: no device needed, nothing written -----------------------------------------------------------

@@ -8,13 +8,13 @@ FrameDelta and TileGather with their default arguments still resolve to the 4-by
 import ctypes as C
 import importlib
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
 import delta as D
+import headers
 import plane_tiles as P
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,15 +47,7 @@ BINDINGS = ("plane_tiles_changed", "plane_tiles_pack", "plane_tiles_pack_counted
 
 
 def test_declared_exported_and_bound(par):
-    header = open(os.path.join(ROOT, "include", "par_raytracer.h")).read()
-    for name, args in DECLARATIONS.items():
-        m = re.search(r"^int\s+%s\(([^;]*)\);" % name, header, flags=re.M)
-        assert m, f"{name} is not declared with an int return type"
-        assert " ".join(m.group(1).split()) == args, name
-        assert name in par.ABI_SYMBOLS
-        assert getattr(par.lib(), name) is not None
-    for fn in BINDINGS:
-        assert callable(getattr(par, fn))
+    headers.assert_declared(par, "par_raytracer.h", DECLARATIONS, BINDINGS)
 
 
 # ---- argument errors: no device needed, nothing written -------------------------------------------------------------

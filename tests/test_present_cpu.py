@@ -8,6 +8,7 @@ import re
 import numpy as np
 import pytest
 
+import headers
 import present as P
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,15 +25,7 @@ DECLARATIONS = {
 
 
 def test_declared_exported_and_bound(par, T):
-    header = open(os.path.join(ROOT, "include", "par_raytracer.h")).read()
-    for name, args in DECLARATIONS.items():
-        m = re.search(r"^int\s+%s\(([^;]*)\);" % name, header, flags=re.M)
-        assert m, f"{name} is not declared with an int return type"
-        assert " ".join(m.group(1).split()) == args, name
-        assert name in par.ABI_SYMBOLS
-        assert getattr(par.lib(), name) is not None
-    for fn in ("present", "present_host", "make_present_desc"):
-        assert callable(getattr(par, fn))
+    headers.assert_declared(par, "par_raytracer.h", DECLARATIONS, ("present", "present_host", "make_present_desc"))
     assert (par.PRESENT_RGBA, par.PRESENT_BGRA, par.MAX_SCALE) == (0, 1, 16) == (P.RGBA, P.BGRA, T.MAX_SCALE)
 
 

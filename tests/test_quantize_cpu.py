@@ -2,15 +2,13 @@
 quantise calls comes back before any device work and with nothing written; par_palette_ramp equals its restatement
 (quantize.ramp) byte for byte; and the vectorised model the GPU tests lean on (quantize.model) equals a per-pixel loop."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
+import headers
 import quantize as Q
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_INVALID_ARG = 1
 
 DECLARATIONS = {
@@ -23,15 +21,7 @@ DECLARATIONS = {
 
 
 def test_declared_exported_and_bound(par):
-    header = open(os.path.join(ROOT, "include", "par_raytracer.h")).read()
-    for name, args in DECLARATIONS.items():
-        m = re.search(r"^int\s+%s\(([^;]*)\);" % name, header, flags=re.M)
-        assert m, f"{name} is not declared with an int return type"
-        assert " ".join(m.group(1).split()) == args, name
-        assert name in par.ABI_SYMBOLS
-        assert getattr(par.lib(), name) is not None
-    for fn in ("quantize", "quantize_host", "palette_ramp"):
-        assert callable(getattr(par, fn))
+    headers.assert_declared(par, "par_raytracer.h", DECLARATIONS, ("quantize", "quantize_host", "palette_ramp"))
 
 
 # ---- argument errors: no device needed, nothing written -----------------------------------------------------------

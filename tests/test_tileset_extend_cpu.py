@@ -1,6 +1,6 @@
 """Shared tile sets without a GPU: the three calls are declared in include/par_tileset_extend.h (and in no other
-header), exported and bound by the tileset_extend module, whose table is held to the header's prototypes by the method of
-tests/test_tileset_cpu.py; the header compiles as pedantic C11 alone, twice and beside the other three; every
+header), exported and wrapped by the tileset_extend module (tests/test_abi_cpu.py holds the binding's table to the header's
+prototypes and compiles the header as pedantic C11 alone, twice and beside the other three in any order); every
 PAR_ERR_INVALID_ARG of both calls comes back before any device work and with nothing written, each rule on its own;
 par_tileset_extend_work_bytes is the header's formula and keeps its bound; the vectorised model the GPU tests lean on
 (tileset_extend.model) equals a per-cell loop with one dict on random sequences and on crafted sets worked out by hand; the
@@ -9,12 +9,12 @@ consequences the contract states hold; and the host form's copy arithmetic holds
 import ctypes as C
 import importlib
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
+import headers
 import tileset as TS
 import tileset_extend as TX
 
@@ -29,66 +29,27 @@ def ext(par):
     return importlib.import_module("pixel-art-raytracer_amd.tileset_extend")
 
 
-def header_without_comments(name=HEADER):
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
-
-
 # ---- declared, exported, bound -------------------------------------------------------------------------------------
 
 def test_declared_exported_and_bound(par, ext):
-    protos = re.findall(r"^(?:int|size_t)\s+(par_[a-z_0-9]+)\(", header_without_comments(), flags=re.M)
-    assert tuple(protos) == SYMBOLS == tuple(ext.ABI_TILESET_EXTEND) == ext.ABI_TILESET_EXTEND_SYMBOLS
+    assert tuple(name for _, name, _ in headers.prototypes(HEADER)) == SYMBOLS
+    assert SYMBOLS == tuple(ext.ABI_TILESET_EXTEND) == ext.ABI_TILESET_EXTEND_SYMBOLS
+    assert ext.ABI_TILESET_EXTEND is par.ABI_HEADERS[HEADER]
     for other in ("par_raytracer.h", "par_cells.h", "par_tileset.h", "par_types.h"):
-        assert "par_tileset_extend" not in open(os.path.join(ROOT, "include", other)).read()
-    plain = header_without_comments()
-    assert re.findall(r'#include "([^"]+)"', plain) == ["par_types.h"]
-    cells = importlib.import_module("pixel-art-raytracer_amd.cells")
+        assert "par_tileset_extend" not in headers.text(other)
+    wrappers = ("tileset_extend_work_bytes", "tileset_extend", "tileset_extend_host", "SharedTileSet")
+    headers.assert_apart(par, HEADER, ext, wrappers)
     tileset = importlib.import_module("pixel-art-raytracer_amd.tileset")
-    for name in SYMBOLS:
-        for table in (par.ABI, par.ABI_DEBUG_HOOKS, cells.ABI_CELLS, tileset.ABI_TILESET):
-            assert name not in table
-        assert getattr(par.lib(), name) is not None
-    for fn in ("tileset_extend_work_bytes", "tileset_extend", "tileset_extend_host", "SharedTileSet"):
-        # (the package has the submodule itself under the name tileset_extend: a module, no wrapper)
-        assert callable(getattr(ext, fn)) and not callable(getattr(par, fn, None)) and not hasattr(tileset, fn)
+    assert not any(hasattr(tileset, fn) for fn in wrappers)
     # the contract's headings, and what is left out on purpose, are in the header
-    text = open(os.path.join(ROOT, "include", HEADER)).read()
+    text = headers.text(HEADER)
     for word in ("removing tiles", "lossy merging", "persists between calls", "rotations", "torch.distributed", "2^30",
                  "low 30 bits", "Overflow", "Merge"):
         assert word in text, word
 
 
-RETURNS = {"int": C.c_int, "size_t": C.c_size_t}
-
-
-def test_the_table_is_the_headers_prototypes(par, ext):
-    protos = re.findall(r"^(size_t|int)\s+(par_[a-z_0-9]+)\(([^;]*?)\);", header_without_comments(), flags=re.M | re.S)
-    assert len(protos) == 3 == len(ext.ABI_TILESET_EXTEND)
-    assert [name for _, name, _ in protos] == list(ext.ABI_TILESET_EXTEND)  # the header's order
-    L = ext.lib()
-    assert L is par.lib()
-    for ret, name, params in protos:
-        want = []
-        for p in (" ".join(p.split()) for p in params.split(",")):
-            if "*" in p:
-                want.append(C.c_void_p)
-            else:
-                kind, _ = p.rsplit(" ", 1)
-                assert kind == "int", f"{name}: no ctypes type decided for a parameter `{p}`"
-                want.append(C.c_int)
-        entry = ext.ABI_TILESET_EXTEND[name]
-        if ret == "int":
-            assert not isinstance(entry, tuple), f"{name}: the default restype is not written out"
-        else:
-            assert isinstance(entry, tuple) and entry[0] is RETURNS[ret], f"{name}: (restype, argument types)"
-            entry = entry[1]
-        assert list(entry) == want, name
-        fn = getattr(L, name)
-        assert list(fn.argtypes) == want and fn.restype is RETURNS[ret], name
-
-
 def test_the_prototypes_are_the_contracts():
-    header = " ".join(header_without_comments().split())
+    header = " ".join(headers.without_comments(HEADER).split())
     for proto in (
             "size_t par_tileset_extend_work_bytes(int n_cells, int capacity);",
             "int par_tileset_extend_device(const par_params* params, void* stream, const uint8_t* index, int row_begin, "
@@ -98,39 +59,6 @@ def test_the_prototypes_are_the_contracts():
             "int row_end, int tile_w, int tile_h, int pad, int flips, uint8_t* tiles, int capacity, int* count, "
             "uint32_t* map_out, int* first_new_out);"):
         assert proto in header, proto
-
-
-def test_the_header_is_plain_c(tmp_path):
-    """par_tileset_extend.h alone, twice, and beside the other three headers in a few orders (first, last, in the middle),
-    as pedantic C11; a C program links the host arithmetic and gets an argument error with `count` untouched."""
-    lib_dir = os.path.join(ROOT, "pixel-art-raytracer_amd", "lib")
-    others = ["par_tileset.h", "par_raytracer.h", "par_cells.h"]
-    orders = {"alone": [HEADER], "twice": [HEADER, HEADER], "first": [HEADER] + others, "last": others + [HEADER],
-              "middle": ["par_cells.h", HEADER, "par_raytracer.h", "par_tileset.h"],
-              "reversed": ["par_cells.h", "par_raytracer.h", HEADER, "par_tileset.h"]}
-    for tag, order in orders.items():
-        src = tmp_path / f"{tag}.c"
-        src.write_text("".join(f'#include "{n}"\n' for n in order) + r'''
-#include <stdio.h>
-int main(void) {
-    uint8_t plane[64] = {0};
-    uint32_t map[1];
-    int count = -5, first_new = -7;
-    printf("%lu %lu %lu\n", (unsigned long)par_tileset_extend_work_bytes(3, 2), (unsigned long)par_tileset_extend_work_bytes(0, 2),
-           (unsigned long)par_tileset_extend_work_bytes(3, -1));
-    return par_tileset_extend_host(0, -1, plane, 0, 8, 8, 8, 0, 3, 0, 0, &count, map, &first_new) == 1 && count == -5 &&
-                   first_new == -7
-               ? 0
-               : 1;
-}
-''')
-        exe = tmp_path / tag
-        p = subprocess.run(["gcc", "-std=c11", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"),
-                            str(src), "-o", str(exe), "-L", lib_dir, "-lpar_raytracer", f"-Wl,-rpath,{lib_dir}"],
-                           capture_output=True, text=True)
-        assert p.returncode == 0, (tag, p.stderr)
-        out = subprocess.run([str(exe)], capture_output=True, text=True)
-        assert out.returncode == 0 and out.stdout.split() == [str(4096 + 48 + 4 * 16 + 8), "0", "0"], (tag, out.stdout)
 
 
 # ---- par_tileset_extend_work_bytes -------------------------------------------------------------------------------------

@@ -9,6 +9,7 @@ import re
 import numpy as np
 import pytest
 
+import headers
 import present as P
 import upscale as U
 
@@ -26,15 +27,7 @@ DECLARATIONS = {
 
 
 def test_declared_exported_and_bound(par, T):
-    header = open(os.path.join(ROOT, "include", "par_raytracer.h")).read()
-    for name, args in DECLARATIONS.items():
-        m = re.search(r"^int\s+%s\(([^;]*)\);" % name, header, flags=re.M)
-        assert m, f"{name} is not declared with an int return type"
-        assert " ".join(m.group(1).split()) == args, name
-        assert name in par.ABI_SYMBOLS
-        assert getattr(par.lib(), name) is not None
-    for fn in ("upscale", "upscale_host", "make_upscale_desc"):
-        assert callable(getattr(par, fn))
+    headers.assert_declared(par, "par_raytracer.h", DECLARATIONS, ("upscale", "upscale_host", "make_upscale_desc"))
     assert (par.UPSCALE_SCALE2X, par.UPSCALE_SCALE3X, par.UPSCALE_SCALE4X) == (2, 3, 4)
     assert (T.UPSCALE_SCALE2X, T.UPSCALE_SCALE3X, T.UPSCALE_SCALE4X) == (2, 3, 4)
 

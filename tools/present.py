@@ -10,7 +10,6 @@ alternate with the kernel's. Prints one JSON line.
 Each size is measured in a child process of its own under a time limit; the first child that fails or runs out of time
 ends the run (nothing is tried again)."""
 import argparse
-import ctypes
 import importlib
 import json
 import os
@@ -58,10 +57,7 @@ def measure(w, h, batches):
     out = torch.zeros(4 * n * max(sx * sy for sx, sy in scales), dtype=torch.uint8, device="cuda")
     stream = torch.cuda.Stream()
     copy_to = torch.empty_like(fb)
-    # the HIP runtime this process already holds (torch's own copy where it ships one)
-    bundled = os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so")
-    hip = ctypes.CDLL(bundled if os.path.exists(bundled) else "libamdhip64.so")
-    hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
+    hip = par.hip_runtime()
     device_to_device = 3  # hipMemcpyDeviceToDevice
     torch.cuda.synchronize()
     rows = []

@@ -23,9 +23,7 @@ r.render_device(ptrs, stream=s, flags=1 << 29)  # the stamped frame
 torch.cuda.synchronize()
 n = 6 * 8192 * 8
 buf = np.zeros(n, dtype=np.uint64)
-L_ = par.lib()
-L_.par_debug_read_stamps.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-rc = L_.par_debug_read_stamps(r._ctx, buf.ctypes.data_as(C.c_void_p), n)
+rc = par.lib().par_debug_read_stamps(r._ctx, buf.ctypes.data_as(C.c_void_p), n)
 assert rc == 0, rc
 st = buf.reshape(6, 8192, 8).astype(np.float64) * 0.01  # us (100 MHz)
 ncol = int(r.stats().occupied_columns)
