@@ -57,7 +57,23 @@ enum {
     PAR_RENDER_PIPELINED = 1u << 2,
     /* par_render_device_timed only: time the frame's launches AS A PRODUCTION FRAME MAKES THEM (the background fill
      * riding with the hash-build and column launches) into par_frame_stats.ms_launch, instead of the kernels apart. */
-    PAR_RENDER_TIMED_AS_LAUNCHED = 1u << 3
+    PAR_RENDER_TIMED_AS_LAUNCHED = 1u << 3,
+    /* par_render_device, par_render_device_timed, par_render_device_slots: the caller promises that
+     *   - the planes passed in this call are the ones this context's most recent frame was rendered into,
+     *   - the rows are the same as in that frame, and
+     *   - nothing has written to those rows of those planes since.
+     * The frame then sets back to background only the tiles that frame can have drawn into (the device's own record of
+     * its hash build; the scene may have changed in between) instead of filling every pixel; the `fb` and `palidx`
+     * planes alone are concerned, and the result is the same frame. The library keeps a record of the context's last
+     * enqueued frame (plane pointers, which of the two planes were given, the rows) and takes this path only when the
+     * record matches; otherwise the flag is ignored and the frame fills as without it, so a caller whose promise holds
+     * whenever the record matches may always set it. The record is dropped by par_graph_launch and the graph captures,
+     * the relight calls, par_render / par_render_rows / par_pick (they render into the context's own buffers), a
+     * reported PAR_ERR_DEVICE, any failed enqueue, and a frame timed with its kernels apart; a captured graph never
+     * takes this path, and every other entry point accepts the flag and ignores it. What the library cannot see is a
+     * write by somebody else:
+     * two contexts drawing into one buffer, or a consumer that post-processes the frame in place, must not set it. */
+    PAR_RENDER_KEPT_OUTPUTS = 0x10u /* bit 4 */
     /* other bits are rejected; bit 29 is reserved for the library's profiling time stamps */
 };
 

@@ -32,6 +32,9 @@ RENDER_TRACE_BACKGROUND = 1 << 0
 RENDER_COUNT_RAYS = 1 << 1
 RENDER_PIPELINED = 1 << 2
 RENDER_TIMED_AS_LAUNCHED = 1 << 3
+# The planes are the ones this context's last frame was rendered into, same rows, untouched since (par_raytracer.h):
+# the frame clears that frame's tiles instead of filling every pixel. Ignored wherever the library's record disagrees.
+RENDER_KEPT_OUTPUTS = 1 << 4
 
 ABI_SYMBOLS = tuple(ABI)  # every symbol include/par_raytracer.h declares
 MAX_LIGHTS = 8  # PAR_MAX_LIGHTS

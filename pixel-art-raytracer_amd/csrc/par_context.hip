@@ -42,6 +42,16 @@ struct par_context {
         int r0 = 0, r1 = 0, set = 0;
         bool host_gbuf = false;
     } kept;
+    // The drawn-into record (PAR_RENDER_KEPT_OUTPUTS): the frame and palette-index planes, the rows and the grid set of
+    // the last frame par_render_device[_timed] enqueued as a production frame makes its launches, while the other grid
+    // set still holds that frame's node list. Unlike `kept` it outlives a change of the scene: the next build's wipe
+    // walks the nodes of the frame that was drawn, whatever the scene has become since.
+    struct {
+        bool valid = false;
+        const void* fb = nullptr;
+        const void* palidx = nullptr;
+        int r0 = 0, r1 = 0, set = 0;
+    } drawn;
     hipStream_t last_stream = nullptr;  // stream of the most recent asynchronous render (scene updates wait for it)
     bool has_last_stream = false;
 
@@ -123,6 +133,9 @@ enum : int {
 namespace {
 
 constexpr size_t kPlaneElem[5] = {sizeof(par_color), sizeof(par_pixel), 1, sizeof(float), 1};
+// A frame takes the kept path (PAR_RENDER_KEPT_OUTPUTS) only while its column bound is at most this share of the tiles
+// of its rows (measured).
+constexpr int64_t kKeptMaxTilesPct = 50;
 
 int fail(par_context* c, int status, const std::string& msg) {
     if (c) {
@@ -161,6 +174,18 @@ void retain_frame(par_context* c, int row_begin, int row_end, int set, bool host
     c->kept.host_gbuf = host_gbuf;
 }
 void drop_retained(par_context* c) { c->kept.valid = false; }
+
+// The drawn-into record: made where a frame is retained (the frame of grid set `set` was enqueued whole, into `out`),
+// dropped wherever something else may have written the planes or the other set's node list is no longer that frame's.
+void record_drawn(par_context* c, const par_outputs& out, int row_begin, int row_end, int set) {
+    c->drawn.valid = true;
+    c->drawn.fb = out.fb;
+    c->drawn.palidx = out.palidx;
+    c->drawn.r0 = row_begin;
+    c->drawn.r1 = row_end;
+    c->drawn.set = set;
+}
+void drop_drawn(par_context* c) { c->drawn.valid = false; }
 
 int hip_fail(par_context* c, hipError_t e, const char* what) {
     return fail(c, e == hipErrorOutOfMemory ? PAR_ERR_OOM : PAR_ERR_HIP,
@@ -239,6 +264,7 @@ int reset_grid(par_context* ctx) {
     PAR_HIP(hipMemsetAsync(ctx->grid.node_counter, 0, 2 * sizeof(int32_t), ctx->stream));
     PAR_HIP(hipStreamSynchronize(ctx->stream));
     ctx->set = 0;
+    drop_drawn(ctx);  // (the node list of the last frame is gone: nothing says which tiles it drew into)
     return PAR_OK;
 }
 
@@ -397,6 +423,7 @@ int check_device_error(par_context* ctx) {
     if (word == 0) return PAR_OK;
     PAR_HIP(hipMemset(ctx->grid.counters + PAR_CNT_ERROR, 0, sizeof(word)));
     drop_retained(ctx);
+    drop_drawn(ctx);
     std::string what;
     if (word & PAR_DEVERR_BARRIER) {
         what += "the hash build's barrier timed out (a build workgroup never arrived); ";
@@ -489,7 +516,12 @@ int enqueue_lights_frame(par_context* ctx, hipStream_t stream, const par_bin_arg
 // Enqueue one frame (alt:690-760) on `stream` using grid set `set`.
 int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, int row_end, const par_outputs& out,
                   unsigned flags, bool graph_mode, hipEvent_t* ev) {
+    // PAR_RENDER_KEPT_OUTPUTS holds only against the record of this context's last frame: the same frame and
+    // palette-index planes (given or not), the same rows, drawn by the frame whose nodes this frame's build wipes.
+    const bool drawn_match = ctx->drawn.valid && ctx->drawn.fb == out.fb && ctx->drawn.palidx == out.palidx &&
+                             ctx->drawn.r0 == row_begin && ctx->drawn.r1 == row_end && ctx->drawn.set == (set ^ 1);
     drop_retained(ctx);  // (a hash build follows; the entry point retains the new frame once it has returned PAR_OK)
+    drop_drawn(ctx);
     par_outputs outs = out;
     if ((flags & PAR_RENDER_TRACE_BACKGROUND) && !outs.lit) {
         // every ray is to be traced but the caller wants no lit plane: the results still go to memory (a scratch
@@ -510,7 +542,7 @@ int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, 
                                (size_t)(ctx->dev_hi - ctx->dev_lo) * sizeof(par_aabb), hipMemcpyHostToDevice, stream));
         ctx->dev_lo = ctx->dev_hi = 0;
     }
-    const par_bin_args b = make_bin_args(ctx, set, row_begin, row_end, flags);
+    par_bin_args b = make_bin_args(ctx, set, row_begin, row_end, flags);
     par_render_args r = make_render_args(ctx, set, row_begin, row_end, outs, flags, graph_mode);
     // (a timed frame keeps its kernels apart unless it is asked to time the launches as a production frame makes them)
     const bool apart = ev && !(flags & PAR_RENDER_TIMED_AS_LAUNCHED);
@@ -533,13 +565,23 @@ int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, 
     // so that the event pairs bracket single ones).
     par_fill_plan plan;
     const bool ride = !apart && par_plan_fill(r, &plan);
+    // A kept frame (PAR_RENDER_KEPT_OUTPUTS with a matching record, never a graph's frame): the planes hold this
+    // context's last frame, so the build lists the tiles that frame can have drawn into and the column launch's riding
+    // workgroups clear those alone; the build launches carry no fill. Only where the fill would ride and tiles are whole
+    // 16-byte runs (B % 8 == 0), and while the book's column bound says the tiles are a minority of the rendered rows
+    // (kKeptMaxTilesPct): a dense frame clears every tile in short rows and loses to the streaming
+    // fill. The bound only chooses; what is cleared is the device's own list.
+    const int64_t tiles_in_rows = (int64_t)ctx->gx * (r.by_hi - r.by_lo + 1);
+    const bool kept_frame = (flags & PAR_RENDER_KEPT_OUTPUTS) && drawn_match && !graph_mode && ride && r.B % 8 == 0 &&
+                            std::min(bound.cols, tiles_in_rows) * 100 <= tiles_in_rows * kKeptMaxTilesPct;
+    b.kept = kept_frame ? 1 : 0;
     par_render_args rf = r;  // what rides along: the frame and palette-index planes
     rf.out.lit = nullptr;
-    const int rc = enqueue_build(ctx, stream, b, bound.pairs, &rf, ride ? &plan : nullptr, apart);
+    const int rc = enqueue_build(ctx, stream, b, bound.pairs, &rf, ride && !kept_frame ? &plan : nullptr, apart);
     if (rc != PAR_OK) return rc;
     if (ev) PAR_HIP(hipEventRecord(ev[EV_BUILT], stream));
     if (ride) {
-        PAR_HIP(par_launch_columns_fill(ctx->grid, rf, bound.cols, plan, ctx->col_roles, stream));
+        PAR_HIP(par_launch_columns_fill(ctx->grid, rf, bound.cols, plan, kept_frame, ctx->col_roles, stream));
     } else {
         PAR_HIP(par_launch_columns(ctx->grid, r, bound.cols, ctx->col_roles, stream));
     }
@@ -622,7 +664,7 @@ struct par_dev_buffer {
     int fill;  // the byte the buffer starts with, or -1
 };
 
-std::array<par_dev_buffer, 19> dev_buffers(par_context* c, bool stamps) {
+std::array<par_dev_buffer, 20> dev_buffers(par_context* c, bool stamps) {
     par_grid_dev& g = c->grid;
     const size_t vol = (size_t)c->volume, cols = (size_t)c->gx * c->gy, i32 = sizeof(int32_t);
     return {{
@@ -634,6 +676,7 @@ std::array<par_dev_buffer, 19> dev_buffers(par_context* c, bool stamps) {
         {(void**)&g.colflag[1], cols * i32, -1},
         {(void**)&g.col_list, cols * i32, -1},
         {(void**)&g.slow_list, cols * i32, -1},
+        {(void**)&g.clear_list, cols * i32, -1},
         {(void**)&g.counters, PAR_CNT_TOTAL * i32, -1},
         {(void**)&g.node_counter, 2 * i32, -1},
         {(void**)&g.build_sync, 64 * i32, 0},
@@ -1016,6 +1059,7 @@ static int par_render_device_impl(par_context* ctx, void* stream, int row_begin,
     ctx->last_stream = (hipStream_t)stream;
     ctx->has_last_stream = true;
     retain_frame(ctx, row_begin, row_end, ctx->set ^ 1, false);
+    record_drawn(ctx, *device_out, row_begin, row_end, ctx->set ^ 1);
     return PAR_OK;
 }
 
@@ -1046,7 +1090,11 @@ static int par_render_device_timed_impl(par_context* ctx, void* stream, int row_
         if (!ctx->timed_overflow) ctx->stats.ms_launch[4] = 0.f;
     }
     rc = stats ? par_get_stats(ctx, stats) : check_device_error(ctx);
-    if (rc == PAR_OK) retain_frame(ctx, row_begin, row_end, ctx->set ^ 1, false);
+    if (rc == PAR_OK) {
+        retain_frame(ctx, row_begin, row_end, ctx->set ^ 1, false);
+        // (a frame timed with its kernels apart leaves no drawn-into record: par_raytracer.h)
+        if (flags & PAR_RENDER_TIMED_AS_LAUNCHED) record_drawn(ctx, *device_out, row_begin, row_end, ctx->set ^ 1);
+    }
     return rc;
 }
 
@@ -1088,6 +1136,7 @@ static int enqueue_relight(par_context* ctx, hipStream_t stream, int row_begin, 
     }
     const par_render_args r = make_render_args(ctx, ctx->kept.set, row_begin, row_end, outs, flags, false);
     const par_light_state lights = make_light_state(ctx, false);
+    drop_drawn(ctx);
     if (flags & PAR_RENDER_COUNT_RAYS) {
         PAR_HIP(hipMemsetAsync(ctx->d_ray_counter, 0, 3 * sizeof(unsigned long long), stream));
     }
@@ -1160,6 +1209,7 @@ static int graph_capture(par_context* ctx, void* stream_v, int row_begin, int ro
     PAR_HIP(hipDeviceSynchronize());
     drop_graphs(ctx);
     drop_retained(ctx);
+    drop_drawn(ctx);
     rc = ensure_room(ctx, ctx->book.capture());
     if (rc != PAR_OK) return rc;
     for (int s = 0; s < 2; s++) {
@@ -1274,6 +1324,7 @@ static int par_graph_launch_impl(par_context* ctx, void* stream) {
         PAR_HIP(hipStreamWaitEvent((hipStream_t)stream, ctx->ev_update, 0));
     }
     drop_retained(ctx);
+    drop_drawn(ctx);
     PAR_HIP(hipGraphLaunch(ctx->graph_exec[s], (hipStream_t)stream));
     ctx->dev_lo = ctx->dev_hi = 0;  // (the graph's first node copies the whole scene)
     PAR_HIP(hipEventRecord(ctx->ev_graph[s], (hipStream_t)stream));

@@ -159,7 +159,7 @@ struct par_light_state {
 // a production frame has neither and runs kernels compiled without them.
 constexpr uint32_t PAR_DEBUG_FLAGS = PAR_RENDER_COUNT_RAYS | (1u << 29);
 // Every flag a caller may pass: the public ones and the time stamps. Anything else is rejected (PAR_ERR_INVALID_ARG).
-constexpr uint32_t PAR_ACCEPTED_FLAGS = 0xFu | (1u << 29);
+constexpr uint32_t PAR_ACCEPTED_FLAGS = 0x1Fu | (1u << 29);
 // Set by the library alone, never by a caller (the record-items-only test hook, par_debug_set_hooks): columns emit
 // no self-contained (simple) and no alone work items, every column is rendered from its record by the general pass.
 constexpr uint32_t PAR_FLAG_RECORD_ITEMS = 1u << 22;
@@ -217,6 +217,8 @@ struct par_grid_dev {
     int32_t* item_counters;   // [PAR_ITEM_LISTS * PAR_ITEM_SHARDS * PAR_ITEM_COUNTER_STRIDE] items per shard (reset by insert)
     int32_t* build_sync;      // [64] barrier words of build_fill_kernel (arrived, left; they reset themselves)
     int32_t* slow_list;       // [gx*gy] indices into col_list of the columns that overflowed their record
+    int32_t* clear_list;      // [gx*gy] a kept frame: the columns the previous build flagged, inside the rendered row
+                              // range, unordered; counters[PAR_CNT_CLEAR + set] of them (clear_tiles_body)
     par_bgwalk* bgwalk;       // [gx] shadow walks of the background rays (traced only on request)
     uint8_t* bglit;           // [width] result of the background ray of screen column x
     unsigned long long* stamps;  // debug (PAR_DEBUG_STAMPS=1): per workgroup phase time stamps, else nullptr
@@ -230,6 +232,7 @@ struct par_bin_args {
     int32_t n;
     int32_t set;             // which head/count/node/colflag set this frame uses
     int32_t by_lo, by_hi;    // bin rows [by_lo, by_hi] the render of this frame touches (column-list filter)
+    int32_t kept;            // 1: a kept frame (PAR_RENDER_KEPT_OUTPUTS taken): the wipe lists the columns it unflags
     uint32_t flags;          // render flags (bit 29: debug time stamps)
     int32_t test_lose_wg;    // tests (par_debug_set_hooks): build workgroup 0 never arrives at the barrier
     uint32_t magic_b;        // floor(n / B) == __umulhi(n, magic_b) for n * B < 2^32 (as par_render_args::magic_b)
@@ -265,7 +268,9 @@ struct par_render_args {
 
 // PAR_CNT_ERROR is STICKY: kernels only ever set bits in it (a frame's insert resets the other counters, not this
 // one); the host clears it when it reports it (PAR_ERR_DEVICE).
-enum { PAR_CNT_COLS = 0, PAR_CNT_SLOW = 1, PAR_CNT_ERROR = 2, PAR_CNT_TOTAL = 8 };
+// PAR_CNT_CLEAR + set: the entries of clear_list a kept frame of grid set `set` listed. A frame zeroes the OTHER set's
+// word, for its successor, never its own: its wipe adds to it in the same launch.
+enum { PAR_CNT_COLS = 0, PAR_CNT_SLOW = 1, PAR_CNT_ERROR = 2, PAR_CNT_CLEAR = 4, PAR_CNT_TOTAL = 8 };
 enum { PAR_DEVERR_BARRIER = 1,    // build_fill_kernel: a build workgroup never arrived at the barrier (bounded wait)
        PAR_DEVERR_OVERFLOW = 2 }; // a column went onto the overflow list in a frame without a launch for that list
 
@@ -292,9 +297,10 @@ hipError_t par_launch_bin_resolve(const par_grid_dev& g, const par_bin_args& a, 
 // `col_roles`: wavefronts per column (1, 2, 4 or 8), 0 = the launch's own choice (column_roles).
 hipError_t par_launch_columns(const par_grid_dev& g, const par_render_args& a, int64_t column_bound, int col_roles,
                               hipStream_t stream);
-// Column records + the last share of the fill in one launch.
+// Column records + the last share of the fill in one launch. `clear_tiles`: a kept frame (par_bin_args::kept): the
+// riding workgroups set the tiles of g.clear_list back to background and fill nothing else. Needs B % 8 == 0.
 hipError_t par_launch_columns_fill(const par_grid_dev& g, const par_render_args& a, int64_t column_bound,
-                                   const par_fill_plan& fill, int col_roles, hipStream_t stream);
+                                   const par_fill_plan& fill, bool clear_tiles, int col_roles, hipStream_t stream);
 // Background for every pixel of the row range; the render kernel then overwrites the pixels primitives cover.
 // Independent of the hash.
 hipError_t par_launch_fill(const par_grid_dev& g, const par_render_args& a, hipStream_t stream);

@@ -162,11 +162,32 @@ __device__ __forceinline__ void bin_insert_body(const par_grid_dev& g, const par
         const int b = g.node_bin[o][i];
         g.head[o][b] = 0;
         g.count[o][b] = 0;
-        g.colflag[o][b / g.gz] = 0;
+        const int col = b / g.gz;
+        if (!a.kept) {
+            g.colflag[o][col] = 0;
+            continue;
+        }
+        // A kept frame (PAR_RENDER_KEPT_OUTPUTS): the columns the previous frame flagged are the tiles it can have drawn
+        // into. The lane that takes a column's flag down lists the column, once, for clear_tiles_body of this frame's
+        // column launch, when the frame's rows meet it (one atomic per wavefront, as bin_resolve_node lists col_list).
+        const int by = col % g.gy;
+        if (atomicExch(&g.colflag[o][col], 0) != 0 && by >= a.by_lo && by <= a.by_hi) {
+            const unsigned long long m = __ballot(1);
+            const int leader = __ffsll((long long)m) - 1;
+            const int wl = threadIdx.x & 63;
+            int base = 0;
+            if (wl == leader) base = atomicAdd(&g.counters[PAR_CNT_CLEAR + s], __popcll(m));
+            base = __shfl(base, leader);
+            const int at = base + __popcll(m & ((1ull << wl) - 1ull));
+            if (at >= 0 && at < g.gx * g.gy) g.clear_list[at] = col;  // (a column is listed once: belt and braces)
+        }
     }
     // (resolve adds to the column counter with atomics: in the one-launch build a plain zero written here could
     // reach memory after them)
-    if (tid < PAR_CNT_TOTAL && tid != PAR_CNT_ERROR) st_shared<COH>(&g.counters[tid], 0);  // (the error word is sticky)
+    // The error word is sticky. The clear list's counter of THIS set is added to above, so it is never zeroed by the
+    // launch that fills it: every frame zeroes the other set's, for its successor (the host zeroes both at creation).
+    if (tid < PAR_CNT_ERROR) st_shared<COH>(&g.counters[tid], 0);
+    if (tid == PAR_CNT_ERROR) st_shared<COH>(&g.counters[PAR_CNT_CLEAR + o], 0);
     if (tid < PAR_ITEM_LISTS * PAR_ITEM_SHARDS) g.item_counters[tid * PAR_ITEM_COUNTER_STRIDE] = 0;
 
     const int W = a.W, H = a.H, L = a.L, B = a.B;
@@ -1149,6 +1170,58 @@ __device__ __forceinline__ void fill_body(const par_render_args& a, uint32_t out
     }
 }
 
+// clear_tiles_body: the background of a KEPT frame (PAR_RENDER_KEPT_OUTPUTS). The planes still hold the frame this
+// context drew into them one turn earlier, so only the tiles that frame can have drawn into are set back to background:
+// the clear list this frame's hash build made of the previous build's flagged columns (bin_insert_body), complete at
+// the kernel boundary before this launch. One wavefront per listed tile, the tile clipped to W and to the rows
+// rendered, with the background word and the palette index of fill_body. Requires what fill_body requires and
+// B % 8 == 0: a tile's rows are then whole 16-byte runs of the frame plane (4 pixels per lane, 64 / (w / 4) rows per
+// store instruction) and whole 8-byte runs of the palette-index plane (8 pixels per lane).
+// The stores are PLAIN ones, unlike fill_body's: a tile row is 160 and 40 bytes at bin 40, parts of 128-byte lines
+// that the L2 can still merge with each other and with the pixels the render launch draws into the same tiles, where
+// a streaming store sends each part to memory by itself (4096^2, 2 536 tiles, four frames in flight: 19.8 - 20.1 us
+// per frame against 20.1 - 21.0 with non-temporal stores; DESIGN.md section 4 has the other forms tried).
+__device__ __forceinline__ void clear_tiles_body(const par_grid_dev& g, const par_render_args& a, uint32_t out_rgba,
+                                                 int block, int n_blocks) {
+    const int W = a.W, B = a.B;
+    const int lane = threadIdx.x & 63;
+    const int wpb = blockDim.x >> 6;
+    const int n_all = g.gx * g.gy;
+    const int n = min(ld_uniform(&g.counters[PAR_CNT_CLEAR + a.set]), n_all);
+    uint32_t* fb = reinterpret_cast<uint32_t*>(a.out.fb);
+    for (int t = __builtin_amdgcn_readfirstlane(block * wpb + ((int)threadIdx.x >> 6)); t < n; t += n_blocks * wpb) {
+        const int col = ld_uniform(&g.clear_list[t]);
+        if (col < 0 || col >= n_all) continue;
+        const int bx = col / g.gy, by = col - bx * g.gy;
+        const int x0 = bx * B, x1 = min(x0 + B, W);
+        const int y0 = max(by * B, a.row_begin), y1 = min(by * B + B, a.row_end);
+        const int w = x1 - x0;  // a multiple of 8
+        if (w <= 0 || y0 >= y1) continue;
+        if (fb) {
+            const int lpr = w >> 2, rpi = 64 / lpr;  // lanes per row, rows per store instruction
+            const int r = lane / lpr, xi = lane - r * lpr;
+            if (r < rpi) {
+                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                const u32x4 v = {out_rgba, out_rgba, out_rgba, out_rgba};
+                for (int y = y0 + r; y < y1; y += rpi) {
+                    *reinterpret_cast<u32x4*>(fb + (size_t)(y - a.row_begin) * W + x0 + xi * 4) = v;
+                }
+            }
+        }
+        if (a.out.palidx) {
+            const int lpr = w >> 3, rpi = 64 / lpr;
+            const int r = lane / lpr, xi = lane - r * lpr;
+            if (r < rpi) {
+                typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+                const u32x2 v = {0xFFFFFFFFu, 0xFFFFFFFFu};
+                for (int y = y0 + r; y < y1; y += rpi) {
+                    *reinterpret_cast<u32x2*>(a.out.palidx + (size_t)(y - a.row_begin) * W + x0 + xi * 8) = v;
+                }
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void fill_kernel(par_render_args a, uint32_t out_rgba, const uint8_t* bglit) {
     fill_body(a, out_rgba, bglit, (int)blockIdx.x, (int)gridDim.x, make_int2(0, -1));
 }
@@ -1159,14 +1232,18 @@ __global__ __launch_bounds__(256) void fill_kernel(par_render_args a, uint32_t o
 template <int ROLES>
 __global__ __launch_bounds__(col_waves<ROLES>() * 64) void columns_fill_kernel(par_grid_dev g, par_render_args a,
                                                                                 uint32_t out_rgba, int n_col_blocks,
-                                                                                int n_cols_bound, int2 part) {
+                                                                                int n_cols_bound, int2 part, int clear) {
     __shared__ ColWave sm[col_waves<ROLES>()];
     __shared__ ColTeam team_sh;
     if ((int)blockIdx.x < n_col_blocks) {
         columns_block<ROLES>(g, a, sm, &team_sh, (int)blockIdx.x, n_cols_bound);
     } else {
         stamp(g, a.flags, 2, 0);
-        fill_body(a, out_rgba, nullptr, (int)blockIdx.x - n_col_blocks, (int)gridDim.x - n_col_blocks, part);
+        if (clear) {  // a kept frame: the riding workgroups clear the listed tiles and fill nothing else
+            clear_tiles_body(g, a, out_rgba, (int)blockIdx.x - n_col_blocks, (int)gridDim.x - n_col_blocks);
+        } else {
+            fill_body(a, out_rgba, nullptr, (int)blockIdx.x - n_col_blocks, (int)gridDim.x - n_col_blocks, part);
+        }
     }
     stamp(g, a.flags, 2, 7);
 }
@@ -3047,16 +3124,22 @@ static int column_roles(const par_grid_dev& g, const par_render_args& a, int64_t
 
 template <int ROLES>
 static hipError_t launch_columns_as(const par_grid_dev& g, const par_render_args& a, int64_t column_bound,
-                                    const par_fill_plan* fill, hipStream_t stream) {
+                                    const par_fill_plan* fill, bool clear, hipStream_t stream) {
     constexpr int waves = col_waves<ROLES>();
     int64_t n_cols;
     const int64_t n_col_blocks = column_blocks(g, a, column_bound, ROLES == 1 ? waves : 1, &n_cols);
     if (fill) {
         // (the same number of fill WAVEFRONTS whatever the workgroup size)
-        const int64_t n_fill = fill_blocks(*fill, 2, waves, 4 * PAR_FILL_RIDE_WGS * 2 / waves);
+        const int64_t ride_cap = 4 * PAR_FILL_RIDE_WGS * 2 / waves;
+        int64_t n_fill = fill_blocks(*fill, 2, waves, ride_cap);
+        if (clear) {  // a kept frame: one wavefront per listed tile, at most every tile of the rendered rows
+            const int64_t tiles = (int64_t)g.gx * (a.by_hi - a.by_lo + 1);
+            n_fill = std::min(ride_cap, (tiles + waves - 1) / waves);
+        }
         if (n_col_blocks + n_fill <= 0) return hipSuccess;
         hipLaunchKernelGGL(columns_fill_kernel<ROLES>, dim3((unsigned)(n_col_blocks + n_fill)), dim3(waves * 64), 0, stream,
-                           g, a, fill->out_rgba, (int)n_col_blocks, (int)n_cols, make_int2(fill->cut[2], fill->cut[3]));
+                           g, a, fill->out_rgba, (int)n_col_blocks, (int)n_cols, make_int2(fill->cut[2], fill->cut[3]),
+                           clear ? 1 : 0);
     } else {
         if (n_col_blocks <= 0) return hipSuccess;
         hipLaunchKernelGGL(columns_kernel<ROLES>, dim3((unsigned)n_col_blocks), dim3(waves * 64), 0, stream, g, a, (int)n_cols);
@@ -3065,13 +3148,13 @@ static hipError_t launch_columns_as(const par_grid_dev& g, const par_render_args
 }
 
 static hipError_t launch_columns(const par_grid_dev& g, const par_render_args& a, int64_t column_bound,
-                                 const par_fill_plan* fill, int col_roles, hipStream_t stream) {
+                                 const par_fill_plan* fill, bool clear, int col_roles, hipStream_t stream) {
     hipError_t e;
     switch (column_roles(g, a, column_bound, col_roles)) {
-        case 1: e = launch_columns_as<1>(g, a, column_bound, fill, stream); break;
-        case 4: e = launch_columns_as<4>(g, a, column_bound, fill, stream); break;
-        case 8: e = launch_columns_as<8>(g, a, column_bound, fill, stream); break;
-        default: e = launch_columns_as<2>(g, a, column_bound, fill, stream); break;
+        case 1: e = launch_columns_as<1>(g, a, column_bound, fill, clear, stream); break;
+        case 4: e = launch_columns_as<4>(g, a, column_bound, fill, clear, stream); break;
+        case 8: e = launch_columns_as<8>(g, a, column_bound, fill, clear, stream); break;
+        default: e = launch_columns_as<2>(g, a, column_bound, fill, clear, stream); break;
     }
     if (e != hipSuccess || !a.trace_bg) return e;
     hipLaunchKernelGGL(bgline_kernel, dim3((unsigned)((a.W + 255) / 256)), dim3(256), 0, stream, g, a);
@@ -3080,13 +3163,14 @@ static hipError_t launch_columns(const par_grid_dev& g, const par_render_args& a
 
 hipError_t par_launch_columns(const par_grid_dev& g, const par_render_args& a, int64_t column_bound, int col_roles,
                               hipStream_t stream) {
-    return launch_columns(g, a, column_bound, nullptr, col_roles, stream);
+    return launch_columns(g, a, column_bound, nullptr, false, col_roles, stream);
 }
 
-// Column records + the last share of the fill in one launch.
+// Column records + the last share of the fill in one launch; `clear_tiles`: a kept frame, whose riding workgroups
+// clear the tiles of the clear list instead (the build launches of such a frame carry no fill).
 hipError_t par_launch_columns_fill(const par_grid_dev& g, const par_render_args& a, int64_t column_bound,
-                                   const par_fill_plan& fill, int col_roles, hipStream_t stream) {
-    return launch_columns(g, a, column_bound, &fill, col_roles, stream);
+                                   const par_fill_plan& fill, bool clear_tiles, int col_roles, hipStream_t stream) {
+    return launch_columns(g, a, column_bound, &fill, clear_tiles, col_roles, stream);
 }
 
 hipError_t par_launch_fill(const par_grid_dev& g, const par_render_args& a, hipStream_t stream) {

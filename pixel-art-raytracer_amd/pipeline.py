@@ -14,7 +14,7 @@ import time
 import numpy as np
 import torch
 
-from . import RENDER_PIPELINED, Renderer, lib, plane_bytes
+from . import RENDER_KEPT_OUTPUTS, RENDER_PIPELINED, Renderer, lib, plane_bytes
 from .types import Outputs
 
 
@@ -53,6 +53,10 @@ class FramePipeline:
                     raise ValueError("fb target smaller than the row block")
                 bufs["fb"] = fb_targets[k_slot]
             self.slots.append(FrameSlot(r, None, bufs, (r0, r1)))
+        # A slot's own buffers are written by its context alone, frame after frame: every frame says so
+        # (RENDER_KEPT_OUTPUTS) and clears its predecessor's tiles instead of filling 16 Mpixel of background. A slot
+        # that renders into a caller's `fb_targets` does not: somebody else assembles, reads or rewrites those.
+        self.kept_flag = 0 if fb_targets else RENDER_KEPT_OUTPUTS
         candidates = [torch.cuda.Stream(device=dev) for _ in range(depth if depth < 2 or not calibrate else 3 * depth)]
         chosen = self._pick_streams(candidates, depth) if calibrate and depth > 1 else candidates[:depth]
         for s, stream in zip(self.slots, chosen):
@@ -109,7 +113,7 @@ class FramePipeline:
             self._slot_args = (ctxs, streams, outs)
         ctxs, streams, outs = self._slot_args
         r0, r1 = self.slots[0].rows
-        rc = lib().par_render_device_slots(ctxs, streams, outs, len(self.slots), r0, r1, first, n, flags)
+        rc = lib().par_render_device_slots(ctxs, streams, outs, len(self.slots), r0, r1, first, n, flags | self.kept_flag)
         if rc != 0:
             raise RuntimeError(f"par_render_device_slots failed with status {rc}")
 
@@ -128,7 +132,8 @@ class FramePipeline:
         def run(j, count):
             torch.cuda.set_device(device)
             ctxs, streams, outs = self._one[j]
-            return lib().par_render_device_slots(ctxs, streams, outs, 1, r0, r1, 0, count, flags | RENDER_PIPELINED)
+            return lib().par_render_device_slots(ctxs, streams, outs, 1, r0, r1, 0, count,
+                                                 flags | RENDER_PIPELINED | self.kept_flag)
 
         counts = [len(range(first + ((j - first) % k), first + n, k)) for j in range(k)]  # frames f with f % k == j
         for rc in self._pool.map(run, range(k), counts):
@@ -159,7 +164,7 @@ class FramePipeline:
         s = self.slot(i)
         if len(self.slots) > 1:
             flags |= RENDER_PIPELINED  # several frames in flight: throughput before latency
-        s.renderer.render_device(s.ptrs, rows=s.rows, flags=flags, stream=s.stream.cuda_stream)
+        s.renderer.render_device(s.ptrs, rows=s.rows, flags=flags | self.kept_flag, stream=s.stream.cuda_stream)
         return s
 
     def update_aabbs(self, i, aabbs, first=0, light=None):

@@ -1,16 +1,19 @@
 #!/usr/bin/env python3
 """Render N frames of one workload (for rocprofv3 --kernel-trace --stats / --pmc runs on the GPU box).
-usage: frames.py [synthetic|floor|graybox|small|trace_bg] [frames] [extra render flags, e.g. 2 = count rays]"""
+usage: frames.py [--kept] [synthetic|floor|graybox|small|trace_bg] [frames] [extra render flags, e.g. 2 = count rays]
+--kept: every frame carries RENDER_KEPT_OUTPUTS (the buffers are this context's own: kept frames from the second on)"""
 import importlib, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 par = importlib.import_module("pixel-art-raytracer_amd")
 T = par.types
+kept = "--kept" in sys.argv
+sys.argv = [v for v in sys.argv if v != "--kept"]
 what = sys.argv[1] if len(sys.argv) > 1 else "synthetic"
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 100
 flags = 0
-extra = int(sys.argv[3], 0) if len(sys.argv) > 3 else 0
+extra = (int(sys.argv[3], 0) if len(sys.argv) > 3 else 0) | (par.RENDER_KEPT_OUTPUTS if kept else 0)
 if what in ("synthetic", "trace_bg"):
     W = H = L = 4096
     p = T.default_params(W, H, L)
