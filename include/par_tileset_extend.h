@@ -50,7 +50,8 @@
  * PAR_TILESET_MAX_CELLS; through the host form also for *count < 0.
  * Left out on purpose: removing tiles from a set; lossy merging of similar tiles to meet a budget; a hash table that
  * persists between calls (every call hashes the stored tiles again); rotations; and the torch.distributed plumbing of a
- * sharded merge (the sharded path has never run on more than one GPU).
+ * sharded merge (the sharded path has never run on more than one GPU). The lossy merge now exists, in an add-on beside
+ * the library: addons/include/par_tileset_reduce.h.
  */
 #ifndef PAR_TILESET_EXTEND_H
 #define PAR_TILESET_EXTEND_H

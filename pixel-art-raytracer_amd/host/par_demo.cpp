@@ -9,7 +9,7 @@
 //   par_demo [--keys RRRRUUUUhhhhjjPP] [--frames N] [--out DIR] [--gif FILE] [--debug-line] [--as-sdl] [--size W H L]
 //            [--palette-levels K] [--dither S] [--outline S,C,D] [--scale SX[,SY]] [--finish] [--upscale K]
 //            [--palette-fit N] [--palette-refine I] [--dither-pattern N[,S]] [--cells CW,CH] [--tileset TW,TH[,FLIPS]]
-//            [--tileset-shared CAP]
+//            [--tileset-shared CAP] [--tileset-budget K]
 //
 // --gif writes the frames as one animated GIF89a (100 ms per frame like the reference's gif.gif); a frame's colours
 // are palette entries times a brightness, at most a few hundred distinct values, so each frame gets an exact local
@@ -46,6 +46,12 @@
 // (par_tileset_extend_host, the same tiles and flips), and after the frame's `tileset frame` line it prints
 // `tileset shared frame <i>: <new> new, <T> tiles, capacity <CAP>`: the tiles the frame adds, its upload, and whether
 // the animation fits the budget (T <= CAP; beyond it T is an upper bound). It changes no byte of the GIF either.
+// --tileset-budget K (with --tileset; K = 1..1024 tiles) also reduces every frame's own tile set to at most K tiles: the
+// frame's set and map are built (par_tileset_build_host with the capacity of its count), reduced through the add-on
+// (par_tileset_reduce_host of addons/include/par_tileset_reduce.h, the palette the frame's colour table), and right after
+// the frame's `tileset frame` line it prints `tileset budget frame <i>: <T> -> <K'> tiles, error <E>`: the tiles kept
+// and the summed L1 error of the reduced picture. A frame of more than 4096 tiles is beyond the add-on and is reported
+// as such. It changes no byte of the GIF either.
 //
 // --outline S,C,D draws every frame's outlines on the GPU (par_outline_host) from the frame's own G-buffer: silhouettes
 // scaled by S / 256, creases by C / 256, a silhouette between two entities from a depth difference of D (128,320,4 is a
@@ -84,6 +90,7 @@
 #include "par_raytracer.h"
 #include "par_tileset.h"
 #include "par_tileset_extend.h"
+#include "par_tileset_reduce.h"
 
 static void apply_key(char k, par_aabb& player, par_light& light) {
     switch (k) {
@@ -252,6 +259,7 @@ int main(int argc, char** argv) {
     int cell_w = 0, cell_h = 0;    // 0: no --cells
     int tile_w = 0, tile_h = 0, tile_flips = 0;  // 0: no --tileset
     int shared_capacity = -1;                    // -1: no --tileset-shared
+    int tile_budget = 0;                         // 0: no --tileset-budget
     par_outline_style outline_style{4, 256, 256};
     for (int i = 1; i < argc; i++) {
         if (!std::strcmp(argv[i], "--keys") && i + 1 < argc) keys = argv[++i];
@@ -294,6 +302,14 @@ int main(int argc, char** argv) {
             if (std::sscanf(argv[++i], "%d%c", &shared_capacity, &tail) != 1 || shared_capacity < 0 ||
                 shared_capacity > PAR_TILESET_MAX_CELLS) {
                 std::fprintf(stderr, "--tileset-shared wants a capacity of 0..%d tiles, got %s\n", PAR_TILESET_MAX_CELLS, argv[i]);
+                return 2;
+            }
+        }
+        else if (!std::strcmp(argv[i], "--tileset-budget") && i + 1 < argc) {
+            char tail = 0;
+            if (std::sscanf(argv[++i], "%d%c", &tile_budget, &tail) != 1 || tile_budget < 1 ||
+                tile_budget > PAR_TILESET_REDUCE_MAX_BUDGET) {
+                std::fprintf(stderr, "--tileset-budget wants 1..%d tiles, got %s\n", PAR_TILESET_REDUCE_MAX_BUDGET, argv[i]);
                 return 2;
             }
         }
@@ -378,6 +394,10 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--tileset-shared wants --tileset TW,TH[,FLIPS]: it keeps the set of those tiles across the frames\n");
         return 2;
     }
+    if (tile_budget != 0 && tile_w == 0) {
+        std::fprintf(stderr, "--tileset-budget wants --tileset TW,TH[,FLIPS]: it reduces the set of those tiles\n");
+        return 2;
+    }
     if (finish) {
         if (out_dir.empty()) { std::fprintf(stderr, "--finish wants --out\n"); return 2; }
         if (!outline && palette_levels == 0) { std::fprintf(stderr, "--finish wants --outline or --palette-levels: without both it is --scale\n"); return 2; }
@@ -445,8 +465,36 @@ int main(int argc, char** argv) {
     std::vector<unsigned char> shared_tiles;
     int shared_count = 0;
     if (shared_capacity > 0) shared_tiles.resize((size_t)shared_capacity * (size_t)(tile_w * tile_h));
-    // --tileset: the tiles of the index plane of frame f as it stands, counted and printed
-    const auto count_tiles = [&](int f) -> int {
+    // --tileset-budget: frame f's own set of `tiles` tiles built, reduced to the budget over `pal` and printed
+    const auto reduce_tiles = [&](int f, int tiles, const std::vector<par_color>& pal) -> int {
+        if (tiles > PAR_TILESET_REDUCE_MAX_TILES) {
+            std::printf("tileset budget frame %d: %d tiles, more than the %d a reduce takes\n", f, tiles, PAR_TILESET_REDUCE_MAX_TILES);
+            return (int)PAR_OK;
+        }
+        const int cells = ((W + tile_w - 1) / tile_w) * ((H + tile_h - 1) / tile_h);
+        const size_t tile_bytes = (size_t)(tile_w * tile_h);
+        std::vector<unsigned char> set((size_t)tiles * tile_bytes), kept((size_t)tile_budget * tile_bytes);
+        std::vector<uint32_t> tile_map((size_t)cells);
+        int built = 0, left = 0;
+        uint64_t error = 0;
+        int status = par_tileset_build_host(&params, 0, index.data(), 0, H, tile_w, tile_h, 0, tile_flips, set.data(), tiles,
+                                            tile_map.data(), &built);
+        if (status != PAR_OK) {
+            std::fprintf(stderr, "par_tileset_build_host: %s\n", par_status_string(status));
+            return status;
+        }
+        status = par_tileset_reduce_host(0, set.data(), built, tile_w, tile_h, tile_flips, tile_map.data(), cells,
+                                         reinterpret_cast<const uint8_t*>(pal.data()), (int)pal.size(), tile_budget, kept.data(),
+                                         tile_map.data(), nullptr, &left, &error);
+        if (status != PAR_OK) {
+            std::fprintf(stderr, "par_tileset_reduce_host: %s\n", par_status_string(status));
+            return status;
+        }
+        std::printf("tileset budget frame %d: %d -> %d tiles, error %llu\n", f, built, left, (unsigned long long)error);
+        return (int)PAR_OK;
+    };
+    // --tileset: the tiles of the index plane of frame f as it stands over `pal`, counted and printed
+    const auto count_tiles = [&](int f, const std::vector<par_color>& pal) -> int {
         if (tile_w == 0) return PAR_OK;
         int tiles = 0;
         const int status = par_tileset_build_host(&params, 0, index.data(), 0, H, tile_w, tile_h, 0, tile_flips, nullptr, 0,
@@ -457,6 +505,10 @@ int main(int argc, char** argv) {
         }
         std::printf("tileset frame %d: %d tiles of %d cells\n", f, tiles,
                     ((W + tile_w - 1) / tile_w) * ((H + tile_h - 1) / tile_h));
+        if (tile_budget != 0) {
+            const int budget_status = reduce_tiles(f, tiles, pal);
+            if (budget_status != PAR_OK) return budget_status;
+        }
         if (shared_capacity < 0) return (int)PAR_OK;
         int first_new = 0;
         const int shared_status = par_tileset_extend_host(&params, 0, index.data(), 0, H, tile_w, tile_h, 0, tile_flips,
@@ -502,7 +554,7 @@ int main(int argc, char** argv) {
             std::snprintf(name, sizeof(name), "/frame_%03d.ppm", f);
             if (!write_ppm(out_dir + name, surface.data(), W * scale_x, H * scale_y)) { std::fprintf(stderr, "cannot write %s%s\n", out_dir.c_str(), name); return 1; }
             if (pal && !gif_path.empty()) {
-                if (count_tiles(f) != PAR_OK) return 1;
+                if (count_tiles(f, ramp) != PAR_OK) return 1;
                 gif.frame(index, ramp, 10);
             } else if (!gif_path.empty()) {
                 // the outlined frame at view size: the surface itself at scale 1, else one more call at scale 1
@@ -572,14 +624,14 @@ int main(int argc, char** argv) {
                     std::fprintf(stderr, "par_quantize_cells_host: %s\n", par_status_string(rc));
                     return 1;
                 }
-                if (count_tiles(f) != PAR_OK) return 1;
+                if (count_tiles(f, pairs) != PAR_OK) return 1;
                 gif.frame(index, pairs, 10);
             } else {
-                if (quantise(fitted) != PAR_OK || count_tiles(f) != PAR_OK) return 1;
+                if (quantise(fitted) != PAR_OK || count_tiles(f, fitted) != PAR_OK) return 1;
                 gif.frame(index, fitted, 10);
             }
         } else if (!ramp.empty()) {
-            if (quantise(ramp) != PAR_OK || count_tiles(f) != PAR_OK) return 1;
+            if (quantise(ramp) != PAR_OK || count_tiles(f, ramp) != PAR_OK) return 1;
             gif.frame(index, ramp, 10);
         } else if (!gif_path.empty()) {
             for (size_t i = 0; i < fb.size(); i++) { rgb[i * 3] = fb[i].red; rgb[i * 3 + 1] = fb[i].green; rgb[i * 3 + 2] = fb[i].blue; }

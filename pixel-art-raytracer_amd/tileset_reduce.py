@@ -1,0 +1,93 @@
+"""Tile budgets: a tile set and its map reduced to at most K tiles (addons/include/par_tileset_reduce.h). An add-on: the
+three calls live in a library of their own, lib/libpar_tileset_reduce.so, which this module loads itself at the first
+call; their signatures are ABI_TILESET_REDUCE below, a table that is NOT one of abi.py's (the core library exports none of
+them), and the package does not import this module. The calls raise the package's ParError with the symbol's name; a
+device pointer or a stream is an int or None.
+
+    reduce = importlib.import_module("pixel-art-raytracer_amd.tileset_reduce")
+"""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+
+from .types import ptr
+
+_par = sys.modules[__package__]  # the package module: its ParError, _ok and _dp, and the HIP runtime it shares with torch
+
+_p, _i = C.c_void_p, C.c_int
+# addons/include/par_tileset_reduce.h, in its order
+ABI_TILESET_REDUCE = {
+    "par_tileset_reduce_work_bytes": (C.c_size_t, [_i, _i]),
+    "par_tileset_reduce_device": [_p, _p, _i, _p, _i, _i, _i, _p, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p],
+    "par_tileset_reduce_host": [_i, _p, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _p, _p, _p, _p],
+}
+ABI_TILESET_REDUCE_SYMBOLS = tuple(ABI_TILESET_REDUCE)
+LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libpar_tileset_reduce.so")
+MAX_TILES, MAX_BUDGET, MAX_CELLS = 4096, 1024, 1 << 20
+
+_lib = None
+
+
+def lib():
+    """Load libpar_tileset_reduce.so (built in-tree by csrc/Makefile) and set the table on its functions. No fallback."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise ImportError(f"{LIB_PATH} is missing: build it with `make -C pixel-art-raytracer_amd/csrc` "
+                              "(or __graft_entry__.build()). There is no CPU fallback.")
+        _par._share_hip_runtime_with_torch()
+        L = C.CDLL(LIB_PATH)
+        for name, sig in ABI_TILESET_REDUCE.items():
+            fn = getattr(L, name)
+            if type(sig) is tuple:
+                fn.restype, sig = sig
+            fn.argtypes = sig
+        _lib = L
+    return _lib
+
+
+def tileset_reduce_work_bytes(cells, capacity):
+    """The bytes of the work block of a tileset_reduce over `cells` map entries and a set of `capacity` tiles
+    (par_tileset_reduce_work_bytes); 0 for cells outside [1, MAX_CELLS] or capacity outside [1, MAX_TILES]."""
+    return lib().par_tileset_reduce_work_bytes(cells, capacity)
+
+
+def tileset_reduce(tiles, capacity, count, tile, tile_map, cells, palette, n_colors, budget, work, tiles_out, map_out,
+                   count_out, remap_out=None, error_out=None, flips=0, stream=None):
+    """Device pointers (ints): the set of `capacity` tiles of tile[0] x tile[1] pixels at `tiles`, whose count is the uint32
+    at `count`, and its map of `cells` entries at `tile_map`, reduced to at most `budget` tiles under the colours of the
+    palette of n_colors four-byte entries at `palette` (par_tileset_reduce_device): the kept tiles go to tiles_out, the
+    rewritten map to map_out (which may be tile_map), their count to the uint32 at count_out, every tile's new number and
+    flip to remap_out and the summed error, a uint64, to error_out when given. `work` holds
+    tileset_reduce_work_bytes(cells, capacity) bytes and needs no preparation. Asynchronous on `stream`."""
+    dp = _par._dp
+    _par._ok(lib().par_tileset_reduce_device, dp(stream), dp(tiles), capacity, dp(count), tile[0], tile[1], flips, dp(tile_map),
+             cells, dp(palette), n_colors, budget, dp(work), dp(tiles_out), dp(map_out), dp(remap_out), dp(count_out),
+             dp(error_out))
+
+
+def tileset_reduce_host(tiles, tile, tile_map, palette, budget, flips=0, device=-1):
+    """The same on host arrays (par_tileset_reduce_host): `tiles` is a uint8 array of whole tiles of tile[0] x tile[1]
+    pixels, `tile_map` a uint32 array, `palette` a uint8 array of four bytes an entry (or a COLOR array). Returns
+    {"tiles": the kept tiles (count, tile[1], tile[0]), "map": uint32 array, "remap": uint32 array, one entry a tile of the
+    input, "count": min(T, budget), "error": the summed error}."""
+    who = "tileset_reduce_host"
+    size = max(1, int(tile[0])) * max(1, int(tile[1]))
+    tiles = _par._flat(tiles, np.uint8)
+    if len(tiles) % size:
+        raise ValueError(f"{who}: tiles holds {len(tiles)} bytes, no whole number of tiles of {size}")
+    n_tiles = len(tiles) // size
+    tile_map = _par._flat(tile_map, np.uint32)
+    palette = np.ascontiguousarray(palette).view(np.uint8).reshape(-1)
+    if len(palette) % 4:
+        raise ValueError(f"{who}: palette holds {len(palette)} bytes, no whole number of entries of 4")
+    kept = np.zeros(max(1, min(max(0, budget), MAX_BUDGET)) * size, dtype=np.uint8)
+    map_out = np.zeros(len(tile_map), dtype=np.uint32)
+    remap = np.zeros(n_tiles, dtype=np.uint32)
+    count, error = C.c_int(0), C.c_uint64(0)
+    _par._ok(lib().par_tileset_reduce_host, device, ptr(tiles), n_tiles, tile[0], tile[1], flips, ptr(tile_map), len(tile_map),
+             ptr(palette), len(palette) // 4, budget, ptr(kept), ptr(map_out), ptr(remap), C.byref(count), C.byref(error))
+    return {"tiles": kept[:count.value * size].reshape(count.value, tile[1], tile[0]), "map": map_out, "remap": remap,
+            "count": count.value, "error": error.value}
