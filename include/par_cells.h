@@ -41,7 +41,8 @@
  * that is not 8 or 16, spread outside [0, 255], params->width <= 0, rows that are not
  * 0 <= row_begin < row_end <= params->height, or a row cut that breaks the cell rule.
  * Left out on purpose: no fitting of sub-palettes to a frame (the fitted-palette calls give a flat palette; how to
- * group it is the caller's art direction), no pattern dither inside cells, no cell sizes other than the four, no fusing
+ * group it is the caller's art direction; the add-on addons/include/par_cells_fit.h fits a table to a frame on the
+ * device, in a library of its own), no pattern dither inside cells, no cell sizes other than the four, no fusing
  * into par_finish_device, and no row cuts through a cell.
  */
 #ifndef PAR_CELLS_H

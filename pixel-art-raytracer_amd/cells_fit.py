@@ -1,0 +1,85 @@
+"""Fitted cells: the table of per-cell sub-palettes of quantize_cells fitted to a frame (addons/include/par_cells_fit.h).
+An add-on: the three calls live in a library of their own, lib/libpar_cells_fit.so, which this module loads itself at the
+first call; their signatures are ABI_CELLS_FIT below, a table that is NOT one of abi.py's (the core library exports none
+of them), and the package does not import this module. The calls raise the package's ParError with the symbol's name; a
+device pointer or a stream is an int or None.
+
+    fit = importlib.import_module("pixel-art-raytracer_amd.cells_fit")
+"""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+
+from .types import ptr
+
+_par = sys.modules[__package__]  # the package module: its ParError, _ok and _dp, and the HIP runtime it shares with torch
+
+_p, _i = C.c_void_p, C.c_int
+# addons/include/par_cells_fit.h, in its order
+ABI_CELLS_FIT = {
+    "par_cells_fit_work_bytes": (C.c_size_t, [_i, _i, _i, _i]),
+    "par_cells_fit_device": [_p, _p, _i, _i, _i, _i, _p, _i, _i, _i, _i, _p, _p, _p, _p],
+    "par_cells_fit_host": [_i, _p, _i, _i, _i, _i, _p, _i, _i, _i, _i, _p, _p, _p],
+}
+ABI_CELLS_FIT_SYMBOLS = tuple(ABI_CELLS_FIT)
+LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libpar_cells_fit.so")
+MAX_CELLS, MAX_SUB_SIZE, MAX_ROUNDS = 1 << 20, 16, 32
+
+_lib = None
+
+
+def lib():
+    """Load libpar_cells_fit.so (built in-tree by csrc/Makefile) and set the table on its functions. No fallback."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise ImportError(f"{LIB_PATH} is missing: build it with `make -C pixel-art-raytracer_amd/csrc` "
+                              "(or __graft_entry__.build()). There is no CPU fallback.")
+        _par._share_hip_runtime_with_torch()
+        L = C.CDLL(LIB_PATH)
+        for name, sig in ABI_CELLS_FIT.items():
+            fn = getattr(L, name)
+            if type(sig) is tuple:
+                fn.restype, sig = sig
+            fn.argtypes = sig
+        _lib = L
+    return _lib
+
+
+def cells_fit_work_bytes(width, height, cell):
+    """The bytes of the work block of a cells_fit over a width x height frame under cells of cell[0] x cell[1] pixels
+    (par_cells_fit_work_bytes); 0 outside the limits."""
+    return lib().par_cells_fit_work_bytes(width, height, cell[0], cell[1])
+
+
+def cells_fit(fb, width, height, cell, palette, n_colors, n_sub, sub_size, rounds, work, table_out, seeds_out=None,
+              errors_out=None, stream=None):
+    """Device pointers (ints): the n_sub sub-palettes of sub_size entries fitted to the width x height frame at `fb` under
+    cells of cell[0] x cell[1] pixels and the master palette of n_colors four-byte entries at `palette`, after `rounds`
+    rounds of assign-and-median (par_cells_fit_device): the n_sub * sub_size four-byte entries go to table_out, the
+    n_sub seed cells (uint32) to seeds_out and the rounds + 1 errors (uint64) to errors_out when given. `work` holds
+    cells_fit_work_bytes(width, height, cell) bytes and needs no preparation. Asynchronous on `stream`."""
+    dp = _par._dp
+    _par._ok(lib().par_cells_fit_device, dp(stream), dp(fb), width, height, cell[0], cell[1], dp(palette), n_colors, n_sub,
+             sub_size, rounds, dp(work), dp(table_out), dp(seeds_out), dp(errors_out))
+
+
+def cells_fit_host(fb, width, height, cell, palette, n_sub, sub_size, rounds=0, device=-1):
+    """The same on host arrays (par_cells_fit_host): `fb` is a COLOR array (or uint8, four bytes a pixel) of
+    width * height pixels, `palette` likewise the master's entries. Returns {"table": uint8 array (n_sub * sub_size, 4),
+    "seeds": uint32 array of n_sub, "errors": uint64 array of rounds + 1}."""
+    who = "cells_fit_host"
+    fb = np.ascontiguousarray(fb).view(np.uint8).reshape(-1)
+    palette = np.ascontiguousarray(palette).view(np.uint8).reshape(-1)
+    if len(palette) % 4:
+        raise ValueError(f"{who}: palette holds {len(palette)} bytes, no whole number of entries of 4")
+    if len(fb) != 4 * max(0, int(width)) * max(0, int(height)):
+        raise ValueError(f"{who}: fb holds {len(fb)} bytes, a {width} x {height} frame {4 * max(0, width) * max(0, height)}")
+    table = np.zeros((max(1, min(256, max(0, n_sub) * max(0, sub_size))), 4), dtype=np.uint8)
+    seeds = np.zeros(max(1, n_sub), dtype=np.uint32)
+    errors = np.zeros(max(1, min(MAX_ROUNDS, rounds) + 1), dtype=np.uint64)
+    _par._ok(lib().par_cells_fit_host, device, ptr(fb), width, height, cell[0], cell[1], ptr(palette), len(palette) // 4,
+             n_sub, sub_size, rounds, ptr(table), ptr(seeds), ptr(errors))
+    return {"table": table, "seeds": seeds, "errors": errors}

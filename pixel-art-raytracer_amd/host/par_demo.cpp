@@ -9,7 +9,7 @@
 //   par_demo [--keys RRRRUUUUhhhhjjPP] [--frames N] [--out DIR] [--gif FILE] [--debug-line] [--as-sdl] [--size W H L]
 //            [--palette-levels K] [--dither S] [--outline S,C,D] [--scale SX[,SY]] [--finish] [--upscale K]
 //            [--palette-fit N] [--palette-refine I] [--dither-pattern N[,S]] [--cells CW,CH] [--tileset TW,TH[,FLIPS]]
-//            [--tileset-shared CAP] [--tileset-budget K]
+//            [--tileset-shared CAP] [--tileset-budget K] [--cells-fit S,K[,R]]
 //
 // --gif writes the frames as one animated GIF89a (100 ms per frame like the reference's gif.gif); a frame's colours
 // are palette entries times a brightness, at most a few hundred distinct values, so each frame gets an exact local
@@ -36,6 +36,11 @@
 // palette. The pairs of that palette (par_cells_pairs: N * (N - 1) / 2 sub-palettes of two entries) are the frame's local
 // colour table and the index plane is written as it comes back; --dither S keeps its meaning. It is refused together
 // with --dither-pattern or --finish.
+// --cells-fit S,K[,R] (with --cells CW,CH and --palette-fit N, K <= N <= 256; S sub-palettes of K = 1..16 entries,
+// S * K <= 256, R = 0..32 rounds, 0 when left out) fits every frame's table of sub-palettes on the GPU through the add-on
+// (par_cells_fit_host of addons/include/par_cells_fit.h, the master the frame's fitted and refined palette) in place of
+// the pairs, and quantises the frame under it: the table is the frame's local colour table. It prints one line a frame,
+// `cells fit frame <i>: <S> x <K>, error <E0> -> <ER>`: the summed L1 error under the seed table and after the rounds.
 // --tileset TW,TH[,FLIPS] (with --gif and --palette-levels, --palette-fit or --cells, wherever a frame of the GIF is an
 // index plane; TW and TH each 8 or 16, FLIPS a mask 0..3 of the mirrors allowed, 0 when left out) counts the distinct
 // tiles of every frame's index plane on the GPU (par_tileset_build_host with capacity 0, behind the quantise) and prints
@@ -87,6 +92,7 @@
 #include <vector>
 
 #include "par_cells.h"
+#include "par_cells_fit.h"
 #include "par_raytracer.h"
 #include "par_tileset.h"
 #include "par_tileset_extend.h"
@@ -257,6 +263,7 @@ int main(int argc, char** argv) {
     int scale_x = 0, scale_y = 0;  // 0: no --scale
     int upscale = 0;               // 0: no --upscale
     int cell_w = 0, cell_h = 0;    // 0: no --cells
+    int fit_sub = 0, fit_size = 0, fit_rounds = 0;  // fit_sub 0: no --cells-fit
     int tile_w = 0, tile_h = 0, tile_flips = 0;  // 0: no --tileset
     int shared_capacity = -1;                    // -1: no --tileset-shared
     int tile_budget = 0;                         // 0: no --tileset-budget
@@ -285,6 +292,17 @@ int main(int argc, char** argv) {
             if (std::sscanf(argv[++i], "%d,%d%c", &cell_w, &cell_h, &tail) != 2 || (cell_w != 8 && cell_w != 16) ||
                 (cell_h != 8 && cell_h != 16)) {
                 std::fprintf(stderr, "--cells wants CW,CH, each 8 or 16, got %s\n", argv[i]);
+                return 2;
+            }
+        }
+        else if (!std::strcmp(argv[i], "--cells-fit") && i + 1 < argc) {
+            char tail = 0;
+            const bool two = std::sscanf(argv[++i], "%d,%d%c", &fit_sub, &fit_size, &tail) == 2;
+            if ((!two && std::sscanf(argv[i], "%d,%d,%d%c", &fit_sub, &fit_size, &fit_rounds, &tail) != 3) || fit_sub < 1 ||
+                fit_size < 1 || fit_size > PAR_CELLS_FIT_MAX_SUB_SIZE || fit_sub > PAR_MAX_PALETTE / fit_size || fit_rounds < 0 ||
+                fit_rounds > PAR_CELLS_FIT_MAX_ROUNDS) {
+                std::fprintf(stderr, "--cells-fit wants S,K[,R], K 1..%d, S * K at most %d and R 0..%d, got %s\n",
+                             PAR_CELLS_FIT_MAX_SUB_SIZE, PAR_MAX_PALETTE, PAR_CELLS_FIT_MAX_ROUNDS, argv[i]);
                 return 2;
             }
         }
@@ -376,8 +394,17 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    if (fit_sub != 0 && cell_w == 0) {
+        std::fprintf(stderr, "--cells-fit wants --cells CW,CH: it fits the sub-palettes of those cells\n");
+        return 2;
+    }
+    if (fit_sub != 0 && (palette_fit < fit_size || palette_fit > PAR_MAX_PALETTE)) {
+        std::fprintf(stderr, "--cells-fit %d,%d wants --palette-fit %d..%d: the master its lists are taken from\n", fit_sub, fit_size,
+                     fit_size, PAR_MAX_PALETTE);
+        return 2;
+    }
     if (cell_w != 0) {
-        if (palette_fit < 2 || palette_fit > 16) {
+        if (fit_sub == 0 && (palette_fit < 2 || palette_fit > 16)) {
             std::fprintf(stderr, "--cells wants --palette-fit 2..16: a cell uses two colours of the fitted palette\n");
             return 2;
         }
@@ -615,7 +642,26 @@ int main(int argc, char** argv) {
                 std::fprintf(stderr, "par_palette_refine_host: %s\n", par_status_string(rc));
                 return 1;
             }
-            if (cell_w != 0) {
+            if (fit_sub != 0) {
+                // (pairs: here the fitted table)
+                pairs.resize((size_t)fit_sub * fit_size);
+                std::vector<uint64_t> errors((size_t)fit_rounds + 1);
+                if ((rc = par_cells_fit_host(0, reinterpret_cast<const uint8_t*>(fb.data()), W, H, cell_w, cell_h,
+                                             reinterpret_cast<const uint8_t*>(fitted.data()), palette_fit, fit_sub, fit_size, fit_rounds,
+                                             reinterpret_cast<uint8_t*>(pairs.data()), nullptr, errors.data())) != PAR_OK) {
+                    std::fprintf(stderr, "par_cells_fit_host: %s\n", par_status_string(rc));
+                    return 1;
+                }
+                std::printf("cells fit frame %d: %d x %d, error %llu -> %llu\n", f, fit_sub, fit_size, (unsigned long long)errors[0],
+                            (unsigned long long)errors[(size_t)fit_rounds]);
+                if ((rc = par_quantize_cells_host(&params, 0, pairs.data(), fit_sub, fit_size, cell_w, cell_h, dither, fb.data(), 0, H,
+                                                  nullptr, index.data(), nullptr)) != PAR_OK) {
+                    std::fprintf(stderr, "par_quantize_cells_host: %s\n", par_status_string(rc));
+                    return 1;
+                }
+                if (count_tiles(f, pairs) != PAR_OK) return 1;
+                gif.frame(index, pairs, 10);
+            } else if (cell_w != 0) {
                 pairs.resize((size_t)palette_fit * (palette_fit - 1));
                 const int n_sub = par_cells_pairs(fitted.data(), palette_fit, pairs.data(), (int)pairs.size());
                 if (n_sub < 0) { std::fprintf(stderr, "par_cells_pairs: %s\n", par_status_string(-n_sub)); return 1; }
