@@ -43,7 +43,8 @@
  * Left out on purpose: no fitting of sub-palettes to a frame (the fitted-palette calls give a flat palette; how to
  * group it is the caller's art direction; the add-on addons/include/par_cells_fit.h fits a table to a frame on the
  * device, in a library of its own), no pattern dither inside cells, no cell sizes other than the four, no fusing
- * into par_finish_device, and no row cuts through a cell.
+ * into par_finish_device, and no row cuts through a cell. The add-on addons/include/par_vram.h takes index_out apart
+ * into what a tile stores (% K) and packs cell_out into a machine's map words.
  */
 #ifndef PAR_CELLS_H
 #define PAR_CELLS_H

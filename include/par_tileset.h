@@ -52,6 +52,7 @@
  * the sets of shards (tile numbers are per call); lossy merging of similar tiles to meet a budget; the sub-palette number
  * in the map word (par_quantize_cells_device's cell_out holds it, one byte a cell in the same numbering); and fusing
  * into the cells kernel. The lossy merge now exists, in an add-on beside the library: addons/include/par_tileset_reduce.h.
+ * So do the match across palette remaps and the sub-palette number in a machine's map word: addons/include/par_vram.h.
  */
 #ifndef PAR_TILESET_H
 #define PAR_TILESET_H

@@ -9,7 +9,7 @@
 //   par_demo [--keys RRRRUUUUhhhhjjPP] [--frames N] [--out DIR] [--gif FILE] [--debug-line] [--as-sdl] [--size W H L]
 //            [--palette-levels K] [--dither S] [--outline S,C,D] [--scale SX[,SY]] [--finish] [--upscale K]
 //            [--palette-fit N] [--palette-refine I] [--dither-pattern N[,S]] [--cells CW,CH] [--tileset TW,TH[,FLIPS]]
-//            [--tileset-shared CAP] [--tileset-budget K] [--cells-fit S,K[,R]]
+//            [--tileset-shared CAP] [--tileset-budget K] [--cells-fit S,K[,R]] [--vram MACHINE[,DIR]]
 //
 // --gif writes the frames as one animated GIF89a (100 ms per frame like the reference's gif.gif); a frame's colours
 // are palette entries times a brightness, at most a few hundred distinct values, so each frame gets an exact local
@@ -57,6 +57,16 @@
 // the frame's `tileset frame` line it prints `tileset budget frame <i>: <T> -> <K'> tiles, error <E>`: the tiles kept
 // and the summed L1 error of the reduced picture. A frame of more than 4096 tiles is beyond the add-on and is reported
 // as such. It changes no byte of the GIF either.
+// --vram MACHINE[,DIR] (with --cells and --tileset 8,8[,FLIPS]; MACHINE one of nes, gbc, sms, megadrive, snes, gba) exports
+// every frame's cells index plane the way that machine loads it, through the add-on of addons/include/par_vram.h: the
+// plane taken modulo the sub-palette size K (what a tile stores; K is 2, or --cells-fit's, and at most the 4 or 16 colours
+// of the machine's tiles), the tile set of that local plane (par_tileset_build_host, the mirrors of --tileset), the set
+// packed into the machine's tile format (par_vram_encode_tiles_host) and the map with every cell's sub-palette into its
+// map words (par_vram_encode_map_host over the cells' cell_out). After the frame's tileset lines it prints
+// `vram frame <i>: <T> tiles (<Tflat> flat), <B> tile bytes, <M> map bytes, bad <b>`: the tiles of the local plane and of
+// the flat one, the bytes of both exports, and the tiles and cells the machine cannot show as they are (a palette or tile
+// number beyond its word, a mirror it lacks). With DIR it writes frame_<i>.chr, frame_<i>.map and, except for nes,
+// frame_<i>.pal (the frame's table as the machine's colour words). It changes no byte of the GIF.
 //
 // --outline S,C,D draws every frame's outlines on the GPU (par_outline_host) from the frame's own G-buffer: silhouettes
 // scaled by S / 256, creases by C / 256, a silhouette between two entities from a depth difference of D (128,320,4 is a
@@ -97,6 +107,7 @@
 #include "par_tileset.h"
 #include "par_tileset_extend.h"
 #include "par_tileset_reduce.h"
+#include "par_vram.h"
 
 static void apply_key(char k, par_aabb& player, par_light& light) {
     switch (k) {
@@ -267,6 +278,8 @@ int main(int argc, char** argv) {
     int tile_w = 0, tile_h = 0, tile_flips = 0;  // 0: no --tileset
     int shared_capacity = -1;                    // -1: no --tileset-shared
     int tile_budget = 0;                         // 0: no --tileset-budget
+    int vram_machine = -1;                       // -1: no --vram
+    std::string vram_name, vram_dir;
     par_outline_style outline_style{4, 256, 256};
     for (int i = 1; i < argc; i++) {
         if (!std::strcmp(argv[i], "--keys") && i + 1 < argc) keys = argv[++i];
@@ -328,6 +341,20 @@ int main(int argc, char** argv) {
             if (std::sscanf(argv[++i], "%d%c", &tile_budget, &tail) != 1 || tile_budget < 1 ||
                 tile_budget > PAR_TILESET_REDUCE_MAX_BUDGET) {
                 std::fprintf(stderr, "--tileset-budget wants 1..%d tiles, got %s\n", PAR_TILESET_REDUCE_MAX_BUDGET, argv[i]);
+                return 2;
+            }
+        }
+        else if (!std::strcmp(argv[i], "--vram") && i + 1 < argc) {
+            static const char* const machines[] = {"nes", "gbc", "sms", "megadrive", "snes", "gba"};
+            const std::string arg = argv[++i];
+            const size_t comma = arg.find(',');
+            vram_name = arg.substr(0, comma);
+            if (comma != std::string::npos) vram_dir = arg.substr(comma + 1);
+            for (int m = PAR_VRAM_NES; m <= PAR_VRAM_GBA; m++) {
+                if (vram_name == machines[m]) vram_machine = m;
+            }
+            if (vram_machine < 0 || (comma != std::string::npos && vram_dir.empty())) {
+                std::fprintf(stderr, "--vram wants MACHINE[,DIR], MACHINE one of nes, gbc, sms, megadrive, snes, gba, got %s\n", argv[i]);
                 return 2;
             }
         }
@@ -425,6 +452,24 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--tileset-budget wants --tileset TW,TH[,FLIPS]: it reduces the set of those tiles\n");
         return 2;
     }
+    // --vram: the machine's tile format, its colour words (-1: none, the NES has a fixed master palette) and its layout
+    static const int vram_formats[] = {PAR_VRAM_2BPP_PLANAR, PAR_VRAM_2BPP_ROWS, PAR_VRAM_4BPP_ROW_PLANES,
+                                       PAR_VRAM_4BPP_PACKED_HI, PAR_VRAM_4BPP_ROWS, PAR_VRAM_4BPP_PACKED_LO};
+    static const int vram_colours[] = {-1, PAR_VRAM_BGR555, PAR_VRAM_BGR222, PAR_VRAM_BGR333_MD, PAR_VRAM_BGR555, PAR_VRAM_BGR555};
+    const int vram_sub_size = fit_sub != 0 ? fit_size : 2;
+    if (vram_machine >= 0) {
+        if (cell_w == 0 || tile_w != 8 || tile_h != 8) {
+            std::fprintf(stderr, "--vram wants --cells CW,CH and --tileset 8,8[,FLIPS]: it exports the 8 x 8 tiles of a cells index plane, "
+                                 "a cell one or two tiles a side\n");
+            return 2;
+        }
+        const int most = vram_machine <= PAR_VRAM_GBC ? 4 : 16;
+        if (vram_sub_size > most) {
+            std::fprintf(stderr, "--vram %s wants sub-palettes of at most %d entries, --cells-fit S,K has K = %d\n", vram_name.c_str(), most,
+                         vram_sub_size);
+            return 2;
+        }
+    }
     if (finish) {
         if (out_dir.empty()) { std::fprintf(stderr, "--finish wants --out\n"); return 2; }
         if (!outline && palette_levels == 0) { std::fprintf(stderr, "--finish wants --outline or --palette-levels: without both it is --scale\n"); return 2; }
@@ -520,6 +565,58 @@ int main(int argc, char** argv) {
         std::printf("tileset budget frame %d: %d -> %d tiles, error %llu\n", f, built, left, (unsigned long long)error);
         return (int)PAR_OK;
     };
+    // --vram: every cell's sub-palette (the cells call's cell_out), and the flat plane's tile count --tileset printed last
+    std::vector<unsigned char> chosen;
+    if (vram_machine >= 0) chosen.resize((size_t)((W + cell_w - 1) / cell_w) * (size_t)((H + cell_h - 1) / cell_h));
+    int flat_tiles = 0;
+    const auto write_file = [&](int f, const char* ext, const std::vector<unsigned char>& bytes) {
+        char name[64];
+        std::snprintf(name, sizeof(name), "/frame_%03d.%s", f, ext);
+        FILE* file = std::fopen((vram_dir + name).c_str(), "wb");
+        const bool ok = file && std::fwrite(bytes.data(), 1, bytes.size(), file) == bytes.size();
+        if (file) std::fclose(file);
+        if (!ok) std::fprintf(stderr, "cannot write %s%s\n", vram_dir.c_str(), name);
+        return ok;
+    };
+    // --vram: frame f's index plane over `table` (sub-palettes of vram_sub_size entries) exported, printed and written
+    const auto export_vram = [&](int f, const std::vector<par_color>& table) -> int {
+        if (vram_machine < 0) return (int)PAR_OK;
+        const int gcx = (W + 7) / 8, gcy = (H + 7) / 8, cells = gcx * gcy, format = vram_formats[vram_machine];
+        std::vector<unsigned char> local(index.size()), set((size_t)cells * 64);
+        for (size_t i = 0; i < index.size(); i++) local[i] = (unsigned char)(index[i] % vram_sub_size);
+        std::vector<uint32_t> tile_map((size_t)cells);
+        int tiles = 0, bad_tiles = 0, bad_cells = 0;
+        int status = par_tileset_build_host(&params, 0, local.data(), 0, H, 8, 8, 0, tile_flips, set.data(), cells, tile_map.data(),
+                                            &tiles);
+        if (status != PAR_OK) {
+            std::fprintf(stderr, "par_tileset_build_host: %s\n", par_status_string(status));
+            return status;
+        }
+        std::vector<unsigned char> chr((size_t)tiles * par_vram_tile_bytes(format, 8, 8));
+        if ((status = par_vram_encode_tiles_host(0, set.data(), cells, tiles, 8, 8, format, chr.data(), &bad_tiles)) != PAR_OK) {
+            std::fprintf(stderr, "par_vram_encode_tiles_host: %s\n", par_status_string(status));
+            return status;
+        }
+        par_vram_map_layout layout;
+        par_vram_map_layout_preset(vram_machine, &layout);
+        std::vector<unsigned char> words((size_t)cells * (size_t)layout.word_bytes);
+        if ((status = par_vram_encode_map_host(0, &layout, tile_map.data(), gcx, gcy, chosen.data(), cell_w / 8, cell_h / 8, words.data(),
+                                               &bad_cells)) != PAR_OK) {
+            std::fprintf(stderr, "par_vram_encode_map_host: %s\n", par_status_string(status));
+            return status;
+        }
+        std::printf("vram frame %d: %d tiles (%d flat), %zu tile bytes, %zu map bytes, bad %d\n", f, tiles, flat_tiles, chr.size(),
+                    words.size(), bad_tiles + bad_cells);
+        if (vram_dir.empty()) return (int)PAR_OK;
+        if (!write_file(f, "chr", chr) || !write_file(f, "map", words)) return -1;  // (any status but PAR_OK ends the run)
+        if (vram_colours[vram_machine] >= 0) {
+            std::vector<unsigned char> colours(2 * table.size());
+            colours.resize(par_vram_palette_words(reinterpret_cast<const uint8_t*>(table.data()), (int)table.size(),
+                                                  vram_colours[vram_machine], colours.data()));
+            if (!write_file(f, "pal", colours)) return -1;
+        }
+        return (int)PAR_OK;
+    };
     // --tileset: the tiles of the index plane of frame f as it stands over `pal`, counted and printed
     const auto count_tiles = [&](int f, const std::vector<par_color>& pal) -> int {
         if (tile_w == 0) return PAR_OK;
@@ -532,6 +629,7 @@ int main(int argc, char** argv) {
         }
         std::printf("tileset frame %d: %d tiles of %d cells\n", f, tiles,
                     ((W + tile_w - 1) / tile_w) * ((H + tile_h - 1) / tile_h));
+        flat_tiles = tiles;
         if (tile_budget != 0) {
             const int budget_status = reduce_tiles(f, tiles, pal);
             if (budget_status != PAR_OK) return budget_status;
@@ -655,22 +753,22 @@ int main(int argc, char** argv) {
                 std::printf("cells fit frame %d: %d x %d, error %llu -> %llu\n", f, fit_sub, fit_size, (unsigned long long)errors[0],
                             (unsigned long long)errors[(size_t)fit_rounds]);
                 if ((rc = par_quantize_cells_host(&params, 0, pairs.data(), fit_sub, fit_size, cell_w, cell_h, dither, fb.data(), 0, H,
-                                                  nullptr, index.data(), nullptr)) != PAR_OK) {
+                                                  nullptr, index.data(), chosen.empty() ? nullptr : chosen.data())) != PAR_OK) {
                     std::fprintf(stderr, "par_quantize_cells_host: %s\n", par_status_string(rc));
                     return 1;
                 }
-                if (count_tiles(f, pairs) != PAR_OK) return 1;
+                if (count_tiles(f, pairs) != PAR_OK || export_vram(f, pairs) != PAR_OK) return 1;
                 gif.frame(index, pairs, 10);
             } else if (cell_w != 0) {
                 pairs.resize((size_t)palette_fit * (palette_fit - 1));
                 const int n_sub = par_cells_pairs(fitted.data(), palette_fit, pairs.data(), (int)pairs.size());
                 if (n_sub < 0) { std::fprintf(stderr, "par_cells_pairs: %s\n", par_status_string(-n_sub)); return 1; }
                 if ((rc = par_quantize_cells_host(&params, 0, pairs.data(), n_sub, 2, cell_w, cell_h, dither, fb.data(), 0, H,
-                                                  nullptr, index.data(), nullptr)) != PAR_OK) {
+                                                  nullptr, index.data(), chosen.empty() ? nullptr : chosen.data())) != PAR_OK) {
                     std::fprintf(stderr, "par_quantize_cells_host: %s\n", par_status_string(rc));
                     return 1;
                 }
-                if (count_tiles(f, pairs) != PAR_OK) return 1;
+                if (count_tiles(f, pairs) != PAR_OK || export_vram(f, pairs) != PAR_OK) return 1;
                 gif.frame(index, pairs, 10);
             } else {
                 if (quantise(fitted) != PAR_OK || count_tiles(f, fitted) != PAR_OK) return 1;

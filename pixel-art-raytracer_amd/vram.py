@@ -1,0 +1,181 @@
+"""VRAM export: a tile set, its map and its palette packed into the formats tile hardware loads
+(addons/include/par_vram.h). An add-on: the ten calls live in a library of their own, lib/libpar_vram.so, which this
+module loads itself at the first call; their signatures are ABI_VRAM below, a table that is NOT one of abi.py's (the core
+library exports none of them), and the package does not import this module. The calls raise the package's ParError with
+the symbol's name; a device pointer or a stream is an int or None.
+
+    vram = importlib.import_module("pixel-art-raytracer_amd.vram")
+"""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+
+from .types import ptr
+
+_par = sys.modules[__package__]  # the package module: its ParError, _ok and _dp, and the HIP runtime it shares with torch
+
+_p, _i = C.c_void_p, C.c_int
+# addons/include/par_vram.h, in its order
+ABI_VRAM = {
+    "par_vram_tile_bytes": (C.c_size_t, [_i, _i, _i]),
+    "par_vram_local_device": [_p, _p, _i, _i, _p],
+    "par_vram_encode_tiles_device": [_p, _p, _i, _p, _i, _i, _i, _p, _p],
+    "par_vram_decode_tiles_device": [_p, _p, _i, _i, _i, _i, _p],
+    "par_vram_map_layout_preset": [_i, _p],
+    "par_vram_encode_map_device": [_p, _p, _p, _i, _i, _p, _i, _i, _p, _p],
+    "par_vram_palette_words": (C.c_size_t, [_p, _i, _i, _p]),
+    "par_vram_encode_tiles_host": [_i, _p, _i, _i, _i, _i, _i, _p, _p],
+    "par_vram_decode_tiles_host": [_i, _p, _i, _i, _i, _i, _p],
+    "par_vram_encode_map_host": [_i, _p, _p, _i, _i, _p, _i, _i, _p, _p],
+}
+ABI_VRAM_SYMBOLS = tuple(ABI_VRAM)
+LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libpar_vram.so")
+MAX_TILES, MAX_CELLS = 1 << 20, 1 << 20
+# enum par_vram_tile_format
+FORMAT_1BPP, FORMAT_2BPP_PLANAR, FORMAT_2BPP_ROWS, FORMAT_4BPP_ROWS, FORMAT_4BPP_PACKED_HI, FORMAT_4BPP_PACKED_LO, \
+    FORMAT_4BPP_ROW_PLANES = range(7)
+FORMATS = tuple(range(7))
+BPP = (1, 2, 2, 4, 4, 4, 4)
+# enum par_vram_machine
+NES, GBC, SMS, MEGADRIVE, SNES, GBA = range(6)
+MACHINES = {"nes": NES, "gbc": GBC, "sms": SMS, "megadrive": MEGADRIVE, "snes": SNES, "gba": GBA}
+# enum par_vram_palette_format, and the bytes of a word
+BGR555, BGR333_MD, BGR222 = range(3)
+PALETTE_WORD_BYTES = (2, 2, 1)
+
+
+class MapLayout(C.Structure):
+    """par_vram_map_layout: where a machine's map word keeps the tile, the palette and the flips."""
+    _fields_ = [(name, C.c_int32) for name in ("word_bytes", "big_endian", "tile_shift", "tile_bits", "pal_shift", "pal_bits",
+                                               "flip_x_bit", "flip_y_bit", "tile_step", "tile_base", "set_bits")]
+
+
+_lib = None
+
+
+def lib():
+    """Load libpar_vram.so (built in-tree by csrc/Makefile) and set the table on its functions. No fallback."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise ImportError(f"{LIB_PATH} is missing: build it with `make -C pixel-art-raytracer_amd/csrc` "
+                              "(or __graft_entry__.build()). There is no CPU fallback.")
+        _par._share_hip_runtime_with_torch()
+        L = C.CDLL(LIB_PATH)
+        for name, sig in ABI_VRAM.items():
+            fn = getattr(L, name)
+            if type(sig) is tuple:
+                fn.restype, sig = sig
+            fn.argtypes = sig
+        _lib = L
+    return _lib
+
+
+def tile_bytes(fmt, tile):
+    """The bytes of one tile of tile[0] x tile[1] pixels in format `fmt` (par_vram_tile_bytes); 0 outside the limits."""
+    return lib().par_vram_tile_bytes(fmt, tile[0], tile[1])
+
+
+def map_layout_preset(machine):
+    """The MapLayout of a machine (par_vram_map_layout_preset): NES, GBC, SMS, MEGADRIVE, SNES or GBA."""
+    layout = MapLayout()
+    _par._ok(lib().par_vram_map_layout_preset, machine, C.byref(layout))
+    return layout
+
+
+def palette_words(palette, fmt):
+    """The entries of `palette` (a COLOR array, or uint8, four bytes an entry) as the machine words of format `fmt`
+    (par_vram_palette_words): a uint8 array. Host arithmetic, no GPU."""
+    palette = np.ascontiguousarray(palette).view(np.uint8).reshape(-1)
+    if len(palette) % 4:
+        raise ValueError(f"palette_words: palette holds {len(palette)} bytes, no whole number of entries of 4")
+    out = np.zeros(max(1, len(palette) // 2), dtype=np.uint8)
+    wrote = lib().par_vram_palette_words(ptr(palette), len(palette) // 4, fmt, ptr(out))
+    if wrote == 0:
+        raise _par.ParError(1, "par_vram_palette_words")
+    return out[:wrote]
+
+
+def local(index, n_bytes, sub_size, local_out, stream=None):
+    """Device pointers (ints): local_out[i] = index[i] % sub_size for n_bytes bytes (par_vram_local_device); in place
+    when local_out == index. Asynchronous on `stream`."""
+    dp = _par._dp
+    _par._ok(lib().par_vram_local_device, dp(stream), dp(index), n_bytes, sub_size, dp(local_out))
+
+
+def encode_tiles(tiles, capacity, count, tile, fmt, out, bad_out=None, stream=None):
+    """Device pointers (ints): the first min(*count, capacity) of the `capacity` tiles of tile[0] x tile[1] bytes at
+    `tiles` packed into format `fmt` at `out` (par_vram_encode_tiles_device). `count` is a device uint32 or None (all the
+    tiles); bad_out, when given, gets the number of tiles with a byte too large as a uint32. Asynchronous on `stream`."""
+    dp = _par._dp
+    _par._ok(lib().par_vram_encode_tiles_device, dp(stream), dp(tiles), capacity, dp(count), tile[0], tile[1], fmt, dp(out),
+             dp(bad_out))
+
+
+def decode_tiles(data, n_tiles, tile, fmt, tiles_out, stream=None):
+    """Device pointers (ints): n_tiles tiles of format `fmt` at `data` unpacked to a byte a pixel at tiles_out
+    (par_vram_decode_tiles_device). Asynchronous on `stream`."""
+    dp = _par._dp
+    _par._ok(lib().par_vram_decode_tiles_device, dp(stream), dp(data), n_tiles, tile[0], tile[1], fmt, dp(tiles_out))
+
+
+def encode_map(layout, tile_map, grid, out, cells=None, ratio=(1, 1), bad_out=None, stream=None):
+    """Device pointers (ints): the grid[0] x grid[1] words of the tile map at `tile_map` as the machine words of
+    `layout` (a MapLayout) at `out` (par_vram_encode_map_device); `cells` is the cell_out of quantize_cells or None,
+    ratio the tiles a colour cell spans each way. Asynchronous on `stream`."""
+    dp = _par._dp
+    _par._ok(lib().par_vram_encode_map_device, dp(stream), C.byref(layout), dp(tile_map), grid[0], grid[1], dp(cells), ratio[0],
+             ratio[1], dp(out), dp(bad_out))
+
+
+def encode_tiles_host(tiles, tile, fmt, count=None, device=-1):
+    """The same on host arrays (par_vram_encode_tiles_host): `tiles` is a uint8 array of whole tiles, `count` the tiles
+    to encode (default: all). Returns {"data": uint8 array, "bad": the tiles with a byte too large}."""
+    who = "encode_tiles_host"
+    tiles = np.ascontiguousarray(tiles, dtype=np.uint8).reshape(-1)
+    size = max(1, int(tile[0])) * max(1, int(tile[1]))
+    if len(tiles) % size:
+        raise ValueError(f"{who}: tiles holds {len(tiles)} bytes, no whole number of tiles of {size}")
+    capacity = len(tiles) // size
+    count = capacity if count is None else count
+    out = np.zeros(max(1, min(max(0, count), capacity) * 4 * size // 8), dtype=np.uint8)
+    bad = C.c_int(0)
+    _par._ok(lib().par_vram_encode_tiles_host, device, ptr(tiles), capacity, count, tile[0], tile[1], fmt, ptr(out), C.byref(bad))
+    return {"data": out[:min(count, capacity) * tile_bytes(fmt, tile)], "bad": bad.value}
+
+
+def decode_tiles_host(data, tile, fmt, device=-1):
+    """Host arrays (par_vram_decode_tiles_host): `data` is a uint8 array of whole encoded tiles. Returns the uint8 array
+    (n_tiles, tile[1], tile[0])."""
+    who = "decode_tiles_host"
+    data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    each = tile_bytes(fmt, tile)
+    if each == 0 or len(data) % each:
+        raise ValueError(f"{who}: data holds {len(data)} bytes, no whole number of tiles of {each}")
+    n = len(data) // each
+    out = np.zeros((max(1, n), tile[1], tile[0]), dtype=np.uint8)
+    _par._ok(lib().par_vram_decode_tiles_host, device, ptr(data), n, tile[0], tile[1], fmt, ptr(out))
+    return out[:n]
+
+
+def encode_map_host(layout, tile_map, grid, cells=None, ratio=(1, 1), device=-1):
+    """Host arrays (par_vram_encode_map_host): `tile_map` is a uint32 array of grid[0] * grid[1] words, `cells` a uint8
+    array of one byte a colour cell or None. Returns {"data": uint8 array of word_bytes bytes a cell, "bad": the bad
+    cells}."""
+    who = "encode_map_host"
+    tile_map = np.ascontiguousarray(tile_map, dtype=np.uint32).reshape(-1)
+    n = max(0, int(grid[0])) * max(0, int(grid[1]))
+    if len(tile_map) != n:
+        raise ValueError(f"{who}: the map holds {len(tile_map)} entries, a {grid[0]} x {grid[1]} grid {n}")
+    if cells is not None:
+        cells = np.ascontiguousarray(cells, dtype=np.uint8).reshape(-1)
+        want = -(-grid[0] // max(1, ratio[0])) * -(-grid[1] // max(1, ratio[1]))
+        if len(cells) != want:
+            raise ValueError(f"{who}: cells holds {len(cells)} bytes, the grid has {want} colour cells")
+    out = np.zeros(max(1, n * 4), dtype=np.uint8)
+    bad = C.c_int(0)
+    _par._ok(lib().par_vram_encode_map_host, device, C.byref(layout), ptr(tile_map), grid[0], grid[1],
+             None if cells is None else ptr(cells), ratio[0], ratio[1], ptr(out), C.byref(bad))
+    return {"data": out[:n * layout.word_bytes], "bad": bad.value}
