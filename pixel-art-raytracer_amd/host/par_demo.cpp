@@ -9,7 +9,7 @@
 //   par_demo [--keys RRRRUUUUhhhhjjPP] [--frames N] [--out DIR] [--gif FILE] [--debug-line] [--as-sdl] [--size W H L]
 //            [--palette-levels K] [--dither S] [--outline S,C,D] [--scale SX[,SY]] [--finish] [--upscale K]
 //            [--palette-fit N] [--palette-refine I] [--dither-pattern N[,S]] [--cells CW,CH] [--tileset TW,TH[,FLIPS]]
-//            [--tileset-shared CAP] [--tileset-budget K] [--cells-fit S,K[,R]] [--vram MACHINE[,DIR]]
+//            [--tileset-shared CAP] [--tileset-budget K] [--cells-fit S,K[,R]] [--vram MACHINE[,DIR]] [--vram-show [backdrop]]
 //
 // --gif writes the frames as one animated GIF89a (100 ms per frame like the reference's gif.gif); a frame's colours
 // are palette entries times a brightness, at most a few hundred distinct values, so each frame gets an exact local
@@ -67,6 +67,13 @@
 // the flat one, the bytes of both exports, and the tiles and cells the machine cannot show as they are (a palette or tile
 // number beyond its word, a mirror it lacks). With DIR it writes frame_<i>.chr, frame_<i>.map and, except for nes,
 // frame_<i>.pal (the frame's table as the machine's colour words). It changes no byte of the GIF.
+// --vram-show [backdrop] (with --vram) draws every frame's export the way the machine shows it, through the add-on of
+// addons/include/par_screen.h: one par_screen_draw_host over the frame's tile bytes, map words and colour words (the nes
+// has no colour words: its table goes in as RGBA8 entries, and the cells' cell_out as the attribute grid) on a screen the
+// size of the frame at scroll 0; with `backdrop` every tile pixel of value 0 shows entry 0. After the `vram frame` line it
+// prints `screen frame <i>: bad <b>, error <E>`: the map cells that name no tile of the export, and the summed L1 over red,
+// green and blue between the shown picture and the cells frame (the table's entry of every index). With --vram's DIR it
+// writes frame_<i>.ppm. Without it nothing the demo prints or writes changes.
 //
 // --outline S,C,D draws every frame's outlines on the GPU (par_outline_host) from the frame's own G-buffer: silhouettes
 // scaled by S / 256, creases by C / 256, a silhouette between two entities from a depth difference of D (128,320,4 is a
@@ -90,6 +97,7 @@
 //
 // Letters: R L U D P N = right, left, up, down, page-up, page-down; a k j u h o as in the reference. Frame 0 gets no
 // key; frame k applies key k-1 (cycling when --frames exceeds the script).
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -104,6 +112,7 @@
 #include "par_cells.h"
 #include "par_cells_fit.h"
 #include "par_raytracer.h"
+#include "par_screen.h"
 #include "par_tileset.h"
 #include "par_tileset_extend.h"
 #include "par_tileset_reduce.h"
@@ -280,6 +289,7 @@ int main(int argc, char** argv) {
     int tile_budget = 0;                         // 0: no --tileset-budget
     int vram_machine = -1;                       // -1: no --vram
     std::string vram_name, vram_dir;
+    int vram_show = -1;                          // -1: no --vram-show; else its backdrop
     par_outline_style outline_style{4, 256, 256};
     for (int i = 1; i < argc; i++) {
         if (!std::strcmp(argv[i], "--keys") && i + 1 < argc) keys = argv[++i];
@@ -357,6 +367,10 @@ int main(int argc, char** argv) {
                 std::fprintf(stderr, "--vram wants MACHINE[,DIR], MACHINE one of nes, gbc, sms, megadrive, snes, gba, got %s\n", argv[i]);
                 return 2;
             }
+        }
+        else if (!std::strcmp(argv[i], "--vram-show")) {
+            vram_show = 0;
+            if (i + 1 < argc && !std::strcmp(argv[i + 1], "backdrop")) { vram_show = 1; i++; }
         }
         else if (!std::strcmp(argv[i], "--palette-fit") && i + 1 < argc) {
             char tail;
@@ -470,6 +484,7 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    if (vram_show >= 0 && vram_machine < 0) { std::fprintf(stderr, "--vram-show wants --vram MACHINE[,DIR]: it draws that export\n"); return 2; }
     if (finish) {
         if (out_dir.empty()) { std::fprintf(stderr, "--finish wants --out\n"); return 2; }
         if (!outline && palette_levels == 0) { std::fprintf(stderr, "--finish wants --outline or --palette-levels: without both it is --scale\n"); return 2; }
@@ -607,7 +622,45 @@ int main(int argc, char** argv) {
         }
         std::printf("vram frame %d: %d tiles (%d flat), %zu tile bytes, %zu map bytes, bad %d\n", f, tiles, flat_tiles, chr.size(),
                     words.size(), bad_tiles + bad_cells);
+        std::vector<par_color> screen;
+        if (vram_show >= 0) {
+            // the machine's last step: the export drawn on a screen the size of the frame (par_screen.h's layout is
+            // par_vram.h's field for field, and its formats have equal values)
+            const int n_colors = (int)std::min<size_t>(table.size(), 256), colour_format = vram_colours[vram_machine];
+            par_screen_desc d;
+            std::memcpy(&d.layout, &layout, sizeof(d.layout));
+            d.tile_w = d.tile_h = 8, d.tile_format = format, d.n_tiles = tiles;
+            d.map_w = gcx, d.map_h = gcy, d.ratio_x = cell_w / 8, d.ratio_y = cell_h / 8;
+            d.pal_format = colour_format >= 0 ? colour_format : (int)PAR_SCREEN_RGBA8, d.n_colors = n_colors, d.sub_size = vram_sub_size;
+            d.backdrop = vram_show, d.width = W, d.height = H, d.scroll_x = d.scroll_y = 0;
+            std::vector<unsigned char> colours(4 * (size_t)n_colors);
+            if (colour_format >= 0) {
+                colours.resize(par_vram_palette_words(reinterpret_cast<const uint8_t*>(table.data()), n_colors, colour_format, colours.data()));
+            } else {
+                std::memcpy(colours.data(), table.data(), colours.size());
+            }
+            screen.resize((size_t)W * H);
+            int bad_shown = 0;
+            // (the nes keeps a cell's palette in its attribute table, which the export leaves to the caller: cell_out is that grid)
+            if ((status = par_screen_draw_host(0, &d, chr.data(), words.data(), vram_machine == PAR_VRAM_NES ? chosen.data() : nullptr,
+                                               colours.data(), nullptr, reinterpret_cast<uint8_t*>(screen.data()), nullptr, &bad_shown)) != PAR_OK) {
+                std::fprintf(stderr, "par_screen_draw_host: %s\n", par_status_string(status));
+                return status;
+            }
+            unsigned long long error = 0;
+            for (size_t i = 0; i < screen.size(); i++) {
+                const par_color meant = table[index[i]], got = screen[i];
+                error += (unsigned long long)(std::abs((int)got.red - (int)meant.red) + std::abs((int)got.green - (int)meant.green) +
+                                              std::abs((int)got.blue - (int)meant.blue));
+            }
+            std::printf("screen frame %d: bad %d, error %llu\n", f, bad_shown, error);
+        }
         if (vram_dir.empty()) return (int)PAR_OK;
+        if (!screen.empty()) {
+            char name[64];
+            std::snprintf(name, sizeof(name), "/frame_%03d.ppm", f);
+            if (!write_ppm(vram_dir + name, screen.data(), W, H)) { std::fprintf(stderr, "cannot write %s%s\n", vram_dir.c_str(), name); return -1; }
+        }
         if (!write_file(f, "chr", chr) || !write_file(f, "map", words)) return -1;  // (any status but PAR_OK ends the run)
         if (vram_colours[vram_machine] >= 0) {
             std::vector<unsigned char> colours(2 * table.size());

@@ -1,0 +1,180 @@
+"""Screen: one background layer of a tile machine drawn from its VRAM bytes (addons/include/par_screen.h). An add-on: the
+six calls live in a library of their own, lib/libpar_screen.so, which this module loads itself at the first call; their
+signatures are ABI_SCREEN below, a table that is NOT one of abi.py's (the core library exports none of them), and the
+package does not import this module. The calls raise the package's ParError with the symbol's name; a device pointer or a
+stream is an int or None.
+
+    screen = importlib.import_module("pixel-art-raytracer_amd.screen")
+"""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+
+from .types import ptr
+
+_par = sys.modules[__package__]  # the package module: its ParError, _ok and _dp, and the HIP runtime it shares with torch
+
+_p, _i = C.c_void_p, C.c_int
+# addons/include/par_screen.h, in its order
+ABI_SCREEN = {
+    "par_screen_tile_bytes": (C.c_size_t, [_i, _i, _i]),
+    "par_screen_palette_rgba": (C.c_size_t, [_p, _i, _i, _p]),
+    "par_screen_draw_device": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "par_screen_decode_map_device": [_p, _p, _p, _i, _p, _p, _p],
+    "par_screen_draw_host": [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "par_screen_decode_map_host": [_i, _p, _p, _i, _p, _p, _p],
+}
+ABI_SCREEN_SYMBOLS = tuple(ABI_SCREEN)
+LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libpar_screen.so")
+MAX_TILES, MAX_CELLS, MAX_SIDE = 1 << 20, 1 << 20, 4096
+# enum par_screen_tile_format
+FORMAT_1BPP, FORMAT_2BPP_PLANAR, FORMAT_2BPP_ROWS, FORMAT_4BPP_ROWS, FORMAT_4BPP_PACKED_HI, FORMAT_4BPP_PACKED_LO, \
+    FORMAT_4BPP_ROW_PLANES = range(7)
+FORMATS = tuple(range(7))
+BPP = (1, 2, 2, 4, 4, 4, 4)
+# enum par_screen_palette_format, and the bytes of an entry
+BGR555, BGR333_MD, BGR222, RGBA8 = range(4)
+PALETTE_ENTRY_BYTES = (2, 2, 1, 4)
+LAYOUT_FIELDS = ("word_bytes", "big_endian", "tile_shift", "tile_bits", "pal_shift", "pal_bits", "flip_x_bit", "flip_y_bit",
+                 "tile_step", "tile_base", "set_bits")
+DESC_FIELDS = ("tile_w", "tile_h", "tile_format", "n_tiles", "map_w", "map_h", "ratio_x", "ratio_y", "pal_format", "n_colors",
+               "sub_size", "backdrop", "width", "height", "scroll_x", "scroll_y")
+
+
+class MapLayout(C.Structure):
+    """par_screen_map_layout: par_vram_map_layout field for field."""
+    _fields_ = [(name, C.c_int32) for name in LAYOUT_FIELDS]
+
+
+class Desc(C.Structure):
+    """par_screen_desc: the layout, then the tiles, the map, the palette, the screen and the scroll."""
+    _fields_ = [("layout", MapLayout)] + [(name, C.c_int32) for name in DESC_FIELDS]
+
+
+def desc(layout, **fields):
+    """A Desc over `layout` (a MapLayout of this module or of the vram module, or a dict of its fields) with `fields` on top
+    of ratios of 1, no backdrop and no scroll."""
+    if isinstance(layout, dict):
+        layout = MapLayout(*(layout[f] for f in LAYOUT_FIELDS))
+    d = Desc(MapLayout(*(getattr(layout, f) for f in LAYOUT_FIELDS)))
+    d.ratio_x = d.ratio_y = 1
+    for name, value in fields.items():
+        if name not in DESC_FIELDS:
+            raise TypeError(f"desc: par_screen_desc has no field {name}")
+        setattr(d, name, value)
+    return d
+
+
+_lib = None
+
+
+def lib():
+    """Load libpar_screen.so (built in-tree by csrc/Makefile) and set the table on its functions. No fallback."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise ImportError(f"{LIB_PATH} is missing: build it with `make -C pixel-art-raytracer_amd/csrc` "
+                              "(or __graft_entry__.build()). There is no CPU fallback.")
+        _par._share_hip_runtime_with_torch()
+        L = C.CDLL(LIB_PATH)
+        for name, sig in ABI_SCREEN.items():
+            fn = getattr(L, name)
+            if type(sig) is tuple:
+                fn.restype, sig = sig
+            fn.argtypes = sig
+        _lib = L
+    return _lib
+
+
+def tile_bytes(fmt, tile):
+    """The bytes of one tile of tile[0] x tile[1] pixels in format `fmt` (par_screen_tile_bytes); 0 outside the limits."""
+    return lib().par_screen_tile_bytes(fmt, tile[0], tile[1])
+
+
+def palette_rgba(words, fmt, n=None):
+    """The entries of `words` (a uint8 array of machine words of format `fmt`, or RGBA8 entries) widened to an (n, 4) uint8
+    array red, green, blue, 255 (par_screen_palette_rgba). Host arithmetic, no GPU."""
+    words = np.ascontiguousarray(words).view(np.uint8).reshape(-1)
+    each = PALETTE_ENTRY_BYTES[fmt] if 0 <= fmt < 4 else 1
+    if n is None:
+        if len(words) % each:
+            raise ValueError(f"palette_rgba: words holds {len(words)} bytes, no whole number of entries of {each}")
+        n = len(words) // each
+    elif len(words) < n * each:
+        raise ValueError(f"palette_rgba: words holds {len(words)} bytes, {n} entries take {n * each}")
+    out = np.zeros((max(1, n), 4), dtype=np.uint8)
+    wrote = lib().par_screen_palette_rgba(ptr(words), n, fmt, ptr(out))
+    if wrote == 0:
+        raise _par.ParError(1, "par_screen_palette_rgba")
+    return out[:wrote // 4]
+
+
+def draw(d, chr_data, map_words, pal_words=None, fb_out=None, index_out=None, attr=None, line_scroll=None, bad_out=None,
+         stream=None):
+    """Device pointers (ints): the screen of Desc `d` drawn from the tile data at `chr_data`, the map words at `map_words`
+    and the colour words at `pal_words` (par_screen_draw_device) to fb_out (RGBA8) and/or index_out (a byte a pixel).
+    `attr` is a byte a colour cell or None (the palette is the word's), line_scroll 2 * height int32 or None, bad_out a
+    uint32 that gets the bad cells of the whole map. Asynchronous on `stream`."""
+    dp = _par._dp
+    _par._ok(lib().par_screen_draw_device, dp(stream), C.byref(d), dp(chr_data), dp(map_words), dp(attr), dp(pal_words),
+             dp(line_scroll), dp(fb_out), dp(index_out), dp(bad_out))
+
+
+def decode_map(layout, map_words, n_cells, map_out, pal_out=None, bad_out=None, stream=None):
+    """Device pointers (ints): n_cells words of `layout` at `map_words` as the tile map words id | fx << 30 | fy << 31 at
+    map_out and the palette fields at pal_out (par_screen_decode_map_device). Asynchronous on `stream`."""
+    dp = _par._dp
+    _par._ok(lib().par_screen_decode_map_device, dp(stream), C.byref(layout), dp(map_words), n_cells, dp(map_out), dp(pal_out),
+             dp(bad_out))
+
+
+def _bytes_of(who, what, array, want):
+    array = np.ascontiguousarray(array).view(np.uint8).reshape(-1)
+    if len(array) != want:
+        raise ValueError(f"{who}: {what} holds {len(array)} bytes, the descriptor wants {want}")
+    return array
+
+
+def draw_host(d, chr_data, map_words, pal_words=None, attr=None, line_scroll=None, fb=True, index=True, device=-1):
+    """The same on host arrays (par_screen_draw_host). Returns {"fb": (height, width, 4) uint8 or None, "index": (height,
+    width) uint8 or None, "bad": the bad cells of the map}."""
+    who = "draw_host"
+    w, h = max(0, d.width), max(0, d.height)
+    cells = max(0, d.map_w) * max(0, d.map_h)
+    chr_data = _bytes_of(who, "chr", chr_data, max(0, d.n_tiles) * tile_bytes(d.tile_format, (d.tile_w, d.tile_h)))
+    map_words = _bytes_of(who, "the map", map_words, cells * max(0, d.layout.word_bytes))
+    if pal_words is not None:
+        pal_words = _bytes_of(who, "the palette", pal_words, max(0, d.n_colors) * (PALETTE_ENTRY_BYTES[d.pal_format] if 0 <= d.pal_format < 4 else 1))
+    if attr is not None:
+        attr = _bytes_of(who, "attr", attr, -(-d.map_w // max(1, d.ratio_x)) * -(-d.map_h // max(1, d.ratio_y)))
+    if line_scroll is not None:
+        line_scroll = np.ascontiguousarray(line_scroll, dtype=np.int32).reshape(-1)
+        if len(line_scroll) != 2 * h:
+            raise ValueError(f"{who}: line_scroll holds {len(line_scroll)} words, the screen has {h} rows of 2")
+    fb_out = np.zeros((max(1, h), max(1, w), 4), dtype=np.uint8) if fb else None
+    index_out = np.zeros((max(1, h), max(1, w)), dtype=np.uint8) if index else None
+    bad = C.c_int(0)
+
+    def p(a):
+        return None if a is None else ptr(a)
+
+    _par._ok(lib().par_screen_draw_host, device, C.byref(d), p(chr_data), p(map_words), p(attr), p(pal_words), p(line_scroll),
+             p(fb_out), p(index_out), C.byref(bad))
+    return {"fb": fb_out, "index": index_out, "bad": bad.value}
+
+
+def decode_map_host(layout, map_words, device=-1):
+    """Host arrays (par_screen_decode_map_host): `map_words` is a uint8 array of whole words of `layout`. Returns {"map":
+    uint32 array, "pal": uint8 array, "bad": the bad cells}."""
+    who = "decode_map_host"
+    map_words = np.ascontiguousarray(map_words, dtype=np.uint8).reshape(-1)
+    wb = layout.word_bytes if layout.word_bytes in (1, 2, 4) else 1
+    if len(map_words) % wb:
+        raise ValueError(f"{who}: the map holds {len(map_words)} bytes, no whole number of words of {wb}")
+    n = len(map_words) // wb
+    map_out, pal_out = np.zeros(max(1, n), dtype=np.uint32), np.zeros(max(1, n), dtype=np.uint8)
+    bad = C.c_int(0)
+    _par._ok(lib().par_screen_decode_map_host, device, C.byref(layout), ptr(map_words), n, ptr(map_out), ptr(pal_out), C.byref(bad))
+    return {"map": map_out[:n], "pal": pal_out[:n], "bad": bad.value}
