@@ -64,7 +64,13 @@ enum {
      *   - nothing has written to those rows of those planes since.
      * The frame then sets back to background only the tiles that frame can have drawn into (the device's own record of
      * its hash build; the scene may have changed in between) instead of filling every pixel; the `fb` and `palidx`
-     * planes alone are concerned, and the result is the same frame. The library keeps a record of the context's last
+     * planes alone are concerned, and the result is the same frame. Of those tiles it sets back only the ones in whose
+     * screen column an entity was rewritten since the context's previous frame (par_update_aabbs[_async] and the graph
+     * stages by their index range, identical values included; par_set_entities*, par_set_sprites and whatever ends the
+     * record below count as every entity): the covered pixels of every other tile are the same set as before, and the
+     * frame stores each of them again. A frame with nothing rewritten sets back nothing. The promise is unchanged; what
+     * the library relies on besides is that it sees every change of the scene, which it does: they all come through its
+     * own entry points. The library keeps a record of the context's last
      * enqueued frame (plane pointers, which of the two planes were given, the rows) and takes this path only when the
      * record matches; otherwise the flag is ignored and the frame fills as without it, so a caller whose promise holds
      * whenever the record matches may always set it. The record is dropped by par_graph_launch and the graph captures,

@@ -112,8 +112,47 @@ const par_book_plan& par_book::plan(par_change kind, const par_aabb* a, int firs
     return p;
 }
 
+// [first, first + count) into the set: merged with every range it overlaps or touches, put in its place, and, should
+// that make one range too many, the two neighbours with the smallest gap between them joined (the gap's indices
+// then count as rewritten: more is cleared, never less).
+void par_dirty_set::add(int first, int count) {
+    if (count <= 0) return;
+    int32_t a = first, b = first + count;
+    int m = 0;
+    for (int i = 0; i < n; i++) {
+        if (hi[i] < a || lo[i] > b) {
+            lo[m] = lo[i];
+            hi[m++] = hi[i];
+        } else {
+            a = std::min(a, lo[i]);
+            b = std::max(b, hi[i]);
+        }
+    }
+    int at = m;
+    for (; at > 0 && lo[at - 1] > a; at--) {
+        lo[at] = lo[at - 1];
+        hi[at] = hi[at - 1];
+    }
+    lo[at] = a;
+    hi[at] = b;
+    n = m + 1;
+    if (n <= MAX) return;
+    int best = 0;
+    for (int i = 1; i + 1 < n; i++) {
+        if (lo[i + 1] - hi[i] < lo[best + 1] - hi[best]) best = i;
+    }
+    hi[best] = hi[best + 1];
+    for (int i = best + 1; i + 1 < n; i++) {
+        lo[i] = lo[i + 1];
+        hi[i] = hi[i + 1];
+    }
+    n--;
+}
+
 void par_book::commit() {
     par_book_plan& p = plan_;
+    if (p.kind == par_change::SET) dirty.mark_all();  // (the count and the sprite ids may have changed too)
+    else dirty.add(p.first, p.n);
     if (p.kind != par_change::ASYNC) exact = p.exact;
     extent = p.extent;
     if (p.kind == par_change::SET) {

@@ -56,6 +56,28 @@ struct par_book_plan {
     std::vector<par_footprint> fp;    // the new footprints (not for ASYNC); reused from call to call
 };
 
+// The entities rewritten since the context's last enqueued frame (what a kept frame, PAR_RENDER_KEPT_OUTPUTS, clears
+// by): at most MAX disjoint index ranges [lo, hi), ascending, no two touching. One more is merged with whatever it
+// touches; past MAX the two ranges with the smallest gap between them become one, so an index once added stays in the
+// set until clear(). An update that rewrites the values it found still counts.
+struct par_dirty_set {
+    static constexpr int MAX = 4;
+    static constexpr int32_t END = INT32_MAX;  // mark_all(): every index an entity can have, whatever the count becomes
+    int n = 0;
+    int32_t lo[MAX + 1] = {}, hi[MAX + 1] = {};
+    void add(int first, int count);
+    void mark_all() { n = 1; lo[0] = 0; hi[0] = END; }
+    void clear() { n = 0; }
+    bool empty() const { return n == 0; }
+    bool all() const { return n == 1 && lo[0] == 0 && hi[0] == END; }
+    bool has(int e) const {
+        for (int i = 0; i < n; i++) {
+            if (e >= lo[i] && e < hi[i]) return true;
+        }
+        return false;
+    }
+};
+
 struct par_book {
     int W = 0, H = 0, L = 0, B = 0, gx = 0, gy = 0, gz = 0;
     par_book_state state = par_book_state::CURRENT;
@@ -71,6 +93,7 @@ struct par_book {
     // where that reaches the tile's own chunks: only those can be visited as tiles
     std::vector<int32_t> colchunks;
     int64_t cols_tileable = 0;
+    par_dirty_set dirty;  // fed by commit(); the context marks what does not come through the book and clears it per frame
     par_book_plan plan_;
 
     void init(const par_params& p, int x, int y, int z) {

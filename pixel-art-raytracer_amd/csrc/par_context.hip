@@ -52,6 +52,10 @@ struct par_context {
         const void* palidx = nullptr;
         int r0 = 0, r1 = 0, set = 0;
     } drawn;
+    // What a kept frame clears by: book.dirty holds the entities rewritten since the last enqueued frame (fed by every
+    // scene change that goes through the book, marked whole by drop_drawn and par_set_sprites, emptied by enqueue_frame),
+    // and every frame takes the next sequence number (par_dirty_dev::seq; from 1, never 0).
+    uint32_t frame_seq = 0;
     hipStream_t last_stream = nullptr;  // stream of the most recent asynchronous render (scene updates wait for it)
     bool has_last_stream = false;
 
@@ -185,7 +189,11 @@ void record_drawn(par_context* c, const par_outputs& out, int row_begin, int row
     c->drawn.r1 = row_end;
     c->drawn.set = set;
 }
-void drop_drawn(par_context* c) { c->drawn.valid = false; }
+// (whatever ends the record may have changed the planes or the node list: the next frame treats every entity as rewritten)
+void drop_drawn(par_context* c) {
+    c->drawn.valid = false;
+    c->book.dirty.mark_all();
+}
 
 int hip_fail(par_context* c, hipError_t e, const char* what) {
     return fail(c, e == hipErrorOutOfMemory ? PAR_ERR_OOM : PAR_ERR_HIP,
@@ -521,7 +529,12 @@ int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, 
     const bool drawn_match = ctx->drawn.valid && ctx->drawn.fb == out.fb && ctx->drawn.palidx == out.palidx &&
                              ctx->drawn.r0 == row_begin && ctx->drawn.r1 == row_end && ctx->drawn.set == (set ^ 1);
     drop_retained(ctx);  // (a hash build follows; the entry point retains the new frame once it has returned PAR_OK)
+    if (ctx->dev_hi > ctx->dev_lo && !graph_mode) ctx->book.dirty.add(ctx->dev_lo, ctx->dev_hi - ctx->dev_lo);  // (staged, copied below)
+    // The entities rewritten since the context's last frame; the set starts again with this frame, whichever path it takes.
+    const par_dirty_set dirty = ctx->book.dirty;
     drop_drawn(ctx);
+    ctx->book.dirty.clear();
+    if (++ctx->frame_seq == 0) ctx->frame_seq = 1;
     par_outputs outs = out;
     if ((flags & PAR_RENDER_TRACE_BACKGROUND) && !outs.lit) {
         // every ray is to be traced but the caller wants no lit plane: the results still go to memory (a scratch
@@ -544,6 +557,7 @@ int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, 
     }
     par_bin_args b = make_bin_args(ctx, set, row_begin, row_end, flags);
     par_render_args r = make_render_args(ctx, set, row_begin, row_end, outs, flags, graph_mode);
+    r.seq = ctx->frame_seq;
     // (a timed frame keeps its kernels apart unless it is asked to time the launches as a production frame makes them)
     const bool apart = ev && !(flags & PAR_RENDER_TIMED_AS_LAUNCHED);
     const par_bound bound = ctx->book.frame_bounds(graph_mode);
@@ -571,16 +585,35 @@ int enqueue_frame(par_context* ctx, hipStream_t stream, int set, int row_begin, 
     // 16-byte runs (B % 8 == 0), and while the book's column bound says the tiles are a minority of the rendered rows
     // (kKeptMaxTilesPct): a dense frame clears every tile in short rows and loses to the streaming
     // fill. The bound only chooses; what is cleared is the device's own list.
+    // Of the listed tiles only those are cleared whose column holds a node of an entity rewritten since the context's
+    // previous frame, in that frame's build or in this one's: the covered pixels of every other tile are the same set
+    // as before, and the render launches store each of them. With NO entity rewritten (an
+    // unchanged frame) nothing is listed and nothing rides: the build wipes as an unkept frame's does and the column
+    // launch is the plain one, whatever the threshold says -- the alternative is a whole fill for nothing.
     const int64_t tiles_in_rows = (int64_t)ctx->gx * (r.by_hi - r.by_lo + 1);
-    const bool kept_frame = (flags & PAR_RENDER_KEPT_OUTPUTS) && drawn_match && !graph_mode && ride && r.B % 8 == 0 &&
+    const bool keepable = (flags & PAR_RENDER_KEPT_OUTPUTS) && drawn_match && !graph_mode && ride && r.B % 8 == 0;
+    const bool unchanged_frame = keepable && dirty.empty();
+    const bool kept_frame = keepable && !unchanged_frame &&
                             std::min(bound.cols, tiles_in_rows) * 100 <= tiles_in_rows * kKeptMaxTilesPct;
     b.kept = kept_frame ? 1 : 0;
+    static_assert(par_dirty_set::MAX == 4, "par_dirty_dev holds four ranges");
+    if (kept_frame) {
+        b.dirty.seq = r.seq;
+        b.dirty.n = dirty.n;
+        for (int i = 0; i < dirty.n && i < 4; i++) {
+            b.dirty.lo[i] = dirty.lo[i];
+            b.dirty.len[i] = (uint32_t)(dirty.hi[i] - dirty.lo[i]);
+        }
+    }
     par_render_args rf = r;  // what rides along: the frame and palette-index planes
     rf.out.lit = nullptr;
-    const int rc = enqueue_build(ctx, stream, b, bound.pairs, &rf, ride && !kept_frame ? &plan : nullptr, apart);
+    const bool fills = ride && !kept_frame && !unchanged_frame;
+    const int rc = enqueue_build(ctx, stream, b, bound.pairs, &rf, fills ? &plan : nullptr, apart);
     if (rc != PAR_OK) return rc;
     if (ev) PAR_HIP(hipEventRecord(ev[EV_BUILT], stream));
-    if (ride) {
+    if (unchanged_frame) {
+        PAR_HIP(par_launch_columns(ctx->grid, rf, bound.cols, ctx->col_roles, stream));
+    } else if (ride) {
         PAR_HIP(par_launch_columns_fill(ctx->grid, rf, bound.cols, plan, kept_frame, ctx->col_roles, stream));
     } else {
         PAR_HIP(par_launch_columns(ctx->grid, r, bound.cols, ctx->col_roles, stream));
@@ -664,7 +697,7 @@ struct par_dev_buffer {
     int fill;  // the byte the buffer starts with, or -1
 };
 
-std::array<par_dev_buffer, 20> dev_buffers(par_context* c, bool stamps) {
+std::array<par_dev_buffer, 21> dev_buffers(par_context* c, bool stamps) {
     par_grid_dev& g = c->grid;
     const size_t vol = (size_t)c->volume, cols = (size_t)c->gx * c->gy, i32 = sizeof(int32_t);
     return {{
@@ -677,6 +710,7 @@ std::array<par_dev_buffer, 20> dev_buffers(par_context* c, bool stamps) {
         {(void**)&g.col_list, cols * i32, -1},
         {(void**)&g.slow_list, cols * i32, -1},
         {(void**)&g.clear_list, cols * i32, -1},
+        {(void**)&g.coldirty, cols * i32, 0},
         {(void**)&g.counters, PAR_CNT_TOTAL * i32, -1},
         {(void**)&g.node_counter, 2 * i32, -1},
         {(void**)&g.build_sync, 64 * i32, 0},
@@ -818,6 +852,7 @@ static int par_set_sprites_impl(par_context* ctx, const par_sprite* sprites, int
     PAR_HIP(hipDeviceSynchronize());
     drop_graphs(ctx);  // (a captured graph bakes the table's pointers)
     drop_retained(ctx);
+    ctx->book.dirty.mark_all();  // (what every entity draws may change)
     ctx->n_sprites = 0;
     PAR_HIP(reallocate(&ctx->d_sprites, (size_t)n_sprites));
     PAR_HIP(hipMemcpy(ctx->d_sprites, sprites, (size_t)n_sprites * sizeof(par_sprite), hipMemcpyHostToDevice));

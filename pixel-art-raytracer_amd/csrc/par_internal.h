@@ -219,12 +219,26 @@ struct par_grid_dev {
     int32_t* slow_list;       // [gx*gy] indices into col_list of the columns that overflowed their record
     int32_t* clear_list;      // [gx*gy] a kept frame: the columns the previous build flagged, inside the rendered row
                               // range, unordered; counters[PAR_CNT_CLEAR + set] of them (clear_tiles_body)
+    int32_t* coldirty;        // [gx*gy] the sequence number (par_dirty_dev::seq) of the last kept frame whose build met a
+                              // node of a rewritten entity in the column, in its own list or the previous build's;
+                              // zero at creation. clear_tiles_body clears a listed tile only when this is its frame's.
     par_bgwalk* bgwalk;       // [gx] shadow walks of the background rays (traced only on request)
     uint8_t* bglit;           // [width] result of the background ray of screen column x
     unsigned long long* stamps;  // debug (PAR_DEBUG_STAMPS=1): per workgroup phase time stamps, else nullptr
     int32_t capacity;
     int32_t col_capacity;
     int32_t item_capacity;    // work items one shard of `items` holds
+};
+
+// What a kept frame's clear goes by (par_dirty_set, par_book.h): the frame's sequence number (per context, from 1, never
+// 0) and the entity index ranges [lo, lo + len) rewritten since the context's previous frame. Ranges the set does not
+// use have len 0. n > 0 only in a kept frame that clears (par_bin_args::kept): with n == 0 the build loads and stores
+// nothing for it.
+struct par_dirty_dev {
+    uint32_t seq;
+    int32_t n;
+    int32_t lo[4];
+    uint32_t len[4];
 };
 
 struct par_bin_args {
@@ -237,6 +251,7 @@ struct par_bin_args {
     int32_t test_lose_wg;    // tests (par_debug_set_hooks): build workgroup 0 never arrives at the barrier
     uint32_t magic_b;        // floor(n / B) == __umulhi(n, magic_b) for n * B < 2^32 (as par_render_args::magic_b)
     const par_aabb* aabbs;
+    par_dirty_dev dirty;     // a kept frame: the build marks the columns (coldirty) that hold a node of these entities
 };
 
 struct par_render_args {
@@ -264,6 +279,7 @@ struct par_render_args {
     const par_color* palette;
     par_outputs out;               // device pointers, addressing (row_begin, 0)
     unsigned long long* ray_counter;  // [3]: shadow rays; (start bin, light) pairs the ranged light kernel walked, culled
+    uint32_t seq;                  // the frame's sequence number (par_dirty_dev::seq): what clear_tiles_body matches coldirty with
 };
 
 // PAR_CNT_ERROR is STICKY: kernels only ever set bits in it (a frame's insert resets the other counters, not this
@@ -298,7 +314,8 @@ hipError_t par_launch_bin_resolve(const par_grid_dev& g, const par_bin_args& a, 
 hipError_t par_launch_columns(const par_grid_dev& g, const par_render_args& a, int64_t column_bound, int col_roles,
                               hipStream_t stream);
 // Column records + the last share of the fill in one launch. `clear_tiles`: a kept frame (par_bin_args::kept): the
-// riding workgroups set the tiles of g.clear_list back to background and fill nothing else. Needs B % 8 == 0.
+// riding workgroups set the tiles of g.clear_list whose column the build marked (g.coldirty == a.seq) back to
+// background and fill nothing else. Needs B % 8 == 0.
 hipError_t par_launch_columns_fill(const par_grid_dev& g, const par_render_args& a, int64_t column_bound,
                                    const par_fill_plan& fill, bool clear_tiles, int col_roles, hipStream_t stream);
 // Background for every pixel of the row range; the render kernel then overwrites the pixels primitives cover.

@@ -146,6 +146,13 @@ __device__ __forceinline__ int div_bin(int n, uint32_t magic) {
 // touched in the other set, so no O(volume) memset is ever issued after context creation.
 // ------------------------------------------------------------------------------------------------------------
 
+// Entity e was rewritten since the context's previous frame (par_dirty_dev): four wave-uniform ranges, an unused one
+// matches nothing.
+__device__ __forceinline__ bool dirty_entity(const par_dirty_dev& d, int e) {
+    return ((uint32_t)(e - d.lo[0]) < d.len[0]) | ((uint32_t)(e - d.lo[1]) < d.len[1]) |
+           ((uint32_t)(e - d.lo[2]) < d.len[2]) | ((uint32_t)(e - d.lo[3]) < d.len[3]);
+}
+
 // ENT entities per wavefront (16 for small scenes so that the pairs of one wavefront fit one or two passes, 64 for
 // large ones so that the node counter sees one atomic per 64 entities). Lane l < ENT culls and sizes entity l; the
 // wavefront reserves its nodes with ONE atomic; then all 64 lanes walk the (entity, bin) pairs side by side, so the
@@ -157,7 +164,8 @@ __device__ __forceinline__ void bin_insert_body(const par_grid_dev& g, const par
     const int s = a.set, o = a.set ^ 1;
 
     // wipe what the previous frame touched in the other set
-    const int prev = min(g.node_counter[o], g.capacity);
+    const int prev_all = g.node_counter[o];
+    const int prev = min(prev_all, g.capacity);
     for (int i = tid; i < prev; i += stride) {
         const int b = g.node_bin[o][i];
         g.head[o][b] = 0;
@@ -166,6 +174,13 @@ __device__ __forceinline__ void bin_insert_body(const par_grid_dev& g, const par
         if (!a.kept) {
             g.colflag[o][col] = 0;
             continue;
+        }
+        // Its tile needs the clear only if an entity of the column was rewritten since the previous frame: EVERY node
+        // of such an entity marks its column with this frame's number (the same plain store from every lane; the
+        // reader is the next launch), here for the previous build's nodes, in bin_resolve_node for this build's. A list
+        // that lost nodes to the pool's end (belt and braces) marks every column it has.
+        if (a.dirty.n > 0 && (prev_all > g.capacity || dirty_entity(a.dirty, g.node_entity[o][i]))) {
+            g.coldirty[col] = (int32_t)a.dirty.seq;
         }
         // A kept frame (PAR_RENDER_KEPT_OUTPUTS): the columns the previous frame flagged are the tiles it can have drawn
         // into. The lane that takes a column's flag down lists the column, once, for clear_tiles_body of this frame's
@@ -275,17 +290,23 @@ __device__ __forceinline__ par_slot slot_of(const par_aabb& box, int entity) {
     return rec;
 }
 
-// Node `tid`: the thread of a bin's most recent insertion resolves the bin.
+// Node `tid`: the thread of a bin's most recent insertion resolves the bin. `lost`: the node list lost nodes to the
+// pool's end (belt and braces): every column then counts as holding a rewritten entity.
 template <bool COH>
-__device__ __forceinline__ void bin_resolve_node(const par_grid_dev& g, const par_bin_args& a, int tid) {
+__device__ __forceinline__ void bin_resolve_node(const par_grid_dev& g, const par_bin_args& a, int tid, bool lost) {
     const int s = a.set;
     const int b = ld_shared<COH>(&g.node_bin[s][tid]);
     if (ld_shared<COH>(&g.head[s][b]) != tid + 1) return;  // only the most recent insertion resolves its bin
 
     int top0 = -1, top1 = -1, top2 = -1, top3 = -1, top4 = -1, top5 = -1, top6 = -1;  // 7 largest, descending
     int k = 0;
+    // A kept frame that clears: does a rewritten entity have a node in this bin? Every node of the list counts, not the
+    // seven that stay visible alone: a ninth insertion changes which slots show without showing itself.
+    const bool marks = a.dirty.n > 0;  // wave-uniform
+    bool rewritten = lost;
     for (int cur = tid + 1; cur != 0; cur = ld_shared<COH>(&g.node_next[s][cur - 1])) {
         int e = ld_shared<COH>(&g.node_entity[s][cur - 1]);
+        if (marks) rewritten |= dirty_entity(a.dirty, e);
         int t;
         // bubble the new index through the sorted registers (static indexing keeps them out of scratch)
         if (e > top0) { t = top0; top0 = e; e = t; }
@@ -307,6 +328,7 @@ __device__ __forceinline__ void bin_resolve_node(const par_grid_dev& g, const pa
         }
     }
     g.count[s][b] = (uint8_t)c;
+    if (marks && rewritten) g.coldirty[b / g.gz] = (int32_t)a.dirty.seq;  // (as the wipe of bin_insert_body marks)
     if (c > 0) {
         // the screen column (bx, by) of this bin shows something: flag it, and list it once if the render of
         // this frame covers its rows
@@ -332,8 +354,9 @@ __device__ __forceinline__ void bin_resolve_body(const par_grid_dev& g, const pa
     const int s = a.set;
     // insert has consumed the other set's counter: free it for the next frame's inserts
     if (tid0 == 0) g.node_counter[s ^ 1] = 0;
-    const int n_nodes = min(ld_shared<COH>(&g.node_counter[s]), g.capacity);
-    for (int tid = tid0; tid < n_nodes; tid += n_blocks * blockDim.x) bin_resolve_node<COH>(g, a, tid);
+    const int n_all = ld_shared<COH>(&g.node_counter[s]);
+    const int n_nodes = min(n_all, g.capacity);
+    for (int tid = tid0; tid < n_nodes; tid += n_blocks * blockDim.x) bin_resolve_node<COH>(g, a, tid, n_all > g.capacity);
 }
 
 __global__ __launch_bounds__(256) void bin_resolve_kernel(par_grid_dev g, par_bin_args a) {
@@ -1173,8 +1196,10 @@ __device__ __forceinline__ void fill_body(const par_render_args& a, uint32_t out
 // clear_tiles_body: the background of a KEPT frame (PAR_RENDER_KEPT_OUTPUTS). The planes still hold the frame this
 // context drew into them one turn earlier, so only the tiles that frame can have drawn into are set back to background:
 // the clear list this frame's hash build made of the previous build's flagged columns (bin_insert_body), complete at
-// the kernel boundary before this launch. One wavefront per listed tile, the tile clipped to W and to the rows
-// rendered, with the background word and the palette index of fill_body. Requires what fill_body requires and
+// the kernel boundary before this launch, and of those only the columns the build marked with this frame's number
+// (coldirty: some entity with a node there was rewritten since the previous frame). One wavefront
+// per listed tile, the tile clipped to W and to the rows rendered, with the background word and the palette index of
+// fill_body. Requires what fill_body requires and
 // B % 8 == 0: a tile's rows are then whole 16-byte runs of the frame plane (4 pixels per lane, 64 / (w / 4) rows per
 // store instruction) and whole 8-byte runs of the palette-index plane (8 pixels per lane).
 // The stores are PLAIN ones, unlike fill_body's: a tile row is 160 and 40 bytes at bin 40, parts of 128-byte lines
@@ -1192,6 +1217,9 @@ __device__ __forceinline__ void clear_tiles_body(const par_grid_dev& g, const pa
     for (int t = __builtin_amdgcn_readfirstlane(block * wpb + ((int)threadIdx.x >> 6)); t < n; t += n_blocks * wpb) {
         const int col = ld_uniform(&g.clear_list[t]);
         if (col < 0 || col >= n_all) continue;
+        // (no entity with a node in the column, in the previous build or in this one, was rewritten since the previous
+        // frame: the tile's covered pixels are the same set, and the render launch stores every one of them)
+        if (ld_uniform(&g.coldirty[col]) != (int32_t)a.seq) continue;
         const int bx = col / g.gy, by = col - bx * g.gy;
         const int x0 = bx * B, x1 = min(x0 + B, W);
         const int y0 = max(by * B, a.row_begin), y1 = min(by * B + B, a.row_end);

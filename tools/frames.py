@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Render N frames of one workload (for rocprofv3 --kernel-trace --stats / --pmc runs on the GPU box).
-usage: frames.py [--kept] [synthetic|floor|graybox|small|trace_bg] [frames] [extra render flags, e.g. 2 = count rays]
---kept: every frame carries RENDER_KEPT_OUTPUTS (the buffers are this context's own: kept frames from the second on)"""
+usage: frames.py [--kept] [--move=K] [synthetic|floor|graybox|small|trace_bg] [frames] [extra render flags, e.g. 2 = count rays]
+--kept: every frame carries RENDER_KEPT_OUTPUTS (the buffers are this context's own: kept frames from the second on)
+--move=K: before every frame but the first, entities [0, K) step 4 pixels to and fro in x, by update_aabbs of that
+          sub-range on the frame's stream (a static level with a few movers; without it nothing changes between frames)"""
 import importlib, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -9,7 +11,8 @@ import torch
 par = importlib.import_module("pixel-art-raytracer_amd")
 T = par.types
 kept = "--kept" in sys.argv
-sys.argv = [v for v in sys.argv if v != "--kept"]
+move = max([int(v.split("=")[1]) for v in sys.argv if v.startswith("--move=")] + [0])
+sys.argv = [v for v in sys.argv if v != "--kept" and not v.startswith("--move=")]
 what = sys.argv[1] if len(sys.argv) > 1 else "synthetic"
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 100
 flags = 0
@@ -38,7 +41,11 @@ fb = torch.zeros(W * H * 4, dtype=torch.uint8, device="cuda")
 pal = torch.zeros(W * H, dtype=torch.uint8, device="cuda")
 ptrs = {"fb": fb.data_ptr(), "palidx": pal.data_ptr()}
 s = torch.cuda.current_stream().cuda_stream
-for _ in range(n):
+movers = [a[:move].copy(), a[:move].copy()]
+movers[1]["px"] += 4
+for f in range(n):
+    if move and f:
+        r.update_aabbs(movers[f % 2], first=0, stream=s)
     r.render_device(ptrs, stream=s, flags=flags | extra)
 torch.cuda.synchronize()
 print("done", what, n, "frames; occupied columns", r.stats().occupied_columns)
