@@ -88,18 +88,24 @@ def hip_runtime():
     return _hip
 
 
+def _load(path, *tables):
+    """The library at `path` (built in-tree by __graft_entry__.build() / csrc/Makefile) with `tables` set on its
+    functions (none: every table of abi.py). The core lib() and every add-on module's lib() load through here. No
+    fallback."""
+    if not os.path.exists(path):
+        raise ImportError(f"{path} is missing: build it with `make -C pixel-art-raytracer_amd/csrc` "
+                          "(or __graft_entry__.build()). There is no CPU fallback.")
+    _share_hip_runtime_with_torch()
+    L = C.CDLL(path)
+    install(L, *tables)
+    return L
+
+
 def lib():
-    """Load libpar_raytracer.so (built in-tree by __graft_entry__.build() / csrc/Makefile) and set every table of abi.py
-    on its functions. No fallback."""
+    """libpar_raytracer.so with every table of abi.py set on its functions, loaded at the first call."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} is missing: build it with `make -C pixel-art-raytracer_amd/csrc` "
-                              "(or __graft_entry__.build()). There is no CPU fallback.")
-        _share_hip_runtime_with_torch()
-        L = C.CDLL(LIB_PATH)
-        install(L)
-        _lib = L
+        _lib = _load(LIB_PATH)
     return _lib
 
 

@@ -1,8 +1,8 @@
 """The C ABI of libpar_raytracer.so as ctypes signatures: one table a header of include/, the hooks the library exports
 beside them, and the one loop that sets them on a loaded library. A table is in its header's order: symbol -> argument
 types, or (return type, argument types) where the function does not return an int. Every pointer is a c_void_p.
-The package's lib() calls install() once, at load; tests/test_abi_cpu.py holds every table to its header's prototypes and
-the tables together to what the library exports."""
+The package's lib() calls install() once, at load, and so does an add-on module's with its own table;
+tests/test_abi_cpu.py holds every table to its header's prototypes and the tables together to what the library exports."""
 import ctypes as C
 
 _p, _i, _u = C.c_void_p, C.c_int, C.c_uint
@@ -116,9 +116,10 @@ ABI_HEADERS = {"par_raytracer.h": ABI, "par_cells.h": ABI_CELLS, "par_tileset.h"
                "par_tileset_extend.h": ABI_TILESET_EXTEND}
 
 
-def install(L):
-    """Set restype and argtypes of every function of every table on the loaded library L."""
-    for table in (*ABI_HEADERS.values(), ABI_DEBUG_HOOKS):
+def install(L, *tables):
+    """Set restype and argtypes of every function of `tables` on the loaded library L: an add-on's own table, or, with
+    none given, every table above (the core library)."""
+    for table in tables or (*ABI_HEADERS.values(), ABI_DEBUG_HOOKS):
         for name, sig in table.items():
             fn = getattr(L, name)
             if type(sig) is tuple:

@@ -30,7 +30,6 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <cstring>
 
 #include "par_cells_fit.h"
 #include "par_cells_lanes.h"
@@ -48,7 +47,6 @@ constexpr uint32_t CF_OFF_BINS = 10240, CF_HEAD_BYTES = CF_OFF_BINS + 4 * CF_BIN
 constexpr uint32_t CF_BYTES_PER_CELL = 25;
 constexpr uint32_t CF_CELL_MASK = PAR_CELLS_FIT_MAX_CELLS - 1;
 constexpr int CF_GAIN_BIAS = 1 << 18;  // above 256 * 765
-constexpr uint32_t CF_HIGH_NIBBLES = 0x00F0F0F0u;
 constexpr uint32_t CF_TALLY_GROUPS = 768;  // workgroups of an assign pass that holds tallies: three a compute unit
 constexpr uint32_t CF_WALK_GROUPS = 2048;  // workgroups of the cell pass and of a step: eight a compute unit
 static_assert(CF_HEAD_BYTES == 59392 && CF_HEAD_BYTES % 16 == 0, "the header's formula; a wanted list is 16 bytes, aligned");
@@ -282,19 +280,6 @@ __global__ __launch_bounds__(CF_THREADS) void fit_step_kernel(Fit w, const uint3
 
 constexpr int CF_HI = 0, CF_LO = 1, CF_ERROR = 2;
 
-template <bool LO>
-__device__ __forceinline__ void tally_add(uint32_t* t, const uint32_t* high, uint32_t k, uint32_t rgb, uint32_t n) {
-    uint32_t* const row = t + k * 48u;
-    if (LO) {
-        const uint32_t other = (rgb ^ high[k]) & CF_HIGH_NIBBLES;
-        for (int c = 0; c < 3; c++) {
-            if (((other >> (8 * c)) & 0xFFu) == 0u) atomicAdd(&row[16 * c + ((rgb >> (8 * c)) & 15u)], n);
-        }
-    } else {
-        for (int c = 0; c < 3; c++) atomicAdd(&row[16 * c + ((rgb >> (8 * c + 4)) & 15u)], n);
-    }
-}
-
 // The assign step of a round over the groups blockIdx.x, + gridDim.x, ...: MODE CF_HI chooses s*, keeps it, adds the
 // error to *error_out (where given) and tallies high nibbles; CF_LO reads s* back and tallies low nibbles; CF_ERROR
 // chooses and adds the error alone.
@@ -503,20 +488,6 @@ hipError_t launch_fit(hipStream_t stream, int cell_w, int cell_h, const FitCall&
     return cell_h == 8 ? launch_fit<16, 8>(stream, a) : launch_fit<16, 16>(stream, a);
 }
 
-// par_select_device's rules (par_context.hip, which is not linked here): a negative *device becomes the current device.
-int fit_select_device(int* device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PAR_ERR_NO_DEVICE;
-    if (*device < 0) {
-        if (hipGetDevice(device) != hipSuccess) return PAR_ERR_NO_DEVICE;
-    }
-    if (*device >= ndev) return PAR_ERR_INVALID_ARG;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, *device) != hipSuccess) return PAR_ERR_NO_DEVICE;
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return PAR_ERR_NO_DEVICE;  // kernels are built for gfx950 only
-    return PAR_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -543,7 +514,7 @@ int par_cells_fit_host(int device, const uint8_t* fb, int width, int height, int
     if (!fit_args_ok(fb, width, height, cell_w, cell_h, palette, n_colors, n_sub, sub_size, rounds, table_out)) {
         return PAR_ERR_INVALID_ARG;
     }
-    const int rc = fit_select_device(&device);
+    const int rc = par_select_device(&device);
     if (rc != PAR_OK) return rc;
     hipError_t e = hipSetDevice(device);
     par_device_buffer d_fb(e, fb, (size_t)width * (size_t)height * 4, true);

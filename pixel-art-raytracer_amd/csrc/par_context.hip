@@ -727,20 +727,6 @@ std::array<par_dev_buffer, 21> dev_buffers(par_context* c, bool stamps) {
 
 }  // namespace
 
-// (declared in par_hostcall.h: the *_host forms of the passes over finished planes open with it too)
-int par_select_device(int* device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PAR_ERR_NO_DEVICE;
-    if (*device < 0) {
-        if (hipGetDevice(device) != hipSuccess) return PAR_ERR_NO_DEVICE;
-    }
-    if (*device >= ndev) return PAR_ERR_INVALID_ARG;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, *device) != hipSuccess) return PAR_ERR_NO_DEVICE;
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return PAR_ERR_NO_DEVICE;  // kernels are built for gfx950 only
-    return PAR_OK;
-}
-
 extern "C" {
 
 const char* par_last_error(const par_context* ctx) { return ctx ? ctx->err.c_str() : ""; }

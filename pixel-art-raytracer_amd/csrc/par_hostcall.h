@@ -58,10 +58,24 @@ inline par_tile_spans par_tileset_extend_spans(uint64_t count_in, uint64_t count
 #ifdef __HIP__
 #include <hip/hip_runtime.h>
 
+#include <cstring>
+
 // The device of a *_host call or of a context: a negative *device becomes the current device. PAR_ERR_NO_DEVICE
 // without a device or when it is no gfx950 (the kernels are built for that alone), PAR_ERR_INVALID_ARG for an index
-// past the last device. It does not make the device current. (par_context.hip)
-int par_select_device(int* device);
+// past the last device. It does not make the device current. The one definition: the core library and every add-on
+// compile it from here, and no library links another for it.
+inline int par_select_device(int* device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PAR_ERR_NO_DEVICE;
+    if (*device < 0) {
+        if (hipGetDevice(device) != hipSuccess) return PAR_ERR_NO_DEVICE;
+    }
+    if (*device >= ndev) return PAR_ERR_INVALID_ARG;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, *device) != hipSuccess) return PAR_ERR_NO_DEVICE;
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return PAR_ERR_NO_DEVICE;  // kernels are built for gfx950 only
+    return PAR_OK;
+}
 
 // (par_status itself is the enumeration of par_raytracer.h)
 inline int par_status_of(hipError_t e) {

@@ -482,24 +482,8 @@ __global__ __launch_bounds__(PAR_MAX_PALETTE) void emit_kernel(const par_palette
 // ---- refine ------------------------------------------------------------------------------------------------------
 
 constexpr int REFINE_BINS = PAR_MAX_PALETTE * 3 * 16;  // dwords of par_palette_refine_work::bins
-constexpr uint32_t HIGH_NIBBLES = 0x00F0F0F0u;         // of red, green and blue in a par_color's word
 constexpr int REFINE_MAX_ITERATIONS = 16;
 static_assert(REFINE_BINS % (4 * PALETTE_THREADS) == 0, "a workgroup zeroes and flushes its tallies in whole rounds");
-
-// `n` pixels of entry k and colour rgb into the tallies t of a stage: every channel's high nibble, or (LO) the low
-// nibble of the channels whose high nibble is the one chosen for (k, channel), high[k].
-template <bool LO>
-__device__ __forceinline__ void tally_add(uint32_t* t, const uint32_t* high, uint32_t k, uint32_t rgb, uint32_t n) {
-    uint32_t* const row = t + k * 48u;
-    if (LO) {
-        const uint32_t other = (rgb ^ high[k]) & HIGH_NIBBLES;
-        for (int c = 0; c < 3; c++) {
-            if (((other >> (8 * c)) & 0xFFu) == 0u) atomicAdd(&row[16 * c + ((rgb >> (8 * c)) & 15u)], n);
-        }
-    } else {
-        for (int c = 0; c < 3; c++) atomicAdd(&row[16 * c + ((rgb >> (8 * c + 4)) & 15u)], n);
-    }
-}
 
 // `index` holds the launch's index bytes; index_words: index + (a whole group's first pixel) is on a 4-byte boundary.
 template <bool VEC, bool LO>

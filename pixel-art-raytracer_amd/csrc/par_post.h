@@ -1,8 +1,9 @@
 // par_post.h — what the passes over finished planes share, one implementation per contract: the outline pass's texel
 // arithmetic and its tile geometry (par_outline.hip), the palette pass's dither (par_quantize.hip) and the present
 // pass's exchange, palette entry and group expand (par_present.hip), shared with the kernel that runs the three in one
-// launch (par_finish.hip), and the scalers' rules (par_upscale.hip, which takes the present pass's exchange and palette
-// entry from here too). Everything here is __forceinline__ device code in an unnamed namespace: each unit gets its own
+// launch (par_finish.hip), the scalers' rules (par_upscale.hip, which takes the present pass's exchange and palette
+// entry from here too), and the tally of a palette refine round (par_palette.hip and the fitted-cells add-on,
+// par_cells_fit.hip). Everything here is __forceinline__ device code in an unnamed namespace: each unit gets its own
 // copy, inlined where it is called. (The staged tile's loads, stores and classification and the palette search are NOT
 // here: as functions they are simplified on their own before they are inlined and came out as other, slower code in
 // outline_kernel, finish_kernel and quantize_kernel; those kernels keep them in their bodies.)
@@ -110,6 +111,26 @@ __device__ __forceinline__ uint32_t dithered(uint32_t px, uint32_t x, uint32_t y
 }
 
 __device__ __forceinline__ uint32_t min3u(uint32_t a, uint32_t b, uint32_t c) { return std::min(std::min(a, b), c); }
+
+// ---- palette refine ------------------------------------------------------------------------------------------------
+
+constexpr uint32_t HIGH_NIBBLES = 0x00F0F0F0u;  // of red, green and blue in a par_color's word
+
+// `n` pixels of entry k and colour rgb into the tallies t of a stage, 3 x 16 dwords an entry: every channel's high
+// nibble, or (LO) the low nibble of the channels whose high nibble is the one chosen for (k, channel), high[k].
+// (par_palette.hip's refine rounds and par_cells_fit.hip's, whose medians are the same by contract)
+template <bool LO>
+__device__ __forceinline__ void tally_add(uint32_t* t, const uint32_t* high, uint32_t k, uint32_t rgb, uint32_t n) {
+    uint32_t* const row = t + k * 48u;
+    if (LO) {
+        const uint32_t other = (rgb ^ high[k]) & HIGH_NIBBLES;
+        for (int c = 0; c < 3; c++) {
+            if (((other >> (8 * c)) & 0xFFu) == 0u) atomicAdd(&row[16 * c + ((rgb >> (8 * c)) & 15u)], n);
+        }
+    } else {
+        for (int c = 0; c < 3; c++) atomicAdd(&row[16 * c + ((rgb >> (8 * c + 4)) & 15u)], n);
+    }
+}
 
 // ---- present -------------------------------------------------------------------------------------------------------
 

@@ -17,10 +17,10 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <cstring>
 
 #include "par_hostcall.h"
 #include "par_screen.h"
+#include "par_tilehw.h"
 
 namespace {
 
@@ -28,24 +28,14 @@ constexpr uint32_t SC_THREADS = 256;
 constexpr uint32_t SC_WAVES = SC_THREADS / 64;
 constexpr uint32_t SC_ID_LIMIT = 1u << 30;
 
-__host__ __device__ inline uint32_t bpp_of(uint32_t format) {
-    return format == PAR_SCREEN_1BPP ? 1u : (format <= PAR_SCREEN_2BPP_ROWS ? 2u : 4u);
-}
-
-__host__ __device__ inline bool packed(uint32_t format) {
-    return format == PAR_SCREEN_4BPP_PACKED_HI || format == PAR_SCREEN_4BPP_PACKED_LO;
-}
-
-// the byte of a sub-tile that holds bit plane b of row y (the planar formats)
-__device__ __forceinline__ uint32_t plane_byte(uint32_t format, uint32_t b, uint32_t y) {
-    switch (format) {
-        case PAR_SCREEN_2BPP_PLANAR: return 8 * b + y;
-        case PAR_SCREEN_2BPP_ROWS: return 2 * y + b;
-        case PAR_SCREEN_4BPP_ROWS: return 16 * (b >> 1) + 2 * y + (b & 1);
-        case PAR_SCREEN_4BPP_ROW_PLANES: return 4 * y + b;
-        default: return y;
-    }
-}
+// par_tilehw.h's formats are par_screen_tile_format's
+static_assert(PAR_SCREEN_1BPP == TILEHW_1BPP);
+static_assert(PAR_SCREEN_2BPP_PLANAR == TILEHW_2BPP_PLANAR);
+static_assert(PAR_SCREEN_2BPP_ROWS == TILEHW_2BPP_ROWS);
+static_assert(PAR_SCREEN_4BPP_ROWS == TILEHW_4BPP_ROWS);
+static_assert(PAR_SCREEN_4BPP_PACKED_HI == TILEHW_4BPP_PACKED_HI);
+static_assert(PAR_SCREEN_4BPP_PACKED_LO == TILEHW_4BPP_PACKED_LO);
+static_assert(PAR_SCREEN_4BPP_ROW_PLANES == TILEHW_4BPP_ROW_PLANES);
 
 // what the kernels need of a layout, as unsigned fields
 struct word_layout {
@@ -74,19 +64,6 @@ __device__ __forceinline__ map_cell read_cell(const word_layout& L, const uint8_
     return cell;
 }
 
-// the workgroup's bad cells in one atomic; every thread of the workgroup calls it
-__device__ __forceinline__ void add_bad(bool bad, uint32_t* bad_out) {
-    __shared__ uint32_t bad_of[SC_WAVES];
-    const uint32_t in_wave = (uint32_t)__popcll(__ballot(bad));
-    if ((threadIdx.x & 63u) == 0) bad_of[threadIdx.x >> 6] = in_wave;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t total = 0;
-        for (uint32_t w = 0; w < SC_WAVES; w++) total += bad_of[w];
-        if (total) atomicAdd(bad_out, total);
-    }
-}
-
 // bit 7 - k of `byte` as byte k of the result, 0 or 1
 __device__ __forceinline__ uint64_t spread_bits(uint32_t byte) {
     const uint64_t picked = ((uint64_t)byte * 0x0101010101010101ull) & 0x0102040810204080ull;
@@ -100,8 +77,8 @@ __device__ __forceinline__ uint64_t spread_bytes(uint32_t x) {
     return (v | v << 8) & 0x00FF00FF00FF00FFull;
 }
 
-// an entry of `pal_words` widened: red | green << 8 | blue << 16 | 255 << 24
-__device__ __forceinline__ uint32_t widen(const uint8_t* pal_words, uint32_t format, uint32_t i) {
+// an entry of `pal_words` widened: red | green << 8 | blue << 16 | 255 << 24 (the kernel's and par_screen_palette_rgba's)
+__host__ __device__ __forceinline__ uint32_t widen(const uint8_t* pal_words, uint32_t format, uint32_t i) {
     uint32_t r, g, b;
     if (format == PAR_SCREEN_RGBA8) {
         r = pal_words[4 * i], g = pal_words[4 * i + 1], b = pal_words[4 * i + 2];
@@ -147,7 +124,7 @@ __global__ __launch_bounds__(SC_THREADS) void draw_kernel(draw_args A, const uin
         if (threadIdx.x < A.n_colors) colours[threadIdx.x] = widen(pal_words, A.pal_format, threadIdx.x);
         __syncthreads();
     }
-    if (bad_out) add_bad(gid < A.n_cells && read_cell(A.L, map_words, gid, A.n_tiles).bad, bad_out);
+    if (bad_out) add_bad<SC_WAVES>(gid < A.n_cells && read_cell(A.L, map_words, gid, A.n_tiles).bad, bad_out);
 
     const uint32_t y = gid / A.slots, slot = gid - y * A.slots;
     if (y >= A.height) return;
@@ -241,28 +218,13 @@ __global__ __launch_bounds__(SC_THREADS) void decode_map_kernel(word_layout L, c
         map_out[c] = (bad ? 0u : cell.id) | cell.fx << 30 | cell.fy << 31;
         if (pal_out) pal_out[c] = (uint8_t)cell.p;
     }
-    if (bad_out) add_bad(bad, bad_out);  // (the same for every lane of the launch)
+    if (bad_out) add_bad<SC_WAVES>(bad, bad_out);  // (the same for every lane of the launch)
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
-bool tile_dim_ok(int d) { return d == 8 || d == 16; }
-bool format_ok(int format) { return format >= PAR_SCREEN_1BPP && format <= PAR_SCREEN_4BPP_ROW_PLANES; }
 bool pal_format_ok(int format) { return format >= PAR_SCREEN_BGR555 && format <= PAR_SCREEN_RGBA8; }
-bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-uint32_t log2_of(int d) { return d == 8 ? 3u : (d == 16 ? 4u : (d == 2 ? 1u : 0u)); }
 size_t pal_entry_bytes(int format) { return format == PAR_SCREEN_RGBA8 ? 4 : (format == PAR_SCREEN_BGR222 ? 1 : 2); }
-
-bool layout_ok(const par_screen_map_layout* L) {
-    if (L->word_bytes != 1 && L->word_bytes != 2 && L->word_bytes != 4) return false;
-    const int bits = 8 * L->word_bytes;
-    if (L->big_endian != 0 && L->big_endian != 1) return false;
-    if (L->tile_bits < 1 || L->tile_shift < 0 || L->tile_bits > bits || L->tile_shift > bits - L->tile_bits) return false;
-    if (L->pal_bits < 0 || L->pal_shift < 0 || L->pal_bits > bits || L->pal_shift > bits - L->pal_bits) return false;
-    if (L->flip_x_bit < -1 || L->flip_x_bit >= bits || L->flip_y_bit < -1 || L->flip_y_bit >= bits) return false;
-    if (L->tile_step < 1 || L->tile_step > 16 || L->tile_base < 0 || L->tile_base > 65535) return false;
-    return bits == 32 || ((uint32_t)L->set_bits >> bits) == 0;
-}
 
 word_layout words_of(const par_screen_map_layout* L) {
     word_layout W;
@@ -290,10 +252,6 @@ bool draw_args_ok(const par_screen_desc* d, const uint8_t* chr, const uint8_t* m
 
 bool decode_args_ok(const par_screen_map_layout* layout, const uint8_t* map_words, int n_cells, const uint32_t* map_out) {
     return layout && map_words && map_out && aligned4(map_out) && n_cells >= 1 && n_cells <= PAR_SCREEN_MAX_CELLS && layout_ok(layout);
-}
-
-hipError_t zero_bad(hipStream_t stream, uint32_t* bad_out) {
-    return bad_out ? hipMemsetAsync(bad_out, 0, sizeof(uint32_t), stream) : hipSuccess;
 }
 
 uint32_t floor_mod_host(int32_t v, uint32_t period) {
@@ -333,48 +291,17 @@ hipError_t launch_decode_map(hipStream_t stream, const par_screen_map_layout* la
     return hipGetLastError();
 }
 
-// par_select_device's rules (par_context.hip, which is not linked here): a negative *device becomes the current device.
-int screen_select_device(int* device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PAR_ERR_NO_DEVICE;
-    if (*device < 0) {
-        if (hipGetDevice(device) != hipSuccess) return PAR_ERR_NO_DEVICE;
-    }
-    if (*device >= ndev) return PAR_ERR_INVALID_ARG;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, *device) != hipSuccess) return PAR_ERR_NO_DEVICE;
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return PAR_ERR_NO_DEVICE;  // kernels are built for gfx950 only
-    return PAR_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
-size_t par_screen_tile_bytes(int format, int tile_w, int tile_h) {
-    if (!format_ok(format) || !tile_dim_ok(tile_w) || !tile_dim_ok(tile_h)) return 0;
-    return (size_t)(8 * bpp_of((uint32_t)format)) * (size_t)(tile_w / 8) * (size_t)(tile_h / 8);
-}
+size_t par_screen_tile_bytes(int format, int tile_w, int tile_h) { return tile_bytes_of(format, tile_w, tile_h); }
 
 size_t par_screen_palette_rgba(const uint8_t* words, int n, int format, uint8_t* rgba_out) {
     if (!words || !rgba_out || n < 1 || n > 256 || !pal_format_ok(format)) return 0;
     for (int i = 0; i < n; i++) {
-        uint32_t r, g, b;
-        if (format == PAR_SCREEN_RGBA8) {
-            r = words[4 * i], g = words[4 * i + 1], b = words[4 * i + 2];
-        } else if (format == PAR_SCREEN_BGR555) {
-            const uint32_t w = words[2 * i] | (uint32_t)words[2 * i + 1] << 8;
-            const uint32_t qr = w & 31u, qg = (w >> 5) & 31u, qb = (w >> 10) & 31u;
-            r = qr << 3 | qr >> 2, g = qg << 3 | qg >> 2, b = qb << 3 | qb >> 2;
-        } else if (format == PAR_SCREEN_BGR333_MD) {
-            const uint32_t w = (uint32_t)words[2 * i] << 8 | words[2 * i + 1];
-            const uint32_t qr = (w >> 1) & 7u, qg = (w >> 5) & 7u, qb = (w >> 9) & 7u;
-            r = qr << 5 | qr << 2 | qr >> 1, g = qg << 5 | qg << 2 | qg >> 1, b = qb << 5 | qb << 2 | qb >> 1;
-        } else {
-            const uint32_t w = words[i];
-            r = (w & 3u) * 0x55u, g = ((w >> 2) & 3u) * 0x55u, b = ((w >> 4) & 3u) * 0x55u;
-        }
-        rgba_out[4 * i] = (uint8_t)r, rgba_out[4 * i + 1] = (uint8_t)g, rgba_out[4 * i + 2] = (uint8_t)b, rgba_out[4 * i + 3] = 255;
+        const uint32_t c = widen(words, (uint32_t)format, (uint32_t)i);
+        for (int k = 0; k < 4; k++) rgba_out[4 * i + k] = (uint8_t)(c >> (8 * k));
     }
     return (size_t)n * 4;
 }
@@ -399,7 +326,7 @@ int par_screen_draw_host(int device, const par_screen_desc* desc, const uint8_t*
                          const uint8_t* attr, const uint8_t* pal_words, const int32_t* line_scroll, uint8_t* fb_out,
                          uint8_t* index_out, int* bad) {
     if (!draw_args_ok(desc, chr, map_words, pal_words, line_scroll, fb_out, index_out) || !bad) return PAR_ERR_INVALID_ARG;
-    const int rc = screen_select_device(&device);
+    const int rc = par_select_device(&device);
     if (rc != PAR_OK) return rc;
     hipError_t e = hipSetDevice(device);
     const size_t cells = (size_t)desc->map_w * (size_t)desc->map_h, pixels = (size_t)desc->width * (size_t)desc->height;
@@ -430,7 +357,7 @@ int par_screen_draw_host(int device, const par_screen_desc* desc, const uint8_t*
 int par_screen_decode_map_host(int device, const par_screen_map_layout* layout, const uint8_t* map_words, int n_cells,
                                uint32_t* map_out, uint8_t* pal_out, int* bad) {
     if (!decode_args_ok(layout, map_words, n_cells, map_out) || !bad) return PAR_ERR_INVALID_ARG;
-    const int rc = screen_select_device(&device);
+    const int rc = par_select_device(&device);
     if (rc != PAR_OK) return rc;
     hipError_t e = hipSetDevice(device);
     uint32_t n_bad = 0;

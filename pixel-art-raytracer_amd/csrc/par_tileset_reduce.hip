@@ -24,7 +24,6 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <cstring>
 
 #include "par_hostcall.h"
 #include "par_tileset_reduce.h"
@@ -334,20 +333,6 @@ hipError_t launch_reduce(hipStream_t stream, const uint8_t* tiles, int capacity,
     return hipGetLastError();
 }
 
-// par_select_device's rules (par_context.hip, which is not linked here): a negative *device becomes the current device.
-int reduce_select_device(int* device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PAR_ERR_NO_DEVICE;
-    if (*device < 0) {
-        if (hipGetDevice(device) != hipSuccess) return PAR_ERR_NO_DEVICE;
-    }
-    if (*device >= ndev) return PAR_ERR_INVALID_ARG;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, *device) != hipSuccess) return PAR_ERR_NO_DEVICE;
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return PAR_ERR_NO_DEVICE;  // kernels are built for gfx950 only
-    return PAR_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -380,7 +365,7 @@ int par_tileset_reduce_host(int device, const uint8_t* tiles, int n_tiles, int t
                         count_out)) {
         return PAR_ERR_INVALID_ARG;
     }
-    const int rc = reduce_select_device(&device);
+    const int rc = par_select_device(&device);
     if (rc != PAR_OK) return rc;
     hipError_t e = hipSetDevice(device);
     const size_t tile_bytes = (size_t)(tile_w * tile_h);

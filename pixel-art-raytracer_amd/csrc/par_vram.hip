@@ -18,9 +18,9 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <cstring>
 
 #include "par_hostcall.h"
+#include "par_tilehw.h"
 #include "par_vram.h"
 
 namespace {
@@ -31,26 +31,16 @@ constexpr uint32_t VR_LOCAL_BYTES = 8;           // bytes a thread of the local 
 constexpr uint32_t VR_ID_MASK = 0x3FFFFFFFu;
 static_assert(VR_WAVES == 4, "a tile's one, two or four sub-tiles share a workgroup");
 
-__host__ __device__ inline uint32_t bpp_of(uint32_t format) {
-    return format == PAR_VRAM_1BPP ? 1u : (format <= PAR_VRAM_2BPP_ROWS ? 2u : 4u);
-}
+// par_tilehw.h's formats are par_vram_tile_format's
+static_assert(PAR_VRAM_1BPP == TILEHW_1BPP);
+static_assert(PAR_VRAM_2BPP_PLANAR == TILEHW_2BPP_PLANAR);
+static_assert(PAR_VRAM_2BPP_ROWS == TILEHW_2BPP_ROWS);
+static_assert(PAR_VRAM_4BPP_ROWS == TILEHW_4BPP_ROWS);
+static_assert(PAR_VRAM_4BPP_PACKED_HI == TILEHW_4BPP_PACKED_HI);
+static_assert(PAR_VRAM_4BPP_PACKED_LO == TILEHW_4BPP_PACKED_LO);
+static_assert(PAR_VRAM_4BPP_ROW_PLANES == TILEHW_4BPP_ROW_PLANES);
 
-__host__ __device__ inline bool packed(uint32_t format) {
-    return format == PAR_VRAM_4BPP_PACKED_HI || format == PAR_VRAM_4BPP_PACKED_LO;
-}
-
-// the byte of a sub-tile that holds bit plane b of row y (the planar formats)
-__device__ __forceinline__ uint32_t plane_byte(uint32_t format, uint32_t b, uint32_t y) {
-    switch (format) {
-        case PAR_VRAM_2BPP_PLANAR: return 8 * b + y;
-        case PAR_VRAM_2BPP_ROWS: return 2 * y + b;
-        case PAR_VRAM_4BPP_ROWS: return 16 * (b >> 1) + 2 * y + (b & 1);
-        case PAR_VRAM_4BPP_ROW_PLANES: return 4 * y + b;
-        default: return y;
-    }
-}
-
-// its inverse: the plane (low two bits) and the row (from bit 2 on) of byte j
+// plane_byte's inverse: the plane (low two bits) and the row (from bit 2 on) of byte j
 __device__ __forceinline__ uint32_t plane_and_row(uint32_t format, uint32_t j) {
     switch (format) {
         case PAR_VRAM_2BPP_PLANAR: return ((j >> 3) & 1) | ((j & 7) << 2);
@@ -154,7 +144,6 @@ __global__ __launch_bounds__(VR_THREADS) void decode_tiles_kernel(const uint8_t*
 __global__ __launch_bounds__(VR_THREADS) void encode_map_kernel(par_vram_map_layout L, const uint32_t* map, uint32_t gcx,
                                                                 uint32_t n, const uint8_t* cells, uint32_t rxs, uint32_t rys,
                                                                 uint32_t ccx, uint8_t* out, uint32_t* bad_out) {
-    __shared__ uint32_t bad_of[VR_WAVES];
     const uint32_t c = blockIdx.x * VR_THREADS + threadIdx.x;
     bool bad = false;
     if (c < n) {
@@ -173,37 +162,13 @@ __global__ __launch_bounds__(VR_THREADS) void encode_map_kernel(par_vram_map_lay
         uint8_t* o = out + (size_t)c * wb;
         for (uint32_t k = 0; k < wb; k++) o[k] = (uint8_t)(w >> (8 * (L.big_endian ? wb - 1 - k : k)));
     }
-    if (!bad_out) return;  // (the same for every lane of the launch)
-    const uint32_t in_wave = (uint32_t)__popcll(__ballot(bad));
-    if ((threadIdx.x & 63u) == 0) bad_of[threadIdx.x >> 6] = in_wave;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t total = 0;
-        for (uint32_t w = 0; w < VR_WAVES; w++) total += bad_of[w];
-        if (total) atomicAdd(bad_out, total);
-    }
+    if (bad_out) add_bad<VR_WAVES>(bad, bad_out);  // (the same for every lane of the launch)
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
-bool tile_dim_ok(int d) { return d == 8 || d == 16; }
-bool format_ok(int format) { return format >= PAR_VRAM_1BPP && format <= PAR_VRAM_4BPP_ROW_PLANES; }
-bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-uint32_t log2_of(int d) { return d == 8 ? 3u : (d == 16 ? 4u : (d == 2 ? 1u : 0u)); }
-
 bool tiles_args_ok(const uint8_t* in, int n_tiles, int tile_w, int tile_h, int format, const uint8_t* out) {
     return in && out && n_tiles >= 1 && n_tiles <= PAR_VRAM_MAX_TILES && tile_dim_ok(tile_w) && tile_dim_ok(tile_h) && format_ok(format);
-}
-
-bool layout_ok(const par_vram_map_layout* L) {
-    if (L->word_bytes != 1 && L->word_bytes != 2 && L->word_bytes != 4) return false;
-    const int bits = 8 * L->word_bytes;
-    if (L->big_endian != 0 && L->big_endian != 1) return false;
-    if (L->tile_bits < 1 || L->tile_shift < 0 || L->tile_bits > bits || L->tile_shift > bits - L->tile_bits) return false;
-    if (L->pal_bits < 0 || L->pal_shift < 0 || L->pal_bits > bits || L->pal_shift > bits - L->pal_bits) return false;
-    if (L->flip_x_bit < -1 || L->flip_x_bit >= bits || L->flip_y_bit < -1 || L->flip_y_bit >= bits) return false;
-    if (L->tile_step < 1 || L->tile_step > 16 || L->tile_base < 0 || L->tile_base > 65535) return false;
-    return bits == 32 || ((uint32_t)L->set_bits >> bits) == 0;
 }
 
 bool map_args_ok(const par_vram_map_layout* layout, const uint32_t* map, int gcx, int gcy, int ratio_x, int ratio_y,
@@ -212,10 +177,6 @@ bool map_args_ok(const par_vram_map_layout* layout, const uint32_t* map, int gcx
     if ((int64_t)gcx * (int64_t)gcy > PAR_VRAM_MAX_CELLS) return false;
     if ((ratio_x != 1 && ratio_x != 2) || (ratio_y != 1 && ratio_y != 2)) return false;
     return layout_ok(layout);
-}
-
-hipError_t zero_bad(hipStream_t stream, uint32_t* bad_out) {
-    return bad_out ? hipMemsetAsync(bad_out, 0, sizeof(uint32_t), stream) : hipSuccess;
 }
 
 hipError_t launch_encode_tiles(hipStream_t stream, const uint8_t* tiles, int capacity, const uint32_t* count, int tile_w, int tile_h,
@@ -249,28 +210,11 @@ hipError_t launch_encode_map(hipStream_t stream, const par_vram_map_layout* layo
     return hipGetLastError();
 }
 
-// par_select_device's rules (par_context.hip, which is not linked here): a negative *device becomes the current device.
-int vram_select_device(int* device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PAR_ERR_NO_DEVICE;
-    if (*device < 0) {
-        if (hipGetDevice(device) != hipSuccess) return PAR_ERR_NO_DEVICE;
-    }
-    if (*device >= ndev) return PAR_ERR_INVALID_ARG;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, *device) != hipSuccess) return PAR_ERR_NO_DEVICE;
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return PAR_ERR_NO_DEVICE;  // kernels are built for gfx950 only
-    return PAR_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
-size_t par_vram_tile_bytes(int format, int tile_w, int tile_h) {
-    if (!format_ok(format) || !tile_dim_ok(tile_w) || !tile_dim_ok(tile_h)) return 0;
-    return (size_t)(8 * bpp_of((uint32_t)format)) * (size_t)(tile_w / 8) * (size_t)(tile_h / 8);
-}
+size_t par_vram_tile_bytes(int format, int tile_w, int tile_h) { return tile_bytes_of(format, tile_w, tile_h); }
 
 int par_vram_local_device(void* stream, const uint8_t* index, int n_bytes, int sub_size, uint8_t* local_out) {
     if (!index || !local_out || n_bytes < 1 || sub_size < 1 || sub_size > 256) return PAR_ERR_INVALID_ARG;
@@ -343,7 +287,7 @@ size_t par_vram_palette_words(const uint8_t* palette, int n, int format, uint8_t
 int par_vram_encode_tiles_host(int device, const uint8_t* tiles, int capacity, int count, int tile_w, int tile_h,
                                int format, uint8_t* out, int* bad) {
     if (!tiles_args_ok(tiles, capacity, tile_w, tile_h, format, out) || count < 0 || !bad) return PAR_ERR_INVALID_ARG;
-    const int rc = vram_select_device(&device);
+    const int rc = par_select_device(&device);
     if (rc != PAR_OK) return rc;
     const int n = std::min(count, capacity);
     if (n == 0) {
@@ -370,7 +314,7 @@ int par_vram_encode_tiles_host(int device, const uint8_t* tiles, int capacity, i
 int par_vram_decode_tiles_host(int device, const uint8_t* data, int n_tiles, int tile_w, int tile_h, int format,
                                uint8_t* tiles_out) {
     if (!tiles_args_ok(data, n_tiles, tile_w, tile_h, format, tiles_out)) return PAR_ERR_INVALID_ARG;
-    const int rc = vram_select_device(&device);
+    const int rc = par_select_device(&device);
     if (rc != PAR_OK) return rc;
     hipError_t e = hipSetDevice(device);
     par_device_buffer d_data(e, data, (size_t)n_tiles * par_vram_tile_bytes(format, tile_w, tile_h), true);
@@ -384,7 +328,7 @@ int par_vram_decode_tiles_host(int device, const uint8_t* data, int n_tiles, int
 int par_vram_encode_map_host(int device, const par_vram_map_layout* layout, const uint32_t* map, int gcx, int gcy,
                              const uint8_t* cells, int ratio_x, int ratio_y, uint8_t* out, int* bad) {
     if (!map_args_ok(layout, map, gcx, gcy, ratio_x, ratio_y, out) || !bad) return PAR_ERR_INVALID_ARG;
-    const int rc = vram_select_device(&device);
+    const int rc = par_select_device(&device);
     if (rc != PAR_OK) return rc;
     hipError_t e = hipSetDevice(device);
     const size_t n = (size_t)gcx * (size_t)gcy;

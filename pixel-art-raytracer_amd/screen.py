@@ -71,20 +71,10 @@ _lib = None
 
 
 def lib():
-    """Load libpar_screen.so (built in-tree by csrc/Makefile) and set the table on its functions. No fallback."""
+    """libpar_screen.so with the table set on its functions, loaded at the first call (the package's loader). No fallback."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} is missing: build it with `make -C pixel-art-raytracer_amd/csrc` "
-                              "(or __graft_entry__.build()). There is no CPU fallback.")
-        _par._share_hip_runtime_with_torch()
-        L = C.CDLL(LIB_PATH)
-        for name, sig in ABI_SCREEN.items():
-            fn = getattr(L, name)
-            if type(sig) is tuple:
-                fn.restype, sig = sig
-            fn.argtypes = sig
-        _lib = L
+        _lib = _par._load(LIB_PATH, ABI_SCREEN)
     return _lib
 
 
