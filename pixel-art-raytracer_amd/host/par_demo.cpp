@@ -9,7 +9,7 @@
 //   par_demo [--keys RRRRUUUUhhhhjjPP] [--frames N] [--out DIR] [--gif FILE] [--debug-line] [--as-sdl] [--size W H L]
 //            [--palette-levels K] [--dither S] [--outline S,C,D] [--scale SX[,SY]] [--finish] [--upscale K]
 //            [--palette-fit N] [--palette-refine I] [--dither-pattern N[,S]] [--cells CW,CH] [--tileset TW,TH[,FLIPS]]
-//            [--tileset-shared CAP] [--tileset-budget K] [--cells-fit S,K[,R]] [--vram MACHINE[,DIR]] [--vram-show [backdrop]]
+//            [--tileset-shared CAP] [--tileset-budget K] [--cells-fit S,K[,R]] [--vram MACHINE[,DIR]] [--vram-show [backdrop]] [--machine-fit]
 //
 // --gif writes the frames as one animated GIF89a (100 ms per frame like the reference's gif.gif); a frame's colours
 // are palette entries times a brightness, at most a few hundred distinct values, so each frame gets an exact local
@@ -74,6 +74,10 @@
 // prints `screen frame <i>: bad <b>, error <E>`: the map cells that name no tile of the export, and the summed L1 over red,
 // green and blue between the shown picture and the cells frame (the table's entry of every index). With --vram's DIR it
 // writes frame_<i>.ppm. Without it nothing the demo prints or writes changes.
+// --machine-fit (with --cells-fit and --vram) fits the table through the add-on of addons/include/par_machine_fit.h
+// (par_machine_fit_host) instead: under the colour depth of the machine's colour words (the nes, which has none, fits at
+// RGBA8) and, with K of 2 or more, one backdrop entry shared by every sub-palette. In the place of the `cells fit` line it
+// prints `machine fit frame <i>: <S> x <K>, error <E0> -> <ER>`. Without it nothing the demo prints or writes changes.
 //
 // --outline S,C,D draws every frame's outlines on the GPU (par_outline_host) from the frame's own G-buffer: silhouettes
 // scaled by S / 256, creases by C / 256, a silhouette between two entities from a depth difference of D (128,320,4 is a
@@ -111,6 +115,7 @@
 
 #include "par_cells.h"
 #include "par_cells_fit.h"
+#include "par_machine_fit.h"
 #include "par_raytracer.h"
 #include "par_screen.h"
 #include "par_tileset.h"
@@ -290,6 +295,7 @@ int main(int argc, char** argv) {
     int vram_machine = -1;                       // -1: no --vram
     std::string vram_name, vram_dir;
     int vram_show = -1;                          // -1: no --vram-show; else its backdrop
+    bool machine_fit = false;                    // --machine-fit
     par_outline_style outline_style{4, 256, 256};
     for (int i = 1; i < argc; i++) {
         if (!std::strcmp(argv[i], "--keys") && i + 1 < argc) keys = argv[++i];
@@ -368,6 +374,7 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
+        else if (!std::strcmp(argv[i], "--machine-fit")) machine_fit = true;
         else if (!std::strcmp(argv[i], "--vram-show")) {
             vram_show = 0;
             if (i + 1 < argc && !std::strcmp(argv[i + 1], "backdrop")) { vram_show = 1; i++; }
@@ -485,6 +492,10 @@ int main(int argc, char** argv) {
         }
     }
     if (vram_show >= 0 && vram_machine < 0) { std::fprintf(stderr, "--vram-show wants --vram MACHINE[,DIR]: it draws that export\n"); return 2; }
+    if (machine_fit && (fit_sub == 0 || vram_machine < 0)) {
+        std::fprintf(stderr, "--machine-fit wants --cells-fit S,K[,R] and --vram MACHINE[,DIR]: it fits that table for that machine\n");
+        return 2;
+    }
     if (finish) {
         if (out_dir.empty()) { std::fprintf(stderr, "--finish wants --out\n"); return 2; }
         if (!outline && palette_levels == 0) { std::fprintf(stderr, "--finish wants --outline or --palette-levels: without both it is --scale\n"); return 2; }
@@ -797,14 +808,24 @@ int main(int argc, char** argv) {
                 // (pairs: here the fitted table)
                 pairs.resize((size_t)fit_sub * fit_size);
                 std::vector<uint64_t> errors((size_t)fit_rounds + 1);
-                if ((rc = par_cells_fit_host(0, reinterpret_cast<const uint8_t*>(fb.data()), W, H, cell_w, cell_h,
-                                             reinterpret_cast<const uint8_t*>(fitted.data()), palette_fit, fit_sub, fit_size, fit_rounds,
-                                             reinterpret_cast<uint8_t*>(pairs.data()), nullptr, errors.data())) != PAR_OK) {
+                if (machine_fit) {
+                    // the depth of the machine's colour words (their formats and the depths are equal in value)
+                    const int depth = vram_colours[vram_machine] >= 0 ? vram_colours[vram_machine] : (int)PAR_MACHINE_RGBA8;
+                    if ((rc = par_machine_fit_host(0, reinterpret_cast<const uint8_t*>(fb.data()), W, H, cell_w, cell_h,
+                                                   reinterpret_cast<const uint8_t*>(fitted.data()), palette_fit, fit_sub, fit_size,
+                                                   fit_rounds, depth, fit_size >= 2 ? 1 : 0, reinterpret_cast<uint8_t*>(pairs.data()),
+                                                   nullptr, errors.data())) != PAR_OK) {
+                        std::fprintf(stderr, "par_machine_fit_host: %s\n", par_status_string(rc));
+                        return 1;
+                    }
+                } else if ((rc = par_cells_fit_host(0, reinterpret_cast<const uint8_t*>(fb.data()), W, H, cell_w, cell_h,
+                                                    reinterpret_cast<const uint8_t*>(fitted.data()), palette_fit, fit_sub, fit_size,
+                                                    fit_rounds, reinterpret_cast<uint8_t*>(pairs.data()), nullptr, errors.data())) != PAR_OK) {
                     std::fprintf(stderr, "par_cells_fit_host: %s\n", par_status_string(rc));
                     return 1;
                 }
-                std::printf("cells fit frame %d: %d x %d, error %llu -> %llu\n", f, fit_sub, fit_size, (unsigned long long)errors[0],
-                            (unsigned long long)errors[(size_t)fit_rounds]);
+                std::printf("%s fit frame %d: %d x %d, error %llu -> %llu\n", machine_fit ? "machine" : "cells", f, fit_sub, fit_size,
+                            (unsigned long long)errors[0], (unsigned long long)errors[(size_t)fit_rounds]);
                 if ((rc = par_quantize_cells_host(&params, 0, pairs.data(), fit_sub, fit_size, cell_w, cell_h, dither, fb.data(), 0, H,
                                                   nullptr, index.data(), chosen.empty() ? nullptr : chosen.data())) != PAR_OK) {
                     std::fprintf(stderr, "par_quantize_cells_host: %s\n", par_status_string(rc));
