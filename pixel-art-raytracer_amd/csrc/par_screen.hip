@@ -36,6 +36,9 @@ static_assert(PAR_SCREEN_4BPP_ROWS == TILEHW_4BPP_ROWS);
 static_assert(PAR_SCREEN_4BPP_PACKED_HI == TILEHW_4BPP_PACKED_HI);
 static_assert(PAR_SCREEN_4BPP_PACKED_LO == TILEHW_4BPP_PACKED_LO);
 static_assert(PAR_SCREEN_4BPP_ROW_PLANES == TILEHW_4BPP_ROW_PLANES);
+// and its colour words (spread_bits, spread_bytes and widen live there, one copy with par_objects.hip) par_screen_palette_format's
+static_assert(PAR_SCREEN_BGR555 == TILEHW_BGR555 && PAR_SCREEN_BGR333_MD == TILEHW_BGR333_MD);
+static_assert(PAR_SCREEN_BGR222 == TILEHW_BGR222 && PAR_SCREEN_RGBA8 == TILEHW_RGBA8);
 
 // what the kernels need of a layout, as unsigned fields
 struct word_layout {
@@ -62,39 +65,6 @@ __device__ __forceinline__ map_cell read_cell(const word_layout& L, const uint8_
     cell.id = L.tile_step == 1 ? above : above / L.tile_step;
     cell.bad = t < L.tile_base || cell.id * L.tile_step != above || cell.id >= limit;
     return cell;
-}
-
-// bit 7 - k of `byte` as byte k of the result, 0 or 1
-__device__ __forceinline__ uint64_t spread_bits(uint32_t byte) {
-    const uint64_t picked = ((uint64_t)byte * 0x0101010101010101ull) & 0x0102040810204080ull;
-    return ((picked + 0x7F7F7F7F7F7F7F7Full) >> 7) & 0x0101010101010101ull;
-}
-
-// byte m of `x` as byte 2 m of the result
-__device__ __forceinline__ uint64_t spread_bytes(uint32_t x) {
-    uint64_t v = x;
-    v = (v | v << 16) & 0x0000FFFF0000FFFFull;
-    return (v | v << 8) & 0x00FF00FF00FF00FFull;
-}
-
-// an entry of `pal_words` widened: red | green << 8 | blue << 16 | 255 << 24 (the kernel's and par_screen_palette_rgba's)
-__host__ __device__ __forceinline__ uint32_t widen(const uint8_t* pal_words, uint32_t format, uint32_t i) {
-    uint32_t r, g, b;
-    if (format == PAR_SCREEN_RGBA8) {
-        r = pal_words[4 * i], g = pal_words[4 * i + 1], b = pal_words[4 * i + 2];
-    } else if (format == PAR_SCREEN_BGR555) {
-        const uint32_t w = pal_words[2 * i] | (uint32_t)pal_words[2 * i + 1] << 8;
-        const uint32_t qr = w & 31u, qg = (w >> 5) & 31u, qb = (w >> 10) & 31u;
-        r = qr << 3 | qr >> 2, g = qg << 3 | qg >> 2, b = qb << 3 | qb >> 2;
-    } else if (format == PAR_SCREEN_BGR333_MD) {
-        const uint32_t w = (uint32_t)pal_words[2 * i] << 8 | pal_words[2 * i + 1];
-        const uint32_t qr = (w >> 1) & 7u, qg = (w >> 5) & 7u, qb = (w >> 9) & 7u;
-        r = qr << 5 | qr << 2 | qr >> 1, g = qg << 5 | qg << 2 | qg >> 1, b = qb << 5 | qb << 2 | qb >> 1;
-    } else {
-        const uint32_t w = pal_words[i];
-        r = (w & 3u) * 0x55u, g = ((w >> 2) & 3u) * 0x55u, b = ((w >> 4) & 3u) * 0x55u;
-    }
-    return r | g << 8 | b << 16 | 0xFF000000u;
 }
 
 struct draw_args {
@@ -222,9 +192,6 @@ __global__ __launch_bounds__(SC_THREADS) void decode_map_kernel(word_layout L, c
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-
-bool pal_format_ok(int format) { return format >= PAR_SCREEN_BGR555 && format <= PAR_SCREEN_RGBA8; }
-size_t pal_entry_bytes(int format) { return format == PAR_SCREEN_RGBA8 ? 4 : (format == PAR_SCREEN_BGR222 ? 1 : 2); }
 
 word_layout words_of(const par_screen_map_layout* L) {
     word_layout W;

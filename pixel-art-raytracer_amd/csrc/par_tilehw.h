@@ -1,5 +1,6 @@
-// par_tilehw.h — what the two add-ons over tile hardware's bytes share, the encoder (par_vram.hip) and the decoder
-// (par_screen.hip): the tile formats, a tile's bytes, the check of a map layout and the count of a launch's bad cells.
+// par_tilehw.h — what the add-ons over tile hardware's bytes share, the encoder (par_vram.hip) and the decoders
+// (par_screen.hip, par_objects.hip): the tile formats, a tile's bytes, the check of a map layout, the count of a launch's
+// bad cells, and for the decoders the spread of a row's bits and nibbles to a byte a pixel and the widened colour word.
 // It includes neither add-on's public header: the formats are its own constants, to which each unit pins its public
 // enumeration with static_asserts, and the layout check is a template over the unit's own layout struct. Everything is
 // in an unnamed namespace, device code __forceinline__: each unit gets its own copy and nothing is linked between the
@@ -37,6 +38,42 @@ __device__ __forceinline__ uint32_t plane_byte(uint32_t format, uint32_t b, uint
     }
 }
 
+// the values of par_screen_palette_format and of par_objects_palette_format
+constexpr uint32_t TILEHW_BGR555 = 0, TILEHW_BGR333_MD = 1, TILEHW_BGR222 = 2, TILEHW_RGBA8 = 3;
+
+// bit 7 - k of `byte` as byte k of the result, 0 or 1
+__device__ __forceinline__ uint64_t spread_bits(uint32_t byte) {
+    const uint64_t picked = ((uint64_t)byte * 0x0101010101010101ull) & 0x0102040810204080ull;
+    return ((picked + 0x7F7F7F7F7F7F7F7Full) >> 7) & 0x0101010101010101ull;
+}
+
+// byte m of `x` as byte 2 m of the result
+__device__ __forceinline__ uint64_t spread_bytes(uint32_t x) {
+    uint64_t v = x;
+    v = (v | v << 16) & 0x0000FFFF0000FFFFull;
+    return (v | v << 8) & 0x00FF00FF00FF00FFull;
+}
+
+// an entry of `pal_words` widened: red | green << 8 | blue << 16 | 255 << 24 (the kernels' and par_screen_palette_rgba's)
+__host__ __device__ __forceinline__ uint32_t widen(const uint8_t* pal_words, uint32_t format, uint32_t i) {
+    uint32_t r, g, b;
+    if (format == TILEHW_RGBA8) {
+        r = pal_words[4 * i], g = pal_words[4 * i + 1], b = pal_words[4 * i + 2];
+    } else if (format == TILEHW_BGR555) {
+        const uint32_t w = pal_words[2 * i] | (uint32_t)pal_words[2 * i + 1] << 8;
+        const uint32_t qr = w & 31u, qg = (w >> 5) & 31u, qb = (w >> 10) & 31u;
+        r = qr << 3 | qr >> 2, g = qg << 3 | qg >> 2, b = qb << 3 | qb >> 2;
+    } else if (format == TILEHW_BGR333_MD) {
+        const uint32_t w = (uint32_t)pal_words[2 * i] << 8 | pal_words[2 * i + 1];
+        const uint32_t qr = (w >> 1) & 7u, qg = (w >> 5) & 7u, qb = (w >> 9) & 7u;
+        r = qr << 5 | qr << 2 | qr >> 1, g = qg << 5 | qg << 2 | qg >> 1, b = qb << 5 | qb << 2 | qb >> 1;
+    } else {
+        const uint32_t w = pal_words[i];
+        r = (w & 3u) * 0x55u, g = ((w >> 2) & 3u) * 0x55u, b = ((w >> 4) & 3u) * 0x55u;
+    }
+    return r | g << 8 | b << 16 | 0xFF000000u;
+}
+
 // The workgroup's bad cells in one atomic; every thread of a workgroup of WAVES wavefronts calls it.
 template <uint32_t WAVES>
 __device__ __forceinline__ void add_bad(bool bad, uint32_t* bad_out) {
@@ -55,6 +92,8 @@ __device__ __forceinline__ void add_bad(bool bad, uint32_t* bad_out) {
 
 inline bool tile_dim_ok(int d) { return d == 8 || d == 16; }
 inline bool format_ok(int format) { return format >= TILEHW_1BPP && format <= TILEHW_4BPP_ROW_PLANES; }
+inline bool pal_format_ok(int format) { return format >= (int)TILEHW_BGR555 && format <= (int)TILEHW_RGBA8; }
+inline size_t pal_entry_bytes(int format) { return format == (int)TILEHW_RGBA8 ? 4 : (format == (int)TILEHW_BGR222 ? 1 : 2); }
 inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 inline uint32_t log2_of(int d) { return d == 8 ? 3u : (d == 16 ? 4u : (d == 2 ? 1u : 0u)); }
 

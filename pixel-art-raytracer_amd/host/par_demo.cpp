@@ -74,6 +74,18 @@
 // prints `screen frame <i>: bad <b>, error <E>`: the map cells that name no tile of the export, and the summed L1 over red,
 // green and blue between the shown picture and the cells frame (the table's entry of every index). With --vram's DIR it
 // writes frame_<i>.ppm. Without it nothing the demo prints or writes changes.
+// --vram-objects [LIMIT] (with --vram-show; LIMIT 1..128 objects a scanline, the machine's nominal figure of
+// par_objects_machine_limits when left out) shows every later frame the way the machine would: frame 0 is the level, whose
+// table, colour words, local tile set, map and cell_out are kept, and frame i >= 1 is objects over it, through the add-on of
+// addons/include/par_objects.h. The frame is quantised under frame 0's table (par_quantize_cells_host) and taken to its
+// local plane, which extends a copy of the kept set (par_tileset_extend_host), so that both maps share one numbering;
+// par_objects_from_maps_host makes an object of every cell that differs; the extended set is encoded, frame 0's screen is
+// drawn and the objects are drawn over it with the hardware's transparency (value 0 shows the level) under LIMIT. After the
+// frame's `screen frame` line it prints `objects frame <i>: <n> objects, <new> new tiles, dropped <d>, error <E>`: the
+// differing cells, the tiles the frame adds to the level's, the objects dropped over the scanlines, and the summed L1 over
+// red, green and blue against frame i's cells frame under frame 0's table. With --vram's DIR it writes
+// frame_<i>.obj.ppm and, for nes and gbc, frame_<i>.oam (par_objects_pack). Without it nothing the demo prints or writes
+// changes.
 // --machine-fit (with --cells-fit and --vram) fits the table through the add-on of addons/include/par_machine_fit.h
 // (par_machine_fit_host) instead: under the colour depth of the machine's colour words (the nes, which has none, fits at
 // RGBA8) and, with K of 2 or more, one backdrop entry shared by every sub-palette. In the place of the `cells fit` line it
@@ -116,6 +128,7 @@
 #include "par_cells.h"
 #include "par_cells_fit.h"
 #include "par_machine_fit.h"
+#include "par_objects.h"
 #include "par_raytracer.h"
 #include "par_screen.h"
 #include "par_tileset.h"
@@ -296,6 +309,7 @@ int main(int argc, char** argv) {
     std::string vram_name, vram_dir;
     int vram_show = -1;                          // -1: no --vram-show; else its backdrop
     bool machine_fit = false;                    // --machine-fit
+    int vram_objects = -1;                       // -1: no --vram-objects; 0: the machine's line limit; else LIMIT
     par_outline_style outline_style{4, 256, 256};
     for (int i = 1; i < argc; i++) {
         if (!std::strcmp(argv[i], "--keys") && i + 1 < argc) keys = argv[++i];
@@ -378,6 +392,19 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--vram-show")) {
             vram_show = 0;
             if (i + 1 < argc && !std::strcmp(argv[i + 1], "backdrop")) { vram_show = 1; i++; }
+        }
+        else if (!std::strcmp(argv[i], "--vram-objects")) {
+            vram_objects = 0;
+            char tail = 0;
+            int limit = 0;
+            if (i + 1 < argc && std::sscanf(argv[i + 1], "%d%c", &limit, &tail) == 1) {
+                vram_objects = limit;
+                if (vram_objects < 1 || vram_objects > PAR_OBJECTS_MAX_LINE) {
+                    std::fprintf(stderr, "--vram-objects wants a LIMIT of 1..%d objects a scanline, got %s\n", PAR_OBJECTS_MAX_LINE, argv[i + 1]);
+                    return 2;
+                }
+                i++;
+            }
         }
         else if (!std::strcmp(argv[i], "--palette-fit") && i + 1 < argc) {
             char tail;
@@ -492,6 +519,10 @@ int main(int argc, char** argv) {
         }
     }
     if (vram_show >= 0 && vram_machine < 0) { std::fprintf(stderr, "--vram-show wants --vram MACHINE[,DIR]: it draws that export\n"); return 2; }
+    if (vram_objects >= 0 && vram_show < 0) {
+        std::fprintf(stderr, "--vram-objects wants --vram-show: it draws the objects over that screen\n");
+        return 2;
+    }
     if (machine_fit && (fit_sub == 0 || vram_machine < 0)) {
         std::fprintf(stderr, "--machine-fit wants --cells-fit S,K[,R] and --vram MACHINE[,DIR]: it fits that table for that machine\n");
         return 2;
@@ -595,6 +626,13 @@ int main(int argc, char** argv) {
     std::vector<unsigned char> chosen;
     if (vram_machine >= 0) chosen.resize((size_t)((W + cell_w - 1) / cell_w) * (size_t)((H + cell_h - 1) / cell_h));
     int flat_tiles = 0;
+    // --vram-objects: the level, frame 0's export as it was shown
+    struct {
+        std::vector<par_color> table;
+        std::vector<unsigned char> colours, set, words, chosen;
+        std::vector<uint32_t> tile_map;
+        int tiles = 0;
+    } level;
     const auto write_file = [&](int f, const char* ext, const std::vector<unsigned char>& bytes) {
         char name[64];
         std::snprintf(name, sizeof(name), "/frame_%03d.%s", f, ext);
@@ -665,6 +703,84 @@ int main(int argc, char** argv) {
                                               std::abs((int)got.blue - (int)meant.blue));
             }
             std::printf("screen frame %d: bad %d, error %llu\n", f, bad_shown, error);
+            if (vram_objects >= 0 && f == 0) {
+                level.table = table, level.colours = colours, level.words = words, level.chosen = chosen, level.tile_map = tile_map;
+                level.set.assign(set.begin(), set.begin() + (size_t)tiles * 64), level.tiles = tiles;
+            } else if (vram_objects >= 0) {
+                // frame f as objects over the level: quantised under the level's table, numbered against the level's set
+                const int n_sub = (int)level.table.size() / vram_sub_size, rx = cell_w / 8, ry = cell_h / 8, ccx = (W + cell_w - 1) / cell_w;
+                std::vector<unsigned char> plane(index.size()), picked(chosen.size()), shared((size_t)2 * cells * 64);
+                if ((status = par_quantize_cells_host(&params, 0, level.table.data(), n_sub, vram_sub_size, cell_w, cell_h, dither, fb.data(), 0, H,
+                                                      nullptr, plane.data(), picked.data())) != PAR_OK) {
+                    std::fprintf(stderr, "par_quantize_cells_host: %s\n", par_status_string(status));
+                    return status;
+                }
+                std::vector<unsigned char> plane_local(plane.size());
+                for (size_t i = 0; i < plane.size(); i++) plane_local[i] = (unsigned char)(plane[i] % vram_sub_size);
+                std::copy(level.set.begin(), level.set.end(), shared.begin());
+                std::vector<uint32_t> frame_map((size_t)cells);
+                int count = level.tiles, first_new = 0;
+                if ((status = par_tileset_extend_host(&params, 0, plane_local.data(), 0, H, 8, 8, 0, tile_flips, shared.data(), 2 * cells, &count,
+                                                      frame_map.data(), &first_new)) != PAR_OK) {
+                    std::fprintf(stderr, "par_tileset_extend_host: %s\n", par_status_string(status));
+                    return status;
+                }
+                // a byte a tile cell: the sub-palette of the colour cell it lies in
+                std::vector<unsigned char> cells_bg((size_t)cells), cells_now((size_t)cells);
+                for (int c = 0; c < cells; c++) {
+                    const size_t cc = (size_t)((c % gcx) / rx) + (size_t)((c / gcx) / ry) * (size_t)ccx;
+                    cells_bg[(size_t)c] = level.chosen[cc], cells_now[(size_t)c] = picked[cc];
+                }
+                std::vector<par_object> objects((size_t)cells);
+                int n_objects = 0, bad_objects = 0, dropped = 0, bad_set = 0, bad_level = 0, line_limit = vram_objects, most = 0;
+                if (line_limit == 0) par_objects_machine_limits(vram_machine, &line_limit, &most);
+                if ((status = par_objects_from_maps_host(0, level.tile_map.data(), cells_bg.data(), frame_map.data(), cells_now.data(), gcx, gcy, 8,
+                                                         8, 0, 0, cells, objects.data(), &n_objects)) != PAR_OK) {
+                    std::fprintf(stderr, "par_objects_from_maps_host: %s\n", par_status_string(status));
+                    return status;
+                }
+                std::vector<unsigned char> chr_shared((size_t)count * par_vram_tile_bytes(format, 8, 8));
+                if ((status = par_vram_encode_tiles_host(0, shared.data(), 2 * cells, count, 8, 8, format, chr_shared.data(), &bad_set)) != PAR_OK) {
+                    std::fprintf(stderr, "par_vram_encode_tiles_host: %s\n", par_status_string(status));
+                    return status;
+                }
+                par_screen_desc ld = d;
+                ld.n_tiles = count;
+                std::vector<par_color> over_level((size_t)W * H);
+                if ((status = par_screen_draw_host(0, &ld, chr_shared.data(), level.words.data(),
+                                                   vram_machine == PAR_VRAM_NES ? level.chosen.data() : nullptr, level.colours.data(), nullptr,
+                                                   reinterpret_cast<uint8_t*>(over_level.data()), nullptr, &bad_level)) != PAR_OK) {
+                    std::fprintf(stderr, "par_screen_draw_host: %s\n", par_status_string(status));
+                    return status;
+                }
+                par_objects_desc od;
+                od.tile_w = od.tile_h = 8, od.tile_format = format, od.n_tiles = count, od.n_objects = cells, od.line_limit = line_limit;
+                od.pal_format = d.pal_format, od.n_colors = d.n_colors, od.sub_size = vram_sub_size, od.pal_base = 0;
+                od.bg_sub_size = vram_sub_size, od.opaque = 0, od.width = W, od.height = H;
+                if ((status = par_objects_draw_host(0, &od, chr_shared.data(), objects.data(), n_objects, level.colours.data(), nullptr,
+                                                    reinterpret_cast<uint8_t*>(over_level.data()), nullptr, &bad_objects, &dropped)) != PAR_OK) {
+                    std::fprintf(stderr, "par_objects_draw_host: %s\n", par_status_string(status));
+                    return status;
+                }
+                unsigned long long off = 0;
+                for (size_t i = 0; i < over_level.size(); i++) {
+                    const par_color meant = level.table[plane[i]], got = over_level[i];
+                    off += (unsigned long long)(std::abs((int)got.red - (int)meant.red) + std::abs((int)got.green - (int)meant.green) +
+                                                std::abs((int)got.blue - (int)meant.blue));
+                }
+                std::printf("objects frame %d: %d objects, %d new tiles, dropped %d, error %llu\n", f, n_objects, count - first_new, dropped, off);
+                if (!vram_dir.empty()) {
+                    char name[64];
+                    std::snprintf(name, sizeof(name), "/frame_%03d.obj.ppm", f);
+                    if (!write_ppm(vram_dir + name, over_level.data(), W, H)) { std::fprintf(stderr, "cannot write %s%s\n", vram_dir.c_str(), name); return -1; }
+                    if (vram_machine <= PAR_VRAM_GBC && n_objects > 0) {
+                        std::vector<unsigned char> oam(4 * (size_t)n_objects);
+                        int unfit = 0;
+                        par_objects_pack(vram_machine == PAR_VRAM_NES ? PAR_OBJECTS_OAM_NES : PAR_OBJECTS_OAM_GB, objects.data(), n_objects, oam.data(), &unfit);
+                        if (!write_file(f, "oam", oam)) return -1;
+                    }
+                }
+            }
         }
         if (vram_dir.empty()) return (int)PAR_OK;
         if (!screen.empty()) {
